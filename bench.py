@@ -70,10 +70,11 @@ def parse_args():
     ap.add_argument("--density", type=int, choices=[1, 3], default=1,
                     help="scene density: 1 = the default synthetic scene (w*h/800 shapes: ~5 k FAST corners on level 0 of a 1080p frame), "
                          "3 = three times the shapes (>= 12 k level-0 corners): FAST's sparse phases scale with the corner load")
-    ap.add_argument("--min-timed-ms", type=float, default=10000.0,
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
                     help="every timed step repeats its batch `inner_repeats` times so that the K timed steps cover at least this much GPU time "
-                         "(0 = one pass per step); value counts every pass.  Default 10 s: an outside observer that samples GPU activity every few "
-                         "seconds (the driver's 5-s sampler saw 0 %% in round 4: the timed region was 0.22 s of a 26-s run) then lands inside the region at least once")
+                         "(0 = one pass per step); value counts every pass.  Default 0: a timed step is one pass of the batch, so --steps sets the "
+                         "number of passes timed and ms_per_step is the duration of one.  10000 keeps the timed region >= 10 s for an outside "
+                         "observer that samples GPU activity every few seconds")
     ap.add_argument("--cpu-worker", type=int, default=-1, help=argparse.SUPPRESS)      # internal: one worker PROCESS of the all-cores CPU baseline (no GPU, no torch)
     ap.add_argument("--cpu-frames", type=str, default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-workers", type=int, default=0, help=argparse.SUPPRESS)
@@ -87,9 +88,15 @@ def parse_args():
     ap.add_argument("--pcie-seconds", type=float, default=1.5, help="c2, N = 1: budget of the host-fed (PCIe-inclusive) secondary measurement (0 = skip)")
     ap.add_argument("--c4-split", type=int, choices=[0, 1], default=1,
                     help="c4: hs_orb_set_split(1) on both camera handles (level 0's FAST + quadtree on a second stream beside the pyramid); 0 = the library default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="c2: after the timed steps, write what the last step computed (rank 0's pairs: keypoints, descriptors, uRight, depth — "
+                         "the valid entries a caller receives) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: ranks rendezvous over gloo, exchange one tensor and rank 0 prints a JSON line (covers the --gpus spawn path on CPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.config != "c2":
+        ap.error("--dump-outputs covers the c2 path only")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 without torchrun: spawn the ranks
@@ -430,6 +437,7 @@ def run_c2(args, rank, world, local_rank, dev, torch, dist, HS, N):
         parity["ok"] = None if all(f == 2 for f in flags) else all(f != 0 for f in flags)
         parity["ranks_checked"] = sum(f != 2 for f in flags)
         parity["ranks_failed"] = [r for r, f in enumerate(flags) if f == 0]
+    pairs_dumped = dump_outputs(args.dump_outputs, N, cap, kL, dL, nL, kR, dR, nR, uR, depth) if (rank == 0 and args.dump_outputs) else None
     if rank != 0:
         rccl_probe_guarded(None, ex, rank, world, dev)
         return
@@ -457,6 +465,8 @@ def run_c2(args, rank, world, local_rank, dev, torch, dist, HS, N):
     out["parity_checksum"] = {k: v for k, v in parity.items() if k != "ok"}
     out["per_rank_pairs_per_s"] = {"min": round(min(per_rank), 1), "max": round(max(per_rank), 1)}
     out["timed_region_ms"] = round(elapsed * 1e3, 1)
+    if pairs_dumped is not None:
+        out["outputs_dumped"] = {"dir": args.dump_outputs, "pairs": pairs_dumped}
     if copy_peak is not None:         # both peaks beside each other: the vendor's 8 TB/s and this box's own device-to-device copy
         out["measured_copy_peak"] = copy_peak
         for rl in rls.values():
@@ -577,6 +587,45 @@ def parity_checksum(rank, args, N, cap, kL, dL, nL, kR, dR, nR, uR, depth):
         res["ok"] = res["pairs_checked"] > 0 and not res["pairs_failed"] and res["copies_identical"]
         res["expected_sha256"] = gp[0]["outputs_sha256"]
     return res
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, N, cap, kL, dL, nL, kR, dR, nR, uR, depth):
+    """--dump-outputs: the last timed step's outputs as a caller receives them — per pair the valid prefix (nL / nR entries) of every buffer,
+    concatenated over pairs in pair order.  Keypoints are the 6 fields of KP_DTYPE (x, y, size, angle, response, octave) in float64 (exact for all
+    of them), descriptors the 32 bytes per keypoint as float32; uRight and depth belong to the left keypoints.  The pairs written are the first
+    `pairs_dumped` of the step, a count fixed by the worst case (every frame at `cap` keypoints) so that the files stay within 64 MB."""
+    kb = N.KP_DTYPE.itemsize
+    B = int(nL.numel())
+    worst_per_pair = 2 * cap * (6 * 8 + 32 * 4) + cap * 2 * 4 + 2 * 8
+    P = max(1, min(B, DUMP_BUDGET_BYTES // worst_per_pair))
+    n_l, n_r = nL.cpu().numpy()[:P].astype(np.int64), nR.cpu().numpy()[:P].astype(np.int64)
+    if not ((n_l >= 0).all() and (n_l <= cap).all() and (n_r >= 0).all() and (n_r <= cap).all()):
+        raise RuntimeError("bench.py --dump-outputs: keypoint counts outside [0, %d]: %s %s" % (cap, n_l.tolist(), n_r.tolist()))
+    kpL = kL.view(B, cap * kb)[:P].cpu().numpy().view(N.KP_DTYPE).reshape(P, cap)
+    kpR = kR.view(B, cap * kb)[:P].cpu().numpy().view(N.KP_DTYPE).reshape(P, cap)
+    h_dL, h_dR = dL.view(B, cap, 32)[:P].cpu().numpy(), dR.view(B, cap, 32)[:P].cpu().numpy()
+    h_uR, h_dp = uR.view(B, cap)[:P].cpu().numpy(), depth.view(B, cap)[:P].cpu().numpy()
+
+    def kp_rows(kp, n):
+        rows = np.concatenate([kp[j, :n[j]] for j in range(P)])
+        return np.stack([rows[f].astype(np.float64) for f in N.KP_DTYPE.names], axis=1) if len(rows) else np.zeros((0, 6), np.float64)
+
+    arrays = {
+        "n_left": n_l.astype(np.float64), "n_right": n_r.astype(np.float64),
+        "keypoints_left": kp_rows(kpL, n_l), "keypoints_right": kp_rows(kpR, n_r),
+        "descriptors_left": np.concatenate([h_dL[j, :n_l[j]] for j in range(P)]).astype(np.float32).reshape(-1, 32),
+        "descriptors_right": np.concatenate([h_dR[j, :n_r[j]] for j in range(P)]).astype(np.float32).reshape(-1, 32),
+        "u_right": np.concatenate([h_uR[j, :n_l[j]] for j in range(P)]).astype(np.float32),
+        "depth": np.concatenate([h_dp[j, :n_l[j]] for j in range(P)]).astype(np.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return P
 
 
 def measured_copy_peak(ex, torch, dev, gib=2.0, reps=6):

@@ -14,8 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "cpp", "host_sanitize")
 EXE = os.path.join(DIR, "_build", "host_sanitize")
 
-# tests/cpp/host_sanitize/ is listed in .gpurunignore: the GPU pool refuses snapshots that hold a hipcc recipe with -fsanitize=address (GPU ASan is not
-# available there), and this CPU-only build never runs on a GPU box
+# a CPU-only build: its hipcc lines pass -fno-gpu-sanitize beside -fsanitize= (no device code is sanitized or even compiled), and it never runs on a GPU
 pytestmark = pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or not os.path.exists(os.path.join(DIR, "Makefile")),
                                 reason="needs hipcc (host-only compile) and tests/cpp/host_sanitize/ (not shipped to GPU boxes)")
 
