@@ -643,7 +643,7 @@ void run_stereo(hs_orb* h, const hs_keypoint* kL, const uint8_t* dL, const int32
     h->last_stereo_launches = 2;
     hs_launch_stereo(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->d_bd, h->d_strip_count, h->d_strip_list, s);
     mark(h, 5, s);
-    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, h->d_strip_count, sp.n_rows, s);
+    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
     mark(h, -1, s);
 }
 
@@ -658,7 +658,7 @@ void run_stereo_fused(hs_orb* h, const hs_keypoint* kL, const uint8_t* dL, const
     h->last_stereo_launches = 1;
     hs_launch_stereo_match_only(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->d_bd, h->d_strip_count, h->d_strip_list, s);
     mark(h, 5, s);
-    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, h->d_strip_count, sp.n_rows, s);
+    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
     mark(h, -1, s);
 }
 

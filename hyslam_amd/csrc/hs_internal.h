@@ -252,7 +252,7 @@ void hs_launch_stereo(const hs_keypoint* kpsL, const uint8_t* descL, const int32
                       int pairs, int cap, hs_stereo_params sp, float* uRight, float* depth,
                       int32_t* best_dist /*[pairs][cap] scratch*/,
                       int32_t* strip_count /*[pairs][strips]*/, void* strip_list /*[pairs][strips][cap] entries of HS_STRIP_ENTRY_BYTES*/, hipStream_t s);
-void hs_launch_stereo_median(const int32_t* nL, int pairs, int cap, float* uRight, float* depth, const int32_t* best_dist,
+void hs_launch_stereo_median(const int32_t* nL, int pairs, int cap, float* uRight, float* depth, const int32_t* best_dist, float th_high,
                              int32_t* strip_count /*zero on entry of hs_launch_stereo; zeroed again here*/, int n_rows, hipStream_t s);
 // the matcher alone, on strips that the describe launch of the stereo front end has already binned (HsStripFuse)
 void hs_launch_stereo_match_only(const hs_keypoint* kpsL, const uint8_t* descL, const int32_t* nL,

@@ -13,6 +13,10 @@
 // Second kernel: the reference's sort + median + 2.1*median rejection (:142-155) is a histogram of the
 // accepted integer distances, one workgroup per pair.
 // Documented deviation D2 (reference UB): rows outside [0,nRows) are ignored, no match => no filtering.
+// A left keypoint whose row has candidates but none closer than TH_HIGH keeps the reference's initial bestDist = TH_HIGH, bestIdxR = 0
+// (:92-93): with TH_LOW > TH_HIGH that passes the acceptance test and pairs it with right keypoint 0.  Its distance is stored as
+// SM_DIST_TH_HIGH, which sorts after every real distance (all of them are below TH_HIGH) in the median's histogram.
+#define SM_DIST_TH_HIGH 257
 #include "hs_internal.h"
 
 // Right keypoints binned into 32-row strips once per pair: a right keypoint lists itself in every strip its row band
@@ -151,13 +155,26 @@ __global__ __launch_bounds__(256) void k_stereo_match(const int32_t* __restrict_
     for (int t = 0; t < SM_KPW; t++) {
 #pragma unroll
         for (int s = 32; s > 0; s >>= 1) best[t] = min(best[t], (uint32_t)__shfl_xor((int)best[t], s, 64));
+        // nothing beat TH_HIGH: bestDist = TH_HIGH stands, and is accepted when TH_HIGH < (TH_HIGH + TH_LOW) / 2 — only if the row has any
+        // candidate at all (vRowIndices[vL] not empty, :84).  Wave-uniform and rare (TH_LOW > TH_HIGH), so the strip is scanned again here
+        // rather than tracked in the loop above.
+        bool rowHasCandidates = false;
+        if (best[t] == 0xFFFFFFFFu && sp.th_high < (sp.th_high + sp.th_low) / 2) {
+            bool hit = false;
+            for (int c = lane; c < nc[t]; c += 64) {
+                const uint32_t ib = cl[t][c].idx_band;
+                hit = hit || !(rowIn[t] < (int)((ib >> 16) & 0xFFu) || rowIn[t] > (int)(ib >> 24));
+            }
+            rowHasCandidates = __ballot(hit) != 0ull;
+        }
         const int iL = iL0 + t;
         if (iL >= cap) break;
         if (lane == 0) {
             float ur_out = -1.0f, depth_out = -1.0f; int bd = -1;
-            if (live[t] && best[t] != 0xFFFFFFFFu) {
-                const float bestDist = (float)(best[t] >> 16);
-                const int bestIdxR = best[t] & 0xFFFF;
+            if (live[t] && (best[t] != 0xFFFFFFFFu || rowHasCandidates)) {
+                const bool found = best[t] != 0xFFFFFFFFu;
+                const float bestDist = found ? (float)(best[t] >> 16) : th_high;                // :92-93 when nothing beat TH_HIGH
+                const int bestIdxR = found ? (int)(best[t] & 0xFFFF) : 0;
                 const float dist_threshold = (sp.th_high + sp.th_low) / 2;          // :41
                 if (bestDist < dist_threshold) {
                     float uR0 = kpsR[o + bestIdxR].x;
@@ -166,7 +183,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(const int32_t* __restrict_
                         if (disparity <= 0) { disparity = 0.01; uR0 = uL[t] - 0.01; }    // double constants, as in the reference (:130-131)
                         depth_out = mbf / disparity;
                         ur_out = uR0;
-                        bd = (int)(best[t] >> 16);
+                        bd = found ? (int)(best[t] >> 16) : SM_DIST_TH_HIGH;
                     }
                 }
             }
@@ -177,15 +194,15 @@ __global__ __launch_bounds__(256) void k_stereo_match(const int32_t* __restrict_
 
 __global__ __launch_bounds__(256) void k_stereo_median(const int32_t* __restrict__ nLs, int cap,
                                                        float* __restrict__ uRight, float* __restrict__ depth,
-                                                       const int32_t* __restrict__ best_dist,
+                                                       const int32_t* __restrict__ best_dist, float th_high,
                                                        int32_t* __restrict__ strip_count, int n_strips)
 {
-    __shared__ int hist[257];
+    __shared__ int hist[258];                                 // distances 0..256, then SM_DIST_TH_HIGH (a distance of TH_HIGH, above all others)
     __shared__ float s_th;
     const int pair = blockIdx.x;
     const int nL = min(nLs[pair], cap);
     const size_t o = (size_t)pair * cap;
-    for (int i = threadIdx.x; i < 257; i += 256) hist[i] = 0;
+    for (int i = threadIdx.x; i < 258; i += 256) hist[i] = 0;
     __syncthreads();
     // the distances stay in registers between the histogram and the rejection sweep (8 per thread cover cap <= 2048; more loop again below)
     constexpr int DPT = 8;
@@ -193,27 +210,27 @@ __global__ __launch_bounds__(256) void k_stereo_median(const int32_t* __restrict
 #pragma unroll
     for (int k = 0; k < DPT; k++) { const int i = threadIdx.x + 256 * k; dreg[k] = i < nL ? best_dist[o + i] : -1; }
 #pragma unroll
-    for (int k = 0; k < DPT; k++) if (dreg[k] >= 0) atomicAdd(&hist[min(dreg[k], 256)], 1);
+    for (int k = 0; k < DPT; k++) if (dreg[k] >= 0) atomicAdd(&hist[min(dreg[k], 257)], 1);
     for (int i = threadIdx.x + 256 * DPT; i < nL; i += 256) {
         int d = best_dist[o + i];
-        if (d >= 0) atomicAdd(&hist[min(d, 256)], 1);
+        if (d >= 0) atomicAdd(&hist[min(d, 257)], 1);
     }
     __syncthreads();
     if (threadIdx.x < 64) {
         // sorted (dist, iL) pairs: element total/2 carries the median distance (:142-144) = the first bin at which the running count exceeds
-        // total/2.  One wavefront: four bins per lane (+ bin 256), inclusive scan over the lanes, the crossing lane finishes inside its bins.
+        // total/2.  One wavefront: four bins per lane (+ bins 256, 257), inclusive scan over the lanes, the crossing lane finishes inside its bins.
         const int lane = threadIdx.x;
         const int b0 = hist[4 * lane], b1 = hist[4 * lane + 1], b2 = hist[4 * lane + 2], b3 = hist[4 * lane + 3];
         int incl = b0 + b1 + b2 + b3;
 #pragma unroll
         for (int s = 1; s < 64; s <<= 1) { const int v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
-        const int total = __shfl(incl, 63, 64) + hist[256];
+        const int below256 = __shfl(incl, 63, 64), total = below256 + hist[256] + hist[257];
         const int target = total / 2, excl = incl - (b0 + b1 + b2 + b3);
         int med = -1;
         if (excl <= target && incl > target) med = 4 * lane + (excl + b0 > target ? 0 : excl + b0 + b1 > target ? 1 : excl + b0 + b1 + b2 > target ? 2 : 3);
         const unsigned long long hit = __ballot(med >= 0);
         if (total == 0) { if (lane == 0) s_th = -1.f; }
-        else if (hit == 0) { if (lane == 0) s_th = 1.5f * 1.4f * 256.f; }            // the crossing is in bin 256
+        else if (hit == 0) { if (lane == 0) s_th = 1.5f * 1.4f * (below256 + hist[256] > target ? 256.f : th_high); }   // the crossing is in bin 256 or 257
         else if (med >= 0) s_th = 1.5f * 1.4f * (float)med;                          // exactly one lane
     }
     __syncthreads();
@@ -222,11 +239,11 @@ __global__ __launch_bounds__(256) void k_stereo_median(const int32_t* __restrict
 #pragma unroll
     for (int k = 0; k < DPT; k++) {
         const int i = threadIdx.x + 256 * k, d = dreg[k];
-        if (d >= 0 && !((float)d < th)) { uRight[o + i] = -1.f; depth[o + i] = -1.f; }      // :146-155
+        if (d >= 0 && (d == SM_DIST_TH_HIGH ? !(th_high < th) : !((float)d < th))) { uRight[o + i] = -1.f; depth[o + i] = -1.f; }      // :146-155
     }
     for (int i = threadIdx.x + 256 * DPT; i < nL; i += 256) {
         int d = best_dist[o + i];
-        if (d >= 0 && !((float)d < th)) { uRight[o + i] = -1.f; depth[o + i] = -1.f; }      // :146-155
+        if (d >= 0 && (d == SM_DIST_TH_HIGH ? !(th_high < th) : !((float)d < th))) { uRight[o + i] = -1.f; depth[o + i] = -1.f; }      // :146-155
     }
 }
 
@@ -248,11 +265,11 @@ void hs_launch_stereo(const hs_keypoint* kpsL, const uint8_t* descL, const int32
     }
 }
 
-void hs_launch_stereo_median(const int32_t* nL, int pairs, int cap, float* uRight, float* depth, const int32_t* best_dist,
+void hs_launch_stereo_median(const int32_t* nL, int pairs, int cap, float* uRight, float* depth, const int32_t* best_dist, float th_high,
                              int32_t* strip_count, int n_rows, hipStream_t s)
 {
     if (pairs <= 0 || cap <= 0) return;
-    hipLaunchKernelGGL(k_stereo_median, dim3(pairs), dim3(256), 0, s, nL, cap, uRight, depth, best_dist, strip_count, hs_stereo_strips(n_rows));
+    hipLaunchKernelGGL(k_stereo_median, dim3(pairs), dim3(256), 0, s, nL, cap, uRight, depth, best_dist, th_high, strip_count, hs_stereo_strips(n_rows));
 }
 
 // the matcher alone, on strips that the describe launch of the stereo front end has already binned (HsStripFuse)

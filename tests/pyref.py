@@ -275,3 +275,75 @@ def distribute_octtree(cands, min_x, max_x, min_y, max_y, n_target):
                 best = i
         out.append(best)
     return out
+
+
+_POPCOUNT8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.int64)
+
+
+def stereo_match(kpsL, descL, kpsR, descR, fx, mbf, n_rows, th_high, th_low, size_ref):
+    """Stereomatcher::computeStereoMatches (src/features/Stereomatcher.cpp:36-156) with deviation D2 (DESIGN.md §1).
+
+    Built without the reference's row table: each left keypoint takes a mask over ALL right keypoints (row band, octave, disparity
+    window), and its best match is the first index of the smallest distance among them.  Every quantity is fp32 as in the reference.
+    -> (uRight, depth, best_idx, best_dist); best_idx / best_dist are -1 where uRight is -1 before the median cut."""
+    f = np.float32
+    nL, nR = len(kpsL), len(kpsR)
+    uRight = np.full(nL, -1, f)
+    depth = np.full(nL, -1, f)
+    best_idx = np.full(nL, -1, np.int32)
+    best_dist = np.full(nL, -1, np.int32)
+    th_high, th_low, fx, mbf, size_ref = f(th_high), f(th_low), f(fx), f(mbf), f(size_ref)
+    accept = f(f(th_high + th_low) / f(2))
+    mb = f(mbf / fx)
+    max_d = f(mbf / mb)                                     # minZ = mb; minD = 0
+    yR = np.asarray(kpsR["y"], f)
+    xR = np.asarray(kpsR["x"], f)
+    octR = np.asarray(kpsR["octave"], np.int64)
+    band = (f(2) * np.asarray(kpsR["size"], f) / size_ref).astype(f)
+    top = np.ceil((yR + band).astype(f)).astype(np.int64)    # a right keypoint covers rows floor(y - r) .. ceil(y + r)
+    bottom = np.floor((yR - band).astype(f)).astype(np.int64)
+    dR = np.asarray(descR, np.uint8).reshape(nR, 32)
+    dL = np.asarray(descL, np.uint8).reshape(nL, 32)
+    accepted = []                                           # (distance, iL)
+    for iL in range(nL):
+        vL, uL, levelL = f(kpsL["y"][iL]), f(kpsL["x"][iL]), int(kpsL["octave"][iL])
+        if not vL >= 0:
+            continue
+        row = int(np.floor(vL))
+        if row >= n_rows:                                   # also every row when n_rows <= 0 (D2)
+            continue
+        in_row = (bottom <= row) & (row <= top)             # rows outside [0, n_rows) were never listed, but `row` is inside
+        if not in_row.any():
+            continue
+        min_u, max_u = f(uL - max_d), f(uL - f(0))
+        if max_u < 0:
+            continue
+        cand = np.nonzero(in_row & (octR >= levelL - 1) & (octR <= levelL + 1) & (xR >= min_u) & (xR <= max_u))[0]
+        best, best_r = th_high, 0                           # the reference's initial values, kept when nothing beats TH_HIGH
+        if len(cand):
+            dist = _POPCOUNT8[np.bitwise_xor(dR[cand], dL[iL])].sum(1)
+            k = int(np.argmin(dist))                        # the first of equal minima: the lowest iR
+            if f(dist[k]) < th_high:
+                best, best_r = f(dist[k]), int(cand[k])
+        if not best < accept:
+            continue
+        u_r = xR[best_r] if nR else f(0)
+        disparity = f(uL - u_r)
+        if not (disparity >= 0 and disparity < max_d):
+            continue
+        if disparity <= 0:
+            disparity = f(0.01)
+            u_r = f(np.float64(uL) - 0.01)
+        uRight[iL] = u_r
+        depth[iL] = f(mbf / disparity)
+        best_idx[iL] = best_r
+        best_dist[iL] = int(best)
+        accepted.append((best, iL))
+    if accepted:                                            # D2: no match, no cut
+        accepted.sort()
+        th_dist = f(f(1.5) * f(1.4)) * accepted[len(accepted) // 2][0]
+        for d, iL in accepted:
+            if not d < th_dist:
+                uRight[iL] = -1
+                depth[iL] = -1
+    return uRight, depth, best_idx, best_dist
