@@ -80,7 +80,7 @@ EXPORTS = [
     "hs_frame_grid", "hs_search_by_projection", "hs_search_by_projection_device", "hs_frame_publish", "hs_frame_find", "hs_frame_release", "hs_frame_info", "hs_frame_cache_clear", "hs_search_by_projection_frame", "hs_stereo_match_frames", "hs_search_by_projection_sim3", "hs_search_by_sim3", "hs_search_by_bow", "hs_search_by_bow_ex", "hs_search_by_bow_legacy", "hs_search_for_initialization",
     "hs_vocab_last_error", "hs_vocab_load", "hs_vocab_from_tree", "hs_vocab_save", "hs_vocab_destroy", "hs_vocab_get_tree", "hs_vocab_info",
     "hs_vocab_upload", "hs_vocab_dev_destroy", "hs_vocab_dev_groups", "hs_bow_transform_device", "hs_records_bow_match_device", "hs_bow_transform", "hs_hamming_knn2", "hs_hamming_knn2_device",
-    "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device",
+    "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device", "hs_landmark_best_descriptors", "hs_landmark_best_descriptors_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
     "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy",
     "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected",
@@ -201,6 +201,8 @@ def lib():
     L.hs_record_offsets.argtypes = [C.c_int, vp, vp, vp]
     L.hs_record_offsets.restype = None
     L.hs_records_knn2_device.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.hs_landmark_best_descriptors.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    L.hs_landmark_best_descriptors_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_host_alloc.argtypes = [sz, C.POINTER(vp)]
     L.hs_host_free.argtypes = [vp]
     L.hs_host_free.restype = None

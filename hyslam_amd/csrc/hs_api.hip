@@ -692,6 +692,8 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
 void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; }
 int hs_orb_device_of(const hs_orb* h) { return h ? h->device : 0; }
 hipStream_t hs_orb_stream_of(const hs_orb* h) { return h ? h->stream : nullptr; }
+// the handle's grow-only device scratch for another translation unit's host entry point (invalidates earlier pieces); nullptr on failure, the error set
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes) { return scratch_begin(h, bytes) == HS_OK ? h->d_scratch : nullptr; }
 
 extern "C" {
 

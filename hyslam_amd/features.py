@@ -293,6 +293,10 @@ class ORBExtractor:
         N.check(self._h, self._lib.hs_orb_extract_batch_device(self._h, d_imgs, batch, w, h, row_stride, image_stride,
                                                                d_kps, d_desc, d_n, cap, stream or None))
 
+    def landmark_best_descriptors_device(self, d_offsets, L, d_desc, d_best, d_median, stream=0):
+        """hs_landmark_best_descriptors_device: d_offsets int64 [L+1], d_desc uint8 [total][32] (16-byte aligned), d_best / d_median int32 [L]"""
+        N.check(self._h, self._lib.hs_landmark_best_descriptors_device(self._h, d_offsets, d_desc, L, d_best, d_median, stream or None))
+
     def stereo_match_batch_device(self, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, sp, d_uRight, d_depth, stream=0):
         N.check(self._h, self._lib.hs_stereo_match_batch_device(self._h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap,
                                                                 C.byref(sp), d_uRight, d_depth, stream or None))
@@ -546,6 +550,33 @@ class FeatureMatcher:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         N.check(ex._h, ex._lib.hs_hamming_knn2(ex._h, p(q), len(q), p(t), len(t), p(bi), p(bd), p(sd)))
         return bi, bd, sd
+
+
+    def ComputeDistinctiveDescriptors(self, descriptors=None, offsets=None, desc=None):
+        """MapPointDBEntry::_computeDistinctiveDescriptor_ (src/core/MapPointDB.cpp:128-175) for a batch of landmarks, in one call.
+        Either `descriptors`, a list of (N_i, 32) uint8 arrays (one per landmark, observations in the order the reference's std::map would
+        walk them), or CSR arrays `offsets` [L+1] and `desc` [offsets[L]][32].  Returns (best, median), int32 [L]: the index within the
+        landmark of its representative descriptor and that row's median Hamming distance; -1 / -1 for a landmark without descriptors."""
+        if descriptors is not None:
+            if offsets is not None or desc is not None:
+                raise ValueError("pass either descriptors or offsets + desc")
+            rows = [np.asarray(d, np.uint8).reshape(-1, 32) for d in descriptors]
+            off = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=off[1:])
+            d = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32), np.uint8))
+        else:
+            if offsets is None or desc is None:
+                raise ValueError("pass either descriptors or offsets + desc")
+            off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+            d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+            if len(off) < 1 or off[-1] > len(d):
+                raise ValueError("offsets[L] exceeds the number of descriptors")
+        L = len(off) - 1
+        best, median = np.zeros(L, np.int32), np.zeros(L, np.int32)
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_landmark_best_descriptors(ex._h, p(off), p(d), L, p(best), p(median)))
+        return best, median
 
 
 class ORBVocabulary:

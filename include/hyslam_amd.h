@@ -412,6 +412,21 @@ int  hs_hamming_knn2(hs_orb* h, const uint8_t* q, int nq, const uint8_t* t, int 
 int  hs_hamming_knn2_device(hs_orb* h, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                             int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist, void* stream);
 
+/* ---- landmark representative descriptors: MapPointDBEntry::_computeDistinctiveDescriptor_ (src/core/MapPointDB.cpp:128-175) for a batch.
+ * CSR input: landmark i has N_i = offsets[i+1] - offsets[i] observation descriptors desc[offsets[i] .. offsets[i+1])[32], offsets non-decreasing,
+ * offsets[0] >= 0.  Container order is the caller's ARRAY ORDER: the reference walks its std::map<KeyFrame*, FeatureDescriptor>, so pass each
+ * landmark's observations sorted by KeyFrame address, with the isBad() key frames left out (MapPointDB.cpp:131-135).  Per landmark: the N x N
+ * Hamming matrix (0 on the diagonal), every row's median = element (size_t)(0.5*(N-1)) of the ascending row, and the FIRST row with the strictly
+ * smallest median (MapPointDB.cpp:160-171).  best[i] = that row's index within the landmark (0 for N = 1), median[i] = its median; both -1 for
+ * N_i = 0, where the reference returns without changing the landmark.  Duplicate descriptors are allowed; N_i < 2^31, otherwise unbounded.
+ * Host pointers; synchronous. */
+int  hs_landmark_best_descriptors(hs_orb* h, const int64_t* offsets, const uint8_t* desc, int L, int32_t* best, int32_t* median);
+/* the same on device pointers (d_offsets [L+1] 8-byte aligned, d_desc 16-byte aligned, d_best / d_median [L]), enqueued on `stream` (NULL = the
+ * handle's own stream) without synchronising; the offsets are not checked on the host.  The handle's one-stream-at-a-time rule applies
+ * (see hs_orb_extract_batch_device).  Asynchronous. */
+int  hs_landmark_best_descriptors_device(hs_orb* h, const int64_t* d_offsets, const uint8_t* d_desc, int L, int32_t* d_best, int32_t* d_median,
+                                         void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the
