@@ -23,6 +23,11 @@
 #define GRID_COLS 64   // FRAME_GRID_COLS, src/core/Frame.h
 #define GRID_ROWS 48
 
+// (int) of an integral float (a floor / ceil / round result) as the reference's x86-64 build converts it (cvttss2si): NaN or a value outside the
+// int range gives INT_MIN.  C++ leaves that conversion undefined; a plain cast here is v_cvt_i32_f32, which clamps to INT_MAX and maps NaN to 0, so
+// a huge or infinite search radius would scan the whole grid where the reference finds nothing.
+__device__ __forceinline__ int cvt_i32(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u; }
+
 struct HsFrameDev {            // hs_frame_view with device pointers
     float Rcw[9], tcw[3], Ow[3];
     float fx, fy, cx, cy, mbf;
@@ -40,8 +45,8 @@ __global__ void k_frame_grid(HsFrameDev F, int8_t* __restrict__ cell)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F.n) return;
     const float invW = (float)GRID_COLS / (F.max_x - F.min_x), invH = (float)GRID_ROWS / (F.max_y - F.min_y);
-    int px = (int)roundf((F.kps[i].x - F.min_x) * invW);
-    int py = (int)roundf((F.kps[i].y - F.min_y) * invH);
+    int px = cvt_i32(roundf((F.kps[i].x - F.min_x) * invW));
+    int py = cvt_i32(roundf((F.kps[i].y - F.min_y) * invH));
     bool ok = !(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS);
     cell[2 * i] = ok ? (int8_t)px : (int8_t)-1;
     cell[2 * i + 1] = ok ? (int8_t)py : (int8_t)-1;
@@ -203,10 +208,10 @@ __global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const h
         const float r = __fdiv_rn(__fmul_rn(pp.th, sizePx), F.size_ref);
         // GetFeaturesInAreaNEW cell range (with its early returns)
         const float invW = (float)GRID_COLS / (F.max_x - F.min_x), invH = (float)GRID_ROWS / (F.max_y - F.min_y);
-        const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW)));
-        const int maxCX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW)));
-        const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH)));
-        const int maxCY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH)));
+        const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW))));
+        const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW))));
+        const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH))));
+        const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH))));
         const bool any = !(minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0);
         const float smin = __fmul_rn(pp.frac_smaller, sizePx), smax = __fmul_rn(pp.frac_larger, sizePx);
         const bool stereo = pp.use_stereo && F.sensor != 0;
@@ -498,10 +503,10 @@ __device__ __forceinline__ unsigned long long best_in_area(const HsFrameDev& F, 
 {
     const int lane = threadIdx.x & 63;
     const float invW = (float)GRID_COLS / (F.max_x - F.min_x), invH = (float)GRID_ROWS / (F.max_y - F.min_y);
-    const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW)));
-    const int maxCX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW)));
-    const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH)));
-    const int maxCY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH)));
+    const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW))));
+    const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW))));
+    const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH))));
+    const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH))));
     unsigned long long best = NO_KEY;
     if (minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0) return best;
     const unsigned long long* dl = reinterpret_cast<const unsigned long long*>(desc32);
@@ -829,10 +834,10 @@ __global__ __launch_bounds__(1024) void k_search_init(HsFrameDev F2, const uint8
     const float r = window;
     for (int i1 = 0; i1 < n1; i1++) {
         const float x = prev_xy[2 * i1], y = prev_xy[2 * i1 + 1];
-        const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F2.min_x), r), invW)));
-        const int maxCX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F2.min_x), r), invW)));
-        const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F2.min_y), r), invH)));
-        const int maxCY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F2.min_y), r), invH)));
+        const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F2.min_x), r), invW))));
+        const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F2.min_x), r), invW))));
+        const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F2.min_y), r), invH))));
+        const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F2.min_y), r), invH))));
         unsigned long long best = NO_KEY; int second = NO_DIST;
         if (!(minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0)) {
             const unsigned long long* d1 = reinterpret_cast<const unsigned long long*>(desc1 + (size_t)i1 * 32);

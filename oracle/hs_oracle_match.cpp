@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -23,6 +24,10 @@
 namespace {
 
 const int FRAME_GRID_COLS = 64, FRAME_GRID_ROWS = 48;   // Frame.h
+
+// (int) of an integral float (a floor / ceil / round result) the way hySLAM's x86-64 build converts it (cvttss2si): NaN or a value outside the
+// int range gives INT_MIN.  The reference's plain cast is undefined there; this states its observed behaviour with defined code.
+inline int cvt_i32(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MIN; }
 
 float ORBDistance(const uint8_t* D1, const uint8_t* D2)   // DescriptorDistance.cpp:9-25
 {
@@ -52,8 +57,8 @@ struct Frame {
         }
     }
     bool PosInGrid(const hso_keypoint& kp, int& posX, int& posY) const {                         // :459-469
-        posX = (int)std::round((kp.x - V.min_x) * mfGridElementWidthInv);
-        posY = (int)std::round((kp.y - V.min_y) * mfGridElementHeightInv);
+        posX = cvt_i32(std::round((kp.x - V.min_x) * mfGridElementWidthInv));
+        posY = cvt_i32(std::round((kp.y - V.min_y) * mfGridElementHeightInv));
         if (posX < 0 || posX >= FRAME_GRID_COLS || posY < 0 || posY >= FRAME_GRID_ROWS) return false;
         return true;
     }
@@ -94,13 +99,13 @@ struct Frame {
     // Frame::GetFeaturesInAreaNEW :416-457
     std::vector<size_t> GetFeaturesInAreaNEW(float x, float y, float r) const {
         std::vector<size_t> vIndices;
-        const int nMinCellX = std::max(0, (int)std::floor((x - V.min_x - r) * mfGridElementWidthInv));
+        const int nMinCellX = std::max(0, cvt_i32(std::floor((x - V.min_x - r) * mfGridElementWidthInv)));
         if (nMinCellX >= FRAME_GRID_COLS) return vIndices;
-        const int nMaxCellX = std::min((int)FRAME_GRID_COLS - 1, (int)std::ceil((x - V.min_x + r) * mfGridElementWidthInv));
+        const int nMaxCellX = std::min((int)FRAME_GRID_COLS - 1, cvt_i32(std::ceil((x - V.min_x + r) * mfGridElementWidthInv)));
         if (nMaxCellX < 0) return vIndices;
-        const int nMinCellY = std::max(0, (int)std::floor((y - V.min_y - r) * mfGridElementHeightInv));
+        const int nMinCellY = std::max(0, cvt_i32(std::floor((y - V.min_y - r) * mfGridElementHeightInv)));
         if (nMinCellY >= FRAME_GRID_ROWS) return vIndices;
-        const int nMaxCellY = std::min((int)FRAME_GRID_ROWS - 1, (int)std::ceil((y - V.min_y + r) * mfGridElementHeightInv));
+        const int nMaxCellY = std::min((int)FRAME_GRID_ROWS - 1, cvt_i32(std::ceil((y - V.min_y + r) * mfGridElementHeightInv)));
         if (nMaxCellY < 0) return vIndices;
         for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
             for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {

@@ -2,6 +2,8 @@
 // (all stages), stereo matching, frame grid, projection search, brute-force 2-NN, Sim3 matchers.  GPU sanitizers are not available on the pool,
 // so the CPU restatement — which every GPU parity test trusts — is the part that can be checked.
 // build: g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all oracle_sanitize.cpp ../../oracle/hs_oracle.cpp ../../oracle/hs_oracle_match.cpp -pthread
+#include <cmath>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +54,21 @@ int main()
     float R12[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t12[3] = { 0.01f, 0, 0 };
     std::vector<int32_t> m12(nL);
     const int n4 = hso_search_by_sim3(&F, lms.data(), &F, lms.data(), 1.0f, R12, t12, 7.5f, 100.f, m12.data());
-    printf("ORACLE SANITIZE OK %d %d keypoints, %d projection, %d sim3-projection, %d sim3 matches\n", nL, nR, nm, n3, n4);
+    // the grid-area queries where the reference's float -> int conversions leave the int range: NaN, infinite and huge keypoint
+    // coordinates, radii of 3e10, +inf and NaN (associated keypoint sizes, landmark sizes), an INT_MAX window.  float-cast-overflow flags a plain cast.
+    std::vector<hso_keypoint> kE(kL.begin(), kL.begin() + nL);
+    kE[0].x = NAN; kE[1].y = 1e10f; kE[2].x = -INFINITY; kE[3].size = INFINITY; kE[4].size = 3e10f * 31.f; kE[5].y = 3e9f;
+    hso_frame_view FE = F; FE.kps = kE.data();
+    for (int i = 0; i < nL; i++) { lms[i].assoc_kp = i % 5 == 0 ? 3 : (i % 5 == 1 ? 4 : -1); if (i % 7 == 0) lms[i].size = NAN; if (i % 11 == 0) lms[i].size = INFINITY; }
+    hso_frame_grid(&FE, cell.data());
+    const int n5 = hso_search_by_projection(&FE, lms.data(), nL, &pp, mi.data(), md.data());
+    std::fill(taken.begin(), taken.end(), 0);
+    const int n6 = hso_search_by_projection_sim3(&FE, Scw, lms.data(), nL, 4, 50.f, taken.data(), m3.data());
+    const int n7 = hso_search_by_sim3(&FE, lms.data(), &FE, lms.data(), 1.0f, R12, t12, 7.5f, 100.f, m12.data());
+    std::vector<float> prev(2 * nL); for (int i = 0; i < nL; i++) { prev[2 * i] = i % 9 == 0 ? NAN : kL[i].x; prev[2 * i + 1] = kL[i].y; }
+    std::vector<int32_t> m13(nL);
+    const int n8 = hso_search_for_initialization(kL.data(), dL.data(), nL, &FE, prev.data(), 2147483647, 50.f, 0.9f, m13.data());
+    printf("ORACLE SANITIZE OK %d %d keypoints, %d projection, %d sim3-projection, %d sim3 matches; out of range: %d %d %d %d\n", nL, nR, nm, n3, n4,
+           n5, n6, n7, n8);
     return 0;
 }

@@ -347,3 +347,223 @@ def stereo_match(kpsL, descL, kpsR, descR, fx, mbf, n_rows, th_high, th_low, siz
                 uRight[iL] = -1
                 depth[iL] = -1
     return uRight, depth, best_idx, best_dist
+
+
+# ---------------------------------------------------------------- grid-area queries and the loop-closing matchers
+# Frame.cc:137-153,416-469 (grid, GetFeaturesInAreaNEW), KeyFrame.cc:258-279,329-374 (landMarkSizePixels, GetFeaturesInArea, IsInImage),
+# Camera.cpp:116-153 (Project), FeatureMatcher.cc:628-934 (SearchByProjection(pKF, Scw, ...), SearchBySim3).
+# Float expressions are evaluated one float32 operation at a time; cv::Mat products (gemm, norm, dot) accumulate float inputs in double, left to
+# right, and round once.  Python floats are the doubles.
+GRID_COLS, GRID_ROWS = 64, 48
+INT_MIN = -(1 << 31)
+_f = np.float32
+
+
+def cvt_i32(v):
+    """(int) of an integral float as hySLAM's x86-64 build converts it (cvttss2si): NaN or a value outside the int range gives INT_MIN."""
+    v = np.asarray(v, np.float64)
+    ok = (v >= -2147483648.0) & (v < 2147483648.0)
+    return np.where(ok, np.where(ok, v, 0.0), float(INT_MIN)).astype(np.int64)
+
+
+def _round_away(a):
+    """std::round on float32: half away from zero (exact in double for every float)"""
+    a = np.asarray(a, np.float64)
+    return np.sign(a) * np.floor(np.abs(a) + 0.5)
+
+
+def _grid_inv(bounds):
+    minx, maxx, miny, maxy = (_f(b) for b in bounds)
+    with np.errstate(all="ignore"):
+        return minx, miny, _f(_f(GRID_COLS) / _f(maxx - minx)), _f(_f(GRID_ROWS) / _f(maxy - miny))
+
+
+def frame_grid(kps, bounds):
+    """Frame::PosInGrid of every keypoint -> (n, 2) int64, -1 outside the 64 x 48 grid"""
+    minx, miny, invW, invH = _grid_inv(bounds)
+    with np.errstate(all="ignore"):
+        px = cvt_i32(_round_away(((kps["x"].astype(_f) - minx).astype(_f) * invW).astype(_f)))
+        py = cvt_i32(_round_away(((kps["y"].astype(_f) - miny).astype(_f) * invH).astype(_f)))
+    ok = (px >= 0) & (px < GRID_COLS) & (py >= 0) & (py < GRID_ROWS)
+    return np.stack([np.where(ok, px, -1), np.where(ok, py, -1)], 1)
+
+
+class AreaGrid:
+    """mGrid[ix][iy] of a frame: cell lists in keypoint index order (AssignFeaturesToGrid pushes in index order)"""
+
+    def __init__(self, kps, bounds):
+        self.kps, self.bounds = kps, bounds
+        self.minx, self.miny, self.invW, self.invH = _grid_inv(bounds)
+        self.cells = frame_grid(kps, bounds)
+        inside = np.nonzero(self.cells[:, 0] >= 0)[0]
+        key = self.cells[inside, 0] * GRID_ROWS + self.cells[inside, 1]           # column-major: the cells of one column are contiguous
+        o = np.argsort(key, kind="stable")
+        self.items = inside[o]
+        self.start = np.searchsorted(key[o], np.arange(GRID_COLS * GRID_ROWS + 1))
+        self.kx, self.ky = kps["x"].astype(_f), kps["y"].astype(_f)
+
+    def features_in_area(self, x, y, r):
+        """GetFeaturesInArea(x, y, r): cells walked ix outer, iy inner; |dx| < r and |dy| < r, strict.  -> indices in that order"""
+        x, y, r = _f(x), _f(y), _f(r)
+        empty = np.zeros(0, np.int64)
+        with np.errstate(all="ignore"):
+            x0 = max(0, int(cvt_i32(np.floor(_f(_f(_f(x - self.minx) - r) * self.invW)))))
+            if x0 >= GRID_COLS:
+                return empty
+            x1 = min(GRID_COLS - 1, int(cvt_i32(np.ceil(_f(_f(_f(x - self.minx) + r) * self.invW)))))
+            if x1 < 0:
+                return empty
+            y0 = max(0, int(cvt_i32(np.floor(_f(_f(_f(y - self.miny) - r) * self.invH)))))
+            if y0 >= GRID_ROWS:
+                return empty
+            y1 = min(GRID_ROWS - 1, int(cvt_i32(np.ceil(_f(_f(_f(y - self.miny) + r) * self.invH)))))
+            if y1 < 0:
+                return empty
+            spans = [self.items[self.start[ix * GRID_ROWS + y0]:self.start[ix * GRID_ROWS + y1 + 1]] for ix in range(x0, x1 + 1)]
+            c = np.concatenate(spans) if spans else empty
+            keep = (np.abs((self.kx[c] - x).astype(_f)) < r) & (np.abs((self.ky[c] - y).astype(_f)) < r)
+        return c[keep]
+
+
+def _gemm_row(a, b, c, alpha=1.0):
+    """one row of a cv::Mat product alpha*A*B + C: float inputs, double accumulation, one rounding"""
+    s = float(a[0]) * float(b[0]) + float(a[1]) * float(b[1]) + float(a[2]) * float(b[2])
+    with np.errstate(all="ignore"):
+        return _f(alpha * s + float(c))
+
+
+def _norm(p):
+    return _f(np.sqrt(float(p[0]) * float(p[0]) + float(p[1]) * float(p[1]) + float(p[2]) * float(p[2])))
+
+
+def camera_project(fr, Pc):
+    """Camera::Project(Pc, uv) -> (u, v, valid); valid: z > 0 and min <= u <= max, min <= v <= max (both bounds inclusive)"""
+    z = _f(Pc[2])
+    with np.errstate(all="ignore"):
+        hx, hy, hz = _f(_f(Pc[0]) / z), _f(_f(Pc[1]) / z), _f(z / z)
+        u = _f(float(fr["fx"]) * float(hx) + 0.0 * float(hy) + float(fr["cx"]) * float(hz))
+        v = _f(0.0 * float(hx) + float(fr["fy"]) * float(hy) + float(fr["cy"]) * float(hz))
+    minx, maxx, miny, maxy = (_f(b) for b in fr["bounds"])
+    return u, v, bool(z > 0 and u >= minx and u <= maxx and v >= miny and v <= maxy)
+
+
+def project_landmark(fr, P):
+    """Frame / KeyFrame::ProjectLandMark with the frame's own pose: Pc = Rcw*P + tcw (one gemm), then Camera::Project"""
+    R, t = np.asarray(fr["Rcw"], _f).reshape(3, 3), np.asarray(fr["tcw"], _f).reshape(3)
+    return camera_project(fr, [_gemm_row(R[i], P, t[i]) for i in range(3)])
+
+
+def landmark_size_px(fr, lm):
+    """landMarkSizePixels: the associated keypoint's size, else the projected width of the landmark along world x (frame's own pose)"""
+    if lm["assoc_kp"] >= 0:
+        return _f(fr["kps"]["size"][lm["assoc_kp"]])
+    p = lm["pos"].astype(_f)
+    with np.errstate(all="ignore"):
+        half = _f(_f(lm["size"]) / _f(2))
+        ul = project_landmark(fr, [_f(p[0] - half), p[1], p[2]])[0]
+        ur = project_landmark(fr, [_f(p[0] + half), p[1], p[2]])[0]
+        return _f(ur - ul)
+
+
+def _hamming_to(desc, idx, d):
+    return np.unpackbits(desc[idx] ^ d[None, :], axis=1).sum(1)
+
+
+def search_by_projection_sim3(fr, Scw, lms, th, th_low, kp_matched, grid=None):
+    """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) -> (match_idx[L], kp_matched'[n], nmatches).  lms: min_dist / max_dist hold the
+    invariance range, skip = bad or already found; kp_matched = vpMatched[idx] != NULL.  Landmarks are taken in order; a match takes its keypoint."""
+    S = np.asarray(Scw, _f).reshape(4, 4)
+    g = grid or AreaGrid(fr["kps"], fr["bounds"])
+    size_ref = _f(fr.get("size_ref", 31.0))
+    taken = np.asarray(kp_matched, np.uint8).copy()
+    out = np.full(len(lms), -1, np.int32)
+    with np.errstate(all="ignore"):
+        scw = _f(np.sqrt(float(S[0, 0]) ** 2 + float(S[0, 1]) ** 2 + float(S[0, 2]) ** 2))       # sqrt(row0.dot(row0))
+        inv = _f(1.0 / float(scw))                                                               # Mat / s: every element times (float)(1/s)
+        Rcw = (S[:3, :3] * inv).astype(_f) + _f(0)
+        tcw = (S[:3, 3] * inv).astype(_f) + _f(0)
+        Ow = [_gemm_row(Rcw[:, i], tcw, 0.0, -1.0) for i in range(3)]                            # -Rcw.t()*tcw
+    minx, maxx, miny, maxy = (_f(b) for b in fr["bounds"])
+    fx, fy, cx, cy = _f(fr["fx"]), _f(fr["fy"]), _f(fr["cx"]), _f(fr["cy"])
+    n = 0
+    for i, lm in enumerate(lms):
+        if lm["skip"]:
+            continue
+        p = lm["pos"].astype(_f)
+        pc = [_gemm_row(Rcw[k], p, tcw[k]) for k in range(3)]
+        if pc[2] < 0.0:
+            continue
+        with np.errstate(all="ignore"):
+            invz = _f(_f(1) / pc[2])
+            u = _f(_f(fx * _f(pc[0] * invz)) + cx)
+            v = _f(_f(fy * _f(pc[1] * invz)) + cy)
+        if not (u >= minx and u < maxx and v >= miny and v < maxy):                               # KeyFrame::IsInImage: upper bounds strict
+            continue
+        with np.errstate(all="ignore"):
+            PO = [_f(p[k] - Ow[k]) for k in range(3)]
+        dist = _norm(PO)
+        if dist < lm["min_dist"] or dist > lm["max_dist"]:
+            continue
+        dot = float(PO[0]) * float(lm["normal"][0]) + float(PO[1]) * float(lm["normal"][1]) + float(PO[2]) * float(lm["normal"][2])
+        if dot < 0.5 * float(dist):
+            continue
+        with np.errstate(all="ignore"):
+            radius = _f(_f(_f(th) * landmark_size_px(fr, lm)) / size_ref)
+        c = g.features_in_area(u, v, radius)
+        c = c[taken[c] == 0]
+        if len(c) == 0:
+            continue
+        d = _hamming_to(fr["desc"], c, lm["desc"])
+        b = int(np.argmin(d))                                                                     # first minimum in candidate order
+        if d[b] <= th_low:
+            taken[c[b]] = 1
+            out[i] = c[b]
+            n += 1
+    return out, taken, n
+
+
+def search_by_sim3(fr1, lms1, fr2, lms2, s12, R12, t12, th, th_high, grids=None):
+    """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) -> (match12[n1], nFound).  lms1 / lms2: the landmark of each keypoint (skip = none,
+    bad or already matched; assoc_kp = its keypoint in the OTHER keyframe).  Both directions, then the agreement check."""
+    R12 = np.asarray(R12, _f).reshape(3, 3)
+    t12 = np.asarray(t12, _f).reshape(3)
+    g1, g2 = grids or (AreaGrid(fr1["kps"], fr1["bounds"]), AreaGrid(fr2["kps"], fr2["bounds"]))
+    with np.errstate(all="ignore"):
+        sR12 = (R12 * _f(float(s12))).astype(_f) + _f(0)                                         # s12*R12
+        sR21 = (R12.T * _f(1.0 / float(_f(s12)))).astype(_f) + _f(0)                              # (1.0/s12)*R12.t()
+        t21 = np.array([_gemm_row(sR21[k], t12, 0.0, -1.0) for k in range(3)], _f)                # -sR21*t12
+
+    def direction(fsrc, lms, fdst, gdst, sR, tt):
+        Rs, ts = np.asarray(fsrc["Rcw"], _f).reshape(3, 3), np.asarray(fsrc["tcw"], _f).reshape(3)
+        size_ref = _f(fdst.get("size_ref", 31.0))
+        out = np.full(len(lms), -1, np.int64)
+        for i, lm in enumerate(lms):
+            if lm["skip"]:
+                continue
+            p = lm["pos"].astype(_f)
+            ps = [_gemm_row(Rs[k], p, ts[k]) for k in range(3)]
+            pd = [_gemm_row(sR[k], ps, tt[k]) for k in range(3)]
+            u, v, ok = camera_project(fdst, pd)
+            if not ok:
+                continue
+            d3 = _norm(pd)
+            if d3 < lm["min_dist"] or d3 > lm["max_dist"]:
+                continue
+            with np.errstate(all="ignore"):
+                radius = _f(_f(_f(th) * landmark_size_px(fdst, lm)) / size_ref)
+            c = gdst.features_in_area(u, v, radius)
+            if len(c) == 0:
+                continue
+            d = _hamming_to(fdst["desc"], c, lm["desc"])
+            b = int(np.argmin(d))
+            if d[b] <= th_high:
+                out[i] = c[b]
+        return out
+
+    m1 = direction(fr1, lms1, fr2, g2, sR21, t21)
+    m2 = direction(fr2, lms2, fr1, g1, sR12, t12)
+    match12 = np.full(len(lms1), -1, np.int32)
+    for i1, i2 in enumerate(m1):
+        if i2 >= 0 and m2[i2] == i1:
+            match12[i1] = i2
+    return match12, int((match12 >= 0).sum())

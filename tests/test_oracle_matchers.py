@@ -71,10 +71,7 @@ def py_search_by_projection(fa, lms, pp):
     Ow = (-(Rcw.T @ tcw)).astype(f32)
     kps, desc, uR, obs = fa["kps"], fa["desc"], fa["uR"], fa["kp_lm_obs"]
     minx, maxx, miny, maxy = (f32(v) for v in fa["bounds"])
-    invW, invH = f32(64) / (maxx - minx), f32(48) / (maxy - miny)
-    gx = np.round((kps["x"] - minx) * invW).astype(int)            # numpy rounds half to even; coordinates never sit on .5 cells here
-    gy = np.round((kps["y"] - miny) * invH).astype(int)
-    ingrid = (gx >= 0) & (gx < 64) & (gy >= 0) & (gy < 48)
+    grid = pyref.AreaGrid(kps, fa["bounds"])                       # GetFeaturesInAreaNEW: the shared statement of the area rule
 
     def proj(P):
         Pc = (Rcw.astype(np.float64) @ P.astype(np.float64) + tcw.astype(np.float64)).astype(f32)
@@ -109,9 +106,9 @@ def py_search_by_projection(fa, lms, pp):
             half = f32(lm["size"] / f32(2))
             size = f32(proj(lm["pos"] + np.array([half, 0, 0], f32))[0] - proj(lm["pos"] - np.array([half, 0, 0], f32))[0])
         r = f32(f32(f32(pp.th) * size) / f32(31))
-        x0 = max(0, int(np.floor(f32(f32(f32(u - minx) - r) * invW)))); x1 = min(63, int(np.ceil(f32(f32(f32(u - minx) + r) * invW))))
-        y0 = max(0, int(np.floor(f32(f32(f32(v - miny) - r) * invH)))); y1 = min(47, int(np.ceil(f32(f32(f32(v - miny) + r) * invH))))
-        m = ingrid & (gx >= x0) & (gx <= x1) & (gy >= y0) & (gy <= y1) & (np.abs(kps["x"] - u) < r) & (np.abs(kps["y"] - v) < r)
+        area = grid.features_in_area(u, v, r)                      # candidate order: grid column, then row, then index
+        m = np.zeros(len(kps), bool)
+        m[area] = True
         if pp.use_prev_matched:
             m &= ~(obs > 0)
         if pp.use_reprojection:
@@ -125,10 +122,9 @@ def py_search_by_projection(fa, lms, pp):
         m &= (kps["size"] > f32(pp.frac_smaller) * size) & (kps["size"] < f32(pp.frac_larger) * size)
         if pp.use_stereo and fa["sensor"] != 0:
             m &= (np.abs(ur - uR) < r) & (uR > 0)
-        cand = np.nonzero(m)[0]
+        cand = area[m[area]]
         if len(cand) == 0:
             continue
-        cand = cand[np.lexsort((cand, gy[cand], gx[cand]))]           # grid column, then row, then insertion order
         d = np.unpackbits(desc[cand] ^ lm["desc"][None, :], axis=1).sum(1)
         b = int(np.argmin(d))
         second = np.sort(d)[1] if len(d) > 1 else np.finfo(np.float32).max
@@ -354,19 +350,14 @@ def test_search_for_initialization_against_python_restatement():
     # python restatement: sequential loop, brute-force window (grid cell range of the query + |dx|,|dy| < r), steal-only-if-better
     k2, d2 = fa["kps"], fa["desc"]
     f32 = np.float32
-    invW, invH = f32(64) / f32(320), f32(48) / f32(240)
-    gx = np.floor((k2["x"] * invW) + f32(0.5)).astype(int); gy = np.floor((k2["y"] * invH) + f32(0.5)).astype(int)
-    ingrid = (gx >= 0) & (gx < 64) & (gy >= 0) & (gy < 48)
+    grid = pyref.AreaGrid(k2, fa["bounds"])
     owner, odist = {}, {}
     r = f32(30)
     for i1 in range(len(k1)):
         x, y = prev[i1]
-        x0 = max(0, int(np.floor(f32(f32(x - r) * invW)))); x1 = min(63, int(np.ceil(f32(f32(x + r) * invW))))
-        y0 = max(0, int(np.floor(f32(f32(y - r) * invH)))); y1 = min(47, int(np.ceil(f32(f32(y + r) * invH))))
-        c = np.nonzero(ingrid & (gx >= x0) & (gx <= x1) & (gy >= y0) & (gy <= y1) & (np.abs(k2["x"] - x) < r) & (np.abs(k2["y"] - y) < r))[0]
+        c = grid.features_in_area(x, y, r)
         if len(c) == 0:
             continue
-        c = c[np.lexsort((c, gy[c], gx[c]))]
         d = np.unpackbits(d2[c] ^ d1[i1][None, :], axis=1).sum(1)
         ok = np.array([(i2 not in odist) or (dd < odist[i2]) for i2, dd in zip(c.tolist(), d.tolist())], bool)
         c, d = c[ok], d[ok]

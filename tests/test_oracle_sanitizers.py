@@ -10,7 +10,7 @@ def test_oracle_runs_clean_under_asan_ubsan():
     build = os.path.join(ROOT, "tests", "cpp", "_build")
     os.makedirs(build, exist_ok=True)
     exe = os.path.join(build, "oracle_sanitize")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-ffp-contract=off",
                            os.path.join(ROOT, "tests", "cpp", "oracle_sanitize.cpp"), os.path.join(ROOT, "oracle", "hs_oracle.cpp"),
                            os.path.join(ROOT, "oracle", "hs_oracle_match.cpp"), "-pthread", "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
