@@ -35,6 +35,20 @@ LM_DTYPE = np.dtype([("pos", "<f4", 3), ("size", "<f4"), ("min_dist", "<f4"), ("
                      ("assoc_kp", "<i4"), ("prev_angle", "<f4"), ("skip", "<i4"), ("desc", "u1", 32)])
 
 
+# hs_lm_entry_in / hs_lm_obs (include/hyslam_amd.h): the landmark entry update's per-landmark and per-observation records
+LM_ENTRY_DTYPE = np.dtype([("pos", "<f4", 3), ("ref_Ow", "<f4", 3)])
+LM_OBS_DTYPE = np.dtype([("Ow", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("u", "<f4"), ("v", "<f4"),
+                         ("kp_size", "<f4"), ("assoc_pos", "<f4", 3), ("assoc", "<i4")])
+HS_LM_SET_NORMAL_DEPTH, HS_LM_SET_DESC, HS_LM_SET_MEAN, HS_LM_SET_SIZE = 1, 2, 4, 8
+
+
+class LmEntryParams(C.Structure):
+    _fields_ = [("max_dist_factor", C.c_float), ("min_dist_factor", C.c_float)]
+
+    def __init__(self, max_dist_factor=2.0, min_dist_factor=0.5):
+        super().__init__(max_dist_factor, min_dist_factor)
+
+
 class FrameView(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float),
@@ -81,6 +95,7 @@ EXPORTS = [
     "hs_vocab_last_error", "hs_vocab_load", "hs_vocab_from_tree", "hs_vocab_save", "hs_vocab_destroy", "hs_vocab_get_tree", "hs_vocab_info",
     "hs_vocab_upload", "hs_vocab_dev_destroy", "hs_vocab_dev_groups", "hs_bow_transform_device", "hs_records_bow_match_device", "hs_bow_transform", "hs_hamming_knn2", "hs_hamming_knn2_device",
     "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device", "hs_landmark_best_descriptors", "hs_landmark_best_descriptors_device",
+    "hs_landmark_update_entries", "hs_landmark_update_entries_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
     "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy",
     "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected",
@@ -203,6 +218,8 @@ def lib():
     L.hs_records_knn2_device.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.hs_landmark_best_descriptors.argtypes = [vp, vp, vp, C.c_int, vp, vp]
     L.hs_landmark_best_descriptors_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    L.hs_landmark_update_entries.argtypes = [vp, vp, C.c_int] + [vp] * 13
+    L.hs_landmark_update_entries_device.argtypes = [vp, vp, C.c_int] + [vp] * 15 + [C.c_int, vp]
     L.hs_host_alloc.argtypes = [sz, C.POINTER(vp)]
     L.hs_host_free.argtypes = [vp]
     L.hs_host_free.restype = None

@@ -2,6 +2,7 @@
 //
 //   k_landmark_small   MapPointDBEntry::_computeDistinctiveDescriptor_, N <= 64       src/core/MapPointDB.cpp:128-175
 //   k_landmark_large   the same, N > 64
+//   k_landmark_entries _updateNormalAndDepth_, _updateMeanDistance_, _updateSize_ + the scatter into hs_landmark records   MapPointDB.cpp:230-310
 //
 // Input is CSR: landmark i owns descriptors desc[off[i] .. off[i+1]) in the caller's order (the reference walks a std::map<KeyFrame*, ...>).
 // Row r of the N x N Hamming matrix (diagonal 0 included) has the median element (size_t)(0.5*(N-1)) = (N-1)/2 of its ascending order; the
@@ -11,8 +12,16 @@
 //   large: one workgroup per landmark, one wavefront per row; the row is counted into a 257-bin LDS histogram and the k-th bin read off a
 //          wave prefix sum.  LDS does not grow with N, so N is bounded only by memory (and by best[]'s int32).
 // Both keep the reference's first-strict-minimum by minimising the key median << 32 | row.
+//
+// k_landmark_entries: one wavefront per landmark, lane j holds observation base + j of a 64-observation chunk.  The per-observation terms (the
+// double cv::norm, 1.0 / norm and its float products, featureSizeMetric) are independent and computed on all lanes; the three float sums depend on
+// their order, so they are added strictly left to right: every lane walks the chunk's terms in lane order (readlane) onto a running sum carried
+// from the previous chunk.  The rounding of every step is DESIGN.md D8.  It runs after the descriptor kernels on the same stream and reads their
+// best[] for the scatter.
 #include "hs_internal.h"
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 #define LM_SMALL 64            // largest N of the wave path
 #define LM_LARGE_WAVES 8       // wavefronts per workgroup of the large path
@@ -138,6 +147,108 @@ static void launch_landmark_best(const int64_t* d_off, const uint8_t* d_desc, in
     if (any_large) hipLaunchKernelGGL(k_landmark_large, dim3(std::min(L, 2048)), dim3(64 * LM_LARGE_WAVES), 0, s, d_off, d_desc, L, d_best, d_median);
 }
 
+// cv::norm of a continuous 3 x 1 CV_32F (D8): squares in double, summed left to right, double sqrt; the double is returned
+__device__ __forceinline__ double lm_norm3(float a, float b, float c)
+{
+    double s = __dmul_rn((double)a, (double)a);
+    s = __dadd_rn(s, __dmul_rn((double)b, (double)b));
+    s = __dadd_rn(s, __dmul_rn((double)c, (double)c));
+    return __dsqrt_rn(s);
+}
+
+// KeyFrame::featureSizeMetric(idx) (KeyFrame.cc:234-255) with Camera::Unproject (Camera.cpp:155-159)
+__device__ __forceinline__ float lm_feature_size(const hs_lm_obs& ob)
+{
+    if (!ob.assoc) return -1.0f;
+    const float z = __double2float_rn(lm_norm3(__fsub_rn(ob.assoc_pos[0], ob.Ow[0]), __fsub_rn(ob.assoc_pos[1], ob.Ow[1]),
+                                               __fsub_rn(ob.assoc_pos[2], ob.Ow[2])));
+    if (z < 0.0f) return -1.0f;                                          // as written (:243); a norm is never negative
+    const float r = __fdiv_rn(ob.kp_size, 2.0f);
+    const float zx = __fdiv_rn(z, ob.fx), zy = __fdiv_rn(z, ob.fy);
+    const float xl = __fmul_rn(__fsub_rn(__fsub_rn(ob.u, r), ob.cx), zx), yl = __fmul_rn(__fsub_rn(ob.v, ob.cy), zy);
+    const float xr = __fmul_rn(__fsub_rn(__fadd_rn(ob.u, r), ob.cx), zx), yr = __fmul_rn(__fsub_rn(ob.v, ob.cy), zy);
+    return __double2float_rn(lm_norm3(__fsub_rn(xr, xl), __fsub_rn(yr, yl), __fsub_rn(z, z)));
+}
+
+__device__ __forceinline__ float lm_lane(float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); }
+
+struct LmEntryArgs {
+    hs_lm_entry_params prm;
+    int L;
+    const hs_lm_entry_in* entries;
+    const int64_t* obs_off;
+    const hs_lm_obs* obs;
+    const int64_t* desc_off;
+    const uint8_t* desc;
+    const int32_t* best;                 // the descriptor kernels' output
+    float *normal, *min_dist, *max_dist, *mean_dist, *size;
+    int32_t* flags;
+    hs_landmark* lms;                    // scatter target, nullptr = none
+    const int32_t* lm_index;
+    int n_lms;
+};
+
+// four landmarks per 256-thread block, one per wavefront
+__global__ __launch_bounds__(256) void k_landmark_entries(LmEntryArgs a)
+{
+    const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (i >= a.L) return;
+    const int lane = threadIdx.x & 63;
+    const long long o = a.obs_off[i];
+    const long long n = __builtin_amdgcn_readfirstlane(a.obs_off[i + 1] - o);
+    const hs_lm_entry_in e = a.entries[i];
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f, mean = 0.0f, size = 0.0f;    // normal = cv::Mat::zeros (:244), mean_dist = 0.0, mean_size = 0.0
+    long long npos = 0;
+    for (long long base = 0; base < n; base += 64) {
+        const int cnt = (int)min(64LL, n - base);
+        float tx = 0.0f, ty = 0.0f, tz = 0.0f, dist = 0.0f, sz = -1.0f;
+        if (lane < cnt) {
+            const hs_lm_obs ob = a.obs[o + base + lane];
+            const float dx = __fsub_rn(e.pos[0], ob.Ow[0]), dy = __fsub_rn(e.pos[1], ob.Ow[1]), dz = __fsub_rn(e.pos[2], ob.Ow[2]);
+            const double s = lm_norm3(dx, dy, dz);
+            const float alpha = __double2float_rn(__ddiv_rn(1.0, s));   // normali / cv::norm(normali): alpha = 1.0/s, scaleAdd rounds it to float
+            tx = __fmul_rn(dx, alpha); ty = __fmul_rn(dy, alpha); tz = __fmul_rn(dz, alpha);
+            dist = __double2float_rn(s);                                // float this_dist = cv::norm(Pos_cam) (:282)
+            sz = lm_feature_size(ob);
+        }
+        for (int j = 0; j < cnt; j++) {                                 // observation order; never a tree
+            nx = __fadd_rn(lm_lane(tx, j), nx); ny = __fadd_rn(lm_lane(ty, j), ny); nz = __fadd_rn(lm_lane(tz, j), nz);
+            mean = __fadd_rn(mean, lm_lane(dist, j));
+            const float sj = lm_lane(sz, j);
+            if (sj > 0.0f) { size = __fadd_rn(size, sj); npos++; }      // (:298-301)
+        }
+    }
+    const bool has = n > 0;
+    // normal / n = convertTo(alpha = 1.0/n, beta = 0): fl(fl(x * (float)alpha) + 0.0f) (D8)
+    const float an = has ? __double2float_rn(__ddiv_rn(1.0, (double)(int)n)) : 0.0f;
+    nx = __fadd_rn(__fmul_rn(nx, an), 0.0f); ny = __fadd_rn(__fmul_rn(ny, an), 0.0f); nz = __fadd_rn(__fmul_rn(nz, an), 0.0f);
+    const float dref = __double2float_rn(lm_norm3(__fsub_rn(e.pos[0], e.ref_Ow[0]), __fsub_rn(e.pos[1], e.ref_Ow[1]), __fsub_rn(e.pos[2], e.ref_Ow[2])));
+    const float maxd = __fmul_rn(a.prm.max_dist_factor, dref), mind = __fmul_rn(a.prm.min_dist_factor, dref);
+    mean = __fdiv_rn(mean, (float)(int)n);
+    size = __fdiv_rn(size, (float)(int)npos);                           // 0.0f / 0.0f = NaN without a positive size (no early return)
+    const int best = a.best[i];
+    if (lane == 0) {
+        if (has) {
+            a.normal[3LL * i] = nx; a.normal[3LL * i + 1] = ny; a.normal[3LL * i + 2] = nz;
+            a.min_dist[i] = mind; a.max_dist[i] = maxd; a.mean_dist[i] = mean;
+        }
+        a.size[i] = size;
+        a.flags[i] = (has ? HS_LM_SET_NORMAL_DEPTH | HS_LM_SET_MEAN : 0) | (best >= 0 ? HS_LM_SET_DESC : 0) | HS_LM_SET_SIZE;
+    }
+    if (!a.lms) return;
+    const int t = a.lm_index[i];
+    if (t < 0 || t >= a.n_lms) return;
+    hs_landmark* r = a.lms + t;                                          // pos, assoc_kp, prev_angle, skip: never written
+    if (lane == 0) {
+        if (has) { r->normal[0] = nx; r->normal[1] = ny; r->normal[2] = nz; r->min_dist = mind; r->max_dist = maxd; }
+        r->size = size;
+    }
+    if (best >= 0 && lane < 8) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.desc + (a.desc_off[i] + best) * 32);
+        reinterpret_cast<uint32_t*>(r->desc)[lane] = src[lane];
+    }
+}
+
 // hs_api.hip (as for hs_comm.hip's entry points)
 void hs_set_error(hs_orb* h, const char* msg);
 int hs_orb_device_of(const hs_orb* h);
@@ -192,6 +303,102 @@ int hs_landmark_best_descriptors(hs_orb* h, const int64_t* offsets, const uint8_
     LM_TRY(h, hipMemcpyAsync(best, d_best, (size_t)L * 4, hipMemcpyDeviceToHost, s));
     LM_TRY(h, hipMemcpyAsync(median, d_med, (size_t)L * 4, hipMemcpyDeviceToHost, s));
     LM_TRY(h, hipStreamSynchronize(s));
+    return HS_OK;
+}
+
+static int lm_check_csr(hs_orb* h, const int64_t* off, int L, bool* any_large)
+{
+    for (int i = 0; i < L; i++) {
+        const int64_t n = off[i + 1] - off[i];
+        if (off[i] < 0 || n < 0 || n > INT32_MAX) return lm_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing, N < 2^31");
+        if (any_large) *any_large |= n > LM_SMALL;
+    }
+    return HS_OK;
+}
+
+int hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* params, int L, const hs_lm_entry_in* d_entries,
+                                      const int64_t* d_obs_offsets, const hs_lm_obs* d_obs, const int64_t* d_desc_offsets, const uint8_t* d_desc,
+                                      float* d_normal, float* d_min_dist, float* d_max_dist, float* d_mean_dist, float* d_size,
+                                      int32_t* d_best, int32_t* d_median, int32_t* d_flags,
+                                      hs_landmark* d_lms, const int32_t* d_lm_index, int n_lms, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!params || L < 0 || n_lms < 0 || (d_lms == nullptr) != (d_lm_index == nullptr)) return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    if (L == 0) return HS_OK;
+    if (!d_entries || !d_obs_offsets || !d_obs || !d_desc_offsets || !d_desc || !d_normal || !d_min_dist || !d_max_dist || !d_mean_dist || !d_size ||
+        !d_best || !d_median || !d_flags || ((uintptr_t)d_desc & 15) || ((uintptr_t)d_obs_offsets & 7) || ((uintptr_t)d_desc_offsets & 7) ||
+        ((uintptr_t)d_entries & 3) || ((uintptr_t)d_obs & 3) || ((uintptr_t)d_lms & 3) || ((uintptr_t)d_lm_index & 3))
+        return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    const hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    const LmEntryArgs a{*params, L, d_entries, d_obs_offsets, d_obs, d_desc_offsets, d_desc, d_best,
+                        d_normal, d_min_dist, d_max_dist, d_mean_dist, d_size, d_flags, d_lms, d_lm_index, n_lms};
+    launch_landmark_best(d_desc_offsets, d_desc, L, d_best, d_median, true, s);
+    hipLaunchKernelGGL(k_landmark_entries, dim3((L + 3) / 4), dim3(256), 0, s, a);
+    LM_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+int hs_landmark_update_entries(hs_orb* h, const hs_lm_entry_params* params, int L, const hs_lm_entry_in* entries,
+                               const int64_t* obs_offsets, const hs_lm_obs* obs, const int64_t* desc_offsets, const uint8_t* desc,
+                               float* out_normal, float* out_min_dist, float* out_max_dist, float* out_mean_dist, float* out_size,
+                               int32_t* out_best, int32_t* out_median, int32_t* out_flags)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!params || L < 0) return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    if (L == 0) return HS_OK;
+    if (!entries || !obs_offsets || !desc_offsets || !out_normal || !out_min_dist || !out_max_dist || !out_mean_dist || !out_size || !out_best ||
+        !out_median || !out_flags)
+        return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    bool any_large = false;
+    int st = lm_check_csr(h, obs_offsets, L, nullptr);
+    if (st == HS_OK) st = lm_check_csr(h, desc_offsets, L, &any_large);
+    if (st != HS_OK) return st;
+    const size_t n_obs = (size_t)obs_offsets[L], n_desc = (size_t)desc_offsets[L];
+    if ((n_obs > 0 && !obs) || (n_desc > 0 && !desc)) return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    const size_t b_ent = lm_pad((size_t)L * sizeof(hs_lm_entry_in)), b_off = lm_pad((size_t)(L + 1) * 8);
+    const size_t b_obs = lm_pad(std::max(n_obs, (size_t)1) * sizeof(hs_lm_obs)), b_desc = lm_pad(std::max(n_desc, (size_t)1) * 32);
+    const size_t b_f = lm_pad((size_t)L * 4);
+    uint8_t* base = hs_orb_scratch_of(h, b_ent + 2 * b_off + b_obs + b_desc + lm_pad((size_t)L * 12) + 7 * b_f);
+    if (!base) return HS_ERR_HIP;
+    uint8_t* q = base;
+    auto take = [&q](size_t b) { uint8_t* r = q; q += b; return r; };
+    hs_lm_entry_in* d_ent = reinterpret_cast<hs_lm_entry_in*>(take(b_ent));
+    int64_t* d_ooff = reinterpret_cast<int64_t*>(take(b_off));
+    int64_t* d_doff = reinterpret_cast<int64_t*>(take(b_off));
+    hs_lm_obs* d_obs = reinterpret_cast<hs_lm_obs*>(take(b_obs));
+    uint8_t* d_desc = take(b_desc);
+    float* d_normal = reinterpret_cast<float*>(take(lm_pad((size_t)L * 12)));
+    float* d_f[4];
+    for (float*& p : d_f) p = reinterpret_cast<float*>(take(b_f));       // min_dist, max_dist, mean_dist, size
+    int32_t* d_i[3];
+    for (int32_t*& p : d_i) p = reinterpret_cast<int32_t*>(take(b_f));   // best, median, flags
+    const hipStream_t s = hs_orb_stream_of(h);
+    LM_TRY(h, hipMemcpyAsync(d_ent, entries, (size_t)L * sizeof(hs_lm_entry_in), hipMemcpyHostToDevice, s));
+    LM_TRY(h, hipMemcpyAsync(d_ooff, obs_offsets, (size_t)(L + 1) * 8, hipMemcpyHostToDevice, s));
+    LM_TRY(h, hipMemcpyAsync(d_doff, desc_offsets, (size_t)(L + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_obs) LM_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs * sizeof(hs_lm_obs), hipMemcpyHostToDevice, s));
+    if (n_desc) LM_TRY(h, hipMemcpyAsync(d_desc, desc, n_desc * 32, hipMemcpyHostToDevice, s));
+    const LmEntryArgs a{*params, L, d_ent, d_ooff, d_obs, d_doff, d_desc, d_i[0],
+                        d_normal, d_f[0], d_f[1], d_f[2], d_f[3], d_i[2], nullptr, nullptr, 0};
+    launch_landmark_best(d_doff, d_desc, L, d_i[0], d_i[1], any_large, s);
+    hipLaunchKernelGGL(k_landmark_entries, dim3((L + 3) / 4), dim3(256), 0, s, a);
+    LM_TRY(h, hipGetLastError());
+    // the outputs the reference leaves unchanged for N = 0 come back through a host copy and are merged by flag
+    std::vector<float> nrm((size_t)L * 3), f3((size_t)L * 3);
+    LM_TRY(h, hipMemcpyAsync(nrm.data(), d_normal, (size_t)L * 12, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < 3; k++) LM_TRY(h, hipMemcpyAsync(f3.data() + (size_t)k * L, d_f[k], (size_t)L * 4, hipMemcpyDeviceToHost, s));
+    LM_TRY(h, hipMemcpyAsync(out_size, d_f[3], (size_t)L * 4, hipMemcpyDeviceToHost, s));
+    LM_TRY(h, hipMemcpyAsync(out_best, d_i[0], (size_t)L * 4, hipMemcpyDeviceToHost, s));
+    LM_TRY(h, hipMemcpyAsync(out_median, d_i[1], (size_t)L * 4, hipMemcpyDeviceToHost, s));
+    LM_TRY(h, hipMemcpyAsync(out_flags, d_i[2], (size_t)L * 4, hipMemcpyDeviceToHost, s));
+    LM_TRY(h, hipStreamSynchronize(s));
+    for (int i = 0; i < L; i++) {
+        if (!(out_flags[i] & HS_LM_SET_NORMAL_DEPTH)) continue;
+        std::memcpy(out_normal + 3 * (size_t)i, nrm.data() + 3 * (size_t)i, 12);
+        out_min_dist[i] = f3[i]; out_max_dist[i] = f3[(size_t)L + i]; out_mean_dist[i] = f3[2 * (size_t)L + i];
+    }
     return HS_OK;
 }
 

@@ -297,6 +297,16 @@ class ORBExtractor:
         """hs_landmark_best_descriptors_device: d_offsets int64 [L+1], d_desc uint8 [total][32] (16-byte aligned), d_best / d_median int32 [L]"""
         N.check(self._h, self._lib.hs_landmark_best_descriptors_device(self._h, d_offsets, d_desc, L, d_best, d_median, stream or None))
 
+    def landmark_update_entries_device(self, L, d_entries, d_obs_offsets, d_obs, d_desc_offsets, d_desc, d_normal, d_min_dist, d_max_dist,
+                                       d_mean_dist, d_size, d_best, d_median, d_flags, d_lms=None, d_lm_index=None, n_lms=0, params=None, stream=0):
+        """hs_landmark_update_entries_device: d_entries hs_lm_entry_in [L], d_obs_offsets / d_desc_offsets int64 [L+1], d_obs hs_lm_obs [..],
+        d_desc uint8 [..][32] (16-byte aligned); outputs d_normal float [L][3], d_min_dist .. d_size float [L], d_best / d_median / d_flags int32 [L].
+        d_lms (hs_landmark [n_lms]) + d_lm_index (int32 [L]): optional scatter target.  `params`: _native.LmEntryParams (default 2.0 / 0.5)."""
+        prm = params or N.LmEntryParams()
+        N.check(self._h, self._lib.hs_landmark_update_entries_device(self._h, C.byref(prm), L, d_entries, d_obs_offsets, d_obs, d_desc_offsets, d_desc,
+                                                                     d_normal, d_min_dist, d_max_dist, d_mean_dist, d_size, d_best, d_median, d_flags,
+                                                                     d_lms, d_lm_index, n_lms, stream or None))
+
     def stereo_match_batch_device(self, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, sp, d_uRight, d_depth, stream=0):
         N.check(self._h, self._lib.hs_stereo_match_batch_device(self._h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap,
                                                                 C.byref(sp), d_uRight, d_depth, stream or None))
@@ -577,6 +587,46 @@ class FeatureMatcher:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         N.check(ex._h, ex._lib.hs_landmark_best_descriptors(ex._h, p(off), p(d), L, p(best), p(median)))
         return best, median
+
+    @staticmethod
+    def _csr(parts, offsets, flat, dtype, row, what):
+        """a list of per-landmark arrays, or CSR `offsets` [L+1] + `flat` -> (int64 offsets, contiguous rows of shape `row`)"""
+        if parts is not None and offsets is None and flat is None:
+            rows = [np.ascontiguousarray(x, dtype).reshape((-1,) + row) for x in parts]
+            off = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=off[1:])
+            return off, np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0,) + row, dtype))
+        if parts is None and offsets is not None and flat is not None:
+            off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+            f = np.ascontiguousarray(flat, dtype).reshape((-1,) + row)
+            if len(off) < 1 or off[-1] > len(f):
+                raise ValueError("%s offsets[L] exceeds the number of rows" % what)
+            return off, f
+        raise ValueError("pass either the %s list or its offsets + flat array" % what)
+
+    def UpdateLandmarkEntries(self, entries, observations=None, descriptors=None, obs_offsets=None, obs=None, desc_offsets=None, desc=None,
+                              max_dist_factor=2.0, min_dist_factor=0.5):
+        """MapPointDBEntry::_updateEntry_ (src/core/MapPointDB.cpp:223-310) for a batch of landmarks, in one call: normal and depth range,
+        representative descriptor, mean distance and size.  `entries`: _native.LM_ENTRY_DTYPE [L] (world position, reference key frame's camera
+        centre).  Observations: either `observations`, a list of _native.LM_OBS_DTYPE arrays (one per landmark, in the reference's std::map order),
+        or CSR `obs_offsets` [L+1] + `obs`.  Descriptor sets (isBad() key frames left out): `descriptors`, a list of (N_i, 32) uint8 arrays, or
+        `desc_offsets` [L+1] + `desc`.  Returns a dict of normal (L, 3), min_dist, max_dist, mean_dist, size (float32 [L]), best, median, flags
+        (int32 [L]).  Where the reference leaves an output unchanged (flags without HS_LM_SET_NORMAL_DEPTH / HS_LM_SET_MEAN) it holds NaN here."""
+        ent = np.ascontiguousarray(entries, N.LM_ENTRY_DTYPE).reshape(-1)
+        ooff, ob = self._csr(observations, obs_offsets, obs, N.LM_OBS_DTYPE, (), "observation")
+        doff, d = self._csr(descriptors, desc_offsets, desc, np.uint8, (32,), "descriptor")
+        L = len(ent)
+        if len(ooff) != L + 1 or len(doff) != L + 1:
+            raise ValueError("entries, observations and descriptors must describe the same number of landmarks")
+        out = dict(normal=np.full((L, 3), np.nan, np.float32), min_dist=np.full(L, np.nan, np.float32), max_dist=np.full(L, np.nan, np.float32),
+                   mean_dist=np.full(L, np.nan, np.float32), size=np.full(L, np.nan, np.float32), best=np.zeros(L, np.int32),
+                   median=np.zeros(L, np.int32), flags=np.zeros(L, np.int32))
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        prm = N.LmEntryParams(max_dist_factor, min_dist_factor)
+        N.check(ex._h, ex._lib.hs_landmark_update_entries(ex._h, C.byref(prm), L, p(ent), p(ooff), p(ob), p(doff), p(d),
+                                                          *[p(out[k]) for k in ("normal", "min_dist", "max_dist", "mean_dist", "size", "best", "median", "flags")]))
+        return out
 
 
 class ORBVocabulary:

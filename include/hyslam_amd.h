@@ -427,6 +427,59 @@ int  hs_landmark_best_descriptors(hs_orb* h, const int64_t* offsets, const uint8
 int  hs_landmark_best_descriptors_device(hs_orb* h, const int64_t* d_offsets, const uint8_t* d_desc, int L, int32_t* d_best, int32_t* d_median,
                                          void* stream);
 
+/* ---- landmark entry update: MapPointDBEntry::_updateEntry_ (src/core/MapPointDB.cpp:223-228) for a batch — all four steps in one call:
+ * _updateNormalAndDepth_ (:230-265), _computeDistinctiveDescriptor_ (:128-175, exactly as hs_landmark_best_descriptors), _updateMeanDistance_
+ * (:267-289) and _updateSize_ (:291-310, with KeyFrame::featureSizeMetric, KeyFrame.cc:234-255, and Camera::Unproject, Camera.cpp:155-159).
+ * The float / double rounding of every step is DESIGN.md D8 (OpenCV 3.4's cv::norm, scaleAdd and convertTo restated). */
+typedef struct hs_lm_entry_in {
+    float pos[3];                      /* pMP_entry->GetWorldPos() (MapPointDB.cpp:238,272)                               */
+    float ref_Ow[3];                   /* pKF_ref->GetCameraCenter() (:255); pKF_ref need not be among the observations   */
+} hs_lm_entry_in;
+
+/* one entry of the landmark's `observations` map (KeyFrame*, keypoint index), in the map's order = sorted by KeyFrame address */
+typedef struct hs_lm_obs {
+    float Ow[3];                       /* pKF->GetCameraCenter() (:247,280; KeyFrame.cc:241)                              */
+    float fx, fy, cx, cy;              /* pKF's camera, Camera::Unproject (Camera.cpp:155-159)                            */
+    float u, v, kp_size;               /* views.keypt(idx).pt.x, .pt.y, .size (KeyFrame.cc:245-247)                       */
+    float assoc_pos[3];                /* hasAssociation(idx)->GetWorldPos() (KeyFrame.cc:235-240), normally = pos        */
+    int32_t assoc;                     /* 0: hasAssociation(idx) is NULL, featureSizeMetric returns -1 (KeyFrame.cc:236-238) */
+} hs_lm_obs;
+
+typedef struct hs_lm_entry_params {
+    float max_dist_factor;             /* max_dist_invariance_factor (2.0f, MapPointDB.h:99)                              */
+    float min_dist_factor;             /* min_dist_invariance_factor (0.5f, MapPointDB.h:100)                             */
+} hs_lm_entry_params;
+
+/* out_flags bits: which outputs the reference sets for that landmark */
+#define HS_LM_SET_NORMAL_DEPTH 1       /* normal, min_dist, max_dist: N > 0 (:241-242)                                    */
+#define HS_LM_SET_DESC         2       /* best / median >= 0: the descriptor set is not empty (:139-141)                  */
+#define HS_LM_SET_MEAN         4       /* mean distance: N > 0 (:275-276)                                                 */
+#define HS_LM_SET_SIZE         8       /* size: always (:291-310 does not return early; 0.0f / 0.0f = NaN without a positive size) */
+
+/* Landmark i has N_i = obs_offsets[i+1] - obs_offsets[i] observations obs[obs_offsets[i] ..) and, separately, the descriptor set
+ * desc[desc_offsets[i] ..)[32] of hs_landmark_best_descriptors (isBad() key frames left out, :131-135 — the observation loops keep them).
+ * Both CSRs: non-decreasing, offsets[0] >= 0, checked here.  Per landmark:
+ *   out_normal[i][3], out_min_dist[i], out_max_dist[i], out_mean_dist[i]   written only when N_i > 0 (left unchanged otherwise, as the reference)
+ *   out_size[i]                                                            always written (NaN when no observation has a positive size)
+ *   out_best[i], out_median[i]                                             as hs_landmark_best_descriptors (-1 / -1 for an empty descriptor set)
+ *   out_flags[i]                                                           HS_LM_SET_* bits
+ * Host pointers; synchronous. */
+int  hs_landmark_update_entries(hs_orb* h, const hs_lm_entry_params* params, int L, const hs_lm_entry_in* entries,
+                                const int64_t* obs_offsets, const hs_lm_obs* obs, const int64_t* desc_offsets, const uint8_t* desc,
+                                float* out_normal, float* out_min_dist, float* out_max_dist, float* out_mean_dist, float* out_size,
+                                int32_t* out_best, int32_t* out_median, int32_t* out_flags);
+/* The same on device pointers (offsets 8-byte aligned, d_desc 16-byte aligned, d_obs / d_entries 4-byte aligned; the offsets are not checked on
+ * the host), enqueued on `stream` (NULL = the handle's own stream) without synchronising.  Every output array is required and written as above.
+ * Scatter (optional, both or neither): for each i with 0 <= d_lm_index[i] < n_lms, record d_lms[d_lm_index[i]] receives normal, min_dist and
+ * max_dist when N_i > 0, size always, and desc = the chosen descriptor's 32 bytes when the descriptor set is not empty; pos, assoc_kp,
+ * prev_angle and skip are never written, nor is any record no index names.  Indices must be distinct.  The handle's one-stream-at-a-time rule
+ * applies (see hs_orb_extract_batch_device).  Asynchronous. */
+int  hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* params, int L, const hs_lm_entry_in* d_entries,
+                                       const int64_t* d_obs_offsets, const hs_lm_obs* d_obs, const int64_t* d_desc_offsets, const uint8_t* d_desc,
+                                       float* d_normal, float* d_min_dist, float* d_max_dist, float* d_mean_dist, float* d_size,
+                                       int32_t* d_best, int32_t* d_median, int32_t* d_flags,
+                                       hs_landmark* d_lms, const int32_t* d_lm_index, int n_lms, void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the

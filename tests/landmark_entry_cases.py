@@ -1,0 +1,136 @@
+"""Landmark entry updates (MapPointDB.cpp:223-310) with hand-derived answers, and a seeded random batch generator, shared by the CPU and GPU tests.
+Expected values are derived here without numpy's float32 arithmetic: Python doubles, rounded to float by struct (rf), where every double step
+is exact or is the double step the contract names."""
+import math
+import struct
+
+import numpy as np
+
+from landmark_cases import KNOWN, on_line
+
+f32 = np.float32
+OBS_DTYPE = np.dtype([("Ow", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("u", "<f4"), ("v", "<f4"),
+                      ("kp_size", "<f4"), ("assoc_pos", "<f4", 3), ("assoc", "<i4")])           # = hyslam_amd._native.LM_OBS_DTYPE
+ENTRY_DTYPE = np.dtype([("pos", "<f4", 3), ("ref_Ow", "<f4", 3)])                         # = hyslam_amd._native.LM_ENTRY_DTYPE
+TINY = 2.0 ** -149                                                                         # the smallest float subnormal
+
+
+def rf(x):
+    """double -> nearest float"""
+    return struct.unpack("<f", struct.pack("<f", x))[0]
+
+
+def obs(Ow, pos, u=10.0, v=20.0, kp_size=2.0, cam=(5.0, 5.0, 0.0, 0.0), assoc_pos=None, assoc=1):
+    o = np.zeros((), OBS_DTYPE)
+    o["Ow"] = Ow
+    o["fx"], o["fy"], o["cx"], o["cy"] = cam
+    o["u"], o["v"], o["kp_size"] = u, v, kp_size
+    o["assoc_pos"] = pos if assoc_pos is None else assoc_pos
+    o["assoc"] = assoc
+    return o
+
+
+def case(pos, ref_Ow, obs_list, descs, expect):
+    return dict(pos=np.array(pos, f32), ref_Ow=np.array(ref_Ow, f32), obs=np.array(obs_list, OBS_DTYPE).reshape(-1),
+                descs=np.asarray(descs, np.uint8).reshape(-1, 32), expect=expect)
+
+
+def _unit_terms(d):
+    s = math.sqrt(sum(x * x for x in d))                      # squares of small integers: exact; the double sqrt is cv::norm's
+    a = rf(1.0 / s)
+    return [rf(x * a) for x in d]                               # a float times a float is exact in double: one rounding, scaleAdd's product
+
+
+ONE = on_line([5])
+_a3, _b4 = rf(3e20), rf(4e20)
+_d_huge = rf(math.sqrt(_a3 * _a3 + _b4 * _b4))
+_t1, _t2 = _unit_terms((1, 1, 1)), _unit_terms((3, 4, 12))
+
+# name -> case; `expect` holds the outputs the case pins (None = left unchanged by the reference; NaN = any NaN)
+KNOWN_ENTRIES = {
+    # norm 5, normal (0.6, 0.8, 0) as floats, depth range 0.5 * 5 / 2 * 5, size: z = 5, z / fx = 1, edges 10 -+ 1 -> 2
+    "pythagoras": case((3, 4, 0), (0, 0, 0), [obs((0, 0, 0), (3, 4, 0))], ONE,
+                       dict(normal=[rf(0.6), rf(0.8), 0.0], min_dist=2.5, max_dist=10.0, mean_dist=5.0, size=2.0, best=0, median=0, flags=15)),
+    # n = 1: d_z = -0 - 0 = -0, and the scale-add's fl(-0 + 0) is already +0
+    "neg_zero_n1": case((3, 4, -0.0), (0, 0, 0), [obs((0, 0, 0), (3, 4, 0))], ONE, dict(normal=[rf(0.6), rf(0.8), 0.0])),
+    # n = 2: the z sum is -2^-149; times (float)0.5 it is the tie -2^-150, rounded to even -0; + 0.0f makes it +0
+    "neg_zero_n2": case((1, 0, 0), (0, 0, 0), [obs((0, 0, TINY), (1, 0, 0)), obs((0, 0, 0), (1, 0, 0))], ONE,
+                        dict(normal=[1.0, 0.0, 0.0], min_dist=0.5, max_dist=2.0, mean_dist=1.0)),
+    # 3e20: the squares overflow a float (inf) but not a double
+    "huge": case((3e20, 4e20, 0), (0, 0, 0), [obs((0, 0, 0), (3e20, 4e20, 0))], ONE,
+                 dict(min_dist=rf(0.5 * _d_huge), max_dist=rf(2.0 * _d_huge), mean_dist=_d_huge,
+                      normal=[rf(_a3 * rf(1.0 / math.sqrt(_a3 * _a3 + _b4 * _b4))), rf(_b4 * rf(1.0 / math.sqrt(_a3 * _a3 + _b4 * _b4))), 0.0])),
+    # the camera centre is the point: 1.0 / 0 = inf, 0 * inf = NaN; the size is 0 (not > 0), so n = 0 and 0.0f / 0.0f
+    "camera_at_point": case((1, 2, 3), (1, 2, 0), [obs((1, 2, 3), (1, 2, 3))], ONE,
+                            dict(normal=[math.nan] * 3, min_dist=1.5, max_dist=6.0, mean_dist=0.0, size=math.nan, flags=15)),
+    # no keypoint has an association: featureSizeMetric is -1 everywhere, the size NaN, the rest set
+    "no_association": case((3, 4, 0), (0, 0, 0), [obs((0, 0, 0), (3, 4, 0), assoc=0), obs((0, 0, 0), (3, 4, 0), assoc=0)], ONE,
+                           dict(normal=[rf(0.6), rf(0.8), 0.0], min_dist=2.5, max_dist=10.0, mean_dist=5.0, size=math.nan, flags=15)),
+    # N = 0: normal, depth and mean untouched, the size is still set (NaN); the descriptor set is not empty
+    "no_observations": case((3, 4, 0), (0, 0, 0), [], on_line([0, 200]),
+                            dict(normal=None, min_dist=None, max_dist=None, mean_dist=None, size=math.nan, best=0, median=0, flags=10)),
+    # nothing at all
+    "nothing": case((3, 4, 0), (0, 0, 0), [], np.zeros((0, 32), np.uint8),
+                    dict(normal=None, mean_dist=None, size=math.nan, best=-1, median=-1, flags=8)),
+    # the descriptor set is its own container (isBad() key frames left out): 3 descriptors against 2 observations
+    "descriptor_set_differs": case((3, 4, 0), (0, 0, 0), [obs((0, 0, 0), (3, 4, 0)), obs((3, 4, 5), (3, 4, 0))], KNOWN["n3"][0],
+                                   dict(best=1, median=10, mean_dist=5.0, flags=15)),
+    # the keypoint's landmark is another point, 20 away: z = 20, z / fx = 2, edges (u -+ 2) * 2 -> 8 (its own position would give 4)
+    "other_landmark": case((0, 0, 10), (0, 0, 0), [obs((0, 0, 0), (0, 0, 10), kp_size=4.0, cam=(10.0, 10.0, 0.0, 0.0), assoc_pos=(0, 0, 20))], ONE,
+                           dict(size=8.0, mean_dist=10.0, normal=[0.0, 0.0, 1.0])),
+    # (1, 1, 6): 6 * (float)(1/sqrt(38)) rounds differently from 6 * (1/sqrt(38)) in double
+    "alpha_rounding": case((1, 1, 6), (0, 0, 0), [obs((0, 0, 0), (1, 1, 6))], ONE, dict(normal=_unit_terms((1, 1, 6)))),
+    # n = 2: the second scale-add fl(fl(d * a) + acc) differs from a fused d * a + acc in x; / 2 is exact
+    "scale_add_two_roundings": case((3, 4, 12), (0, 0, 0), [obs((2, 3, 11), (3, 4, 12)), obs((0, 0, 0), (3, 4, 12))], ONE,
+                                    dict(normal=[rf(_t2[k] + _t1[k]) * 0.5 for k in range(3)])),
+    # distances 1e8, then eight of 1: in order each + 1 is lost (the float spacing at 1e8 is 8); halves would give 1e8 + 8
+    "sequential_mean": case((0, 0, 0), (1, 0, 0), [obs((1e8, 0, 0), (0, 0, 0))] + [obs((1, 0, 0), (0, 0, 0))] * 8, ONE,
+                            dict(mean_dist=rf(1e8 / 9.0), min_dist=0.5, max_dist=2.0)),
+}
+
+
+def random_batch(seed, L, n_max=40, big=(), special=True):
+    """-> (entries [L] ENTRY_DTYPE, obs_offsets int64 [L+1], obs OBS_DTYPE, descriptor lists).  Scales from 1e-3 to 1e20, N from 0 to n_max
+    (`big`: (landmark, N) overrides), and with `special`: camera centres on the point, signed zeros, keypoints without or with another landmark,
+    zero and huge keypoint sizes, reference key frames outside the observations."""
+    rng = np.random.default_rng(seed)
+    n = rng.integers(0, n_max + 1, L)
+    n[rng.random(L) < 0.03] = 0
+    for i, m in big:
+        n[i] = m
+    off = np.zeros(L + 1, np.int64)
+    np.cumsum(n, out=off[1:])
+    T = int(off[-1])
+    owner = np.repeat(np.arange(L), n)
+    scale = 10.0 ** rng.uniform(-3, 20, L)
+    ent = np.zeros(L, ENTRY_DTYPE)
+    ent["pos"] = (rng.normal(0, 1, (L, 3)) * scale[:, None]).astype(f32)
+    ent["ref_Ow"] = (ent["pos"] + rng.normal(0, 1, (L, 3)) * scale[:, None] * rng.uniform(0.1, 10, (L, 1))).astype(f32)
+    ob = np.zeros(T, OBS_DTYPE)
+    dist = scale[owner] * rng.uniform(0.05, 20, T)
+    dirs = rng.normal(0, 1, (T, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    ob["Ow"] = (ent["pos"][owner] - dirs * dist[:, None]).astype(f32)
+    ob["fx"] = rng.uniform(300, 1500, T)
+    ob["fy"] = ob["fx"] * rng.uniform(0.95, 1.05, T)
+    ob["cx"], ob["cy"] = rng.uniform(300, 700, T), rng.uniform(200, 500, T)
+    ob["u"], ob["v"] = rng.uniform(0, 1280, T), rng.uniform(0, 960, T)
+    ob["kp_size"] = (31.0 * 1.2 ** rng.integers(0, 8, T)).astype(f32)
+    ob["assoc_pos"] = ent["pos"][owner]
+    ob["assoc"] = 1
+    if special and T:
+        pick = lambda p: rng.random(T) < p
+        m = pick(0.002); ob["Ow"][m] = ent["pos"][owner[m]]                                   # camera centre on the point
+        m = pick(0.03); ob["assoc"][m] = 0                                                    # hasAssociation(idx) == NULL
+        m = pick(0.03); ob["assoc_pos"][m] = (ob["assoc_pos"][m] * rng.uniform(0.5, 2, (m.sum(), 1))).astype(f32)   # another landmark
+        m = pick(0.01); ob["kp_size"][m] = 0.0
+        m = pick(0.01); ob["kp_size"][m] = 3e30
+        m = pick(0.01); ob["Ow"][m, 2] = -0.0
+        m = pick(0.005); ob["Ow"][m] = rng.normal(0, 1e-3, (m.sum(), 3)).astype(f32)
+        z = rng.random(L) < 0.01; ent["pos"][z, 2] = -0.0
+    descs = []
+    for i in range(L):
+        k = int(rng.integers(0, n[i] + 2)) if n[i] < 64 else int(n[i]) - int(rng.integers(0, 3))   # a descriptor set of its own size
+        base = rng.integers(0, 256, (2, 32), dtype=np.uint8)
+        descs.append(base[rng.integers(0, 2, k)] ^ (rng.random((k, 32)) < 0.02).astype(np.uint8))
+    return ent, off, ob, descs

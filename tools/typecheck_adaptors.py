@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
@@ -76,7 +76,9 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    HYSLAM::HipStereomatcher sm(v, cam, f->getFeatureMatcherSettings()); sm.computeStereoMatches(); sm.getData(v);\n"
              "    HYSLAM::HipLandmarkDescriptors lmd; std::vector<std::vector<HYSLAM::FeatureDescriptor>> obs(1, d); std::vector<int> med;\n"
              "    const std::vector<int> best = lmd.bestDescriptors(obs, &med);\n"
-             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size();\n}\n")
+             "    HYSLAM::HipLandmarkEntries lme; std::vector<HYSLAM::HipLandmarkEntries::Input> lin(1); lin[0].descriptors = d;\n"
+             "    const std::vector<HYSLAM::HipLandmarkEntries::Result> ent = lme.updateEntries(lin); cv::Mat nrm = ent[0].normal.clone();\n"
+             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows;\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
           ["-I" + os.path.join(ROOT, "tests", "cpp", "thirdparty_stubs"), "-I" + host_dir, "-I" + os.path.join(ROOT, "include"), tu]
