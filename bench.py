@@ -13,7 +13,15 @@ Prints ONE JSON line on rank 0:
   value         whole-job stereo pairs per second (all ranks)
   roofline      the dominant kernel of the step: algorithmic bytes per launch / its HIP-event-measured duration vs 8 TB/s, the PMC traffic
                 and the VALU issue fraction of the same launch shape from the committed counter passes
-  cpu_baseline  the oracle ("port" of the reference's CPU path) timed on this box, N = 1 only: 2 threads (the reference's structure) and all cores
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full adds, after the timed steps, what takes
+runs or checks of its own (C2):
+  parity_checksum_ok   the timed loop's outputs hashed against the committed oracle checksums (every rank)
+  measured_copy_peak   the GPU's own device-to-device copy bandwidth, measured in the run, beside the vendor peak in every roofline block
+  latency_one_pair     one pair per call on a handle of its own (N = 1)
+  pcie_inclusive       host memory in -> host memory out through the pipelined ingest (N = 1)
+  call_site            the drop-in C++ classes timed at hySLAM's call sites (N = 1)
+  cpu_baseline         the oracle ("port" of the reference's CPU path) timed on this box, N = 1 only: 2 threads (the reference's structure) and all cores
+  rccl                 a throw-away RCCL communicator over all ranks (N > 1)
 Other BASELINE configurations: --config c3 | c4 | c5.
 """
 import argparse
@@ -48,7 +56,11 @@ def parse_args():
     ap.add_argument("--distinct", type=int, default=4,
                     help="distinct synthetic pairs generated per rank; the batch holds --pairs separate copies (pair i = distinct pair i %% distinct), "
                          "so no two frames of a step share an address")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of EACH of the two CPU baseline samples (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: after the timed steps, also run every secondary leg and check of the line (oracle parity checksums, measured copy peak, "
+                         "one-pair latency, host-fed rate, call-site adaptor timings, CPU baselines; the RCCL probe at N > 1).  Off by default: a plain "
+                         "run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: budget of EACH of the two CPU baseline samples (0 = skip)")
     ap.add_argument("--handles", type=int, default=1,
                     help="extractor handles per GPU; the pairs of a step are dealt over them and each runs on its own stream (the reference also "
                          "keeps separate extractor instances side by side, ImageProcessing.cpp:31-32).  Default 1: every kernel then has the GPU "
@@ -79,13 +91,13 @@ def parse_args():
     ap.add_argument("--cpu-frames", type=str, default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-workers", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--call-site", type=int, choices=[0, 1], default=1,
-                    help="c2, N = 1: also run tests/cpp/_build/bench_adaptor (when __graft_entry__.build() has made it) AFTER the timed loop and report, as "
+                    help="c2, N = 1, --full: also run tests/cpp/_build/bench_adaptor (when the build has made it) AFTER the timed loop and report, as "
                          "`call_site`, what hySLAM's own call sites would see through the drop-in C++ classes (ProcessStereoImage ms per pair, split gather / C ABI / scatter)")
     ap.add_argument("--copy-gib", type=float, default=2.0,
-                    help="c2: GiB of the device-to-device copy that measures this box's own HBM copy bandwidth (hipMemcpyAsync and a 16-byte-per-lane kernel), "
+                    help="c2, --full: GiB of the device-to-device copy that measures this box's own HBM copy bandwidth (hipMemcpyAsync and a 16-byte-per-lane kernel), "
                          "printed as roofline.peak_measured_copy beside the vendor peak (0 = skip)")
-    ap.add_argument("--latency-calls", type=int, default=400, help="c2, N = 1: calls of the one-pair-per-call latency leg after the timed loop (0 = skip)")
-    ap.add_argument("--pcie-seconds", type=float, default=1.5, help="c2, N = 1: budget of the host-fed (PCIe-inclusive) secondary measurement (0 = skip)")
+    ap.add_argument("--latency-calls", type=int, default=400, help="c2, N = 1, --full: calls of the one-pair-per-call latency leg after the timed loop (0 = skip)")
+    ap.add_argument("--pcie-seconds", type=float, default=1.5, help="c2, N = 1, --full: budget of the host-fed (PCIe-inclusive) secondary measurement (0 = skip)")
     ap.add_argument("--c4-split", type=int, choices=[0, 1], default=1,
                     help="c4: hs_orb_set_split(1) on both camera handles (level 0's FAST + quadtree on a second stream beside the pyramid); 0 = the library default")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
@@ -424,25 +436,28 @@ def run_c2(args, rank, world, local_rank, dev, torch, dist, HS, N):
     value = world * B * args.steps * args.inner_repeats / elapsed
     n_left = nL.cpu().numpy()
     n_match = int((depth.view(B, cap)[0] > 0).sum().item())
-    # what the timed loop left in EVERY pair's output buffers, hashed like tools/make_golden.py hashed the oracle's outputs for the same seeded pairs
-    # (tests/golden/bench_c2_seed1000.json: data only); every rank checks its own pairs, the line carries the conjunction
-    parity = parity_checksum(rank, args, N, cap, kL, dL, nL, kR, dR, nR, uR, depth)
+    # --full: what the timed loop left in EVERY pair's output buffers, hashed like tools/make_golden.py hashed the oracle's outputs for the same seeded
+    # pairs (tests/golden/bench_c2_seed1000.json: data only); every rank checks its own pairs, the line carries the conjunction
+    parity = parity_checksum(rank, args, N, cap, kL, dL, nL, kR, dR, nR, uR, depth) if args.full else None
     per_rank = [B * args.steps * args.inner_repeats / args.local_elapsed]
     if world > 1:
-        t = torch.tensor([1 if parity["ok"] else (0 if parity["ok"] is False else 2), int(per_rank[0]), parity["pairs_checked"]], dtype=torch.int64, device=dev)
+        flag = 2 if parity is None or parity["ok"] is None else (1 if parity["ok"] else 0)
+        t = torch.tensor([flag, int(per_rank[0]), parity["pairs_checked"] if parity else 0], dtype=torch.int64, device=dev)
         allt = torch.empty((world, 3), dtype=torch.int64, device=dev)
         dist.all_gather_into_tensor(allt.view(-1), t)
         flags, per_rank = allt[:, 0].tolist(), [float(v) for v in allt[:, 1].tolist()]
-        parity["pairs_checked_per_rank"] = allt[:, 2].tolist()
-        parity["ok"] = None if all(f == 2 for f in flags) else all(f != 0 for f in flags)
-        parity["ranks_checked"] = sum(f != 2 for f in flags)
-        parity["ranks_failed"] = [r for r, f in enumerate(flags) if f == 0]
+        if parity is not None:
+            parity["pairs_checked_per_rank"] = allt[:, 2].tolist()
+            parity["ok"] = None if all(f == 2 for f in flags) else all(f != 0 for f in flags)
+            parity["ranks_checked"] = sum(f != 2 for f in flags)
+            parity["ranks_failed"] = [r for r, f in enumerate(flags) if f == 0]
     pairs_dumped = dump_outputs(args.dump_outputs, N, cap, kL, dL, nL, kR, dR, nR, uR, depth) if (rank == 0 and args.dump_outputs) else None
     if rank != 0:
-        rccl_probe_guarded(None, ex, rank, world, dev)
+        if args.full:
+            rccl_probe_guarded(None, ex, rank, world, dev)
         return
-    copy_peak = measured_copy_peak(ex, torch, dev) if args.copy_gib > 0 else None
-    lat1 = one_pair_latency(HS, N, torch, dev, local_rank, pairs[0], sp) if (world == 1 and args.latency_calls > 0) else None
+    copy_peak = measured_copy_peak(ex, torch, dev) if (args.full and args.copy_gib > 0) else None
+    lat1 = one_pair_latency(HS, N, torch, dev, local_rank, pairs[0], sp) if (args.full and world == 1 and args.latency_calls > 0) else None
     px = pyramid_pixels(ex, W, H)
     per_stage, per_frame = algorithmic_bytes(px, NFEAT)
     frames_per_launch = 2 * max(b - a for a, b in parts) // lanes     # every launch sequence covers its own share of the pairs
@@ -460,9 +475,10 @@ def run_c2(args, rank, world, local_rank, dev, torch, dist, HS, N):
                                        "no address reuse inside a step, every step re-reads the same %d MB of frames" % (nd, B, nd, 2 * B * W * H // 1000000),
                      "sharding": "pairs sharded over ranks, no collective",
                      "keypoints_left_frame0": int(n_left[0]), "stereo_matches_frame0": n_match}
-    out["parity_checksum_ok"] = parity["ok"]
-    out["pairs_checked"] = parity["pairs_checked"]          # of rank 0's `pairs_per_pass` (N > 1: parity_checksum.pairs_checked_per_rank)
-    out["parity_checksum"] = {k: v for k, v in parity.items() if k != "ok"}
+    if parity is not None:
+        out["parity_checksum_ok"] = parity["ok"]
+        out["pairs_checked"] = parity["pairs_checked"]          # of rank 0's `pairs_per_pass` (N > 1: parity_checksum.pairs_checked_per_rank)
+        out["parity_checksum"] = {k: v for k, v in parity.items() if k != "ok"}
     out["per_rank_pairs_per_s"] = {"min": round(min(per_rank), 1), "max": round(max(per_rank), 1)}
     out["timed_region_ms"] = round(elapsed * 1e3, 1)
     if pairs_dumped is not None:
@@ -493,22 +509,22 @@ def run_c2(args, rank, world, local_rank, dev, torch, dist, HS, N):
         out["end_to_end"]["peak_measured_copy"] = copy_peak["GBps"]
         out["end_to_end"]["frac_of_measured"] = round(value / world * pair_bytes / 1e9 / copy_peak["GBps"], 5)
         out["end_to_end"]["frac_of_measured_on_moved_bytes"] = round(value / world * moved_pair / 1e9 / copy_peak["GBps"], 5)
-    if world == 1 and args.pcie_seconds > 0:
+    if args.full and world == 1 and args.pcie_seconds > 0:
         out["pcie_inclusive"] = pcie_inclusive(HS, exs[0], sp, pairs, min(B, 16), args.pcie_seconds)      # 16 pairs per ticket (two tickets in flight), whatever the step's batch
-    if world == 1 and args.call_site:
+    if args.full and world == 1 and args.call_site:
         cs = call_site()
         if cs is not None:
             out["call_site"] = cs
-    if world == 1 and args.cpu_seconds > 0 and not under_profiler():
+    if args.full and world == 1 and args.cpu_seconds > 0 and not under_profiler():
         out["cpu_baseline"] = cpu_baseline(pairs, args.cpu_seconds)
-    if world > 1:
+    if args.full and world > 1:
         rccl_probe_guarded(out, ex, rank, world, dev)      # prints the line (with the `rccl` block) itself
         return
     print(json.dumps(out), flush=True)
 
 
 def rccl_probe_guarded(out, ex, rank, world, dev, timeout_s=60.0):
-    """N > 1, AFTER everything else: evidence for the first multi-GPU run — a throw-away RCCL communicator over all ranks through the C ABI (hs_comm_*;
+    """N > 1, --full, AFTER everything else: evidence for the first multi-GPU run — a throw-away RCCL communicator over all ranks through the C ABI (hs_comm_*;
     C2 itself needs no collective), reporting what RCCL says about it (ncclCommCount per rank, version) and that a 16-byte all-gather moved bytes.
     The measurement is complete when this runs, so it must not be able to take the line down: ncclCommInitRank has never run with more than one rank
     anywhere (no multi-GPU node was available to this build), and if it blocks, a watchdog prints the line with an error note and ends every rank with

@@ -1,4 +1,5 @@
-"""bench.py --dump-outputs (the last timed step's outputs as .npy files) and the meaning of --steps / ms_per_step."""
+"""bench.py --dump-outputs (the last timed step's outputs as .npy files), the meaning of --steps / ms_per_step, and what a plain run (no --full)
+leaves out."""
 import json
 import os
 import subprocess
@@ -67,6 +68,9 @@ def test_steps_are_single_passes_by_default_and_dump_is_c2_only(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
     a = bench.parse_args()
     assert a.steps == 7 and a.min_timed_ms == 0 and a.dump_outputs == ""
+    assert a.full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse_args().full is True
     monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "c3", "--dump-outputs", "x"])
     with pytest.raises(SystemExit):
         bench.parse_args()
@@ -75,7 +79,7 @@ def test_steps_are_single_passes_by_default_and_dump_is_c2_only(monkeypatch):
 @pytest.mark.gpu
 def test_bench_dumps_the_last_step(gpu, tmp_path):
     out = tmp_path / "dump"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs", "4", "--cpu-seconds", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs", "4", "--full", "--cpu-seconds", "0",
                         "--pcie-seconds", "0", "--call-site", "0", "--latency-calls", "0", "--copy-gib", "0", "--dump-outputs", str(out)],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -88,3 +92,23 @@ def test_bench_dumps_the_last_step(gpu, tmp_path):
     assert np.load(out / "keypoints_left.npy").shape == (int(n_l.sum()), 6) and np.load(out / "descriptors_right.npy").shape == (int(n_r.sum()), 32)
     assert np.load(out / "depth.npy").shape == (int(n_l.sum()),) and (np.load(out / "depth.npy") > 0).sum() > 100
     assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+
+
+# what --full adds to the C2 line; a plain run carries none of it
+FULL_ONLY = ("parity_checksum_ok", "pairs_checked", "parity_checksum", "measured_copy_peak", "latency_one_pair_ms", "latency_one_pair", "pcie_inclusive",
+             "call_site", "cpu_baseline", "rccl")
+
+
+@pytest.mark.gpu
+def test_plain_run_does_only_the_headline(gpu):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "2"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["value"] > 0 and line["steps"] == 3 and line["warmup"] == 1 and line["roofline"]["frac"] > 0
+    assert not [k for k in FULL_ONLY if k in line]
+    assert "peak_measured_copy" not in line["roofline"] and "peak_measured_copy" not in line["end_to_end"]

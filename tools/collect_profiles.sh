@@ -6,7 +6,7 @@ OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT      # a tag used before must not leave its files behind (summarize_profiles.py takes the first match)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python3 -c "import json; from hyslam_amd._native import source_digests; json.dump(source_digests(), open('$OUT/source_digests.json', 'w'))"
-timeout 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 20 --warmup 3 --cpu-seconds 0 --pcie-seconds 0 --call-site 0 --latency-calls 0 --copy-gib 0 --min-timed-ms 0 > $OUT/bench_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 tools/pmc_traffic.py run > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 tools/pmc_traffic.py run > /dev/null 2>&1
@@ -18,7 +18,7 @@ timeout 300 python3 bench.py --config c3 --steps 20 --warmup 3 --min-timed-ms 20
 timeout 300 python3 bench.py --config c4 --steps 30 --warmup 3 --min-timed-ms 2000 > $OUT/c4.json 2>/dev/null
 timeout 300 python3 bench.py --config c5 --steps 50 --warmup 5 --min-timed-ms 2000 > $OUT/c5.json 2>/dev/null
 timeout 300 python3 bench.py --config c5 --c5-match bow --steps 50 --warmup 5 --min-timed-ms 2000 > $OUT/c5_bow.json 2>/dev/null
-Q="--cpu-seconds 0 --pcie-seconds 0 --call-site 0 --copy-gib 0 --min-timed-ms 2000"      # the sweeps: 2 s of timed region each, no secondary legs
+Q="--full --cpu-seconds 0 --pcie-seconds 0 --call-site 0 --copy-gib 0 --min-timed-ms 2000"      # the sweeps: 2 s of timed region each, parity and one-pair latency but no other secondary legs
 for b in 1 4 16 128; do timeout 300 python3 bench.py --pairs $b --steps 30 --warmup 3 $Q 2>/dev/null | tail -1 > $OUT/bench_pairs$b.json; done
 for hn in 2 3; do timeout 300 python3 bench.py --handles $hn --steps 30 --warmup 3 $Q 2>/dev/null | tail -1 > $OUT/bench_handles$hn.json; done
 timeout 300 python3 bench.py --density 3 --steps 100 $Q 2>/dev/null | tail -1 > $OUT/bench_density3.json

@@ -3,7 +3,7 @@
 # the level-A passes (TBX * 1.2 + halo) / 256.  Narrower tiles lower BOTH utilisations by a known amount; the slope of time against utilisation says what full
 # lanes would be worth.  GPU box: bash tools/experiments/r6_pyramid_tbx.sh
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-Q="--cpu-seconds 0 --pcie-seconds 0 --call-site 0 --copy-gib 0 --latency-calls 0 --min-timed-ms 1500 --steps 20"
+Q="--full --cpu-seconds 0 --pcie-seconds 0 --call-site 0 --copy-gib 0 --latency-calls 0 --min-timed-ms 1500 --steps 20"
 for t in 0 208 192 176 160 144 128; do
   HS_PYRAMID_TBX_MAX=$t timeout -k 10 200 python3 bench.py $Q 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('HS_PYRAMID_TBX_MAX=$t: pyramid %.4f ms per 128 frames, %.0f pairs/s, parity %s' % (d['stage_ms_per_step']['pyramid'], d['value'], d['parity_checksum_ok']))"
 done

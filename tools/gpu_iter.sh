@@ -8,8 +8,8 @@ TESTS=${@:-tests/test_gpu_parity.py tests/test_gpu_configs.py tests/test_gpu_fuz
 timeout 900 python3 -m pytest $TESTS -m gpu -q -x > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log
 tail -4 $OUT/pytest.log
 grep -q "pytest rc=0" $OUT/pytest.log || exit 1
-timeout 300 python3 bench.py --cpu-seconds 0 --call-site 0 --pcie-seconds 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
-timeout 300 python3 bench.py --cpu-seconds 0 --call-site 0 --pcie-seconds 0 --pairs 1 > $OUT/bench_p1.json 2>/dev/null
+timeout 300 python3 bench.py --full --cpu-seconds 0 --call-site 0 --pcie-seconds 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout 300 python3 bench.py --full --cpu-seconds 0 --call-site 0 --pcie-seconds 0 --pairs 1 > $OUT/bench_p1.json 2>/dev/null
 bash tools/sq_kernel_counters.sh --call-site 0 --pcie-seconds 0 --min-timed-ms 0 > $OUT/sq.txt 2>&1; cat $OUT/sq.txt
 python3 - <<PY
 import json
