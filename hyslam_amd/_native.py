@@ -96,6 +96,8 @@ EXPORTS = [
     "hs_vocab_upload", "hs_vocab_dev_destroy", "hs_vocab_dev_groups", "hs_bow_transform_device", "hs_records_bow_match_device", "hs_bow_transform", "hs_hamming_knn2", "hs_hamming_knn2_device",
     "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device", "hs_landmark_best_descriptors", "hs_landmark_best_descriptors_device",
     "hs_landmark_update_entries", "hs_landmark_update_entries_device",
+    "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
+    "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
     "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy",
     "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected",
@@ -220,6 +222,20 @@ def lib():
     L.hs_landmark_best_descriptors_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_landmark_update_entries.argtypes = [vp, vp, C.c_int] + [vp] * 13
     L.hs_landmark_update_entries_device.argtypes = [vp, vp, C.c_int] + [vp] * 15 + [C.c_int, vp]
+    L.hs_bow_vector.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    L.hs_bow_vector_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.hs_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.hs_place_db_destroy.argtypes = [vp]
+    L.hs_place_db_destroy.restype = None
+    L.hs_place_db_add.argtypes = [vp, C.c_uint64, vp, vp, C.c_int, vp]
+    L.hs_place_db_add_device.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_int, vp, vp]
+    L.hs_place_db_erase.argtypes = [vp, i32]
+    L.hs_place_db_clear.argtypes = [vp]
+    L.hs_place_db_size.argtypes = [vp, vp, vp]
+    L.hs_place_query_reloc.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_place_query_loop.argtypes = [vp, vp, vp, C.c_int, vp, f32, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_place_query_reloc_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.hs_place_query_loop_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, f32, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.hs_host_alloc.argtypes = [sz, C.POINTER(vp)]
     L.hs_host_free.argtypes = [vp]
     L.hs_host_free.restype = None

@@ -3,6 +3,7 @@
 //   hs_vocab_upload              the flat vocabulary tree (hs_vocab_tree) copied to HBM once, plus the dense rank ("group") of every node at
 //                                the feature-vector level L - levelsup (Frame.cc:472-479 calls transform(..., levelsup = 4))
 //   hs_bow_transform_device      DBoW2 transform of descriptors that already live in HBM (the extractor's outputs)
+//   hs_bow_vector(_device)       the L1-normalised BoW vector (Frame::mBowVec) from that transform's (word, weight) arrays
 //   hs_records_bow_match_device  BASELINE config 5 "cross-camera BoW match": for every gathered frame record p != rank the matching core of
 //                                SearchByBoW / _SearchByBoW_ (src/features/FeatureMatcher.cc:216-345, BestMatchBoWCriterion MatchCriteria.cpp:601-635,
 //                                RotationConsistencyBoW :679-726) between record `rank` (side 1) and record p (side 2)
@@ -203,6 +204,85 @@ __global__ __launch_bounds__(1024) void k_records_rotation(const uint8_t* __rest
     if (tid == 0) n_matches[peer] = total;
 }
 
+// ---- hs_bow_vector: the BoW vector DBoW2's transform leaves in Frame::mBowVec (TemplatedVocabulary::transform: `if (w > 0) v.addWeight(id, w)` per
+// feature in feature order, then v.normalize(L1)) from the (word, weight) arrays hs_bow_transform_device wrote.  One workgroup: the features are
+// sorted by (word, feature index) in LDS (bitonic, u64 keys), ONE LANE PER WORD adds the word's weights in feature order (double, the float weight
+// widened), one wavefront adds the norm in ascending word order along a readlane chain, and every value is divided by it.  Both sums are
+// order-dependent, so neither is a tree.
+#define BOWV_MAX 16384
+#define BOWV_PAD 0xFFFFFFFFFFFFFFFFull
+__device__ __forceinline__ double bowv_lane(double x, int j)
+{
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)__double_as_longlong(x), j), hi = __builtin_amdgcn_readlane((unsigned)(__double_as_longlong(x) >> 32), j);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+__global__ __launch_bounds__(1024) void k_bow_vector(const int32_t* __restrict__ word, const float* __restrict__ weight, const int32_t* __restrict__ d_n, int n_max, int N /*power of two >= n_max, >= 64*/,
+                                                     int32_t* out_word, double* out_value, int32_t* out_m)
+{
+    extern __shared__ unsigned long long bowv_keys[];      // [N]
+    __shared__ uint32_t s_wave[16];
+    __shared__ double s_norm;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n = d_n ? min(max(*d_n, 0), n_max) : n_max;
+    for (int i = tid; i < N; i += 1024) {
+        unsigned long long k = BOWV_PAD;
+        if (i < n) { const int w = word[i]; if (weight[i] > 0.0f && w >= 0) k = ((unsigned long long)(unsigned)w << 32) | (unsigned)i; }
+        bowv_keys[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (N >> 1); t += 1024) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = bowv_keys[i], b = bowv_keys[l];
+                if ((a > b) == ((i & k) == 0)) { bowv_keys[i] = b; bowv_keys[l] = a; }
+            }
+            __syncthreads();
+        }
+    // heads of the word segments: PER consecutive positions per thread, ranks by an exclusive scan over the workgroup
+    const int PER = max(1, N >> 10);
+    const int p0 = tid * PER;
+    auto is_head = [&](int p) { return p < N && bowv_keys[p] != BOWV_PAD && (p == 0 || (bowv_keys[p] >> 32) != (bowv_keys[p - 1] >> 32)); };
+    uint32_t heads = 0;
+    for (int k = 0; k < PER; k++) heads += is_head(p0 + k) ? 1u : 0u;
+    uint32_t incl = heads;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+    if (lane == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) { const uint32_t x = s_wave[w]; if (w < (tid >> 6)) base += x; total += x; }
+    uint32_t rank = base + incl - heads;
+    for (int k = 0; k < PER; k++) {
+        const int p = p0 + k;
+        if (!is_head(p)) continue;
+        const unsigned w = (unsigned)(bowv_keys[p] >> 32);
+        double sum = 0.0;                                    // addWeight: `vit->second += v` per feature, in feature order
+        for (int q = p; q < N; q++) {
+            const unsigned long long key = bowv_keys[q];
+            if (key == BOWV_PAD || (unsigned)(key >> 32) != w) break;
+            sum = __dadd_rn(sum, (double)weight[(unsigned)key]);
+        }
+        out_word[rank] = (int32_t)w; out_value[rank] = sum; rank++;
+    }
+    __syncthreads();
+    const int m = (int)total;
+    if (tid < 64) {                                          // norm += fabs(value) in ascending word order (BowVector::normalize)
+        double norm = 0.0;
+        for (int b = 0; b < m; b += 64) {
+            const int cnt = min(64, m - b);
+            const double v = lane < cnt ? fabs(out_value[b + lane]) : 0.0;
+            for (int j = 0; j < cnt; j++) norm = __dadd_rn(norm, bowv_lane(v, j));
+        }
+        if (tid == 0) { s_norm = norm; *out_m = m; }
+    }
+    __syncthreads();
+    const double norm = s_norm;
+    if (norm > 0.0) for (int r = tid; r < m; r += 1024) out_value[r] = __ddiv_rn(out_value[r], norm);
+}
+
 namespace {
 BowTree tree_of(const hs_vocab_dev* v)
 {
@@ -216,6 +296,7 @@ BowTree tree_of(const hs_vocab_dev* v)
 void hs_set_error(hs_orb* h, const char* msg);       // hs_api.hip
 int hs_orb_device_of(const hs_orb* h);              // hs_api.hip
 hipStream_t hs_orb_stream_of(const hs_orb* h);      // hs_api.hip
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes); // hs_api.hip
 
 extern "C" {
 
@@ -307,6 +388,57 @@ int hs_records_bow_match_device(hs_orb* h, hs_vocab_dev* v, const uint8_t* d_rec
                        score_threshold, second_best_ratio, d_match12);
     hipLaunchKernelGGL(k_records_rotation, dim3(world), dim3(1024), 0, s, d_records, record_stride, rank, cap, off_kps, check_rotation, d_match12, d_n_matches);
     if (hipGetLastError() != hipSuccess) { hs_set_error(h, "BoW record matcher launch failed"); return HS_ERR_HIP; }
+    return HS_OK;
+}
+
+static int bowv_launch(hs_orb* h, const int32_t* d_word, const float* d_weight, const int32_t* d_n, int n_max, int32_t* d_out_word, double* d_out_value, int32_t* d_m, hipStream_t s)
+{
+    int N = 64;
+    while (N < n_max) N <<= 1;
+    // more than the default 64 KiB of LDS for the long lists (per device, so asked for whenever it is needed)
+    if (N * 8 > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bow_vector), hipFuncAttributeMaxDynamicSharedMemorySize, BOWV_MAX * 8) != hipSuccess) {
+        (void)hipGetLastError(); hs_set_error(h, "k_bow_vector: cannot reserve LDS"); return HS_ERR_HIP;
+    }
+    hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), (size_t)N * 8, s, d_word, d_weight, d_n, n_max, N, d_out_word, d_out_value, d_m);
+    if (hipGetLastError() != hipSuccess) { hs_set_error(h, "k_bow_vector launch failed"); return HS_ERR_HIP; }
+    return HS_OK;
+}
+
+int hs_bow_vector_device(hs_orb* h, const int32_t* d_word, const float* d_weight, const int32_t* d_n, int n_max,
+                         int32_t* d_out_word, double* d_out_value, int32_t* d_m, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (n_max < 0 || n_max > BOWV_MAX || !d_m || (n_max > 0 && (!d_word || !d_weight || !d_out_word || !d_out_value)) || ((uintptr_t)d_out_value & 7)) {
+        hs_set_error(h, "bad argument (n_max <= 16384)"); return HS_ERR_INVALID;
+    }
+    if (hipSetDevice(hs_orb_device_of(h)) != hipSuccess) return HS_ERR_HIP;
+    return bowv_launch(h, d_word, d_weight, d_n, n_max, d_out_word, d_out_value, d_m, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+}
+
+int hs_bow_vector(hs_orb* h, const int32_t* word, const float* weight, int n, int32_t* out_word, double* out_value, int32_t* m)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (n < 0 || n > BOWV_MAX || !m || (n > 0 && (!word || !weight || !out_word || !out_value))) { hs_set_error(h, "bad argument (n <= 16384)"); return HS_ERR_INVALID; }
+    *m = 0;
+    if (n == 0) return HS_OK;
+    if (hipSetDevice(hs_orb_device_of(h)) != hipSuccess) return HS_ERR_HIP;
+    const size_t b4 = ((size_t)n * 4 + 255) & ~(size_t)255, b8 = ((size_t)n * 8 + 255) & ~(size_t)255;
+    uint8_t* base = hs_orb_scratch_of(h, 3 * b4 + b8 + 256);
+    if (!base) return HS_ERR_HIP;
+    int32_t* d_w = reinterpret_cast<int32_t*>(base); float* d_wt = reinterpret_cast<float*>(base + b4);
+    int32_t* d_ow = reinterpret_cast<int32_t*>(base + 2 * b4); double* d_ov = reinterpret_cast<double*>(base + 3 * b4); int32_t* d_m = reinterpret_cast<int32_t*>(base + 3 * b4 + b8);
+    hipStream_t s = hs_orb_stream_of(h);
+    hipError_t e = hipMemcpyAsync(d_w, word, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_wt, weight, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, hipGetErrorString(e)); return HS_ERR_HIP; }
+    const int st = bowv_launch(h, d_w, d_wt, nullptr, n, d_ow, d_ov, d_m, s);
+    if (st != HS_OK) return st;
+    int32_t mm = 0;
+    e = hipMemcpyAsync(&mm, d_m, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && mm > 0) { e = hipMemcpy(out_word, d_ow, (size_t)mm * 4, hipMemcpyDeviceToHost); if (e == hipSuccess) e = hipMemcpy(out_value, d_ov, (size_t)mm * 8, hipMemcpyDeviceToHost); }
+    if (e != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, hipGetErrorString(e)); return HS_ERR_HIP; }
+    *m = mm;
     return HS_OK;
 }
 

@@ -691,6 +691,139 @@ class ORBVocabulary:
         ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         return bow, (ids.astype(np.int32), ptr, idx[order].astype(np.int32)), (word, weight, node)
 
+    def bow_vector(self, word, weight):
+        """The BoW vector of `containers`, built on the device (hs_bow_vector) from a transform's per-feature (word, weight): (words int32 [m]
+        ascending and unique, values float64 [m], L1-normalised) — what DBoW2's transform leaves in Frame::mBowVec (Frame.cc:472-479)."""
+        ex = self._ex
+        w = np.ascontiguousarray(word, np.int32).reshape(-1)
+        wt = np.ascontiguousarray(weight, np.float32).reshape(-1)
+        if len(w) != len(wt):
+            raise ValueError("word and weight must have one entry per feature")
+        ow, ov, m = np.zeros(len(w), np.int32), np.zeros(len(w), np.float64), C.c_int32()
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_bow_vector(ex._h, p(w), p(wt), len(w), p(ow), p(ov), C.byref(m)))
+        return ow[:m.value].copy(), ov[:m.value].copy()
+
+    def score(self, a, b):
+        """FeatureVocabulary::score(a, b) (ORBVocabulary.cpp:44-46): DBoW2's L1 score of two BoW vectors, as a double rounded to the `float` every
+        caller in the reference assigns it to.  a, b: {word: value} or (words, values).  0.0 when they share no word.
+        A convenience for single comparisons: every call builds and destroys a one-entry database (device allocations of n_words * 8 bytes and
+        several synchronisations).  To score one vector against many, add them to a PlaceRecognizer and read `score` of a query with details=True."""
+        rec = PlaceRecognizer(self.size(), self._ex)
+        try:
+            rec.add(0, b)
+            return float(rec.detectRelocalizationCandidates(a, details=True)[1]["score"][0])
+        finally:
+            rec.close()
+
+
+def _bow_arrays(bow):
+    """{word: value} or (words, values) -> (int32 [m] ascending, float64 [m])"""
+    if isinstance(bow, dict):
+        ks = sorted(bow)
+        return np.asarray(ks, np.int32), np.asarray([bow[k] for k in ks], np.float64)
+    w, v = bow
+    return np.ascontiguousarray(w, np.int32).reshape(-1), np.ascontiguousarray(v, np.float64).reshape(-1)
+
+
+class PlaceRecognizer:
+    """HYSLAM::PlaceRecognizer (src/core/PlaceRecognizer.cpp:43-311) over a key-frame BoW database resident on the device (hs_place_db).  A key
+    frame is named by a caller-chosen integer `key` (< 2^64, unique among live entries): it stands for the KeyFrame* and orders the results where
+    the reference orders by address.  Covisibility is the caller's: `neighbours` maps a key to the keys of GetBestCovisibilityKeyFrames(10) in
+    that call's order (a dict, or a callable key -> list); unknown or erased keys in a list are ignored."""
+
+    def __init__(self, n_words, extractor=None, scoring=0):
+        self._ex = extractor or ORBExtractor()
+        self._lib = self._ex._lib
+        self._db = C.c_void_p()
+        N.check(self._ex._h, self._lib.hs_place_db_create(self._ex._h, int(n_words), int(scoring), C.byref(self._db)))
+        self._slot = {}                                    # key -> slot (live entries)
+        self._keys = []                                    # slot -> key
+
+    def close(self):
+        if getattr(self, "_db", None) and self._db.value:
+            self._lib.hs_place_db_destroy(self._db)
+            self._db = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        live, slots = C.c_int32(), C.c_int32()
+        self._lib.hs_place_db_size(self._db, C.byref(live), C.byref(slots))
+        return live.value, slots.value
+
+    def add(self, key, bow):
+        if key in self._slot:
+            raise ValueError("key %r is already in the database" % (key,))
+        w, v = _bow_arrays(bow)
+        slot = C.c_int32()
+        N.check(self._ex._h, self._lib.hs_place_db_add(self._db, int(key), w.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), len(w), C.byref(slot)))
+        self._slot[key] = slot.value
+        self._keys.append(key)
+        return slot.value
+
+    def add_device(self, key, d_word, d_value, d_m, m_max, stream=None):
+        """the outputs of hs_bow_vector_device, without a host round trip"""
+        if key in self._slot:
+            raise ValueError("key %r is already in the database" % (key,))
+        slot = C.c_int32()
+        N.check(self._ex._h, self._lib.hs_place_db_add_device(self._db, int(key), C.c_void_p(d_word), C.c_void_p(d_value), C.c_void_p(d_m), int(m_max),
+                                                              C.byref(slot), C.c_void_p(stream)))
+        self._slot[key] = slot.value
+        self._keys.append(key)
+        return slot.value
+
+    def erase(self, key):
+        N.check(self._ex._h, self._lib.hs_place_db_erase(self._db, self._slot[key]))
+        del self._slot[key]
+
+    def clear(self):
+        N.check(self._ex._h, self._lib.hs_place_db_clear(self._db))
+        self._slot, self._keys = {}, []
+
+    def neighbour_table(self, neighbours):
+        """[slots][10] int32 for the C ABI"""
+        t = np.full((len(self._keys), 10), -1, np.int32)
+        if neighbours is None:
+            return t
+        get = neighbours if callable(neighbours) else (lambda k: neighbours.get(k, ()))
+        for key, slot in self._slot.items():
+            row = [self._slot[k] for k in list(get(key))[:10] if k in self._slot]      # an erased key frame is no longer in the inverted file
+            t[slot, :len(row)] = row
+        return t
+
+    def _query(self, loop, bow, neighbours, connected, min_score, details):
+        w, v = _bow_arrays(bow)
+        slots = len(self._keys)
+        neigh = self.neighbour_table(neighbours)
+        cand, n = np.zeros(max(slots, 1), np.int32), C.c_int32()
+        out = dict(words=np.zeros(slots, np.int32), score=np.zeros(slots, np.float32), acc=np.zeros(slots, np.float32), best=np.zeros(slots, np.int32))
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        opt = [p(out[k]) if details else None for k in ("words", "score", "acc", "best")]
+        if loop:
+            excl = np.zeros(max(slots, 1), np.uint8)
+            for k in connected or ():
+                if k in self._slot:
+                    excl[self._slot[k]] = 1
+            st = self._lib.hs_place_query_loop(self._db, p(w), p(v), len(w), p(excl), float(min_score), p(neigh), p(cand), slots, C.byref(n), *opt)
+        else:
+            st = self._lib.hs_place_query_reloc(self._db, p(w), p(v), len(w), p(neigh), p(cand), slots, C.byref(n), *opt)
+        N.check(self._ex._h, st)
+        keys = [self._keys[s] for s in cand[:n.value]]
+        return (keys, out) if details else keys
+
+    def detectRelocalizationCandidates(self, bow, neighbours=None, details=False):
+        """(:201-311) the candidate keys in ascending key order; details=True also returns the per-slot words / score / acc / best arrays"""
+        return self._query(False, bow, neighbours, None, 0.0, details)
+
+    def detectLoopCandidates(self, bow, minScore, connected=(), neighbours=None, details=False):
+        """(:81-199) `connected`: the keys of the query key frame's GetConnectedKeyFrames(), left out of the search"""
+        return self._query(True, bow, neighbours, connected, minScore, details)
+
 
 class ORBFactory:
     """HYSLAM::ORBFactory: hands out extractors and matcher settings (FeatureFactory.h:21-33, ORBFactory.cpp:13-45)."""

@@ -404,6 +404,66 @@ int  hs_records_bow_match_device(hs_orb* h, hs_vocab_dev* v, const uint8_t* d_re
 int  hs_bow_transform(hs_orb* h, const hs_vocab_tree* tree, const uint8_t* desc, int n, int levelsup,
                       int32_t* word_id, float* weight, int32_t* node_id);
 
+/* ---- place recognition: the BoW vector, DBoW2's L1 score and HYSLAM::PlaceRecognizer (src/core/PlaceRecognizer.cpp:43-311), which KeyFrameDB::
+ * DetectRelocalizationCandidates / DetectLoopCandidates (KeyFrameDB.cc:392-419) and Map::detectRelocalizationCandidates (Map.cc:552-559) reach ---- */
+/* The BoW vector DBoW2::TemplatedVocabulary::transform leaves in Frame::mBowVec (Frame.cc:472-479), from the (word, weight) arrays of
+ * hs_bow_transform(_device): `if (w > 0) v.addWeight(word, w)` per feature in feature order (double sums of the float weights), then
+ * v.normalize(L1): norm = sum of |v| in ascending word order, every value divided by it when norm > 0.  out_word [m] ascending and unique,
+ * out_value [m], *m <= n; outputs hold room for n (n_max) entries; n (n_max) <= 16384.  d_n (may be NULL) = device count clamped to n_max.
+ * hs_bow_vector_device is asynchronous on `stream`; hs_bow_vector takes host pointers and returns when done. */
+int  hs_bow_vector_device(hs_orb* h, const int32_t* d_word, const float* d_weight, const int32_t* d_n, int n_max,
+                          int32_t* d_out_word, double* d_out_value, int32_t* d_m, void* stream);
+int  hs_bow_vector(hs_orb* h, const int32_t* word, const float* weight, int n, int32_t* out_word, double* out_value, int32_t* m);
+
+/* The key frames' BoW vectors resident in HBM of h's device (h lends its stream and error text and must outlive the database): what
+ * PlaceRecognizer keeps as an inverted file (:43-78), here a CSR of (int32 word, double value) per slot.  `scoring`: DBoW2::ScoringType as
+ * hs_vocab_info reports it; only 0 (L1_NORM, the one hySLAM's vocabulary uses) is accepted, anything else is HS_ERR_INVALID.
+ * One caller at a time.  The dense query table, the maximum count and the default per-slot arrays exist ONCE per database: all work on one database
+ * — queries included — must be ordered on a single stream or otherwise serialised by the caller; two queries in flight on different streams, or an
+ * add / erase / clear next to a query in flight, corrupt each other silently. */
+typedef struct hs_place_db hs_place_db;
+int  hs_place_db_create(hs_orb* h, int n_words, int scoring, hs_place_db** out);
+void hs_place_db_destroy(hs_place_db* db);
+/* PlaceRecognizer::add (:43-51): stores a copy of the vector.  `key`: caller-chosen, unique among live entries; it takes the place of the
+ * KeyFrame* address wherever the reference orders by address (the C++ adaptor passes the pointer value).  *slot is stable until
+ * erase.  Words ascending, unique and < n_words, values finite and > 0 (checked by the host form: HS_ERR_INVALID); no limit on m below n_words,
+ * HS_ERR_CAPACITY beyond 2^20 slots.  Storage grows by doubling (reallocate + copy, which drains the device); the host form returns when the copy
+ * is done.  hs_place_db_add_device takes the outputs of hs_bow_vector_device without a host round trip: it reserves m_max entries, the length is
+ * *d_m clamped to m_max (d_m NULL: m_max), nothing is checked; asynchronous on `stream` unless the storage has to grow. */
+int  hs_place_db_add(hs_place_db* db, uint64_t key, const int32_t* word, const double* value, int m, int32_t* slot);
+int  hs_place_db_add_device(hs_place_db* db, uint64_t key, const int32_t* d_word, const double* d_value, const int32_t* d_m, int m_max, int32_t* slot, void* stream);
+/* PlaceRecognizer::erase (:53-72): leaves a tombstone; slots are reused only after hs_place_db_clear (PlaceRecognizer::clear, :74-78), which keeps
+ * the allocations.  Both wait for the device. */
+int  hs_place_db_erase(hs_place_db* db, int32_t slot);
+int  hs_place_db_clear(hs_place_db* db);
+int  hs_place_db_size(const hs_place_db* db, int32_t* live, int32_t* slots);     /* either pointer may be NULL */
+/* PlaceRecognizer::detectRelocalizationCandidates (:201-311) / detectLoopCandidates (:81-199) for the query vector (qword, qvalue, qm).
+ *   neigh    [slots][10] int32: the slots of GetBestCovisibilityKeyFrames(10) of every key frame, in that call's order (:153,267); -1 pads a row,
+ *            a tombstoned or out-of-range slot is ignored; NULL = no key frame has neighbours
+ *   exclude  [slots] u8 (loop; may be NULL): spConnectedKeyFrames (:83,97) — nothing else is excluded, not even the query key frame itself
+ * Score pass: per slot the shared-word count and float si = (float)L1Scoring::score(query, key frame) — `fabs(vi - wi) - fabs(vi) - fabs(wi)` added
+ * per shared word in ascending word order in double, -s / 2.0.  Then `int minCommonWords = maxCommonWords * 0.8f`; reloc: scored = words >
+ * minCommonWords, every neighbour that shares a word adds its score (the score it HAS, also when it was not scored) and replaces
+ * pBestKF on a strictly greater one, bestAccScore from 0, retained = acc > 0.75f * bestAccScore, result = the SET of retained pBestKF in ascending
+ * key order (KeyFrameDB's std::set<KeyFrame*>).  loop: the count is the number of shared words MINUS ONE (`insert({pKFi, 0})` on the first hit,
+ * :98-102), listed = scored and si >= min_score, a neighbour contributes only when it is scored, bestAccScore from min_score, entries walked in
+ * ascending key order (std::map<KeyFrame*, int>), result = pBestKF of every retained entry in walk order, first occurrence only.
+ * Outputs: cand_slot [cap], *n_cand; optional (NULL = not wanted) per-slot arrays [slots]: words (the reference's count; -1 = the key frame is not
+ * in lKFsSharingWords / shared_words), score (si; 0 without a shared word), acc and best (accScore and pBestKF's slot of a listed key frame; 0 / -1
+ * otherwise) — the scores KeyFrameDB.cc:393's note asks for.  Host forms: synchronous; HS_ERR_CAPACITY when cap is too small (*n_cand = the
+ * required count, no candidate written).  Device forms: every pointer in HBM, d_qm (may be NULL) = device count clamped to qm_max, asynchronous on
+ * `stream`; they cannot return a capacity status: *d_n_cand ALWAYS holds the required count and NO candidate is written when it exceeds cap.  The
+ * first query after an add / erase / clear uploads the key order and waits for `stream`; steady-state queries allocate and wait for nothing. */
+int  hs_place_query_reloc(hs_place_db* db, const int32_t* qword, const double* qvalue, int qm, const int32_t* neigh,
+                          int32_t* cand_slot, int cap, int32_t* n_cand, int32_t* words, float* score, float* acc, int32_t* best);
+int  hs_place_query_loop(hs_place_db* db, const int32_t* qword, const double* qvalue, int qm, const uint8_t* exclude, float min_score, const int32_t* neigh,
+                         int32_t* cand_slot, int cap, int32_t* n_cand, int32_t* words, float* score, float* acc, int32_t* best);
+int  hs_place_query_reloc_device(hs_place_db* db, const int32_t* d_qword, const double* d_qvalue, const int32_t* d_qm, int qm_max, const int32_t* d_neigh,
+                                 int32_t* d_cand_slot, int cap, int32_t* d_n_cand, int32_t* d_words, float* d_score, float* d_acc, int32_t* d_best, void* stream);
+int  hs_place_query_loop_device(hs_place_db* db, const int32_t* d_qword, const double* d_qvalue, const int32_t* d_qm, int qm_max, const uint8_t* d_exclude,
+                                float min_score, const int32_t* d_neigh, int32_t* d_cand_slot, int cap, int32_t* d_n_cand,
+                                int32_t* d_words, float* d_score, float* d_acc, int32_t* d_best, void* stream);
+
 /* brute-force Hamming 2-NN (cross-camera matching without a vocabulary): for each of nq query descriptors the first-minimum
  * train index, its distance and the second-smallest distance (-1 when absent). */
 int  hs_hamming_knn2(hs_orb* h, const uint8_t* q, int nq, const uint8_t* t, int nt,

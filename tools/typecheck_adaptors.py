@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
@@ -78,7 +78,9 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    const std::vector<int> best = lmd.bestDescriptors(obs, &med);\n"
              "    HYSLAM::HipLandmarkEntries lme; std::vector<HYSLAM::HipLandmarkEntries::Input> lin(1); lin[0].descriptors = d;\n"
              "    const std::vector<HYSLAM::HipLandmarkEntries::Result> ent = lme.updateEntries(lin); cv::Mat nrm = ent[0].normal.clone();\n"
-             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows;\n}\n")
+             "    HYSLAM::HipPlaceRecognizer pr(1000); HYSLAM::KeyFrame* pkf = nullptr; HYSLAM::Frame* pf = nullptr; pr.add(pkf); pr.erase(pkf);\n"
+             "    const std::vector<HYSLAM::KeyFrame*> lc = pr.detectLoopCandidates(pkf, 0.01f); const std::set<HYSLAM::KeyFrame*> rc = pr.relocalizationCandidateSet(pf);\n"
+             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size();\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
           ["-I" + os.path.join(ROOT, "tests", "cpp", "thirdparty_stubs"), "-I" + host_dir, "-I" + os.path.join(ROOT, "include"), tu]
