@@ -1815,6 +1815,8 @@ static int bow_host(hs_orb* h, int legacy, const hs_keypoint* kps1, const uint8_
     if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !n_matches || (n1 > 0 && (!kps1 || !desc1 || !match12)) || (n2 > 0 && (!kps2 || !desc2)) ||
         (nn1 > 0 && (!node_id1 || !node_ptr1 || !idx1)) || (nn2 > 0 && (!node_id2 || !node_ptr2 || !idx2)))
         return fail(h, HS_ERR_INVALID, "bad argument");
+    for (int a = 0; a < nn1; a++) if (node_ptr1[a] < 0 || node_ptr1[a + 1] < node_ptr1[a]) return fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
+    for (int b = 0; b < nn2; b++) if (node_ptr2[b] < 0 || node_ptr2[b + 1] < node_ptr2[b]) return fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
     *n_matches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0 || nn1 == 0 || nn2 == 0) return HS_OK;

@@ -312,8 +312,11 @@ int  hs_search_by_sim3(hs_orb* h, const hs_frame_view* KF1, const hs_landmark* l
 /* the inner loops of SearchByBoW / SearchByBoW2 / _SearchByBoW_ (FeatureMatcher.cc:216-371): for every vocabulary node present in
  * both feature vectors, best / second-best Hamming of each side-1 index over the node's side-2 indices (BestMatchBoWCriterion,
  * MatchCriteria.cpp:601-635: d < threshold and d < ratio*d2, both strict), then RotationConsistencyBoW (:679-726).
- * Feature vectors (DBoW2::FeatureVector) as CSR: node ids ascending, node_ptr[n_nodes+1], idx[].  keep1[n1] (may be NULL) = 1 for
- * side-1 indices that pass the index criteria (PreviouslyMatchedIndexCriterion).  match12[n1] = side-2 index or -1. */
+ * Feature vectors (DBoW2::FeatureVector) as CSR: node ids ascending, node_ptr[n_nodes+1] (non-negative, non-decreasing), idx[] with
+ * node_ptr[n_nodes] entries inside [0, n).  node_ptr is always checked on the host, idx whenever both sides have features and nodes
+ * (HS_ERR_INVALID); the length of idx[] and the order of the node ids are the caller's.  keep1[n1] (may be NULL) = 1 for
+ * side-1 indices that pass the index criteria (PreviouslyMatchedIndexCriterion).  match12[n1] = side-2 index or -1.  A side-1 feature
+ * without any candidate is never matched, whatever the thresholds. */
 int  hs_search_by_bow(hs_orb* h, const hs_keypoint* kps1, const uint8_t* desc1, int n1,
                       const int32_t* node_id1, const int32_t* node_ptr1, const int32_t* idx1, int n_nodes1,
                       const hs_keypoint* kps2, const uint8_t* desc2, int n2,

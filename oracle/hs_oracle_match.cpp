@@ -343,7 +343,7 @@ int hso_search_by_bow_ex(const hso_keypoint* kps1, const uint8_t* desc1, int n1,
                     if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx2 = i2; }
                     else if (dist < bestDist2) bestDist2 = dist;
                 }
-                if (bestDist1 < score_threshold)
+                if (bestIdx2 >= 0 && bestDist1 < score_threshold)                   // no candidate, no match
                     if (static_cast<float>(bestDist1) < second_best_ratio * static_cast<float>(bestDist2))
                         matches_internal.insert(std::make_pair((size_t)i1, (size_t)bestIdx2));
             }
@@ -386,7 +386,7 @@ int hso_search_by_bow_legacy(const hso_keypoint* kps1, const uint8_t* desc1, int
                     if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx2 = i2; }
                     else if (dist < bestDist2) bestDist2 = dist;
                 }
-                if (bestDist1 < th_low && static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {
+                if (bestIdx2 >= 0 && bestDist1 < th_low && static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {   // D10
                     match12[i1] = bestIdx2;
                     vbMatched2[bestIdx2] = true;
                     if (check_orientation) {

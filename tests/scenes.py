@@ -500,3 +500,567 @@ def area_size_cases(seed):
         case = _area_case(rng, kind, n=n, L=L)
         case["sim3"] = area_sim3_pair(rng, case)
         yield case
+
+
+# ---------------------------------------------------------------- vocabulary-grouped matchers, vocabulary transform, 2-NN: edge cases
+# Input domain of the reference (tests/ref_bow.py): angles finite in [0, 360), node ids ascending and unique, a feature index in at most one node.
+BOW_KINDS = ("ties", "list_sizes", "single_candidate", "thresholds", "rotation_bins", "three_maxima", "epipolar", "competition",
+             "disjoint_and_empty_nodes", "unsorted_lists", "mixed")
+BOW_GPU_SEEDS = tuple(range(300, 312))         # the seeds the GPU test runs bow_edge_cases with; the CPU self-checks of the generators cover the same
+BOW_PYREF_MAX_N = 2000                          # above this many features per side the oracle alone is the expectation
+F12_RECTIFIED = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)         # pure x translation: l = (0, 1, -y1), dsqr = (y2 - y1)^2
+# sigma_ref with size == size_ref for which 3.84 * sigma2 is exactly 9.0 in double (3.84 * 150 rounds to 576.0; 150 / 64 scales it exactly)
+SIGMA_REF_BOUND_9 = 2.34375
+
+
+def desc_bits(*set_bits):
+    """the 32-byte descriptor with exactly these bits set"""
+    m = np.zeros(256, np.uint8); m[list(set_bits)] = 1
+    return np.packbits(m, bitorder="little")
+
+
+def plain_kps(n, **fields):
+    """n key points of size 31 and angle 0, named fields overwritten"""
+    from oracle import KP_DTYPE
+    k = np.zeros(n, KP_DTYPE)
+    k["size"] = 31.0
+    for name, v in fields.items():
+        k[name] = v
+    return k
+
+
+def _bow_kps(rng, n):
+    from oracle import KP_DTYPE
+    k = np.zeros(n, KP_DTYPE)
+    k["x"] = rng.uniform(0, 640, n); k["y"] = rng.uniform(0, 480, n)
+    k["octave"] = rng.integers(0, 8, n)
+    k["size"] = np.float32(31) * np.float32(1.2) ** k["octave"].astype(np.float32)
+    k["angle"] = rng.uniform(0, 359.99, n); k["response"] = rng.integers(20, 90, n)
+    return k
+
+
+def _near(rng, base, k):
+    """len(k) descriptors at exactly k[i] bits from `base` (32 bytes)"""
+    k = np.atleast_1d(np.asarray(k, np.int64))
+    return flip_bits(rng, np.repeat(np.asarray(base, np.uint8)[None, :], len(k), 0), k)
+
+
+def _scatter_keep_order(rng, labels):
+    """global index of every local slot: random, but ascending inside a label in local order (list position == local position)"""
+    n = len(labels)
+    slot = rng.permutation(n)
+    g = np.empty(n, np.int64)
+    g[np.lexsort((np.arange(n), labels))] = slot[np.lexsort((slot, labels))]
+    return g
+
+
+def _featvec_from_labels(labels, empty_ids=()):
+    """CSR feature vector from a node label per feature (-1 = in no node): ids ascending, indices ascending per node; empty_ids = nodes that are
+    present with an empty list"""
+    labels = np.asarray(labels, np.int64)
+    ids = np.unique(np.concatenate([labels[labels >= 0], np.asarray(empty_ids, np.int64)]))
+    order = np.argsort(labels, kind="stable")
+    order = order[labels[order] >= 0]
+    counts = np.array([(labels == i).sum() for i in ids], np.int64) if len(ids) < 4096 else np.bincount(np.searchsorted(ids, labels[labels >= 0]), minlength=len(ids))
+    ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return ids.astype(np.int32), ptr, order.astype(np.int32)
+
+
+def _bow_finish(rng, kind, lab1, k1, d1, lab2, k2, d2, empty1=(), empty2=(), shuffle2=False, **params):
+    """scatter the local (node, list position) arrays to global feature indices and add the case's parameters"""
+    g1, g2 = _scatter_keep_order(rng, lab1), _scatter_keep_order(rng, lab2)
+    K1, K2 = np.zeros_like(k1), np.zeros_like(k2)
+    D1, D2 = np.zeros_like(d1), np.zeros_like(d2)
+    L1, L2 = np.zeros_like(lab1), np.zeros_like(lab2)
+    K1[g1], D1[g1], L1[g1] = k1, d1, lab1
+    K2[g2], D2[g2], L2[g2] = k2, d2, lab2
+    fv1, fv2 = _featvec_from_labels(L1, empty1), _featvec_from_labels(L2, empty2)
+    if shuffle2:
+        idx = fv2[2].copy()
+        for j in range(len(fv2[0])):
+            idx[fv2[1][j]:fv2[1][j + 1]] = rng.permutation(idx[fv2[1][j]:fv2[1][j + 1]])
+        fv2 = (fv2[0], fv2[1], idx)
+    case = dict(kind=kind, k1=K1, d1=D1, fv1=fv1, k2=K2, d2=D2, fv2=fv2, keep1=None, keep2=None, F12=None, size_ref=31.0, sigma_ref=1.0,
+                score_threshold=50.0, ratio=0.8, check_rotation=int(rng.integers(0, 2)), host_only=bool(shuffle2))
+    case.update(params)
+    return case
+
+
+class _BowBuilder:
+    """collects nodes as local arrays: add(node id, side-1 descriptors, side-2 descriptors) -> (slice of side 1, slice of side 2)"""
+
+    def __init__(self, rng):
+        self.rng = rng
+        self.lab1, self.lab2, self.d1, self.d2 = [], [], [], []
+        self.n1 = self.n2 = 0
+        self.empty1, self.empty2 = [], []
+
+    def add(self, nid, d1, d2, on1=True, on2=True):
+        d1 = np.asarray(d1, np.uint8).reshape(-1, 32); d2 = np.asarray(d2, np.uint8).reshape(-1, 32)
+        s1, s2 = slice(self.n1, self.n1 + len(d1)), slice(self.n2, self.n2 + len(d2))
+        self.lab1.append(np.full(len(d1), nid if on1 else -1)); self.lab2.append(np.full(len(d2), nid if on2 else -1))
+        self.d1.append(d1); self.d2.append(d2)
+        self.n1 += len(d1); self.n2 += len(d2)
+        if on1 and len(d1) == 0:
+            self.empty1.append(nid)
+        if on2 and len(d2) == 0:
+            self.empty2.append(nid)
+        return s1, s2
+
+    def related(self, nid, a, b, flips, unrelated=0.2, **kw):
+        """a random side-1 descriptors; side 2: copies of them with a number of bits from `flips` flipped, or unrelated"""
+        rng = self.rng
+        d1 = rng.integers(0, 256, (a, 32), dtype=np.uint8)
+        d2 = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        if a and b:
+            own = rng.random(b) >= unrelated
+            src = rng.integers(0, a, b)
+            d2 = np.where(own[:, None], flip_bits(rng, d1[src], rng.choice(flips, b)), d2)
+        return self.add(nid, d1, d2, **kw)
+
+    def arrays(self):
+        cat = lambda x, w: np.concatenate(x) if x else np.zeros((0,) + w, np.uint8)
+        lab1 = np.concatenate(self.lab1).astype(np.int64) if self.lab1 else np.zeros(0, np.int64)
+        lab2 = np.concatenate(self.lab2).astype(np.int64) if self.lab2 else np.zeros(0, np.int64)
+        return lab1, _bow_kps(self.rng, self.n1), cat(self.d1, (32,)), lab2, _bow_kps(self.rng, self.n2), cat(self.d2, (32,))
+
+    def finish(self, kind, k1=None, k2=None, **params):
+        lab1, K1, d1, lab2, K2, d2 = self.arrays()
+        return _bow_finish(self.rng, kind, lab1, K1 if k1 is None else k1, d1, lab2, K2 if k2 is None else k2, d2,
+                           empty1=self.empty1, empty2=self.empty2, **params)
+
+
+def _node_ids(rng, n):
+    return np.sort(rng.choice(np.arange(1, 40 * n + 50), n, replace=False)) * 3 + 1
+
+
+def _bow_ties(rng):
+    """equal best distances at different list positions (different lanes, and the same lane 64 apart), equal second-best, over lists up to 200"""
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(3, 7))):
+        a, b = int(rng.integers(1, 10)), int(rng.choice([2, 5, 66, 70, 130, 200]))
+        d1 = rng.integers(0, 256, (a, 32), dtype=np.uint8)
+        d2 = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        free = list(rng.permutation(b))
+        for r in range(a):
+            t = int(rng.integers(2, 5))
+            if len(free) < t + 1:
+                break
+            pos = [free.pop() for _ in range(t)]
+            if b >= 66 and rng.random() < 0.5:                                  # two of them 64 apart: the same lane of the strided scan
+                j = int(rng.integers(0, b - 64))
+                if j in free and j + 64 in free:
+                    free.remove(j); free.remove(j + 64); pos[:2] = [j, j + 64]
+            k = int(rng.integers(0, 40))
+            if rng.random() < 0.5:
+                d2[pos] = _near(rng, d1[r], [k] * t)                              # tie on the best distance
+            else:
+                d2[pos] = _near(rng, d1[r], [k] + [k + int(rng.integers(1, 9))] * (t - 1))   # unique best, tie on the second
+        B.add(nid, d1, d2)
+    return B.finish("ties", ratio=float(rng.choice([0.8, 1.0, 1.5, 1.0])), score_threshold=float(rng.choice([50.0, 30.5])))
+
+
+def _bow_list_sizes(rng):
+    """side-2 lists of 0, 1, 63, 64, 65, 129 (the lanes stride by 64), side-1 lists that are not multiples of 4 (the waves stride by 4)"""
+    B = _BowBuilder(rng)
+    sizes2 = [0, 1, 63, 64, 65, 129]
+    sizes1 = list(rng.permutation([0, 1, 2, 3, 5, 6, 7, 9]))
+    for nid, b in zip(_node_ids(rng, len(sizes2)), rng.permutation(sizes2)):
+        B.related(nid, int(sizes1.pop()), int(b), [0, 3, 10, 20, 49, 50], unrelated=0.5)
+    return B.finish("list_sizes")
+
+
+def _bow_single(rng):
+    """exactly one candidate: bestDist2 stays FLT_MAX.  Through a list of one and through keep2 leaving one of many"""
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(3, 8))):
+        B.related(nid, int(rng.integers(1, 7)), int(rng.choice([1, 1, 7, 70])), [0, 5, 30, 49, 50, 60], unrelated=0.0)
+    case = B.finish("single_candidate", ratio=float(rng.choice([0.5, 1e-30, 0.0, 1.0])))
+    # keep2 leaves one feature of every longer side-2 list
+    keep2 = np.ones(len(case["k2"]), np.uint8)
+    ids, ptr, idx = case["fv2"]
+    for j in range(len(ids)):
+        lst = idx[ptr[j]:ptr[j + 1]]
+        if len(lst) > 1:
+            keep2[lst] = 0
+            keep2[lst[int(rng.integers(0, len(lst)))]] = 1
+    case["keep2"] = keep2
+    return case
+
+
+BOW_THRESHOLDS = (0.0, 0.5, 30.5, 50.0, 255.5, 256.0, 257.0, 1e30, np.inf, -1.0)
+BOW_RATIOS = (0.0, 0.5, float(np.nextafter(np.float32(1), np.float32(0))), 1.0, float(np.nextafter(np.float32(1), np.float32(2))), 2.0, np.inf)
+
+
+def _bow_thresholds(rng, thr=None, ratio=None):
+    """best distances at and beside the score threshold, second-best at and beside best / ratio; fractional and extreme thresholds and ratios"""
+    thr = float(rng.choice(BOW_THRESHOLDS)) if thr is None else thr
+    ratio = float(rng.choice(BOW_RATIOS)) if ratio is None else ratio
+    if thr > np.finfo(np.float32).max and ratio > 1:                              # outside the reference's domain (DESIGN.md D10)
+        ratio = 1.0
+    t0 = int(np.clip(np.floor(thr) if np.isfinite(thr) else 256, 0, 256))
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(3, 7))):
+        a, b = int(rng.integers(1, 8)), int(rng.choice([3, 20, 70]))
+        d1 = rng.integers(0, 256, (a, 32), dtype=np.uint8)
+        d2 = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        free = list(rng.permutation(b))
+        for r in range(a):
+            if len(free) < 2:
+                break
+            kb = int(np.clip(rng.choice([t0 - 1, t0, t0 + 1, 0, 10, 20]), 0, 256))
+            ks = int(np.clip(rng.choice([kb, kb + 1, 2 * kb, 2 * kb + 1, 256]), kb, 256))
+            d2[[free.pop(), free.pop()]] = _near(rng, d1[r], [kb, ks])
+        B.add(nid, d1, d2)
+    return B.finish("thresholds", score_threshold=thr, ratio=ratio)
+
+
+def _rotation_pairs():
+    f = np.float32
+    n15l, n15h = np.nextafter(f(15), f(0)), np.nextafter(f(15), f(16))
+    pairs = [(0, 15), (0, n15l), (0, n15h), (10, 25), (0, 45), (0, 75), (0, 345), (20, 5), (f(1e-6), 0), (0, 0), (f(359.99), 0), (0, f(359.99)),
+             (100, 205), (15, 0), (n15h, 0), (345, 0), (0, f(1e-6)), (200, 95), (30, 60), (60, 30), (7.5, 22.5), (352.5, 7.5), (0, 14.999), (0, 15.001)]
+    return np.array(pairs, f)
+
+
+def _bow_rotation(rng, kind="rotation_bins", counts=None):
+    """every pair at distance 0 in its own node (accepted by construction), angles chosen for the histogram.  rotation_bins: rot on a half bin
+    (15, 45, ... degrees), one ulp beside, 0, 360 after the wrap; three_maxima: bin populations at the 10 % rule's boundary"""
+    f = np.float32
+    if counts is None:
+        pool = _rotation_pairs()
+        ang = pool[rng.integers(0, len(pool), int(rng.integers(40, 120)))]
+        ang = np.concatenate([pool, ang])
+    else:
+        bins = rng.choice(12, len(counts), replace=False)                       # rot = 30 * bin exactly (angle1 = 0)
+        ang = np.concatenate([np.tile(np.array([[0, 30.0 * b]], f), (c, 1)) for b, c in zip(bins, counts)] + [np.zeros((0, 2), f)])
+        ang = ang[rng.permutation(len(ang))]
+    n = len(ang)
+    per = int(rng.choice([1, 3, n if n else 1]))
+    ids = _node_ids(rng, max((n + per - 1) // per, 1))
+    d1 = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    lab = np.repeat(ids, per)[:n].astype(np.int64)
+    k1, k2 = _bow_kps(rng, n), _bow_kps(rng, n)
+    k1["angle"], k2["angle"] = ang[:, 0], ang[:, 1]
+    return _bow_finish(rng, kind, lab, k1, d1, lab.copy(), k2, d1.copy(), check_rotation=1, ratio=0.8, score_threshold=50.0)
+
+
+THREE_MAXIMA_COUNTS = ([10, 1], [10], [20, 2, 1], [20, 1, 1], [30, 3, 2], [30, 2, 3], [11, 1, 1], [19, 2, 1], [10, 10, 10, 10], [5, 5, 5, 5],
+                       [40, 4, 3], [40, 3, 4], [1], [], [100, 10, 9, 9], [100, 9, 10])
+
+
+def _bow_epipolar(rng, variant):
+    """the epipolar gate: `bound` = rectified pair with dsqr exactly on, one ulp below and above 3.84 * sigma2; `den0` = lines with a = b = 0 for one
+    keypoint (F maps it to the epipole) or for all (zero F); `nonfinite` = NaN / inf in F12 or in a keypoint"""
+    f = np.float32
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(2, 6))):
+        B.related(nid, int(rng.integers(1, 9)), int(rng.choice([1, 4, 30, 70])), [0, 3, 10, 20, 40], unrelated=0.1)
+    lab1, k1, d1, lab2, k2, d2 = B.arrays()
+    n1, n2 = len(k1), len(k2)
+    params = dict(check_rotation=int(rng.integers(0, 2)), ratio=1.0, score_threshold=90.0, keep1=(rng.random(n1) < 0.9).astype(np.uint8),
+                  keep2=(rng.random(n2) < 0.9).astype(np.uint8))
+    if variant == "bound":
+        k1["y"] = np.where(rng.random(n1) < 0.5, 0.0, rng.integers(0, 400, n1)).astype(f)
+        # one side-1 row per node decides the side-2 rows: y2 = y1 + dy, exact in float
+        for nid in np.unique(lab1):
+            i1 = np.nonzero(lab1 == nid)[0]; i2 = np.nonzero(lab2 == nid)[0]
+            y1 = k1["y"][i1[rng.integers(0, len(i1), len(i2))]]
+            big = rng.random(len(i2)) < 0.3                                       # size = 2 * size_ref: the bound is 36, dy = 6
+            s = np.where(big, 2.0, 1.0).astype(f)
+            dy0 = np.choose(rng.integers(0, 5, len(i2)), [f(3), np.nextafter(f(3), f(0)), np.nextafter(f(3), f(4)), f(0), f(1.5)])
+            dyn = rng.choice(np.array([3.0, 2.5, 3.5, 0.0, -3.0, -2.5, -3.5], f), len(i2))
+            k2["y"][i2] = np.where(y1 == 0, dy0 * s, y1 + dyn * s).astype(f)
+            k2["size"][i2] = f(31) * s
+        params.update(F12=F12_RECTIFIED.copy(), size_ref=31.0, sigma_ref=SIGMA_REF_BOUND_9)
+    elif variant == "den0":
+        if rng.random() < 0.3:
+            F = np.zeros((3, 3), f); F[:, 2] = rng.normal(0, 1, 3)
+        else:
+            F = np.array([[1, 0, 0.01], [0, 1, -0.02], [-5, -7, 1]], f)           # a = x1 - 5, b = y1 - 7
+            hit = rng.random(n1) < 0.4
+            k1["x"][hit], k1["y"][hit] = 5.0, 7.0
+        params.update(F12=F, sigma_ref=float(rng.choice([1.0, 1e4, 1e12])))
+    else:
+        F = (rng.normal(0, 1, (3, 3)) * np.array([[1e-5, 1e-5, 1e-2], [1e-5, 1e-5, 1e-2], [1e-2, 1e-2, 1.0]])).astype(f)
+        which = int(rng.integers(0, 4))
+        if which == 0:
+            F[rng.integers(0, 3), rng.integers(0, 3)] = np.nan
+        elif which == 1:
+            F[rng.integers(0, 3), rng.integers(0, 3)] = rng.choice([np.inf, -np.inf])
+        else:
+            for k in (k1, k2):
+                hit = rng.random(len(k)) < 0.25
+                k["x"][hit] = rng.choice(np.array([np.nan, np.inf, -np.inf, 1e30], f), hit.sum())
+                hit = rng.random(len(k)) < 0.1
+                k["y"][hit] = rng.choice(np.array([np.nan, np.inf], f), hit.sum())
+            hit = rng.random(n2) < 0.2
+            k2["size"][hit] = rng.choice(np.array([0.0, np.inf, np.nan, 1e30, -31.0], f), hit.sum())
+        params.update(F12=F, sigma_ref=float(rng.choice([1.0, 4.0, 1e6])))
+    return _bow_finish(rng, "epipolar", lab1, k1, d1, lab2, k2, d2, empty1=B.empty1, empty2=B.empty2, **params)
+
+
+def _bow_competition(rng):
+    """many side-1 features of one node are closest to the same few side-2 features, which sit at list positions around the 64-lane boundary:
+    in the legacy matcher every step must see what the step before took"""
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(1, 4))):
+        a, b = int(rng.integers(20, 100)), int(rng.integers(66, 140))
+        base = rng.integers(0, 256, 32, dtype=np.uint8)
+        d1 = _near(rng, base, rng.integers(0, 12, a))
+        d2 = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        good = np.unique(np.concatenate([[0, b - 1], rng.choice([62, 63, 64, 65, 66], 3, replace=False), rng.integers(0, b, 2)]))
+        d2[good] = _near(rng, base, rng.integers(0, 14, len(good)))
+        B.add(nid, d1, d2)
+    return B.finish("competition", ratio=float(rng.choice([0.9, 1.0, 1.2])), score_threshold=50.0)
+
+
+def _bow_disjoint(rng, variant=0):
+    """node ids that only one side has, in runs (the merge walk jumps with lower_bound), shared nodes with an empty list on either side;
+    variant 1: no node at all on side 2; variant 2: none on side 1"""
+    B = _BowBuilder(rng)
+    ids = _node_ids(rng, int(rng.integers(12, 30)))
+    state = rng.choice(4, len(ids), p=[0.35, 0.25, 0.25, 0.15])                   # shared, side 1 only, side 2 only, shared with an empty list
+    state[:4] = [1, 1, 0, 3]; state[-4:] = [2, 2, 2, 0]
+    for nid, s in zip(ids, state):
+        a, b = int(rng.integers(1, 6)), int(rng.integers(1, 9))
+        if s == 3:
+            a, b = (0, b) if rng.random() < 0.5 else (a, 0)
+        on1, on2 = s != 2, s != 1
+        if variant == 1:
+            on2 = False
+        if variant == 2:
+            on1 = False
+        B.related(nid, a, b, [0, 5, 20, 49, 50], on1=on1, on2=on2)
+    return B.finish("disjoint_and_empty_nodes")
+
+
+def _bow_unsorted(rng):
+    """side-2 lists in shuffled index order holding duplicate descriptors: list order, not index order, breaks the tie (host entry points)"""
+    B = _BowBuilder(rng)
+    for nid in _node_ids(rng, int(rng.integers(3, 7))):
+        a, b = int(rng.integers(1, 8)), int(rng.choice([4, 30, 70, 131]))
+        d1 = rng.integers(0, 256, (a, 32), dtype=np.uint8)
+        d2 = rng.integers(0, 256, (b, 32), dtype=np.uint8)
+        for r in range(a):
+            pos = rng.choice(b, min(b, int(rng.integers(2, 5))), replace=False)
+            d2[pos] = _near(rng, d1[r], [int(rng.integers(0, 30))])[0]            # the same descriptor several times
+        B.add(nid, d1, d2)
+    return B.finish("unsorted_lists", shuffle2=True, ratio=float(rng.choice([1.5, 2.0, 1.0])))
+
+
+def _bow_mixed(rng, n1=None, n2=None, n_nodes=None, **params):
+    """features labelled with random nodes, side 2 mostly copies of side-1 features of the same node; random masks and parameters"""
+    n1 = int(rng.integers(0, 600)) if n1 is None else n1
+    n2 = int(rng.integers(0, 600)) if n2 is None else n2
+    n_nodes = int(rng.choice([1, 7, 60, 300])) if n_nodes is None else n_nodes
+    ids = _node_ids(rng, max(n_nodes, 1))[:n_nodes]
+    lab1 = ids[rng.integers(0, n_nodes, n1)] if n_nodes else np.full(n1, -1, np.int64)
+    lab1 = np.where(rng.random(n1) < 0.05, -1, lab1).astype(np.int64)
+    d1 = rng.integers(0, 256, (n1, 32), dtype=np.uint8)
+    k1, k2 = _bow_kps(rng, n1), _bow_kps(rng, n2)
+    d2 = rng.integers(0, 256, (n2, 32), dtype=np.uint8)
+    lab2 = (ids[rng.integers(0, n_nodes, n2)] if n_nodes else np.full(n2, -1)).astype(np.int64)
+    if n1 and n2:
+        src = rng.integers(0, n1, n2)
+        own = rng.random(n2) < 0.8
+        d2 = np.where(own[:, None], flip_bits(rng, d1[src], rng.choice([0, 3, 10, 25, 49, 50, 51], n2)), d2)
+        lab2 = np.where(own, lab1[src], lab2)
+        k2["angle"] = np.where(own, (k1["angle"][src] + rng.choice([0.0, 0.0, 0.0, 90.0, 15.0], n2)) % np.float32(359.99), k2["angle"])
+    fv1, fv2 = _featvec_from_labels(lab1), _featvec_from_labels(lab2)
+    case = dict(kind="mixed", k1=k1, d1=d1, fv1=fv1, k2=k2, d2=d2, fv2=fv2,
+                keep1=None if rng.random() < 0.3 else (rng.random(n1) < 0.85).astype(np.uint8),
+                keep2=None if rng.random() < 0.3 else (rng.random(n2) < 0.85).astype(np.uint8),
+                F12=None, size_ref=31.0, sigma_ref=1.0, score_threshold=float(rng.choice([50.0, 90.0, 30.5])), ratio=float(rng.choice([0.6, 0.8, 0.9, 1.0])),
+                check_rotation=int(rng.integers(0, 2)), host_only=False)
+    if rng.random() < 0.3:
+        case.update(F12=(rng.normal(0, 1, (3, 3)) * np.array([[1e-5, 1e-5, 1e-2], [1e-5, 1e-5, 1e-2], [1e-2, 1e-2, 1.0]])).astype(np.float32),
+                    sigma_ref=float(rng.choice([1.0, 400.0, 1e5])))
+    case.update(params)
+    return case
+
+
+def bow_edge_cases(seed):
+    """Cases for hs_search_by_bow / _ex / _legacy, each a dict tagged with `kind` (one of BOW_KINDS; a kind may come more than once per seed) that
+    carries its own score_threshold, ratio, check_rotation, keep1, keep2, F12, size_ref, sigma_ref.  host_only marks feature vectors a DBoW2
+    transform cannot produce (unsorted lists): they are for the entry points that take feature vectors from the host."""
+    rng = np.random.default_rng(seed)
+    yield _bow_ties(rng)
+    yield _bow_list_sizes(rng)
+    yield _bow_single(rng)
+    yield _bow_thresholds(rng)
+    yield _bow_thresholds(rng, thr=BOW_THRESHOLDS[seed % len(BOW_THRESHOLDS)], ratio=BOW_RATIOS[seed % len(BOW_RATIOS)])
+    yield _bow_rotation(rng)
+    yield _bow_rotation(rng, "three_maxima", THREE_MAXIMA_COUNTS[seed % len(THREE_MAXIMA_COUNTS)])
+    yield _bow_rotation(rng, "three_maxima", THREE_MAXIMA_COUNTS[int(rng.integers(0, len(THREE_MAXIMA_COUNTS)))])
+    for variant in ("bound", "den0", "nonfinite"):
+        yield _bow_epipolar(rng, variant)
+    yield _bow_competition(rng)
+    yield _bow_disjoint(rng, 0)
+    yield _bow_disjoint(rng, 1 + seed % 2)
+    yield _bow_unsorted(rng)
+    yield _bow_mixed(rng)
+
+
+def bow_size_cases(seed):
+    """n1 / n2 of 0, 1, 65 535 and above 65 535 (the host entry points take int32 indices), no node on one side, one node holding everything,
+    as many nodes as features"""
+    rng = np.random.default_rng(seed)
+    yield _bow_mixed(rng, 0, 5, 2)
+    yield _bow_mixed(rng, 5, 0, 2)
+    yield _bow_mixed(rng, 1, 1, 1, keep1=None, keep2=None)
+    yield _bow_disjoint(rng, 1)
+    yield _bow_mixed(rng, 2000, 2000, 1)                                          # one node holds everything
+    yield _bow_mixed(rng, 1500, 1500, 1500)                                       # about as many nodes as features
+    yield _bow_mixed(rng, 65535, 65535, 600, F12=None, score_threshold=50.0, ratio=0.9, check_rotation=1)
+    yield _bow_mixed(rng, 65600, 70000, 700, F12=None, score_threshold=50.0, ratio=0.9, check_rotation=0)
+
+
+# ---- vocabulary trees
+def flat_tree(rng, levels, children_of, orig_id=False, dup=0.0, zero_weight=0.0):
+    """A flat forward-linked vocabulary tree in breadth-first order as dict(levels, n_nodes, child_begin, child_count, desc, word_id, weight,
+    orig_id).  children_of(index, level, siblings) -> number of children (0 = leaf; forced to 0 at `levels`).  A child's descriptor is its
+    parent's with bits flipped; `dup` = share of children that copy their left sibling (equal distances), `zero_weight` = share of words with
+    a weight that is not positive."""
+    cb, cc, level, desc = [0], [0], [0], [rng.integers(0, 256, 32, dtype=np.uint8)]
+    i = 0
+    while i < len(cb):
+        c = 0 if level[i] >= levels else int(children_of(i, level[i], len(cb)))
+        if i == 0:
+            c = max(c, 1)
+        cb[i], cc[i] = (len(cb) if c else 0), c
+        if c:
+            kids = flip_bits(rng, np.repeat(desc[i][None], c, 0), rng.integers(8, 120, c))
+            for j in range(1, c):
+                if rng.random() < dup:
+                    kids[j] = kids[j - 1]
+            for j in range(c):
+                cb.append(0); cc.append(0); level.append(level[i] + 1); desc.append(kids[j])
+        i += 1
+    n = len(cb)
+    cc_a = np.array(cc, np.int32)
+    leaves = np.nonzero(cc_a == 0)[0]
+    word = np.full(n, -1, np.int32); word[leaves] = np.arange(len(leaves))
+    weight = np.zeros(n, np.float32); weight[leaves] = rng.uniform(0.5, 9.0, len(leaves))
+    z = leaves[rng.random(len(leaves)) < zero_weight]
+    weight[z] = rng.choice(np.array([0.0, -0.0, -1.5, 1e-42], np.float32), len(z))        # 1e-42 (subnormal) is > 0 and stays in the feature vector
+    oid = None
+    if orig_id:
+        oid = (rng.permutation(n) * 5 + 11).astype(np.int32)
+    return dict(levels=levels, n_nodes=n, child_begin=np.array(cb, np.int32), child_count=cc_a, desc=np.ascontiguousarray(np.stack(desc), np.uint8),
+                word_id=word, weight=weight, orig_id=oid, level=np.array(level, np.int32))
+
+
+def tree_struct(cls, tree):
+    """the ctypes hs_vocab_tree / hso_vocab_tree of a flat_tree dict (the dict keeps the arrays alive)"""
+    return cls(tree["n_nodes"], tree["levels"], tree["child_begin"].ctypes.data, tree["child_count"].ctypes.data, tree["desc"].ctypes.data,
+               tree["word_id"].ctypes.data, tree["weight"].ctypes.data, None if tree["orig_id"] is None else tree["orig_id"].ctypes.data)
+
+
+def tree_descriptors(rng, tree, n_random=60):
+    """descriptors aimed at a tree: exact node descriptors, descriptors equidistant to two siblings, at distance 256 from a child, random"""
+    nd, cb, cc = tree["desc"], tree["child_begin"], tree["child_count"]
+    n = tree["n_nodes"]
+    out = [rng.integers(0, 256, (n_random, 32), dtype=np.uint8), nd[rng.integers(0, n, 40)], np.bitwise_not(nd[rng.integers(1, n, 10)]),
+           flip_bits(rng, nd[rng.integers(1, n, 40)], rng.integers(0, 30, 40))]
+    parents = np.nonzero(cc >= 2)[0]
+    for p in rng.choice(parents, min(len(parents), 30), replace=False) if len(parents) else []:
+        j = cb[p] + int(rng.integers(0, cc[p] - 1))
+        diff = np.unpackbits(nd[j] ^ nd[j + 1], bitorder="little")
+        bits = np.nonzero(diff)[0]
+        half = rng.permutation(bits)[:len(bits) // 2]                              # even difference: exactly equidistant to both siblings
+        m = np.zeros(256, np.uint8); m[half] = 1
+        out.append((nd[j] ^ np.packbits(m, bitorder="little"))[None])
+    return np.ascontiguousarray(np.concatenate(out), np.uint8)
+
+
+def vocab_edge_trees(seed):
+    """Flat trees that are not complete uniform k-ary trees, each with descriptors aimed at it and the levelsup values to try.  `upload_refused`:
+    levelsup values for which the feature-vector level has more than 8192 nodes (hs_vocab_upload must answer HS_ERR_INVALID)."""
+    rng = np.random.default_rng(seed)
+    specs = [
+        ("shallow_leaf", 3, lambda i, lv, m: 0 if (lv == 1 and i % 3 == 1) or (lv == 2 and i % 4 == 0) else int(rng.integers(2, 5)), {}),
+        ("ragged", 4, lambda i, lv, m: int(rng.choice([1, 2, 5, 17])) if lv < 2 or rng.random() < 0.7 else 0, {}),
+        ("renumbered", 3, lambda i, lv, m: int(rng.integers(2, 7)), dict(orig_id=True)),
+        ("ties_zero_weight", 3, lambda i, lv, m: int(rng.integers(2, 6)), dict(dup=0.4, zero_weight=0.4)),
+        ("renumbered_shallow_ties", 4, lambda i, lv, m: 0 if lv >= 1 and rng.random() < 0.25 else int(rng.integers(1, 5)), dict(orig_id=True, dup=0.3, zero_weight=0.2)),
+    ]
+    for name, L, fn, kw in specs:
+        t = flat_tree(rng, L, fn, **kw)
+        yield dict(name=name, tree=t, desc=tree_descriptors(rng, t), levelsups=(0, 1, 2, L, L + 2), upload_refused=())
+    t = flat_tree(rng, 2, lambda i, lv, m: 64 if lv == 0 else 128)                 # 8192 nodes at level 2
+    yield dict(name="wide8192", tree=t, desc=tree_descriptors(rng, t, 300), levelsups=(0, 1, 2), upload_refused=())
+    t = flat_tree(rng, 2, lambda i, lv, m: 64 if lv == 0 else (129 if i == 7 else 128))     # 8193
+    yield dict(name="wide8193", tree=t, desc=tree_descriptors(rng, t, 300), levelsups=(0, 1), upload_refused=(0,))
+
+
+# ---- brute-force 2-NN
+KNN2_SIZES = (0, 1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129, 1000)
+
+
+def knn2_edge_cases(seed):
+    """(kind, q, t): every size of KNN2_SIZES as nq and as nt; train sets all identical, all at one distance from the query, the query's complement
+    (distance 256), duplicates of the best in different lanes and in the same lane (j and j + 64)"""
+    rng = np.random.default_rng(seed)
+    R = lambda n: rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    for nq, nt in zip(rng.permutation(KNN2_SIZES), rng.permutation(KNN2_SIZES)):
+        q, t = R(int(nq)), R(int(nt))
+        if nq and nt:
+            hit = rng.integers(0, nq, min(nt, 40))
+            t[rng.choice(nt, len(hit), replace=False)] = flip_bits(rng, q[hit], rng.integers(0, 20, len(hit)))
+        yield dict(kind="sizes", q=q, t=t)
+    nt = int(rng.choice([2, 64, 65, 129, 200]))
+    yield dict(kind="identical", q=R(5), t=np.repeat(R(1), nt, 0))
+    q = R(int(rng.choice([1, 4, 7])))
+    yield dict(kind="one_distance", q=q, t=_near(rng, q[0], np.full(nt, int(rng.integers(0, 200)))))
+    yield dict(kind="complement", q=q, t=np.repeat(np.bitwise_not(q[:1]), nt, 0))
+    q, t = R(6), R(200)
+    j = int(rng.integers(0, 130))
+    t[[j, j + 64]] = q[0]                                                         # the same lane
+    t[[j + 1, j + 6]] = _near(rng, q[1], [3])[0]                                  # different lanes
+    t[[199, 0]] = q[2] if j > 1 else t[[199, 0]]
+    t[[j + 2, j + 66, j + 3]] = _near(rng, q[3], [9, 9, 8])                       # unique best, tied seconds
+    yield dict(kind="duplicates", q=q, t=t)
+
+
+# ---- frame records
+def record_edge_sets(seed, pool=None):
+    """Packed frame records for hs_records_bow_match_device / hs_records_knn2_device: dict(world, rank, cap, stride, buf (uint8 [world * stride]),
+    frames = [(kps, desc)] as the device sees them: cut to the header count clamped to [0, cap]).  Peers hold flipped copies of the rank's
+    descriptors; `pool` = descriptors to draw from (vocabulary node descriptors, so that the features spread over a tree's words).
+    The set with cap = 65 535 is tagged big=True."""
+    from hyslam_amd.distributed import pack_record, record_bytes
+    rng = np.random.default_rng(seed)
+    sets = [  # world, rank, cap, extra stride, counts, header overrides {record: raw header}
+        (1, 0, 3, 0, [2], {}),
+        (2, 1, 1, 0, [1, 1], {}),
+        (2, 0, 3, 16, [3, 0], {}),
+        (2, 1, 64, 0, [5, 0], {}),                                                # the rank's own record is short, the peer's empty
+        (5, 2, 64, 0, [64, 1, 40, 64, 64], {0: 64 + 1000, 3: -5}),
+        (5, 4, 301, 48, [301, 0, 1, 150, 299], {}),
+        (5, 0, 300, 32, [300, 300, 17, 300, 64], {1: 300 + 1000, 0: 300 + 1000}),
+        (2, 0, 65535, 0, [65535, 3000], {}),
+    ]
+    for world, rank, cap, extra, counts, hdr in sets:
+        stride = record_bytes(cap) + extra
+        base_n = max(counts[rank], 1)
+        src = rng.integers(0, 256, (base_n, 32), dtype=np.uint8) if pool is None else \
+            flip_bits(rng, pool[rng.integers(0, len(pool), base_n)], rng.integers(0, 12, base_n))
+        buf = np.zeros(world * stride, np.uint8)
+        frames = []
+        for r in range(world):
+            n = counts[r]
+            k = _bow_kps(rng, n)
+            if r == rank:
+                d = src[:n].copy()
+            else:
+                pick = rng.integers(0, base_n, n)
+                d = flip_bits(rng, src[pick], rng.choice([0, 2, 9, 30, 49, 50, 60], n))
+                k["angle"] = np.float32(rng.choice([0.0, 15.0, 30.0, 200.0], n))
+            rec = pack_record(k, d, cap)
+            raw = hdr.get(r, n)
+            rec[:4] = np.frombuffer(np.int32(raw).tobytes(), np.uint8)
+            buf[r * stride:r * stride + len(rec)] = rec
+            seen = min(max(raw, 0), cap)
+            frames.append((k[:seen].copy(), d[:seen].copy()))
+        yield dict(world=world, rank=rank, cap=cap, stride=stride, buf=buf, frames=frames, big=cap > 2000)

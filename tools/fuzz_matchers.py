@@ -116,6 +116,31 @@ def one_case(rng, i, ex):
     return desc + " -> " + ", ".join(n + ("" if g else " MISMATCH") for n, g in res), good
 
 
+def edge_case(rng, i, ex):
+    """the BoW and 2-NN legs on the generated edge cases of tests/scenes.py (bow_edge_cases, knn2_edge_cases) at a random seed: ties, list sizes
+    around the 64-lane stride, single candidates, fractional and extreme thresholds, rotation bins, the epipolar bound, competition for side-2
+    features, disjoint and empty nodes, unsorted lists"""
+    seed = int(rng.integers(0, 1 << 30))
+    res = []
+    for c in scenes.bow_edge_cases(seed):
+        fvs = (c["k1"], c["d1"], c["fv1"], c["k2"], c["d2"], c["fv2"])
+        rot = bool(c["check_rotation"])
+        m = HS.FeatureMatcher(HS.FeatureMatcherSettings(nnratio=c["ratio"], TH_LOW=c["score_threshold"], checkOri=rot), ex)
+        gm, gn = m.SearchByBoW(*fvs, c["keep1"], rot, keep2=c["keep2"], F12=c["F12"], size_ref=c["size_ref"], sigma_ref=c["sigma_ref"])
+        om, on = oracle.search_by_bow(*fvs, c["keep1"], c["score_threshold"], c["ratio"], rot, keep2=c["keep2"], F12=c["F12"], size_ref=c["size_ref"],
+                                      sigma_ref=c["sigma_ref"])
+        good = gn == on and np.array_equal(gm, om)
+        gm, gn = m.SearchByBoWLegacy(*fvs, c["keep1"], c["keep2"])
+        om, on = oracle.search_by_bow_legacy(*fvs, c["keep1"], c["keep2"], c["score_threshold"], c["ratio"], rot)
+        res.append((c["kind"], good and gn == on and np.array_equal(gm, om)))
+    m = HS.FeatureMatcher(HS.FeatureMatcherSettings(), ex)
+    for c in scenes.knn2_edge_cases(seed):
+        g, o = m.HammingKnn2(c["q"], c["t"]), oracle.hamming_knn2(c["q"], c["t"])
+        res.append(("knn2 %s %dx%d" % (c["kind"], len(c["q"]), len(c["t"])), all(np.array_equal(a, b) for a, b in zip(g, o))))
+    bad = [n for n, g in res if not g]
+    return "case %d: edge cases seed %d -> %d checks%s" % (i, seed, len(res), "".join(", %s MISMATCH" % n for n in bad)), not bad
+
+
 def records_case(rng, i, ex):
     """BASELINE config 5's device path on random shapes: `world` frame records (odd and even capacities: the padded descriptor offset), random counts
     incl. empty records, descriptors with planted near-duplicates across the ranks; the cross-camera 2-NN of a random rank against every peer and the
@@ -201,7 +226,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=1e9)
     ap.add_argument("--stress", action="store_true", help="large frames, thousands of keypoints per frame, up to 160 000 landmarks")
-    ap.add_argument("--records", action="store_true", help="only the frame-record cases (BASELINE config 5's device path); otherwise every fifth case is one")
+    ap.add_argument("--records", action="store_true", help="only the frame-record cases (BASELINE config 5's device path); otherwise every fifth case is one, and every fifth runs the generated BoW / 2-NN edge cases")
     a = ap.parse_args()
     global STRESS
     STRESS = a.stress
@@ -209,7 +234,7 @@ def main():
     ex = HS.ORBExtractor(HS.FeatureExtractorSettings(nFeatures=500))
     t0, bad = time.time(), 0
     for i in range(a.cases):
-        msg, good = records_case(rng, i, ex) if (a.records or i % 5 == 4) else one_case(rng, i, ex)
+        msg, good = records_case(rng, i, ex) if (a.records or i % 5 == 4) else edge_case(rng, i, ex) if i % 5 == 2 else one_case(rng, i, ex)
         print(msg, flush=True)
         bad += not good
         if not good or time.time() - t0 > a.seconds:
