@@ -97,8 +97,8 @@ struct hs_orb {
     int last_stereo_launches = 2;      // launches of stage 4 in the last stereo call: strips + match (run_stereo) or match only (the front end with the strips inside the describe launch)
     // where the last host-pointer extraction (hs_orb_extract[_batch], hs_orb_wait) left its results on the DEVICE: what hs_frame_publish keeps
     const hs_keypoint* pub_kps = nullptr; const uint8_t* pub_desc = nullptr; int pub_cap = 0, pub_batch = 0;
-    // bump-allocated scratch for the host-pointer matcher entry points
-    uint8_t* d_scratch = nullptr; size_t scratch_bytes = 0, scratch_used = 0;
+    // grow-only scratch arena of the host-pointer entry points (HsStage, hs_internal.h)
+    uint8_t* d_scratch = nullptr; size_t scratch_bytes = 0;
     // pipelined host ingest (hs_orb_submit_batch / hs_orb_wait): two staging slots, a copy-in and a copy-out stream next to the compute stream
     struct IngestSlot {
         uint8_t* d_in = nullptr; size_t in_bytes = 0;          // frames of the batch in HBM
@@ -126,8 +126,6 @@ inline int cv_round_f(float v) { return (int)nearbyintf(v); }           // cvRou
 inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
 inline short sat_short(float v) { int i = cv_round_f(v); return (short)(i < -32768 ? -32768 : (i > 32767 ? 32767 : i)); }
 
-int fail(hs_orb* h, int code, const std::string& msg) { if (h) h->err = msg; return code; }
-
 // record "stage `stage` starts here" (stage -1 closes the previous one) when profiling is on
 void mark(hs_orb* h, int stage, hipStream_t s)
 {
@@ -136,11 +134,6 @@ void mark(hs_orb* h, int stage, hipStream_t s)
     (void)hipEventRecord(h->ev_pool[h->ev_used++], s);
     h->prof_stage.push_back(stage);
 }
-
-// a failed HIP call leaves its code in the runtime's sticky "last error": it is cleared here so that the next successful call sequence on this
-// thread does not report it again through hipGetLastError()
-#define HIP_TRY(h, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); \
-    return fail(h, HS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
 
 void free_geometry(hs_orb* h)
 {
@@ -169,7 +162,7 @@ int configure(hs_orb* h, int w, int hh, int batch)
 {
     if (w == h->w && hh == h->h && batch <= h->batch_cap) return HS_OK;
     if (w < 1 || hh < 1 || w > 16384 || hh > 16384 || batch < 1 || batch > 65535)
-        return fail(h, HS_ERR_INVALID, "image size / batch out of range");
+        return hs_fail(h, HS_ERR_INVALID, "image size / batch out of range");
     const int rc = configure_impl(h, w, hh, batch);
     if (rc != HS_OK) free_geometry(h);             // partial allocations of a failed attempt go away; the handle stays usable
     return rc;
@@ -188,7 +181,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         HsLevel& V = h->lv[l];
         V.w = cv_round_f((float)w * h->inv_scale[l]);          // ORBExtractor.cpp:568-569
         V.h = cv_round_f((float)hh * h->inv_scale[l]);
-        if (V.w < 1 || V.h < 1) return fail(h, HS_ERR_INVALID, "pyramid level collapses to zero size");
+        if (V.w < 1 || V.h < 1) return hs_fail(h, HS_ERR_INVALID, "pyramid level collapses to zero size");
         V.pitch = (V.w + 63) & ~63;
         if (l > 0) { pyr_off[l] = pyr_per_img; pyr_per_img += (size_t)V.pitch * V.h; }
         // cell grid, ORBExtractor.cpp:413-428
@@ -200,7 +193,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         if (V.ncols < 1 || V.nrows < 1) { V.ncols = V.nrows = 0; V.wcell = V.hcell = 0; }   // reference: division by zero (UB); no keypoints here
         else { V.wcell = (int)ceilf(width / V.ncols); V.hcell = (int)ceilf(height / V.nrows); }
         if (V.wcell > hs_fast_max_cell_w(6) || V.hcell > HS_MAX_CELL_H)
-            return fail(h, HS_ERR_INVALID, "FAST cell wider than 247 px or taller than 125 px is not supported");
+            return hs_fail(h, HS_ERR_INVALID, "FAST cell wider than 247 px or taller than 125 px is not supported");
         V.cell_begin = cells; cells += V.ncols * V.nrows;
         V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 6);
         V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
@@ -210,9 +203,9 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         // quadtree, ORBExtractor.cpp:183-185
         V.qt_w = maxBX - minB; V.qt_h = maxBY - minB;
         V.n_ini = (V.qt_w > 0 && V.qt_h > 0) ? (int)roundf((float)V.qt_w / (float)V.qt_h) : 0;
-        if (V.ncols > 0 && V.n_ini < 1) return fail(h, HS_ERR_INVALID, "aspect ratio w/h < 0.5 is undefined behaviour in the reference (nIni == 0)");
+        if (V.ncols > 0 && V.n_ini < 1) return hs_fail(h, HS_ERR_INVALID, "aspect ratio w/h < 0.5 is undefined behaviour in the reference (nIni == 0)");
         if (V.ncols < 1) V.n_ini = 0;      // a level without a FAST cell has no keypoints (D4) and no tree: its aspect ratio refuses nothing (until round 6 a 560 x 33 level 7 did: 528 roots)
-        if (V.n_ini > (h->qt_large ? HS_QT_LARGE_NODES : HS_QT_MAX_NODES) / 4) return fail(h, HS_ERR_INVALID, "aspect ratio too wide");
+        if (V.n_ini > (h->qt_large ? HS_QT_LARGE_NODES : HS_QT_MAX_NODES) / 4) return hs_fail(h, HS_ERR_INVALID, "aspect ratio too wide");
         V.hx = V.n_ini > 0 ? (float)V.qt_w / V.n_ini : 1.f;
         V.quota = h->quota[l];
         V.cand_cap = V.ncols * V.nrows * hs_cell_cap(V.wcell, V.hcell);
@@ -448,7 +441,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         };
         HIP_TRY(h, upload_items(h->lv, items, &h->d_fast_items, 6));
         if (h->fast_items_n > 0) HIP_TRY(h, upload_items(h->lv_n, h->fast_items_n, &h->d_fast_items_n, 5));
-        if (!items_fit) return fail(h, HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused");
+        if (!items_fit) return hs_fail(h, HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused");
         HIP_TRY(h, hipMalloc(&h->d_fast_ovf, std::max<size_t>(hs_fast_overflow_bytes(h->max_hcell, std::max(items, h->fast_items_n) * batch, h->fast_knobs), 256)));
         HIP_TRY(h, hipMemsetAsync(h->d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream));       // all four work-queue counter sets start at zero (stream-ordered before the first launch)
     }
@@ -488,7 +481,7 @@ int ensure_outputs(hs_orb* h, int batch, int cap)
 int ensure_stereo_strips(hs_orb* h, int pairs, int cap, int n_rows)
 {
     // two capacities: the counters (pairs * strips) and the lists (pairs * strips * cap) grow independently
-    if (n_rows > 65536) return fail(h, HS_ERR_INVALID, "stereo: more than 65536 image rows");      // k_stereo_strips keeps one counter per 32 rows in LDS
+    if (n_rows > 65536) return hs_fail(h, HS_ERR_INVALID, "stereo: more than 65536 image rows");      // k_stereo_strips keeps one counter per 32 rows in LDS
     const size_t need_count = (size_t)pairs * hs_stereo_strips(n_rows), need_list = need_count * (size_t)cap;
     if (need_count <= h->strip_count_entries && need_list <= h->strip_list_entries) return HS_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -569,7 +562,7 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
             if (h->d_qhist) (void)hipMemsetAsync(h->d_qhist, 0, (size_t)h->qhist_stride * h->batch_cap * 4, h->stream);      // a launch that died half-way may have left keys behind
             if (h->d_qbest) (void)hipMemsetAsync(h->d_qbest, 0, (size_t)h->qbest_stride * h->batch_cap * 8, h->stream);
             (void)hipStreamSynchronize(h->stream);
-            return fail(h, HS_ERR_HIP, std::string("FAST launch: ") + hipGetErrorString(e));
+            return hs_fail(h, HS_ERR_HIP, std::string("FAST launch: ") + hipGetErrorString(e));
         }
         if (launched) h->fast_epoch++;
         return HS_OK;
@@ -616,24 +609,25 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     return HS_OK;
 }
 
-// grow-only device scratch, carved in 256-byte aligned pieces; scratch_begin() invalidates earlier pieces
-int scratch_begin(hs_orb* h, size_t total)
+// the grow-only device scratch arena behind hs_orb_scratch_of() (HsStage, hs_internal.h, lays the host-pointer entry points' pieces out in it)
+int scratch_claim(hs_orb* h, size_t total)
 {
-    total += 4096;
     if (total > h->scratch_bytes) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         hipFree(h->d_scratch); h->d_scratch = nullptr; h->scratch_bytes = 0;
         HIP_TRY(h, hipMalloc(&h->d_scratch, total));
         h->scratch_bytes = total;
     }
-    h->scratch_used = 0;
     return HS_OK;
 }
-template <class T> T* carve(hs_orb* h, size_t count)
+
+// registers what the matchers read of a frame that comes as host arrays: keypoints, descriptors and, as a temporary, the grid that
+// hs_launch_frame_grid builds from the keypoints
+struct DevFrame { hs_keypoint* kps; uint8_t* desc; int8_t* cell; };
+void stage_frame(HsStage& st, const hs_frame_view* F, DevFrame* o)
 {
-    T* p = reinterpret_cast<T*>(h->d_scratch + h->scratch_used);
-    h->scratch_used += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
+    st.in(&o->kps, F->n, F->kps); st.in(&o->desc, (size_t)F->n * 32, F->desc);
+    st.temp(&o->cell, hs_frame_grid_bytes(std::max(F->n, 1)));
 }
 
 void run_stereo(hs_orb* h, const hs_keypoint* kL, const uint8_t* dL, const int32_t* nL, const hs_keypoint* kR, const uint8_t* dR,
@@ -688,12 +682,11 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
     if (L > 1 && !h->pyr_deep.empty() && h->pyr_deep[1].valid) out[7] = h->pyr_deep[1].grid_x * h->pyr_deep[1].grid_y;
 }
 
-// accessors for the other translation units of the library (kernels_bow.hip)
+// accessors for the other translation units of the library (declared in hs_internal.h)
 void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; }
 int hs_orb_device_of(const hs_orb* h) { return h ? h->device : 0; }
 hipStream_t hs_orb_stream_of(const hs_orb* h) { return h ? h->stream : nullptr; }
-// the handle's grow-only device scratch for another translation unit's host entry point (invalidates earlier pieces); nullptr on failure, the error set
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes) { return scratch_begin(h, bytes) == HS_OK ? h->d_scratch : nullptr; }
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes) { return scratch_claim(h, bytes) == HS_OK ? h->d_scratch : nullptr; }
 
 extern "C" {
 
@@ -884,9 +877,9 @@ int hs_orb_extract_batch_device(hs_orb* h, const uint8_t* d_imgs, int batch, int
 {
     if (!h) return HS_ERR_INVALID;
     if (!d_imgs || !d_kps || !d_desc || !d_n || batch < 1 || row_stride < (size_t)w || cap < 1 || cap > 65535)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (((uintptr_t)d_desc & 15) != 0 || (((uintptr_t)d_kps | (uintptr_t)d_n) & 3) != 0)
-        return fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores; hs_record_offsets pads for it), keypoints and counts 4");
+        return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores; hs_record_offsets pads for it), keypoints and counts 4");
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->lane2 && batch >= 2) {      // two lanes: the second half runs on the child handle's stream, fenced by fork / join events
         hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -908,7 +901,7 @@ int hs_orb_extract_batch_device(hs_orb* h, const uint8_t* d_imgs, int batch, int
     }
     int rc = configure(h, w, h_px, batch);
     if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     HsImg0 img0{ d_imgs, d_imgs, batch, (uint64_t)row_stride, (uint64_t)image_stride };
     HsOut out{ d_kps, d_desc, d_n, d_kps, d_desc, d_n, batch, cap };
@@ -925,10 +918,10 @@ int extract_host_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int w,
     h->pub_kps = nullptr; h->pub_desc = nullptr; h->pub_batch = 0;
     int gw = w, gh = h_px;                                   // size of the grey level 0
     if (pp) hs_preprocess_out_size(w, h_px, pp->scale, &gw, &gh);
-    if (gw < 1 || gh < 1) return fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
+    if (gw < 1 || gh < 1) return hs_fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
     int rc = configure(h, gw, gh, batch);
     if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     const size_t pitch = ((size_t)gw + 63) & ~(size_t)63, per_img = pitch * gh;
     if (per_img * batch > h->in_bytes) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -939,7 +932,7 @@ int extract_host_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int w,
     rc = ensure_outputs(h, batch, cap);
     if (rc != HS_OK) return rc;
     hipStream_t s = h->stream;
-    for (int i = 0; i < batch; i++) if (!imgs[i]) return fail(h, HS_ERR_INVALID, "null image in batch");
+    for (int i = 0; i < batch; i++) if (!imgs[i]) return hs_fail(h, HS_ERR_INVALID, "null image in batch");
     if (!pp) {
         // Frames: the runtime's own pageable-memory path (measured: packing the rows into a pinned buffer on the calling thread first is SLOWER —
         // one core copies 2 MB frames at ~10 GB/s, the runtime's staged copy moves them at more than twice that)
@@ -992,9 +985,9 @@ int hs_orb_extract_batch(hs_orb* h, const uint8_t* const* imgs, int batch, int w
                          hs_keypoint* kps, uint8_t* desc, int cap, int32_t* n)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!n || batch < 1) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!n || batch < 1) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (w == 0 || h_px == 0 || !imgs) { for (int i = 0; i < batch; i++) n[i] = 0; return HS_OK; }   // ORBExtractor.cpp:499-500
-    if (!kps || !desc || stride < w || cap < 1 || cap > 65535) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!kps || !desc || stride < w || cap < 1 || cap > 65535) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     return extract_host_frames(h, imgs, batch, w, h_px, (size_t)stride, nullptr, kps, desc, cap, n, nullptr);
 }
 
@@ -1016,11 +1009,11 @@ int hs_preprocess_device(hs_orb* h, const uint8_t* d_src, int w, int h_px, size_
 {
     if (!h) return HS_ERR_INVALID;
     if (!preprocess_params_ok(pp) || !d_src || !d_grey || w < 1 || h_px < 1 || w > 32768 || h_px > 32768 || batch < 1 || row_stride < (size_t)w * pp->channels)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     int gw, gh;
     hs_preprocess_out_size(w, h_px, pp->scale, &gw, &gh);
-    if (gw < 1 || gh < 1 || gw > 16384 || gh > 16384) return fail(h, HS_ERR_INVALID, "the scaled frame is empty or larger than 16384 px");
-    if (grey_row_stride < (size_t)gw) return fail(h, HS_ERR_INVALID, "grey_row_stride < scaled width");
+    if (gw < 1 || gh < 1 || gw > 16384 || gh > 16384) return hs_fail(h, HS_ERR_INVALID, "the scaled frame is empty or larger than 16384 px");
+    if (grey_row_stride < (size_t)gw) return hs_fail(h, HS_ERR_INVALID, "grey_row_stride < scaled width");
     HIP_TRY(h, hipSetDevice(h->device));
     hs_launch_preprocess(d_src, w, h_px, row_stride, image_stride, pp->channels, pp->rgb, pp->scale, d_grey, gw, gh, grey_row_stride, grey_image_stride, 0, batch,
                          stream ? (hipStream_t)stream : h->stream);
@@ -1032,10 +1025,10 @@ int hs_orb_extract_camera_batch(hs_orb* h, const uint8_t* const* imgs, int batch
                                 hs_keypoint* kps, uint8_t* desc, int cap, int32_t* n, uint8_t* grey_out)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!n || batch < 1) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!n || batch < 1) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (w == 0 || h_px == 0 || !imgs) { for (int i = 0; i < batch; i++) n[i] = 0; return HS_OK; }   // ORBExtractor.cpp:499-500
     if (!preprocess_params_ok(pp) || !kps || !desc || w < 0 || h_px < 0 || w > 32768 || h_px > 32768 || row_stride < (size_t)w * pp->channels || cap < 1 || cap > 65535)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     return extract_host_frames(h, imgs, batch, w, h_px, row_stride, pp, kps, desc, cap, n, grey_out);
 }
 
@@ -1043,7 +1036,7 @@ int hs_orb_extract(hs_orb* h, const uint8_t* img, int w, int h_px, int stride,
                    hs_keypoint* kps, uint8_t* desc, int cap, int32_t* n)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!n) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!n) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (!img || w == 0 || h_px == 0) { *n = 0; return HS_OK; }
     const uint8_t* one[1] = { img };
     return hs_orb_extract_batch(h, one, 1, w, h_px, stride, kps, desc, cap, n);
@@ -1057,7 +1050,7 @@ int hs_stereo_match_batch_device(hs_orb* h, const hs_keypoint* d_kpsL, const uin
     if (!h) return HS_ERR_INVALID;
     if (!d_kpsL || !d_descL || !d_nL || !d_kpsR || !d_descR || !d_nR || !sp || !d_uRight || !d_depth ||
         pairs < 1 || pairs > 65535 || cap < 1 || cap > 65535)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_stereo_scratch(h, (size_t)pairs * cap);
     if (rc == HS_OK) rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
@@ -1073,9 +1066,9 @@ int hs_stereo_match(hs_orb* h, const hs_keypoint* kpsL, const uint8_t* descL, in
                     const hs_stereo_params* sp, float* uRight, float* depth)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!sp || nL < 0 || nR < 0 || nL > 65535 || nR > 65535) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!sp || nL < 0 || nR < 0 || nL > 65535 || nR > 65535) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (nL == 0) return HS_OK;
-    if (!kpsL || !descL || !uRight || !depth || (nR > 0 && (!kpsR || !descR))) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!kpsL || !descL || !uRight || !depth || (nR > 0 && (!kpsR || !descR))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     const int cap = std::max(std::max(nL, nR), 1);
     hipStream_t s = h->stream;
@@ -1092,15 +1085,8 @@ int hs_stereo_match(hs_orb* h, const hs_keypoint* kpsL, const uint8_t* descL, in
     }
     const size_t kb = (size_t)cap * sizeof(hs_keypoint), db = (size_t)cap * HS_DESC_BYTES;
     const size_t pin_need = 2 * kb + 2 * db + 16 + 2 * (size_t)cap * 4;
-    if (pin_need > h->pin_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (h->h_pin) hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_bytes = 0;
-        const size_t grow = std::max<size_t>(pin_need, 1 << 18);
-        HIP_TRY(h, hipHostMalloc(&h->h_pin, grow, hipHostMallocDefault));
-        h->pin_bytes = grow;
-    }
-    int rc = ensure_stereo_scratch(h, (size_t)cap);
+    int rc = ensure_pinned(h, &h->h_pin, &h->pin_bytes, std::max<size_t>(pin_need, 1 << 18));
+    if (rc == HS_OK) rc = ensure_stereo_scratch(h, (size_t)cap);
     if (rc == HS_OK) rc = ensure_stereo_strips(h, 1, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
     hs_keypoint* dk = h->d_sm_kps; uint8_t* dd = h->d_sm_desc; int32_t* dn = h->d_sm_n;
@@ -1134,9 +1120,9 @@ int hs_stereo_frontend_batch_device(hs_orb* h, const uint8_t* d_left, const uint
     if (!h) return HS_ERR_INVALID;
     if (!d_left || !d_right || !d_kpsL || !d_descL || !d_nL || !d_kpsR || !d_descR || !d_nR || !sp || !d_uRight || !d_depth ||
         pairs < 1 || 2 * pairs > 65535 || row_stride < (size_t)w || cap < 1 || cap > 65535)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if ((((uintptr_t)d_descL | (uintptr_t)d_descR) & 15) != 0 || (((uintptr_t)d_kpsL | (uintptr_t)d_kpsR | (uintptr_t)d_nL | (uintptr_t)d_nR | (uintptr_t)d_uRight | (uintptr_t)d_depth) & 3) != 0)
-        return fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores), everything else 4");
+        return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores), everything else 4");
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->lane2 && pairs >= 2) {      // two lanes: each handles half of the pairs end to end (extract L+R, match) on its own stream
         hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -1161,7 +1147,7 @@ int hs_stereo_frontend_batch_device(hs_orb* h, const uint8_t* d_left, const uint
     }
     int rc = configure(h, w, h_px, 2 * pairs);
     if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     rc = ensure_stereo_scratch(h, (size_t)pairs * cap);
     if (rc == HS_OK) rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
@@ -1200,16 +1186,16 @@ void hs_host_free(void* p) { if (p) (void)hipHostFree(p); }
 // ImageProcessing::PreProcessImg runs on the compute stream between the copy-in and the pyramid)
 static int submit_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int src_w, int src_h, size_t stride, const hs_preprocess_params* pp, const hs_stereo_params* sp, int32_t* ticket)
 {
-    for (int i = 0; i < batch; i++) if (!imgs[i]) return fail(h, HS_ERR_INVALID, "null image in batch");
+    for (int i = 0; i < batch; i++) if (!imgs[i]) return hs_fail(h, HS_ERR_INVALID, "null image in batch");
     int w = src_w, h_px = src_h;
     if (pp) hs_preprocess_out_size(src_w, src_h, pp->scale, &w, &h_px);
-    if (w < 1 || h_px < 1) return fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
+    if (w < 1 || h_px < 1) return hs_fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
     *ticket = 0;
     h->pub_kps = nullptr; h->pub_desc = nullptr; h->pub_batch = 0;      // a slot's device block may be rewritten from here on
     HIP_TRY(h, hipSetDevice(h->device));
     hs_orb::IngestSlot* sl = nullptr;
     for (auto& c : h->slot) if (!c.busy) { sl = &c; break; }
-    if (!sl) return fail(h, HS_ERR_INVALID, "both staging slots are in flight: hs_orb_wait for the oldest ticket first");
+    if (!sl) return hs_fail(h, HS_ERR_INVALID, "both staging slots are in flight: hs_orb_wait for the oldest ticket first");
     if (!h->s_in) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
         HIP_TRY(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
@@ -1225,7 +1211,7 @@ static int submit_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int s
     int rc = configure(h, w, h_px, batch);
     if (rc != HS_OK) return rc;
     const int cap = h->max_kp, pairs = sp ? batch / 2 : 0;
-    if (cap < 1) return fail(h, HS_ERR_INVALID, "this frame size yields no keypoints");
+    if (cap < 1) return hs_fail(h, HS_ERR_INVALID, "this frame size yields no keypoints");
     const size_t pitch = ((size_t)w + 63) & ~(size_t)63, per_img = pitch * h_px;
     if (per_img * batch > sl->in_bytes) {
         hipFree(sl->d_in); sl->d_in = nullptr; sl->in_bytes = 0;           // the slot is idle: its last batch was waited for
@@ -1323,7 +1309,7 @@ static int submit_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int s
 int hs_orb_submit_batch(hs_orb* h, const uint8_t* const* imgs, int batch, int w, int h_px, int stride, const hs_stereo_params* sp, int32_t* ticket)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!imgs || !ticket || batch < 1 || batch > 65535 || w < 1 || h_px < 1 || stride < w || (sp && (batch & 1))) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!imgs || !ticket || batch < 1 || batch > 65535 || w < 1 || h_px < 1 || stride < w || (sp && (batch & 1))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     return submit_frames(h, imgs, batch, w, h_px, (size_t)stride, nullptr, sp, ticket);
 }
 
@@ -1333,7 +1319,7 @@ int hs_orb_submit_camera_batch(hs_orb* h, const uint8_t* const* imgs, int batch,
     if (!h) return HS_ERR_INVALID;
     if (!preprocess_params_ok(pp) || !imgs || !ticket || batch < 1 || batch > 65535 || w < 1 || h_px < 1 || w > 32768 || h_px > 32768 ||
         row_stride < (size_t)w * pp->channels || (sp && (batch & 1)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     return submit_frames(h, imgs, batch, w, h_px, row_stride, pp, sp, ticket);
 }
 
@@ -1342,9 +1328,9 @@ int hs_orb_wait(hs_orb* h, int32_t ticket, hs_keypoint* kps, uint8_t* desc, int3
     if (!h) return HS_ERR_INVALID;
     hs_orb::IngestSlot* sl = nullptr;
     for (auto& c : h->slot) if (c.busy && c.ticket == ticket) sl = &c;
-    if (!sl || ticket <= 0) return fail(h, HS_ERR_INVALID, "unknown ticket");
-    if (!kps || !desc || !n || (sl->pairs && (!uRight || !depth))) return fail(h, HS_ERR_INVALID, "bad argument");
-    if (cap < sl->cap) return fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+    if (!sl || ticket <= 0) return hs_fail(h, HS_ERR_INVALID, "unknown ticket");
+    if (!kps || !desc || !n || (sl->pairs && (!uRight || !depth))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (cap < sl->cap) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     HIP_TRY(h, hipSetDevice(h->device));
     {
         const hipError_t e = hipEventSynchronize(sl->ev_out);
@@ -1352,7 +1338,7 @@ int hs_orb_wait(hs_orb* h, int32_t ticket, hs_keypoint* kps, uint8_t* desc, int3
             (void)hipGetLastError();
             (void)hipStreamSynchronize(h->s_in); (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->s_out); (void)hipGetLastError();
             sl->busy = false;
-            return fail(h, HS_ERR_HIP, std::string("hipEventSynchronize(ticket): ") + hipGetErrorString(e));
+            return hs_fail(h, HS_ERR_HIP, std::string("hipEventSynchronize(ticket): ") + hipGetErrorString(e));
         }
     }
     const int B = sl->batch, c0 = sl->cap;
@@ -1378,7 +1364,7 @@ int hs_orb_cancel(hs_orb* h, int32_t ticket)
     if (!h) return HS_ERR_INVALID;
     hs_orb::IngestSlot* sl = nullptr;
     for (auto& c : h->slot) if (c.busy && c.ticket == ticket) sl = &c;
-    if (!sl || ticket <= 0) return fail(h, HS_ERR_INVALID, "unknown ticket");
+    if (!sl || ticket <= 0) return hs_fail(h, HS_ERR_INVALID, "unknown ticket");
     (void)hipSetDevice(h->device);
     if (hipEventSynchronize(sl->ev_out) != hipSuccess) {      // let the batch finish (its frames may be read until then), then drop the results
         (void)hipGetLastError();
@@ -1401,37 +1387,25 @@ int hs_search_by_projection(hs_orb* h, const hs_frame_view* F, const hs_landmark
     if (!h) return HS_ERR_INVALID;
     if (!F || !pp || L < 0 || !n_matches || (L > 0 && (!lms || !match_idx || !match_dist)) || F->n < 0 || F->n > 65535 ||
         (F->n > 0 && (!F->kps || !F->desc)) || (pp->use_stereo && F->sensor != 0 && F->n > 0 && !F->uR))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     *n_matches = 0;
     if (L == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const int n = F->n;
-    const size_t nn = (size_t)std::max(n, 1);
-    int rc = scratch_begin(h, pad256(nn * sizeof(hs_keypoint)) + pad256(nn * 32) + 2 * pad256(nn * 4) + pad256(hs_frame_grid_bytes((int)nn)) + pad256(nn * 4) +
-                              pad256((size_t)L * sizeof(hs_landmark)) + 3 * pad256((size_t)L * 4) + 256);
+    HsStage st(h);
+    DevFrame D; float *d_uR, *d_mdist, *d_pangle; int32_t *d_obs, *d_winner, *d_midx, *d_nm; hs_landmark* d_lms;
+    stage_frame(st, F, &D);
+    st.in(&d_uR, n, F->uR); st.in(&d_obs, n, F->kp_lm_obs); st.temp(&d_winner, n);
+    st.in(&d_lms, L, lms);
+    st.out(&d_midx, L, match_idx); st.out(&d_mdist, L, match_dist); st.temp(&d_pangle, L); st.out(&d_nm, 1, n_matches);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    hs_keypoint* d_kps = carve<hs_keypoint>(h, nn); uint8_t* d_desc = carve<uint8_t>(h, nn * 32);
-    float* d_uR = carve<float>(h, nn); int32_t* d_obs = carve<int32_t>(h, nn); int8_t* d_cell = carve<int8_t>(h, hs_frame_grid_bytes((int)nn));
-    int32_t* d_winner = carve<int32_t>(h, nn);
-    hs_landmark* d_lms = carve<hs_landmark>(h, L);
-    int32_t* d_midx = carve<int32_t>(h, L); float* d_mdist = carve<float>(h, L); float* d_pangle = carve<float>(h, L);
-    int32_t* d_nm = carve<int32_t>(h, 1);
-    if (n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(d_kps, F->kps, (size_t)n * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_desc, F->desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        if (F->uR) HIP_TRY(h, hipMemcpyAsync(d_uR, F->uR, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        if (F->kp_lm_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, F->kp_lm_obs, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipMemcpyAsync(d_lms, lms, (size_t)L * sizeof(hs_landmark), hipMemcpyHostToDevice, s));
-    hs_launch_frame_grid(*F, d_kps, d_cell, true, s);
-    hs_launch_search_projection(*F, d_kps, d_desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, d_cell, d_lms, L, *pp,
+    hipStream_t s = st.stream();
+    hs_launch_frame_grid(*F, D.kps, D.cell, true, s);
+    hs_launch_search_projection(*F, D.kps, D.desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, D.cell, d_lms, L, *pp,
                                 d_midx, d_mdist, d_winner, d_pangle, d_nm, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(match_idx, d_midx, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(match_dist, d_mdist, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_matches, d_nm, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    rc = st.finish();
+    if (rc != HS_OK) return rc;
     for (int i = 0; i < L; i++) if (match_idx[i] < 0) match_dist[i] = -1.f;      // entries dropped by the rotation check
     return HS_OK;
 }
@@ -1480,8 +1454,8 @@ int hs_frame_publish(hs_orb* h, int image, const hs_keypoint* kps, int n, hs_fra
 {
     if (!h) return HS_ERR_INVALID;
     if (token) *token = 0;
-    if (!token || !kps || n < 1 || n > 65535 || image < 0) return fail(h, HS_ERR_INVALID, "bad argument");
-    if (!h->pub_kps || image >= h->pub_batch || n > h->pub_cap) return fail(h, HS_ERR_INVALID, "hs_frame_publish: no host-pointer extraction result of this handle to publish (call right after hs_orb_extract / hs_orb_extract_batch / hs_orb_wait)");
+    if (!token || !kps || n < 1 || n > 65535 || image < 0) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!h->pub_kps || image >= h->pub_batch || n > h->pub_cap) return hs_fail(h, HS_ERR_INVALID, "hs_frame_publish: no host-pointer extraction result of this handle to publish (call right after hs_orb_extract / hs_orb_extract_batch / hs_orb_wait)");
     HIP_TRY(h, hipSetDevice(h->device));
     // The slot is picked and RESERVED under the process-wide lock (readers = -1: neither a publisher nor a reader nor hs_frame_cache_clear touches it),
     // the HIP calls (event wait, a possible free + allocation, two copy enqueues) run without it — hs_frame_find / frame_acquire / hs_frame_release of other
@@ -1491,7 +1465,7 @@ int hs_frame_publish(hs_orb* h, int image, const hs_keypoint* kps, int n, hs_fra
         std::lock_guard<std::mutex> g(g_frames_mu);
         FrameCache* c = frame_cache_of(h->device, true);
         for (FrameSlot& q : c->slot) if (q.readers == 0 && (!sl || (q.token == 0 && sl->token != 0) || ((q.token == 0) == (sl->token == 0) && q.stamp < sl->stamp))) sl = &q;
-        if (!sl) return fail(h, HS_ERR_CAPACITY, "hs_frame_publish: every cache slot is being read");
+        if (!sl) return hs_fail(h, HS_ERR_CAPACITY, "hs_frame_publish: every cache slot is being read");
         sl->token = 0;
         sl->readers = -1;
     }
@@ -1583,36 +1557,29 @@ int hs_search_by_projection_frame(hs_orb* h, hs_frame_token frame, const hs_fram
     if (!h) return HS_ERR_INVALID;
     if (!F || !pp || L < 0 || !n_matches || (L > 0 && (!lms || !match_idx || !match_dist)) || F->n < 1 || F->n > 65535 ||
         (pp->use_stereo && F->sensor != 0 && !F->uR))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     *n_matches = 0;
     FrameRef ref;
-    if (!frame_acquire(frame, h->device, &ref)) return fail(h, HS_ERR_INVALID, "hs_search_by_projection_frame: unknown frame token (its cache slot was reused, or it lives on another device)");
+    if (!frame_acquire(frame, h->device, &ref)) return hs_fail(h, HS_ERR_INVALID, "hs_search_by_projection_frame: unknown frame token (its cache slot was reused, or it lives on another device)");
     FrameGuard guard{ &ref, nullptr };
-    if (ref.n != F->n) return fail(h, HS_ERR_INVALID, "hs_search_by_projection_frame: F->n differs from the published frame");
+    if (ref.n != F->n) return hs_fail(h, HS_ERR_INVALID, "hs_search_by_projection_frame: F->n differs from the published frame");
     if (L == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const int n = F->n;
-    const size_t nn = (size_t)n;
-    int rc = scratch_begin(h, 2 * pad256(nn * 4) + pad256(hs_frame_grid_bytes((int)nn)) + pad256(nn * 4) + pad256((size_t)L * sizeof(hs_landmark)) + 3 * pad256((size_t)L * 4) + 256);
+    HsStage st(h);
+    float *d_uR, *d_mdist, *d_pangle; int32_t *d_obs, *d_winner, *d_midx, *d_nm; int8_t* d_cell; hs_landmark* d_lms;
+    st.in(&d_uR, n, F->uR); st.in(&d_obs, n, F->kp_lm_obs); st.temp(&d_cell, hs_frame_grid_bytes(n)); st.temp(&d_winner, n);
+    st.in(&d_lms, L, lms);
+    st.out(&d_midx, L, match_idx); st.out(&d_mdist, L, match_dist); st.temp(&d_pangle, L); st.out(&d_nm, 1, n_matches);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    float* d_uR = carve<float>(h, nn); int32_t* d_obs = carve<int32_t>(h, nn); int8_t* d_cell = carve<int8_t>(h, hs_frame_grid_bytes((int)nn));
-    int32_t* d_winner = carve<int32_t>(h, nn);
-    hs_landmark* d_lms = carve<hs_landmark>(h, L);
-    int32_t* d_midx = carve<int32_t>(h, L); float* d_mdist = carve<float>(h, L); float* d_pangle = carve<float>(h, L);
-    int32_t* d_nm = carve<int32_t>(h, 1);
-    if (F->uR) HIP_TRY(h, hipMemcpyAsync(d_uR, F->uR, nn * 4, hipMemcpyHostToDevice, s));
-    if (F->kp_lm_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, F->kp_lm_obs, nn * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_lms, lms, (size_t)L * sizeof(hs_landmark), hipMemcpyHostToDevice, s));
+    hipStream_t s = st.stream();
     HIP_TRY(h, hipStreamWaitEvent(s, ref.ready, 0));
     hs_launch_frame_grid(*F, ref.d_kps, d_cell, true, s);
     hs_launch_search_projection(*F, ref.d_kps, ref.d_desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, d_cell, d_lms, L, *pp,
                                 d_midx, d_mdist, d_winner, d_pangle, d_nm, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(match_idx, d_midx, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(match_dist, d_mdist, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_matches, d_nm, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    rc = st.finish();
+    if (rc != HS_OK) return rc;
     for (int i = 0; i < L; i++) if (match_idx[i] < 0) match_dist[i] = -1.f;      // entries dropped by the rotation check
     return HS_OK;
 }
@@ -1620,26 +1587,19 @@ int hs_search_by_projection_frame(hs_orb* h, hs_frame_token frame, const hs_fram
 int hs_stereo_match_frames(hs_orb* h, hs_frame_token left, hs_frame_token right, const hs_stereo_params* sp, float* uRight, float* depth)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!sp || !uRight || !depth) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!sp || !uRight || !depth) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     FrameRef L, R;
-    if (!frame_acquire(left, h->device, &L)) return fail(h, HS_ERR_INVALID, "hs_stereo_match_frames: unknown left frame token");
+    if (!frame_acquire(left, h->device, &L)) return hs_fail(h, HS_ERR_INVALID, "hs_stereo_match_frames: unknown left frame token");
     FrameGuard guard{ &L, nullptr };
-    if (!frame_acquire(right, h->device, &R)) return fail(h, HS_ERR_INVALID, "hs_stereo_match_frames: unknown right frame token");
+    if (!frame_acquire(right, h->device, &R)) return hs_fail(h, HS_ERR_INVALID, "hs_stereo_match_frames: unknown right frame token");
     guard.b = &R;
     HIP_TRY(h, hipSetDevice(h->device));
     const int nL = L.n, nR = R.n, cap = std::max(nL, nR);
     hipStream_t s = h->stream;
     if (!h->d_sm_n) HIP_TRY(h, hipMalloc(&h->d_sm_n, 8));
     const size_t pin_need = 16 + 2 * (size_t)cap * 4;
-    if (pin_need > h->pin_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (h->h_pin) hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_bytes = 0;
-        const size_t grow = std::max<size_t>(pin_need, 1 << 18);
-        HIP_TRY(h, hipHostMalloc(&h->h_pin, grow, hipHostMallocDefault));
-        h->pin_bytes = grow;
-    }
-    int rc = ensure_stereo_scratch(h, (size_t)cap);
+    int rc = ensure_pinned(h, &h->h_pin, &h->pin_bytes, std::max<size_t>(pin_need, 1 << 18));
+    if (rc == HS_OK) rc = ensure_stereo_scratch(h, (size_t)cap);
     if (rc == HS_OK) rc = ensure_stereo_strips(h, 1, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
     int32_t* pn = reinterpret_cast<int32_t*>(h->h_pin); float* pout = reinterpret_cast<float*>(h->h_pin + 16);
@@ -1660,20 +1620,16 @@ int hs_stereo_match_frames(hs_orb* h, hs_frame_token left, hs_frame_token right,
 int hs_frame_grid(hs_orb* h, const hs_frame_view* F, int8_t* cell_xy)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!F || F->n < 0 || F->n > 65535 || (F->n > 0 && (!F->kps || !cell_xy))) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!F || F->n < 0 || F->n > 65535 || (F->n > 0 && (!F->kps || !cell_xy))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (F->n == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t nn = F->n;
-    int rc = scratch_begin(h, pad256(nn * sizeof(hs_keypoint)) + pad256(hs_frame_grid_bytes((int)nn)) + 256);
+    HsStage st(h);
+    hs_keypoint* d_kps; int8_t* d_cell;
+    st.in(&d_kps, F->n, F->kps); st.out(&d_cell, hs_frame_grid_bytes(F->n), cell_xy, (size_t)F->n * 2);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    hs_keypoint* d_kps = carve<hs_keypoint>(h, nn); int8_t* d_cell = carve<int8_t>(h, hs_frame_grid_bytes((int)nn));
-    HIP_TRY(h, hipMemcpyAsync(d_kps, F->kps, nn * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-    hs_launch_frame_grid(*F, d_kps, d_cell, false, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(cell_xy, d_cell, nn * 2, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HS_OK;
+    hs_launch_frame_grid(*F, d_kps, d_cell, false, st.stream());
+    return st.finish();
 }
 
 int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
@@ -1682,14 +1638,15 @@ int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_l
     if (!h) return HS_ERR_INVALID;
     if (!F || !pp || L < 1 || !d_lms || !d_match_idx || !d_match_dist || !d_n_matches || F->n < 1 || F->n > 65535 || !F->kps || !F->desc ||
         (pp->use_stereo && F->sensor != 0 && !F->uR))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t nn = F->n;
-    // scratch is per handle: a second call may only start after the first finished (same stream ordering is enough)
-    const size_t need = pad256(hs_frame_grid_bytes((int)nn)) + pad256(nn * 4) + pad256((size_t)L * 4) + 4096;
-    if (need > h->scratch_bytes) { int rc = scratch_begin(h, need); if (rc != HS_OK) return rc; }
-    h->scratch_used = 0;
-    int8_t* d_cell = carve<int8_t>(h, hs_frame_grid_bytes((int)nn)); int32_t* d_winner = carve<int32_t>(h, nn); float* d_pangle = carve<float>(h, L);
+    // temporaries only, and no synchronisation: the call runs on the caller's stream.  Scratch is per handle: a second call may only start
+    // after the first finished (same stream ordering is enough)
+    HsStage st(h);
+    int8_t* d_cell; int32_t* d_winner; float* d_pangle;
+    st.temp(&d_cell, hs_frame_grid_bytes(F->n)); st.temp(&d_winner, F->n); st.temp(&d_pangle, L);
+    int rc = st.begin();
+    if (rc != HS_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
     hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s);
@@ -1698,20 +1655,6 @@ int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_l
 }
 
 namespace {
-// uploads what the Sim3 matchers read of a keyframe and builds its grid lists; returns the carved device pointers
-struct DevFrame { hs_keypoint* kps; uint8_t* desc; int8_t* cell; };
-int upload_frame(hs_orb* h, const hs_frame_view* F, hipStream_t s, DevFrame* o)
-{
-    const size_t nn = (size_t)std::max(F->n, 1);
-    o->kps = carve<hs_keypoint>(h, nn); o->desc = carve<uint8_t>(h, nn * 32); o->cell = carve<int8_t>(h, hs_frame_grid_bytes((int)nn));
-    if (F->n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(o->kps, F->kps, (size_t)F->n * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(o->desc, F->desc, (size_t)F->n * 32, hipMemcpyHostToDevice, s));
-        hs_launch_frame_grid(*F, o->kps, o->cell, true, s);
-    }
-    return HS_OK;
-}
-size_t frame_bytes(int n) { const size_t nn = (size_t)std::max(n, 1); return pad256(nn * sizeof(hs_keypoint)) + pad256(nn * 32) + pad256(hs_frame_grid_bytes((int)nn)); }
 // one row of A*B (+c): double accumulation, alpha in double, one rounding (cv::gemm on float matrices)
 float gemm3h(const float* A, const float* B, float c, double alpha = 1.0)
 {
@@ -1726,7 +1669,7 @@ int hs_search_by_projection_sim3(hs_orb* h, const hs_frame_view* KF, const float
 {
     if (!h) return HS_ERR_INVALID;
     if (!KF || !Scw || L < 0 || !n_matches || (L > 0 && (!lms || !match_idx)) || KF->n < 0 || KF->n > 65535 || (KF->n > 0 && (!KF->kps || !KF->desc || !kp_matched)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     *n_matches = 0;
     for (int i = 0; i < L; i++) match_idx[i] = -1;
     if (L == 0 || KF->n == 0) return HS_OK;
@@ -1738,22 +1681,16 @@ int hs_search_by_projection_sim3(hs_orb* h, const hs_frame_view* KF, const float
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[3 * r + c] = Scw[4 * r + c] * inv + 0.0f; t[r] = Scw[4 * r + 3] * inv + 0.0f; }
     for (int i = 0; i < 3; i++) { const float col[3] = { R[i], R[3 + i], R[6 + i] }; Ow[i] = gemm3h(col, t, 0.f, -1.0); }
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = scratch_begin(h, frame_bytes(KF->n) + pad256((size_t)L * sizeof(hs_landmark)) + pad256((size_t)L * 12) + pad256((size_t)KF->n) + pad256((size_t)L * 4) + 512);
+    HsStage st(h);
+    DevFrame D; hs_landmark* d_lms; float* d_geo; uint8_t* d_taken; int32_t *d_midx, *d_n;
+    stage_frame(st, KF, &D);
+    st.in(&d_lms, L, lms); st.temp(&d_geo, (size_t)L * 3);
+    st.inout(&d_taken, KF->n, kp_matched); st.out(&d_midx, L, match_idx); st.out(&d_n, 1, n_matches);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    DevFrame D; rc = upload_frame(h, KF, s, &D);
-    if (rc != HS_OK) return rc;
-    hs_landmark* d_lms = carve<hs_landmark>(h, L); float* d_geo = carve<float>(h, (size_t)L * 3);
-    uint8_t* d_taken = carve<uint8_t>(h, KF->n); int32_t* d_midx = carve<int32_t>(h, L); int32_t* d_n = carve<int32_t>(h, 1);
-    HIP_TRY(h, hipMemcpyAsync(d_lms, lms, (size_t)L * sizeof(hs_landmark), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_taken, kp_matched, KF->n, hipMemcpyHostToDevice, s));
-    hs_launch_sim3_projection(*KF, D.kps, D.desc, D.cell, R, t, Ow, d_lms, L, (float)th, th_low, d_geo, d_taken, d_midx, d_n, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(match_idx, d_midx, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(kp_matched, d_taken, KF->n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_matches, d_n, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HS_OK;
+    hs_launch_frame_grid(*KF, D.kps, D.cell, true, st.stream());
+    hs_launch_sim3_projection(*KF, D.kps, D.desc, D.cell, R, t, Ow, d_lms, L, (float)th, th_low, d_geo, d_taken, d_midx, d_n, st.stream());
+    return st.finish();
 }
 
 int hs_search_by_sim3(hs_orb* h, const hs_frame_view* KF1, const hs_landmark* lms1, const hs_frame_view* KF2, const hs_landmark* lms2,
@@ -1762,7 +1699,7 @@ int hs_search_by_sim3(hs_orb* h, const hs_frame_view* KF1, const hs_landmark* lm
     if (!h) return HS_ERR_INVALID;
     if (!KF1 || !KF2 || !R12 || !t12 || !n_found || KF1->n < 0 || KF2->n < 0 || KF1->n > 65535 || KF2->n > 65535 ||
         (KF1->n > 0 && (!KF1->kps || !KF1->desc || !lms1 || !match12)) || (KF2->n > 0 && (!KF2->kps || !KF2->desc || !lms2)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     *n_found = 0;
     for (int i = 0; i < KF1->n; i++) match12[i] = -1;
     if (KF1->n == 0 || KF2->n == 0) return HS_OK;
@@ -1773,23 +1710,18 @@ int hs_search_by_sim3(hs_orb* h, const hs_frame_view* KF1, const hs_landmark* lm
     for (int i = 0; i < 3; i++) t21[i] = gemm3h(&sR21[3 * i], t12, 0.f, -1.0);
     HIP_TRY(h, hipSetDevice(h->device));
     const int n1 = KF1->n, n2 = KF2->n;
-    int rc = scratch_begin(h, frame_bytes(n1) + frame_bytes(n2) + pad256((size_t)n1 * sizeof(hs_landmark)) + pad256((size_t)n2 * sizeof(hs_landmark)) +
-                              2 * pad256((size_t)n1 * 4) + pad256((size_t)n2 * 4) + 512);
+    HsStage st(h);
+    DevFrame D1, D2; hs_landmark *d_l1, *d_l2; int32_t *d_m1, *d_m12, *d_m2, *d_n;
+    stage_frame(st, KF1, &D1); stage_frame(st, KF2, &D2);
+    st.in(&d_l1, n1, lms1); st.in(&d_l2, n2, lms2);
+    st.temp(&d_m1, n1); st.out(&d_m12, n1, match12); st.temp(&d_m2, n2); st.out(&d_n, 1, n_found);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    DevFrame D1, D2;
-    rc = upload_frame(h, KF1, s, &D1); if (rc != HS_OK) return rc;
-    rc = upload_frame(h, KF2, s, &D2); if (rc != HS_OK) return rc;
-    hs_landmark* d_l1 = carve<hs_landmark>(h, n1); hs_landmark* d_l2 = carve<hs_landmark>(h, n2);
-    int32_t* d_m1 = carve<int32_t>(h, n1); int32_t* d_m12 = carve<int32_t>(h, n1); int32_t* d_m2 = carve<int32_t>(h, n2); int32_t* d_n = carve<int32_t>(h, 1);
-    HIP_TRY(h, hipMemcpyAsync(d_l1, lms1, (size_t)n1 * sizeof(hs_landmark), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_l2, lms2, (size_t)n2 * sizeof(hs_landmark), hipMemcpyHostToDevice, s));
+    hipStream_t s = st.stream();
+    hs_launch_frame_grid(*KF1, D1.kps, D1.cell, true, s);
+    hs_launch_frame_grid(*KF2, D2.kps, D2.cell, true, s);
     hs_launch_sim3_search(*KF1, D1.kps, D1.desc, D1.cell, *KF2, D2.kps, D2.desc, D2.cell, d_l1, d_l2, sR21, t21, sR12, t12, th, th_high, d_m1, d_m2, d_m12, d_n, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(match12, d_m12, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_found, d_n, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HS_OK;
+    return st.finish();
 }
 
 int hs_search_by_bow(hs_orb* h, const hs_keypoint* kps1, const uint8_t* desc1, int n1,
@@ -1814,9 +1746,9 @@ static int bow_host(hs_orb* h, int legacy, const hs_keypoint* kps1, const uint8_
     if (!h) return HS_ERR_INVALID;
     if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !n_matches || (n1 > 0 && (!kps1 || !desc1 || !match12)) || (n2 > 0 && (!kps2 || !desc2)) ||
         (nn1 > 0 && (!node_id1 || !node_ptr1 || !idx1)) || (nn2 > 0 && (!node_id2 || !node_ptr2 || !idx2)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
-    for (int a = 0; a < nn1; a++) if (node_ptr1[a] < 0 || node_ptr1[a + 1] < node_ptr1[a]) return fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
-    for (int b = 0; b < nn2; b++) if (node_ptr2[b] < 0 || node_ptr2[b + 1] < node_ptr2[b]) return fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    for (int a = 0; a < nn1; a++) if (node_ptr1[a] < 0 || node_ptr1[a + 1] < node_ptr1[a]) return hs_fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
+    for (int b = 0; b < nn2; b++) if (node_ptr2[b] < 0 || node_ptr2[b + 1] < node_ptr2[b]) return hs_fail(h, HS_ERR_INVALID, "feature vector node_ptr must be non-negative and non-decreasing");
     *n_matches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0 || nn1 == 0 || nn2 == 0) return HS_OK;
@@ -1828,34 +1760,20 @@ static int bow_host(hs_orb* h, int legacy, const hs_keypoint* kps1, const uint8_
     }
     const int np = (int)pa.size();
     const int m1 = node_ptr1[nn1], m2 = node_ptr2[nn2];
-    for (int i = 0; i < m1; i++) if (idx1[i] < 0 || idx1[i] >= n1) return fail(h, HS_ERR_INVALID, "feature vector index out of range");
-    for (int i = 0; i < m2; i++) if (idx2[i] < 0 || idx2[i] >= n2) return fail(h, HS_ERR_INVALID, "feature vector index out of range");
+    for (int i = 0; i < m1; i++) if (idx1[i] < 0 || idx1[i] >= n1) return hs_fail(h, HS_ERR_INVALID, "feature vector index out of range");
+    for (int i = 0; i < m2; i++) if (idx2[i] < 0 || idx2[i] >= n2) return hs_fail(h, HS_ERR_INVALID, "feature vector index out of range");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = scratch_begin(h, pad256((size_t)n1 * sizeof(hs_keypoint)) + pad256((size_t)n2 * sizeof(hs_keypoint)) + pad256((size_t)n1 * 32) + pad256((size_t)n2 * 32) +
-                              pad256((size_t)(nn1 + 1) * 4) + pad256((size_t)(nn2 + 1) * 4) + pad256((size_t)std::max(m1, 1) * 4) + pad256((size_t)std::max(m2, 1) * 4) +
-                              2 * pad256((size_t)std::max(np, 1) * 4) + pad256(n1) + pad256(n2) + 3 * pad256((size_t)n1 * 4) + pad256((size_t)n2 * 4) + 256);
+    HsStage st(h);
+    hs_keypoint *d_k1, *d_k2; uint8_t *d_d1, *d_d2, *d_keep, *d_keep2; int32_t *d_p1, *d_p2, *d_i1, *d_i2, *d_pa, *d_pb, *d_m, *d_self, *d_nm;
+    float* d_ang; uint32_t* d_taken2;
+    st.in(&d_k1, n1, kps1); st.in(&d_k2, n2, kps2); st.in(&d_d1, (size_t)n1 * 32, desc1); st.in(&d_d2, (size_t)n2 * 32, desc2);
+    st.in(&d_p1, nn1 + 1, node_ptr1); st.in(&d_p2, nn2 + 1, node_ptr2); st.in(&d_i1, m1, idx1); st.in(&d_i2, m2, idx2);
+    st.in(&d_pa, np, pa.data()); st.in(&d_pb, np, pb.data());
+    st.in(&d_keep, n1, keep1); st.in(&d_keep2, n2, keep2);
+    st.out(&d_m, n1, match12); st.temp(&d_ang, n1); st.temp(&d_self, n1); st.out(&d_nm, 1, n_matches); st.temp(&d_taken2, n2);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    hs_keypoint* d_k1 = carve<hs_keypoint>(h, n1); hs_keypoint* d_k2 = carve<hs_keypoint>(h, n2);
-    uint8_t* d_d1 = carve<uint8_t>(h, (size_t)n1 * 32); uint8_t* d_d2 = carve<uint8_t>(h, (size_t)n2 * 32);
-    int32_t* d_p1 = carve<int32_t>(h, nn1 + 1); int32_t* d_p2 = carve<int32_t>(h, nn2 + 1);
-    int32_t* d_i1 = carve<int32_t>(h, std::max(m1, 1)); int32_t* d_i2 = carve<int32_t>(h, std::max(m2, 1));
-    int32_t* d_pa = carve<int32_t>(h, std::max(np, 1)); int32_t* d_pb = carve<int32_t>(h, std::max(np, 1));
-    uint8_t* d_keep = carve<uint8_t>(h, n1); uint8_t* d_keep2 = carve<uint8_t>(h, n2);
-    int32_t* d_m = carve<int32_t>(h, n1); float* d_ang = carve<float>(h, n1); int32_t* d_self = carve<int32_t>(h, n1);
-    int32_t* d_nm = carve<int32_t>(h, 1);
-    uint32_t* d_taken2 = carve<uint32_t>(h, n2);
-    HIP_TRY(h, hipMemcpyAsync(d_k1, kps1, (size_t)n1 * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_k2, kps2, (size_t)n2 * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_d1, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_d2, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_p1, node_ptr1, (size_t)(nn1 + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_p2, node_ptr2, (size_t)(nn2 + 1) * 4, hipMemcpyHostToDevice, s));
-    if (m1) HIP_TRY(h, hipMemcpyAsync(d_i1, idx1, (size_t)m1 * 4, hipMemcpyHostToDevice, s));
-    if (m2) HIP_TRY(h, hipMemcpyAsync(d_i2, idx2, (size_t)m2 * 4, hipMemcpyHostToDevice, s));
-    if (np) { HIP_TRY(h, hipMemcpyAsync(d_pa, pa.data(), (size_t)np * 4, hipMemcpyHostToDevice, s)); HIP_TRY(h, hipMemcpyAsync(d_pb, pb.data(), (size_t)np * 4, hipMemcpyHostToDevice, s)); }
-    if (keep1) HIP_TRY(h, hipMemcpyAsync(d_keep, keep1, n1, hipMemcpyHostToDevice, s));
-    if (keep2) HIP_TRY(h, hipMemcpyAsync(d_keep2, keep2, n2, hipMemcpyHostToDevice, s));
+    hipStream_t s = st.stream();
     if (legacy)
         hs_launch_bow_legacy(d_pa, d_pb, np, d_p1, d_i1, d_p2, d_i2, d_d1, d_d2, keep1 ? d_keep : nullptr, keep2 ? d_keep2 : nullptr,
                              score_threshold, second_best_ratio, d_m, n1, n2, d_k1, d_k2, d_ang, check_rotation, d_self, d_taken2, d_nm, s);
@@ -1863,11 +1781,7 @@ static int bow_host(hs_orb* h, int legacy, const hs_keypoint* kps1, const uint8_
         hs_launch_bow(d_pa, d_pb, np, d_p1, d_i1, d_p2, d_i2, d_d1, d_d2, keep1 ? d_keep : nullptr, keep2 ? d_keep2 : nullptr,
                       F12, size_ref, sigma_ref, score_threshold, second_best_ratio,
                       d_m, n1, d_k1, d_k2, d_ang, check_rotation, d_self, d_nm, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(match12, d_m, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_matches, d_nm, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HS_OK;
+    return st.finish();
 }
 
 int hs_search_by_bow_ex(hs_orb* h, const hs_keypoint* kps1, const uint8_t* desc1, int n1,
@@ -1899,33 +1813,24 @@ int hs_search_for_initialization(hs_orb* h, const hs_keypoint* kps1, const uint8
     if (!h) return HS_ERR_INVALID;
     if (!F2 || n1 < 0 || !n_matches || F2->n < 0 || F2->n > 65535 || (n1 > 0 && (!kps1 || !desc1 || !prev_matched_xy || !matches12)) ||
         (F2->n > 0 && (!F2->kps || !F2->desc)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     *n_matches = 0;
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0 || F2->n == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const int n2 = F2->n;
-    int rc = scratch_begin(h, pad256((size_t)n1 * sizeof(hs_keypoint)) + pad256((size_t)n2 * sizeof(hs_keypoint)) + pad256((size_t)n1 * 32) + pad256((size_t)n2 * 32) +
-                              pad256((size_t)n2 * 2) + pad256((size_t)n1 * 8) + 4 * pad256((size_t)n2 * 4) + 256);
-    if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    hs_keypoint* d_k1 = carve<hs_keypoint>(h, n1); hs_keypoint* d_k2 = carve<hs_keypoint>(h, n2);
-    uint8_t* d_d1 = carve<uint8_t>(h, (size_t)n1 * 32); uint8_t* d_d2 = carve<uint8_t>(h, (size_t)n2 * 32);
-    int8_t* d_cell = carve<int8_t>(h, (size_t)n2 * 2); float* d_prev = carve<float>(h, (size_t)n1 * 2);
-    int32_t* d_owner = carve<int32_t>(h, n2); int32_t* d_odist = carve<int32_t>(h, n2); float* d_ang = carve<float>(h, n2); int32_t* d_self = carve<int32_t>(h, n2);
-    int32_t* d_nm = carve<int32_t>(h, 1);
-    HIP_TRY(h, hipMemcpyAsync(d_k1, kps1, (size_t)n1 * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_k2, F2->kps, (size_t)n2 * sizeof(hs_keypoint), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_d1, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_d2, F2->desc, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_prev, prev_matched_xy, (size_t)n1 * 8, hipMemcpyHostToDevice, s));
-    hs_launch_frame_grid(*F2, d_k2, d_cell, false, s);
-    hs_launch_search_init(*F2, d_k2, d_d2, d_cell, d_k1, d_d1, n1, d_prev, (float)window, th_low, nnratio, d_owner, d_odist, d_ang, d_self, d_nm, s);
-    HIP_TRY(h, hipGetLastError());
     std::vector<int32_t> owner(n2);
-    HIP_TRY(h, hipMemcpyAsync(owner.data(), d_owner, (size_t)n2 * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(n_matches, d_nm, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    HsStage st(h);
+    hs_keypoint *d_k1, *d_k2; uint8_t *d_d1, *d_d2; int8_t* d_cell; float *d_prev, *d_ang; int32_t *d_owner, *d_odist, *d_self, *d_nm;
+    st.in(&d_k1, n1, kps1); st.in(&d_k2, n2, F2->kps); st.in(&d_d1, (size_t)n1 * 32, desc1); st.in(&d_d2, (size_t)n2 * 32, F2->desc);
+    st.temp(&d_cell, (size_t)n2 * 2); st.in(&d_prev, (size_t)n1 * 2, prev_matched_xy);
+    st.out(&d_owner, n2, owner.data()); st.temp(&d_odist, n2); st.temp(&d_ang, n2); st.temp(&d_self, n2); st.out(&d_nm, 1, n_matches);
+    int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    hs_launch_frame_grid(*F2, d_k2, d_cell, false, st.stream());
+    hs_launch_search_init(*F2, d_k2, d_d2, d_cell, d_k1, d_d1, n1, d_prev, (float)window, th_low, nnratio, d_owner, d_odist, d_ang, d_self, d_nm, st.stream());
+    rc = st.finish();
+    if (rc != HS_OK) return rc;
     for (int i2 = 0; i2 < n2; i2++) {                          // matches_inverse + vbPrevMatched update (:446-458)
         const int i1 = owner[i2];
         if (i1 < 0) continue;
@@ -1940,34 +1845,26 @@ int hs_bow_transform(hs_orb* h, const hs_vocab_tree* T, const uint8_t* desc, int
     if (!h) return HS_ERR_INVALID;
     if (!T || n < 0 || T->n_nodes < 2 || T->levels < 1 || !T->child_begin || !T->child_count || !T->desc || !T->word_id || !T->weight ||
         (n > 0 && (!desc || !word_id || !weight || !node_id)))
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (n == 0) return HS_OK;
     // the walk must terminate inside the tree: children in range, the root has children
-    if (T->child_count[0] < 1) return fail(h, HS_ERR_INVALID, "vocabulary root has no children");
+    if (T->child_count[0] < 1) return hs_fail(h, HS_ERR_INVALID, "vocabulary root has no children");
     for (int i = 0; i < T->n_nodes; i++) {
         const long cb = T->child_begin[i], cc = T->child_count[i];
-        if (cc < 0 || (cc > 0 && (cb <= i || cb + cc > T->n_nodes))) return fail(h, HS_ERR_INVALID, "vocabulary tree is not a forward-linked flat tree");
+        if (cc < 0 || (cc > 0 && (cb <= i || cb + cc > T->n_nodes))) return hs_fail(h, HS_ERR_INVALID, "vocabulary tree is not a forward-linked flat tree");
     }
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nn = T->n_nodes;
-    int rc = scratch_begin(h, pad256(nn * 4) * 3 + pad256(nn * 4) + pad256(nn * 32) + pad256((size_t)n * 32) + 3 * pad256((size_t)n * 4));
+    HsStage st(h);
+    int32_t *d_cb, *d_cc, *d_w, *o_w, *o_n; float *d_wt, *o_wt; uint8_t *d_nd, *d_d;
+    st.in(&d_cb, nn, T->child_begin); st.in(&d_cc, nn, T->child_count); st.in(&d_w, nn, T->word_id); st.in(&d_wt, nn, T->weight);
+    st.in(&d_nd, nn * 32, T->desc); st.in(&d_d, (size_t)n * 32, desc);
+    st.out(&o_w, n, word_id); st.out(&o_wt, n, weight); st.out(&o_n, n, node_id);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    int32_t* d_cb = carve<int32_t>(h, nn); int32_t* d_cc = carve<int32_t>(h, nn); int32_t* d_w = carve<int32_t>(h, nn);
-    float* d_wt = carve<float>(h, nn); uint8_t* d_nd = carve<uint8_t>(h, nn * 32); uint8_t* d_d = carve<uint8_t>(h, (size_t)n * 32);
-    int32_t* o_w = carve<int32_t>(h, n); float* o_wt = carve<float>(h, n); int32_t* o_n = carve<int32_t>(h, n);
-    HIP_TRY(h, hipMemcpyAsync(d_cb, T->child_begin, nn * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_cc, T->child_count, nn * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_w, T->word_id, nn * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_wt, T->weight, nn * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_nd, T->desc, nn * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
-    hs_launch_bow_transform(n, d_d, d_cb, d_cc, d_nd, d_w, d_wt, T->levels, levelsup, o_w, o_wt, o_n, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(word_id, o_w, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(weight, o_wt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(node_id, o_n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    hs_launch_bow_transform(n, d_d, d_cb, d_cc, d_nd, d_w, d_wt, T->levels, levelsup, o_w, o_wt, o_n, st.stream());
+    rc = st.finish();
+    if (rc != HS_OK) return rc;
     if (T->orig_id) for (int i = 0; i < n; i++) node_id[i] = T->orig_id[node_id[i]];      // renumbered vocabulary: report DBoW2's NodeId
     return HS_OK;
 }
@@ -1976,7 +1873,7 @@ int hs_hamming_knn2_device(hs_orb* h, const uint8_t* d_q, int nq, const uint8_t*
                            int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_best_idx || !d_best_dist || !d_second_dist)) || (nt > 0 && !d_t)) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_best_idx || !d_best_dist || !d_second_dist)) || (nt > 0 && !d_t)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     hs_launch_knn2(d_q, nq, d_t, nt, d_best_idx, d_best_dist, d_second_dist, stream ? (hipStream_t)stream : h->stream);
     HIP_TRY(h, hipGetLastError());
@@ -1986,23 +1883,17 @@ int hs_hamming_knn2_device(hs_orb* h, const uint8_t* d_q, int nq, const uint8_t*
 int hs_hamming_knn2(hs_orb* h, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist)
 {
     if (!h) return HS_ERR_INVALID;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !best_idx || !best_dist || !second_dist)) || (nt > 0 && !t)) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !best_idx || !best_dist || !second_dist)) || (nt > 0 && !t)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (nq == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = scratch_begin(h, pad256((size_t)nq * 32) + pad256((size_t)std::max(nt, 1) * 32) + 3 * pad256((size_t)nq * 4));
+    HsStage st(h);
+    uint8_t *dq, *dt; int32_t *bi, *bd, *sd;
+    st.in(&dq, (size_t)nq * 32, q); st.in(&dt, (size_t)nt * 32, t);
+    st.out(&bi, nq, best_idx); st.out(&bd, nq, best_dist); st.out(&sd, nq, second_dist);
+    int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = h->stream;
-    uint8_t* dq = carve<uint8_t>(h, (size_t)nq * 32); uint8_t* dt = carve<uint8_t>(h, (size_t)std::max(nt, 1) * 32);
-    int32_t* bi = carve<int32_t>(h, nq); int32_t* bd = carve<int32_t>(h, nq); int32_t* sd = carve<int32_t>(h, nq);
-    HIP_TRY(h, hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-    if (nt) HIP_TRY(h, hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, s));
-    hs_launch_knn2(dq, nq, dt, nt, bi, bd, sd, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(best_idx, bi, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(best_dist, bd, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(second_dist, sd, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HS_OK;
+    hs_launch_knn2(dq, nq, dt, nt, bi, bd, sd, st.stream());
+    return st.finish();
 }
 
 // [ count | pad to 16 | keypoints[cap] | pad to 16 | descriptors[cap][32] ]: the descriptor block starts on a 16-byte boundary whatever the parity of
@@ -2023,7 +1914,7 @@ int hs_records_knn2_device(hs_orb* h, const uint8_t* d_records, size_t record_st
     if (!h) return HS_ERR_INVALID;
     if (!d_records || world < 1 || world > 65535 || rank < 0 || rank >= world || cap < 1 || cap > 65535 || record_stride < hs_record_bytes(cap) ||
         (record_stride & 3) || ((uintptr_t)d_records & 15) || !d_best_idx || !d_best_dist || !d_second_dist)
-        return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     size_t od; hs_record_offsets(cap, nullptr, nullptr, &od);
     hs_launch_knn2_records(d_records, record_stride, world, rank, cap, od, d_best_idx, d_best_dist, d_second_dist, stream ? (hipStream_t)stream : h->stream);
@@ -2034,7 +1925,7 @@ int hs_records_knn2_device(hs_orb* h, const uint8_t* d_records, size_t record_st
 int hs_debug_stream_copy(hs_orb* h, void* d_dst, const void* d_src, size_t bytes, int width, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!d_dst || !d_src || (width != 4 && width != 16 && width != 64) || bytes % 16) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!d_dst || !d_src || (width != 4 && width != 16 && width != 64) || bytes % 16) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     hs_launch_stream_copy(d_dst, d_src, bytes, width, stream ? (hipStream_t)stream : h->stream);
     HIP_TRY(h, hipGetLastError());
@@ -2074,7 +1965,7 @@ int hs_orb_profile_pause(hs_orb* h)
 int hs_orb_profile_end(hs_orb* h, double* ms, int32_t* launches)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!ms || !launches) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!ms || !launches) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     for (int i = 0; i < HS_NUM_STAGES; i++) { ms[i] = 0; launches[i] = 0; }
     // the second lane (hs_orb_set_lanes) records its own event sequence: both are summed
@@ -2097,12 +1988,12 @@ int hs_orb_profile_end(hs_orb* h, double* ms, int32_t* launches)
 int hs_orb_set_lanes(hs_orb* h, int lanes)
 {
     if (!h) return HS_ERR_INVALID;
-    if (lanes < 1 || lanes > 2) return fail(h, HS_ERR_INVALID, "lanes must be 1 or 2");
+    if (lanes < 1 || lanes > 2) return hs_fail(h, HS_ERR_INVALID, "lanes must be 1 or 2");
     HIP_TRY(h, hipSetDevice(h->device));
     if (lanes == 1) { if (h->lane2) { hs_orb_destroy(h->lane2); h->lane2 = nullptr; } return HS_OK; }
     if (!h->lane2) {
         int rc = hs_orb_create(&h->p, h->device, &h->lane2);
-        if (rc != HS_OK) return fail(h, rc, "could not create the second lane");
+        if (rc != HS_OK) return hs_fail(h, rc, "could not create the second lane");
         if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         if (!h->ev_join) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
@@ -2112,7 +2003,7 @@ int hs_orb_set_lanes(hs_orb* h, int lanes)
 int hs_orb_set_split(hs_orb* h, int mode)
 {
     if (!h) return HS_ERR_INVALID;
-    if (mode < -1 || mode > 1) return fail(h, HS_ERR_INVALID, "split mode must be -1 (auto), 0 or 1");
+    if (mode < -1 || mode > 1) return hs_fail(h, HS_ERR_INVALID, "split mode must be -1 (auto), 0 or 1");
     h->split_mode = mode;
     if (h->lane2) h->lane2->split_mode = mode;
     return HS_OK;
@@ -2129,11 +2020,11 @@ int hs_orb_synchronize(hs_orb* h, void* stream)
 int hs_orb_debug_level(hs_orb* h, int image, int level, uint8_t* out, size_t cap_bytes, int32_t* lw, int32_t* lh)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!out || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!out || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
     const HsLevel& V = h->lv[level];
-    if ((size_t)V.w * V.h > cap_bytes) return fail(h, HS_ERR_CAPACITY, "level larger than buffer");
+    if ((size_t)V.w * V.h > cap_bytes) return hs_fail(h, HS_ERR_CAPACITY, "level larger than buffer");
     if (lw) *lw = V.w;
     if (lh) *lh = V.h;
     const uint8_t* src; size_t pitch;
@@ -2155,8 +2046,8 @@ int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int c
 {
     if (!h) return HS_ERR_INVALID;
     if (h->fast_keys && h->last_batch <= h->fast_keys_max_batch && !h->keep_points)
-        return fail(h, HS_ERR_INVALID, "hs_orb_debug_candidates: call hs_orb_set_debug(h, 1) before the extraction (the candidates are only gathered into a dense list in debug mode)");
-    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "hs_orb_debug_candidates: call hs_orb_set_debug(h, 1) before the extraction (the candidates are only gathered into a dense list in debug mode)");
+    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
     const HsLevel& V = h->lv[level];
@@ -2164,7 +2055,7 @@ int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int c
     HIP_TRY(h, hipMemcpy(&cnt, h->d_cand_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     cnt = std::min(cnt, V.cand_cap);
     *n = cnt;
-    if (cnt > cap) return fail(h, HS_ERR_CAPACITY, "more candidates than buffer");
+    if (cnt > cap) return hs_fail(h, HS_ERR_CAPACITY, "more candidates than buffer");
     std::vector<uint32_t> xy(cnt), sk(cnt);
     if (cnt) {
         HIP_TRY(h, hipMemcpy(xy.data(), h->d_pts_xy + (size_t)image * h->cand_img_stride + V.cand_off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
@@ -2177,14 +2068,14 @@ int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int c
 int hs_orb_debug_selected(hs_orb* h, int image, int level, int32_t* xys, int cap, int32_t* n)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return fail(h, HS_ERR_INVALID, "bad argument");
+    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
     const HsLevel& V = h->lv[level];
     int32_t cnt = 0;
     HIP_TRY(h, hipMemcpy(&cnt, h->d_sel_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     *n = cnt;
-    if (cnt > cap) return fail(h, HS_ERR_CAPACITY, "more keypoints than buffer");
+    if (cnt > cap) return hs_fail(h, HS_ERR_CAPACITY, "more keypoints than buffer");
     if (cnt) HIP_TRY(h, hipMemcpy(xys, h->d_sel + ((size_t)image * h->sel_img_stride + V.sel_off) * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost));
     return HS_OK;
 }

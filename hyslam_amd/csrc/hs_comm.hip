@@ -13,9 +13,6 @@
 #include <mutex>
 #include <string>
 
-void hs_set_error(hs_orb* h, const char* msg);       // hs_api.hip
-int hs_orb_device_of(const hs_orb* h);              // hs_api.hip
-hipStream_t hs_orb_stream_of(const hs_orb* h);      // hs_api.hip
 void hs_orb_borrow(hs_orb* h, int delta);           // hs_api.hip: a communicator borrows the handle it was created on
 
 // the RCCL types this file needs (rccl.h: ncclResult_t is an enum, ncclComm_t an opaque pointer, ncclUniqueId 128 opaque bytes, ncclChar = 0)

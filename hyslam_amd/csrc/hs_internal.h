@@ -2,6 +2,8 @@
 // gfx950 (MI355X) only: wave64, 160 KiB LDS/CU.  Compiled with -ffp-contract=off: several results
 // (resize tables, fastAtan2, rBRIEF rotation) are defined by separately rounded fp32 operations.
 #pragma once
+#include <algorithm>
+#include <string>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -294,3 +296,66 @@ void hs_launch_bow_transform(int n, const uint8_t* d_desc, const int32_t* d_cb, 
 void hs_launch_search_init(const hs_frame_view& F2, const hs_keypoint* d_kps2, const uint8_t* d_desc2, const int8_t* d_cell2,
                            const hs_keypoint* d_kps1, const uint8_t* d_desc1, int n1, const float* d_prev_xy, float window, float th_low, float nnratio,
                            int32_t* d_owner, int32_t* d_odist, float* d_angle_scratch, int32_t* d_self_scratch, int32_t* d_n_matches, hipStream_t s);
+
+// ---- host entry points that work on a handle (hs_api.hip, kernels_landmark.hip, kernels_bow.hip, kernels_place.hip, hs_comm.hip) ----
+// hs_orb is opaque outside hs_api.hip; the other translation units reach it through these four accessors (defined in hs_api.hip).
+void hs_set_error(hs_orb* h, const char* msg);
+int hs_orb_device_of(const hs_orb* h);
+hipStream_t hs_orb_stream_of(const hs_orb* h);
+// claims `bytes` of the handle's grow-only device scratch arena and invalidates what an earlier claim handed out; a regrow synchronises the
+// handle's stream first.  nullptr on failure, the error text set (HS_ERR_HIP)
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes);
+
+inline int hs_fail(hs_orb* h, int code, const std::string& msg) { hs_set_error(h, msg.c_str()); return code; }
+// a failed HIP call leaves its code in the runtime's sticky "last error": it is cleared here so that the next successful call sequence on this
+// thread does not report it again through hipGetLastError()
+#define HIP_TRY(h, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); \
+    return hs_fail(h, HS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
+
+#define HS_STAGE_MAX_PIECES 17      // the largest user: bow_host (hs_api.hip)
+// bytes claimed past the last piece.  Unmeasured headroom: nobody has shown that anything needs it, nor that nothing does.
+#define HS_STAGE_SLACK 4096
+
+// The device side of one host-pointer call, laid out in the handle's scratch arena.  The caller registers every piece (element type, count and
+// what to copy; add() below is the only place a size is added up), begin() claims the arena for their sum, hands every piece its 256-byte
+// aligned address (distinct and valid also for a count of 0) and enqueues the uploads in registration order; after the launches finish() checks them, enqueues
+// the downloads in registration order and synchronises.  No heap allocation; one call at a time per handle (begin() invalidates the last layout).
+class HsStage {
+public:
+    explicit HsStage(hs_orb* h) : h_(h), s_(hs_orb_stream_of(h)) {}
+    hipStream_t stream() const { return s_; }
+    template <class T> void temp(T** d, size_t count) { add(d, count * sizeof(T), nullptr, nullptr, 0); }
+    // src == nullptr (an optional input that is absent): the piece is laid out, nothing is copied
+    template <class T> void in(T** d, size_t count, const T* src) { add(d, count * sizeof(T), src, nullptr, 0); }
+    // the first `n_back` of `count` elements come back to dst (default: all of them)
+    template <class T> void out(T** d, size_t count, T* dst, size_t n_back = SIZE_MAX) { add(d, count * sizeof(T), nullptr, dst, std::min(n_back, count) * sizeof(T)); }
+    template <class T> void inout(T** d, size_t count, T* host) { add(d, count * sizeof(T), host, host, count * sizeof(T)); }
+    int begin()
+    {
+        if (n_ > HS_STAGE_MAX_PIECES) return hs_fail(h_, HS_ERR_INVALID, "internal: a host call stages more than HS_STAGE_MAX_PIECES pieces");
+        uint8_t* base = hs_orb_scratch_of(h_, total_ + HS_STAGE_SLACK);
+        if (!base) return HS_ERR_HIP;
+        for (int i = 0; i < n_; i++) {
+            const Piece& p = p_[i];
+            *p.dev = base + p.off;
+            if (p.src && p.bytes) HIP_TRY(h_, hipMemcpyAsync(*p.dev, p.src, p.bytes, hipMemcpyHostToDevice, s_));
+        }
+        return HS_OK;
+    }
+    int finish()
+    {
+        HIP_TRY(h_, hipGetLastError());
+        for (int i = 0; i < n_; i++)
+            if (p_[i].back) HIP_TRY(h_, hipMemcpyAsync(p_[i].dst, *p_[i].dev, p_[i].back, hipMemcpyDeviceToHost, s_));
+        HIP_TRY(h_, hipStreamSynchronize(s_));
+        return HS_OK;
+    }
+private:
+    struct Piece { void** dev; size_t off, bytes, back; const void* src; void* dst; };
+    template <class T> void add(T** d, size_t bytes, const void* src, void* dst, size_t back)
+    {
+        if (n_ < HS_STAGE_MAX_PIECES) { p_[n_] = Piece{ reinterpret_cast<void**>(d), total_, bytes, back, src, dst }; total_ += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }
+        n_++;                       // past the capacity: begin() refuses
+    }
+    hs_orb* h_; hipStream_t s_; int n_ = 0; size_t total_ = 0; Piece p_[HS_STAGE_MAX_PIECES];
+};

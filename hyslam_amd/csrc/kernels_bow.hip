@@ -292,11 +292,7 @@ BowTree tree_of(const hs_vocab_dev* v)
 }
 }
 
-// ---- host side (declared in include/hyslam_amd.h); error text goes through hs_api.hip's handle via hs_set_error
-void hs_set_error(hs_orb* h, const char* msg);       // hs_api.hip
-int hs_orb_device_of(const hs_orb* h);              // hs_api.hip
-hipStream_t hs_orb_stream_of(const hs_orb* h);      // hs_api.hip
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes); // hs_api.hip
+// ---- host side (declared in include/hyslam_amd.h); error text goes through hs_api.hip's handle via hs_set_error (hs_internal.h)
 
 extern "C" {
 
@@ -422,22 +418,20 @@ int hs_bow_vector(hs_orb* h, const int32_t* word, const float* weight, int n, in
     *m = 0;
     if (n == 0) return HS_OK;
     if (hipSetDevice(hs_orb_device_of(h)) != hipSuccess) return HS_ERR_HIP;
-    const size_t b4 = ((size_t)n * 4 + 255) & ~(size_t)255, b8 = ((size_t)n * 8 + 255) & ~(size_t)255;
-    uint8_t* base = hs_orb_scratch_of(h, 3 * b4 + b8 + 256);
-    if (!base) return HS_ERR_HIP;
-    int32_t* d_w = reinterpret_cast<int32_t*>(base); float* d_wt = reinterpret_cast<float*>(base + b4);
-    int32_t* d_ow = reinterpret_cast<int32_t*>(base + 2 * b4); double* d_ov = reinterpret_cast<double*>(base + 3 * b4); int32_t* d_m = reinterpret_cast<int32_t*>(base + 3 * b4 + b8);
-    hipStream_t s = hs_orb_stream_of(h);
-    hipError_t e = hipMemcpyAsync(d_w, word, (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wt, weight, (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, hipGetErrorString(e)); return HS_ERR_HIP; }
-    const int st = bowv_launch(h, d_w, d_wt, nullptr, n, d_ow, d_ov, d_m, s);
+    HsStage stg(h);
+    int32_t *d_w, *d_ow, *d_m; float* d_wt; double* d_ov;
+    stg.in(&d_w, n, word); stg.in(&d_wt, n, weight); stg.temp(&d_ow, n); stg.temp(&d_ov, n); stg.temp(&d_m, 1);
+    int st = stg.begin();
+    if (st == HS_OK) st = bowv_launch(h, d_w, d_wt, nullptr, n, d_ow, d_ov, d_m, stg.stream());
     if (st != HS_OK) return st;
+    // two phases, so not HsStage::finish(): the count first, then that many entries
     int32_t mm = 0;
-    e = hipMemcpyAsync(&mm, d_m, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && mm > 0) { e = hipMemcpy(out_word, d_ow, (size_t)mm * 4, hipMemcpyDeviceToHost); if (e == hipSuccess) e = hipMemcpy(out_value, d_ov, (size_t)mm * 8, hipMemcpyDeviceToHost); }
-    if (e != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, hipGetErrorString(e)); return HS_ERR_HIP; }
+    HIP_TRY(h, hipMemcpyAsync(&mm, d_m, 4, hipMemcpyDeviceToHost, stg.stream()));
+    HIP_TRY(h, hipStreamSynchronize(stg.stream()));
+    if (mm > 0) {
+        HIP_TRY(h, hipMemcpy(out_word, d_ow, (size_t)mm * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(out_value, d_ov, (size_t)mm * 8, hipMemcpyDeviceToHost));
+    }
     *m = mm;
     return HS_OK;
 }

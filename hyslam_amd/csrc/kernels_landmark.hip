@@ -249,60 +249,17 @@ __global__ __launch_bounds__(256) void k_landmark_entries(LmEntryArgs a)
     }
 }
 
-// hs_api.hip (as for hs_comm.hip's entry points)
-void hs_set_error(hs_orb* h, const char* msg);
-int hs_orb_device_of(const hs_orb* h);
-hipStream_t hs_orb_stream_of(const hs_orb* h);
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes);
-
-static int lm_fail(hs_orb* h, int code, const char* msg) { hs_set_error(h, msg); return code; }
-#define LM_TRY(h, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); \
-    return lm_fail(h, HS_ERR_HIP, hipGetErrorString(e__)); } } while (0)
-static size_t lm_pad(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" {
 
 int hs_landmark_best_descriptors_device(hs_orb* h, const int64_t* d_offsets, const uint8_t* d_desc, int L, int32_t* d_best, int32_t* d_median, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
     if (L < 0 || (L > 0 && (!d_offsets || !d_desc || !d_best || !d_median)) || ((uintptr_t)d_desc & 15) || ((uintptr_t)d_offsets & 7))
-        return lm_fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (L == 0) return HS_OK;
-    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     launch_landmark_best(d_offsets, d_desc, L, d_best, d_median, true, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
-    LM_TRY(h, hipGetLastError());
-    return HS_OK;
-}
-
-int hs_landmark_best_descriptors(hs_orb* h, const int64_t* offsets, const uint8_t* desc, int L, int32_t* best, int32_t* median)
-{
-    if (!h) return HS_ERR_INVALID;
-    if (L < 0 || (L > 0 && (!offsets || !best || !median))) return lm_fail(h, HS_ERR_INVALID, "bad argument");
-    if (L == 0) return HS_OK;
-    bool any_large = false;
-    for (int i = 0; i < L; i++) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (offsets[i] < 0 || n < 0 || n > INT32_MAX) return lm_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing, N < 2^31");
-        any_large |= n > LM_SMALL;
-    }
-    const size_t total = (size_t)offsets[L];
-    if (total > 0 && !desc) return lm_fail(h, HS_ERR_INVALID, "bad argument");
-    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    const size_t b_off = lm_pad((size_t)(L + 1) * 8), b_desc = lm_pad(std::max(total, (size_t)1) * 32), b_out = lm_pad((size_t)L * 4);
-    uint8_t* base = hs_orb_scratch_of(h, b_off + b_desc + 2 * b_out);
-    if (!base) return HS_ERR_HIP;
-    int64_t* d_off = reinterpret_cast<int64_t*>(base);
-    uint8_t* d_desc = base + b_off;
-    int32_t* d_best = reinterpret_cast<int32_t*>(base + b_off + b_desc);
-    int32_t* d_med = reinterpret_cast<int32_t*>(base + b_off + b_desc + b_out);
-    hipStream_t s = hs_orb_stream_of(h);
-    LM_TRY(h, hipMemcpyAsync(d_off, offsets, (size_t)(L + 1) * 8, hipMemcpyHostToDevice, s));
-    if (total) LM_TRY(h, hipMemcpyAsync(d_desc, desc, total * 32, hipMemcpyHostToDevice, s));
-    launch_landmark_best(d_off, d_desc, L, d_best, d_med, any_large, s);
-    LM_TRY(h, hipGetLastError());
-    LM_TRY(h, hipMemcpyAsync(best, d_best, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipMemcpyAsync(median, d_med, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
 
@@ -310,10 +267,30 @@ static int lm_check_csr(hs_orb* h, const int64_t* off, int L, bool* any_large)
 {
     for (int i = 0; i < L; i++) {
         const int64_t n = off[i + 1] - off[i];
-        if (off[i] < 0 || n < 0 || n > INT32_MAX) return lm_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing, N < 2^31");
+        if (off[i] < 0 || n < 0 || n > INT32_MAX) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing, N < 2^31");
         if (any_large) *any_large |= n > LM_SMALL;
     }
     return HS_OK;
+}
+
+int hs_landmark_best_descriptors(hs_orb* h, const int64_t* offsets, const uint8_t* desc, int L, int32_t* best, int32_t* median)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (L < 0 || (L > 0 && (!offsets || !best || !median))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (L == 0) return HS_OK;
+    bool any_large = false;
+    int rc = lm_check_csr(h, offsets, L, &any_large);
+    if (rc != HS_OK) return rc;
+    const size_t total = (size_t)offsets[L];
+    if (total > 0 && !desc) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    HsStage st(h);
+    int64_t* d_off; uint8_t* d_desc; int32_t *d_best, *d_med;
+    st.in(&d_off, (size_t)L + 1, offsets); st.in(&d_desc, total * 32, desc); st.out(&d_best, L, best); st.out(&d_med, L, median);
+    rc = st.begin();
+    if (rc != HS_OK) return rc;
+    launch_landmark_best(d_off, d_desc, L, d_best, d_med, any_large, st.stream());
+    return st.finish();
 }
 
 int hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* params, int L, const hs_lm_entry_in* d_entries,
@@ -323,19 +300,19 @@ int hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* param
                                       hs_landmark* d_lms, const int32_t* d_lm_index, int n_lms, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!params || L < 0 || n_lms < 0 || (d_lms == nullptr) != (d_lm_index == nullptr)) return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!params || L < 0 || n_lms < 0 || (d_lms == nullptr) != (d_lm_index == nullptr)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (L == 0) return HS_OK;
     if (!d_entries || !d_obs_offsets || !d_obs || !d_desc_offsets || !d_desc || !d_normal || !d_min_dist || !d_max_dist || !d_mean_dist || !d_size ||
         !d_best || !d_median || !d_flags || ((uintptr_t)d_desc & 15) || ((uintptr_t)d_obs_offsets & 7) || ((uintptr_t)d_desc_offsets & 7) ||
         ((uintptr_t)d_entries & 3) || ((uintptr_t)d_obs & 3) || ((uintptr_t)d_lms & 3) || ((uintptr_t)d_lm_index & 3))
-        return lm_fail(h, HS_ERR_INVALID, "bad argument");
-    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     const hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
     const LmEntryArgs a{*params, L, d_entries, d_obs_offsets, d_obs, d_desc_offsets, d_desc, d_best,
                         d_normal, d_min_dist, d_max_dist, d_mean_dist, d_size, d_flags, d_lms, d_lm_index, n_lms};
     launch_landmark_best(d_desc_offsets, d_desc, L, d_best, d_median, true, s);
     hipLaunchKernelGGL(k_landmark_entries, dim3((L + 3) / 4), dim3(256), 0, s, a);
-    LM_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
 
@@ -345,55 +322,37 @@ int hs_landmark_update_entries(hs_orb* h, const hs_lm_entry_params* params, int 
                                int32_t* out_best, int32_t* out_median, int32_t* out_flags)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!params || L < 0) return lm_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!params || L < 0) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (L == 0) return HS_OK;
     if (!entries || !obs_offsets || !desc_offsets || !out_normal || !out_min_dist || !out_max_dist || !out_mean_dist || !out_size || !out_best ||
         !out_median || !out_flags)
-        return lm_fail(h, HS_ERR_INVALID, "bad argument");
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
     bool any_large = false;
     int st = lm_check_csr(h, obs_offsets, L, nullptr);
     if (st == HS_OK) st = lm_check_csr(h, desc_offsets, L, &any_large);
     if (st != HS_OK) return st;
     const size_t n_obs = (size_t)obs_offsets[L], n_desc = (size_t)desc_offsets[L];
-    if ((n_obs > 0 && !obs) || (n_desc > 0 && !desc)) return lm_fail(h, HS_ERR_INVALID, "bad argument");
-    LM_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    const size_t b_ent = lm_pad((size_t)L * sizeof(hs_lm_entry_in)), b_off = lm_pad((size_t)(L + 1) * 8);
-    const size_t b_obs = lm_pad(std::max(n_obs, (size_t)1) * sizeof(hs_lm_obs)), b_desc = lm_pad(std::max(n_desc, (size_t)1) * 32);
-    const size_t b_f = lm_pad((size_t)L * 4);
-    uint8_t* base = hs_orb_scratch_of(h, b_ent + 2 * b_off + b_obs + b_desc + lm_pad((size_t)L * 12) + 7 * b_f);
-    if (!base) return HS_ERR_HIP;
-    uint8_t* q = base;
-    auto take = [&q](size_t b) { uint8_t* r = q; q += b; return r; };
-    hs_lm_entry_in* d_ent = reinterpret_cast<hs_lm_entry_in*>(take(b_ent));
-    int64_t* d_ooff = reinterpret_cast<int64_t*>(take(b_off));
-    int64_t* d_doff = reinterpret_cast<int64_t*>(take(b_off));
-    hs_lm_obs* d_obs = reinterpret_cast<hs_lm_obs*>(take(b_obs));
-    uint8_t* d_desc = take(b_desc);
-    float* d_normal = reinterpret_cast<float*>(take(lm_pad((size_t)L * 12)));
-    float* d_f[4];
-    for (float*& p : d_f) p = reinterpret_cast<float*>(take(b_f));       // min_dist, max_dist, mean_dist, size
-    int32_t* d_i[3];
-    for (int32_t*& p : d_i) p = reinterpret_cast<int32_t*>(take(b_f));   // best, median, flags
-    const hipStream_t s = hs_orb_stream_of(h);
-    LM_TRY(h, hipMemcpyAsync(d_ent, entries, (size_t)L * sizeof(hs_lm_entry_in), hipMemcpyHostToDevice, s));
-    LM_TRY(h, hipMemcpyAsync(d_ooff, obs_offsets, (size_t)(L + 1) * 8, hipMemcpyHostToDevice, s));
-    LM_TRY(h, hipMemcpyAsync(d_doff, desc_offsets, (size_t)(L + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_obs) LM_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs * sizeof(hs_lm_obs), hipMemcpyHostToDevice, s));
-    if (n_desc) LM_TRY(h, hipMemcpyAsync(d_desc, desc, n_desc * 32, hipMemcpyHostToDevice, s));
+    if ((n_obs > 0 && !obs) || (n_desc > 0 && !desc)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    // the outputs the reference leaves unchanged for N = 0 come back through a host copy and are merged by flag
+    std::vector<float> nrm((size_t)L * 3), f3((size_t)L * 3);
+    HsStage stg(h);
+    hs_lm_entry_in* d_ent; int64_t *d_ooff, *d_doff; hs_lm_obs* d_obs; uint8_t* d_desc; float *d_normal, *d_f[4]; int32_t* d_i[3];
+    stg.in(&d_ent, L, entries); stg.in(&d_ooff, (size_t)L + 1, obs_offsets); stg.in(&d_doff, (size_t)L + 1, desc_offsets);
+    stg.in(&d_obs, n_obs, obs); stg.in(&d_desc, n_desc * 32, desc);
+    stg.out(&d_normal, (size_t)L * 3, nrm.data());
+    for (int k = 0; k < 3; k++) stg.out(&d_f[k], L, f3.data() + (size_t)k * L);       // min_dist, max_dist, mean_dist
+    stg.out(&d_f[3], L, out_size);
+    stg.out(&d_i[0], L, out_best); stg.out(&d_i[1], L, out_median); stg.out(&d_i[2], L, out_flags);
+    st = stg.begin();
+    if (st != HS_OK) return st;
+    const hipStream_t s = stg.stream();
     const LmEntryArgs a{*params, L, d_ent, d_ooff, d_obs, d_doff, d_desc, d_i[0],
                         d_normal, d_f[0], d_f[1], d_f[2], d_f[3], d_i[2], nullptr, nullptr, 0};
     launch_landmark_best(d_doff, d_desc, L, d_i[0], d_i[1], any_large, s);
     hipLaunchKernelGGL(k_landmark_entries, dim3((L + 3) / 4), dim3(256), 0, s, a);
-    LM_TRY(h, hipGetLastError());
-    // the outputs the reference leaves unchanged for N = 0 come back through a host copy and are merged by flag
-    std::vector<float> nrm((size_t)L * 3), f3((size_t)L * 3);
-    LM_TRY(h, hipMemcpyAsync(nrm.data(), d_normal, (size_t)L * 12, hipMemcpyDeviceToHost, s));
-    for (int k = 0; k < 3; k++) LM_TRY(h, hipMemcpyAsync(f3.data() + (size_t)k * L, d_f[k], (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipMemcpyAsync(out_size, d_f[3], (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipMemcpyAsync(out_best, d_i[0], (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipMemcpyAsync(out_median, d_i[1], (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipMemcpyAsync(out_flags, d_i[2], (size_t)L * 4, hipMemcpyDeviceToHost, s));
-    LM_TRY(h, hipStreamSynchronize(s));
+    st = stg.finish();
+    if (st != HS_OK) return st;
     for (int i = 0; i < L; i++) {
         if (!(out_flags[i] & HS_LM_SET_NORMAL_DEPTH)) continue;
         std::memcpy(out_normal + 3 * (size_t)i, nrm.data() + 3 * (size_t)i, 12);

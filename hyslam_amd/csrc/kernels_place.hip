@@ -184,11 +184,6 @@ __global__ __launch_bounds__(1024) void k_place_select(PlSelArgs a)
     }
 }
 
-// hs_api.hip
-void hs_set_error(hs_orb* h, const char* msg);
-int hs_orb_device_of(const hs_orb* h);
-hipStream_t hs_orb_stream_of(const hs_orb* h);
-
 struct hs_place_db {
     hs_orb* h = nullptr;
     int device = 0, n_words = 0;

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <map>
+#include <mutex>
 
 extern "C" {
 typedef int hipError_t;                     // hipSuccess = 0
@@ -25,8 +27,14 @@ hipError_t hipGetDevice(int* d) { *d = 0; return 0; }
 hipError_t hipDeviceSynchronize() { return 0; }
 hipError_t hipGetLastError() { return 0; }
 const char* hipGetErrorString(hipError_t) { return "hip_stub"; }
-hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
-hipError_t hipFree(void* p) { free(p); return 0; }
+// live "device" allocations, so that a test can put them back into the state a kernel-less run starts from (hip_stub_zero_device)
+static std::mutex g_dev_mu;
+static std::map<void*, size_t> g_dev;
+hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); if (*p) { std::lock_guard<std::mutex> g(g_dev_mu); g_dev[*p] = n; } return *p ? 0 : 2; }
+hipError_t hipFree(void* p) { { std::lock_guard<std::mutex> g(g_dev_mu); g_dev.erase(p); } free(p); return 0; }
+// no kernel writes the outputs here: a reused allocation would hand the host code the last call's uploads as "results" (indices, counts).  Zero
+// everything instead, as a fresh allocation is
+void hip_stub_zero_device() { std::lock_guard<std::mutex> g(g_dev_mu); for (auto& a : g_dev) memset(a.first, 0, a.second); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
 hipError_t hipHostFree(void* p) { free(p); return 0; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, int) { memcpy(d, s, n); return 0; }

@@ -3,7 +3,8 @@
 // host memory, launches = no-ops).  Covered: hs_orb_create's tables, configure_impl's geometry for a random sweep of frame sizes / scale factors /
 // level counts / cell sizes / feature counts (the sweep of tests/test_gpu_parity.py plus extremes): pyramid fusion, chain and deep-chain planners,
 // FAST work items (wide and narrow), quadtree key tables, workspace sizing and uploads; the host-pointer entry points' staging (extract, batch,
-// stereo, the matchers' CSR / scratch handling), the ingest ticket state machine (submit / wait, errors, both slots busy), and the vocabulary
+// stereo, the matchers' CSR / scratch handling, and a sweep of all thirteen entry points that stage through HsStage on ONE handle, so that its scratch
+// arena grows and is reused: staged_sweep), the ingest ticket state machine (submit / wait, errors, both slots busy), and the vocabulary
 // loaders on valid, truncated and randomly corrupted text / binary files (hs_vocab_last_error instead of stderr).
 // usage: host_sanitize [seed] [geometries] [vocab_cases]      prints "HOST SANITIZE OK ..." (any sanitizer report aborts with a non-zero status)
 #include <cstdio>
@@ -19,6 +20,7 @@
 void hs_orb_borrow(hs_orb* h, int delta);      // hs_api.hip (internal: what hs_comm_create / hs_comm_destroy call)
 
 extern "C" long hip_stub_launches();
+extern "C" void hip_stub_zero_device();
 void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/);        // hs_api.hip: launches of the pyramid's two plans, item counts (host-side facts of the last configuration)
 
 #define CHECK(c) do { if (!(c)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
@@ -114,6 +116,143 @@ static hs_vocab* make_vocab(int k, int levels, std::vector<int32_t>& cb, std::ve
 
 static std::vector<uint8_t> slurp(const std::string& p) { std::vector<uint8_t> b; FILE* f = fopen(p.c_str(), "rb"); if (!f) return b; int c; while ((c = fgetc(f)) != EOF) b.push_back((uint8_t)c); fclose(f); return b; }
 static void spit(const std::string& p, const std::vector<uint8_t>& b) { FILE* f = fopen(p.c_str(), "wb"); if (f) { if (!b.empty()) fwrite(b.data(), 1, b.size(), f); fclose(f); } }
+
+
+// ---- the thirteen host-pointer entry points that lay their device side out with HsStage (hs_internal.h), on ONE handle in a random order: the
+// scratch arena grows with the largest call so far and smaller calls reuse it.  Every count is drawn from [0, 300] (0 and 1 forced), every host
+// buffer is a std::vector of exactly the documented size (a copy of the wrong length is a sanitizer report), the optional inputs are toggled.
+// What this cannot see: an overrun that stays inside the arena (a piece running into its neighbour, or into HS_STAGE_SLACK) is no sanitizer report.
+static int cnt(int forced) { return forced >= 0 ? forced : rnd(0, 300); }
+static std::vector<hs_keypoint> rand_kps(int n, int w, int h)
+{
+    std::vector<hs_keypoint> k(n);
+    for (auto& q : k) q = hs_keypoint{ (float)rnd(0, w), (float)rnd(0, h), 31.f, (float)rnd(0, 359), 1.f, rnd(0, 7) };
+    return k;
+}
+static std::vector<uint8_t> rand_bytes(size_t n) { std::vector<uint8_t> b(n); for (auto& v : b) v = (uint8_t)rng(); return b; }
+static std::vector<hs_landmark> rand_lms(int n)
+{
+    std::vector<hs_landmark> lm(n);
+    for (auto& m : lm) { memset(&m, 0, sizeof(m)); m.pos[0] = (float)rnd(-3, 3); m.pos[2] = 5.f; m.size = 0.5f; m.max_dist = 100.f; m.assoc_kp = -1; }
+    return lm;
+}
+// a feature vector over n features: `nn` nodes with ascending ids, CSR lists of feature indices
+static void rand_featvec(int n, int nn, std::vector<int32_t>& id, std::vector<int32_t>& ptr, std::vector<int32_t>& idx)
+{
+    if (n == 0) nn = 0;                                      // (nodes need a non-null index list: the first node gets an entry)
+    id.resize(nn); ptr.assign((size_t)nn + 1, 0); idx.clear();
+    for (int a = 0, v = 0; a < nn; a++) { v += rnd(1, 3); id[a] = v; }
+    for (int a = 0; a < nn; a++) { const int m = rnd(a == 0, 3); for (int j = 0; j < m; j++) idx.push_back(rnd(0, n - 1)); ptr[a + 1] = (int32_t)idx.size(); }
+}
+// CSR offsets of L lists with 0..3 entries each
+static std::vector<int64_t> rand_csr(int L) { std::vector<int64_t> o((size_t)L + 1, 0); for (int i = 0; i < L; i++) o[i + 1] = o[i] + rnd(0, 3); return o; }
+
+static int staged_sweep(int rounds)
+{
+    hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300;
+    hs_orb *ex = nullptr, *h = nullptr;                          // ex extracts and publishes frames, h is the ONE handle of the sweep
+    CHECK(hs_orb_create(&p, 0, &ex) == HS_OK && hs_orb_create(&p, 0, &h) == HS_OK);
+    const int w = 320, hh = 240;
+    const std::vector<uint8_t> img = rand_bytes((size_t)w * hh);
+    CHECK(hs_orb_reserve(ex, w, hh, 1) == HS_OK);
+    const int cap = hs_orb_max_keypoints(ex);
+    CHECK(cap >= 300);
+    { std::vector<hs_keypoint> k(cap); std::vector<uint8_t> d((size_t)cap * 32); int32_t n = 0; CHECK(hs_orb_extract(ex, img.data(), w, hh, w, k.data(), d.data(), cap, &n) == HS_OK); }
+    hs_frame_view F0; memset(&F0, 0, sizeof(F0));
+    F0.fx = F0.fy = 300.f; F0.cx = 160.f; F0.cy = 120.f; F0.max_x = (float)w; F0.max_y = (float)hh; F0.size_ref = 31.f; F0.Rcw[0] = F0.Rcw[4] = F0.Rcw[8] = 1.f; F0.mbf = 40.f; F0.sensor = 1;
+    hs_proj_params pp; memset(&pp, 0, sizeof(pp)); pp.th = 3.f; pp.score_threshold = 100.f; pp.second_best_ratio = 0.8f; pp.frac_smaller = 0.5f; pp.frac_larger = 1.5f;
+    std::vector<int32_t> cb, cc, word; std::vector<uint8_t> vdesc; std::vector<float> weight;
+    { hs_vocab* v = make_vocab(3, 3, cb, cc, vdesc, word, weight); CHECK(v != nullptr); hs_vocab_destroy(v); }
+    const hs_lm_entry_params ep{ 2.0f, 0.5f };
+    const float Scw[12] = { 2, 0, 0, 0.1f, 0, 2, 0, 0.2f, 0, 0, 2, 0.3f }, R12[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t12[3] = { 0.1f, 0.f, 0.f }, F12[9] = { 0, 0, 0, 0, 0, -1, 0, 1, 0 };
+    int calls = 0;
+    for (int r = 0; r < rounds; r++) {
+        int order[14]; for (int i = 0; i < 14; i++) order[i] = i;
+        for (int i = 13; i > 0; i--) std::swap(order[i], order[rnd(0, i)]);
+        for (int oi = 0; oi < 14; oi++) {
+            const int forced = r == 0 ? 0 : (r == 1 ? 1 : -1);       // the first two rounds: every count 0, then every count 1
+            const int n = cnt(forced), n2 = cnt(forced), L = cnt(forced);
+            const bool opt_a = rnd(0, 1), opt_b = rnd(0, 1), opt_c = rnd(0, 1);
+            const std::vector<hs_keypoint> k1 = rand_kps(n, w, hh), k2 = rand_kps(n2, w, hh);
+            const std::vector<uint8_t> d1 = rand_bytes((size_t)n * 32), d2 = rand_bytes((size_t)n2 * 32);
+            const std::vector<float> uR(n, -1.f); const std::vector<int32_t> obs(n, -1);
+            hs_frame_view F = F0; F.n = n; F.kps = k1.data(); F.desc = d1.data(); F.uR = opt_a ? uR.data() : nullptr; F.kp_lm_obs = opt_b ? obs.data() : nullptr;
+            hs_frame_view G = F0; G.n = n2; G.kps = k2.data(); G.desc = d2.data();
+            pp.use_stereo = opt_a;
+            const std::vector<hs_landmark> lms = rand_lms(L);
+            std::vector<int32_t> mi(L); std::vector<float> md(L); int32_t nm = -1;
+            hip_stub_zero_device();
+            int st = HS_OK;
+            switch (order[oi]) {
+            case 0: st = hs_search_by_projection(h, &F, lms.data(), L, &pp, mi.data(), md.data(), &nm); break;
+            case 1: {                                                // a published frame of max(n, 1) keypoints
+                const int nf = std::max(n, 1);
+                const std::vector<hs_keypoint> kf = rand_kps(nf, w, hh); const std::vector<float> uf(nf, -1.f); const std::vector<int32_t> of(nf, -1);
+                hs_frame_token tok = 0;
+                CHECK(hs_frame_publish(ex, 0, kf.data(), nf, &tok) == HS_OK);
+                hs_frame_view P = F0; P.n = nf; P.uR = opt_a ? uf.data() : nullptr; P.kp_lm_obs = opt_b ? of.data() : nullptr;
+                st = hs_search_by_projection_frame(h, tok, &P, lms.data(), L, &pp, mi.data(), md.data(), &nm);
+                CHECK(hs_frame_release(0, tok) == HS_OK);
+                break; }
+            case 2: {                                                // "device" pointers are host memory under the stub; n, L >= 1 by contract
+                const int nf = std::max(n, 1), Lf = std::max(L, 1);
+                const std::vector<hs_keypoint> kf = rand_kps(nf, w, hh); const std::vector<uint8_t> df = rand_bytes((size_t)nf * 32);
+                const std::vector<float> uf(nf, -1.f); const std::vector<int32_t> of(nf, -1); const std::vector<hs_landmark> lf = rand_lms(Lf);
+                std::vector<int32_t> mf(Lf); std::vector<float> mdf(Lf);
+                hs_frame_view P = F0; P.n = nf; P.kps = kf.data(); P.desc = df.data(); P.uR = opt_a ? uf.data() : nullptr; P.kp_lm_obs = opt_b ? of.data() : nullptr;
+                st = hs_search_by_projection_device(h, &P, lf.data(), Lf, &pp, mf.data(), mdf.data(), &nm, nullptr);
+                break; }
+            case 3: { std::vector<int8_t> cell((size_t)n * 2); st = hs_frame_grid(h, &F, cell.data()); break; }
+            case 4: { std::vector<uint8_t> taken(n, 0); st = hs_search_by_projection_sim3(h, &F, Scw, lms.data(), L, 10, 50.f, taken.data(), mi.data(), &nm); break; }
+            case 5: {
+                const std::vector<hs_landmark> l1 = rand_lms(n), l2 = rand_lms(n2); std::vector<int32_t> m12(n);
+                st = hs_search_by_sim3(h, &F, l1.data(), &G, l2.data(), 1.1f, R12, t12, 7.5f, 100.f, m12.data(), &nm);
+                break; }
+            case 6: case 7: {                                       // bow_host through both of its doors
+                std::vector<int32_t> id1, p1, i1, id2, p2, i2, m12(n);
+                rand_featvec(n, cnt(forced), id1, p1, i1); rand_featvec(n2, cnt(forced), id2, p2, i2);
+                const std::vector<uint8_t> keep1(n, 1), keep2(n2, 1);
+                if (order[oi] == 6)
+                    st = hs_search_by_bow_ex(h, k1.data(), d1.data(), n, id1.data(), p1.data(), i1.data(), (int)id1.size(), k2.data(), d2.data(), n2, id2.data(), p2.data(), i2.data(), (int)id2.size(),
+                                             opt_a ? keep1.data() : nullptr, opt_b ? keep2.data() : nullptr, opt_c ? F12 : nullptr, 31.f, 1.f, 50.f, 0.6f, 1, m12.data(), &nm);
+                else
+                    st = hs_search_by_bow_legacy(h, k1.data(), d1.data(), n, id1.data(), p1.data(), i1.data(), (int)id1.size(), k2.data(), d2.data(), n2, id2.data(), p2.data(), i2.data(), (int)id2.size(),
+                                                 opt_a ? keep1.data() : nullptr, opt_b ? keep2.data() : nullptr, 50.f, 0.6f, 1, m12.data(), &nm);
+                break; }
+            case 8: { std::vector<float> prev((size_t)n * 2, 10.f); std::vector<int32_t> m12(n); st = hs_search_for_initialization(h, k1.data(), d1.data(), n, &G, prev.data(), 100, 50.f, 0.9f, m12.data(), &nm); break; }
+            case 9: {
+                const std::vector<int32_t> orig(cb.size(), 0);
+                const hs_vocab_tree T{ (int32_t)cb.size(), 3, cb.data(), cc.data(), vdesc.data(), word.data(), weight.data(), opt_a ? orig.data() : nullptr };
+                std::vector<int32_t> wi(n), ni(n); std::vector<float> wt(n);
+                st = hs_bow_transform(h, &T, d1.data(), n, 1, wi.data(), wt.data(), ni.data());
+                break; }
+            case 10: { std::vector<int32_t> bi(n), bd(n), sd(n); st = hs_hamming_knn2(h, d1.data(), n, d2.data(), n2, bi.data(), bd.data(), sd.data()); break; }
+            case 11: {
+                const std::vector<int64_t> off = rand_csr(L); const std::vector<uint8_t> dd = rand_bytes((size_t)off[L] * 32); std::vector<int32_t> best(L), med(L);
+                st = hs_landmark_best_descriptors(h, off.data(), dd.data(), L, best.data(), med.data());
+                break; }
+            case 12: {
+                const std::vector<int64_t> oo = rand_csr(L), od = rand_csr(L);
+                const std::vector<hs_lm_entry_in> ent(L); const std::vector<hs_lm_obs> ob((size_t)oo[L]); const std::vector<uint8_t> dd = rand_bytes((size_t)od[L] * 32);
+                std::vector<float> nrm((size_t)L * 3), mind(L), maxd(L), mean(L), size(L); std::vector<int32_t> best(L), med(L), flags(L);
+                st = hs_landmark_update_entries(h, &ep, L, ent.data(), oo.data(), ob.data(), od.data(), dd.data(), nrm.data(), mind.data(), maxd.data(), mean.data(), size.data(),
+                                                best.data(), med.data(), flags.data());
+                break; }
+            case 13: {
+                std::vector<int32_t> wd(n), ow(n); const std::vector<float> wt(n, 1.f); std::vector<double> ov(n); int32_t m = -1;
+                for (auto& v : wd) v = rnd(0, 50);
+                st = hs_bow_vector(h, wd.data(), wt.data(), n, ow.data(), ov.data(), &m);
+                CHECK(m == 0);
+                break; }
+            }
+            if (st != HS_OK) { printf("staged sweep: entry point %d, n %d n2 %d L %d: status %d (%s)\n", order[oi], n, n2, L, st, hs_orb_last_error(h)); return 1; }
+            calls++;
+        }
+    }
+    hs_orb_destroy(ex); hs_orb_destroy(h);
+    CHECK(hs_frame_cache_clear(0) == HS_OK);
+    return calls > 0 ? 0 : 1;
+}
 
 int main(int argc, char** argv)
 {
@@ -249,6 +388,8 @@ int main(int argc, char** argv)
         CHECK(hs_frame_cache_clear(0) == HS_OK && hs_frame_cache_clear(0) == HS_OK && hs_frame_cache_clear(3) == HS_OK);      // (LeakSanitizer: nothing of the cache may outlive this)
         CHECK(hs_frame_info(0, latest.load(), &ninfo) != HS_OK);
     }
+
+    CHECK(staged_sweep(12) == 0);
 
     // ---- vocabulary files: valid round trips, then truncations and random corruptions of both formats
     char dir[] = "/tmp/hs_host_sanitize_XXXXXX";
