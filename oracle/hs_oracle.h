@@ -23,6 +23,10 @@
  * error), the disc table and the rBRIEF pattern (exact), the steered-BRIEF bits (identical on
  * the test frame; double vs float rotation tolerated); PyTorch for the geometry of resize and
  * blur (tests/test_skimage_crosscheck.py).
+ * How the primitives are put together (scale tables and quotas, level sizes, the cell loop and its skip rules, the retry, candidate order,
+ * border offset, keypoint size and coordinate scaling, empty levels) is restated independently as well, in numpy: tests/ref_extract.py, held
+ * against this file bit for bit on directed scenes (tests/test_extract_ref.py).  The OpenCV primitives themselves are still not pinned against a
+ * real OpenCV.
  *
  * Documented deviations from the (non-deterministic / UB) reference behaviour:
  *   D1  DistributeOctTree sorts pair<int,ExtractorNode*> (src/features/ORBExtractor.cpp:321-324),
