@@ -5,6 +5,7 @@
 // distribution -> blur+orientation+rBRIEF, 10 kernel launches for an 8-level pyramid regardless of batch size.
 #include "hs_internal.h"
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -13,6 +14,51 @@
 #include <vector>
 
 #define HS_VERSION "hyslam_amd 0.1 (gfx950)"
+
+// One owned allocation — device memory, or page-locked host memory with Pinned — and its capacity in elements of T.  Grow-only; it never
+// synchronises by itself: whoever regrows a buffer that enqueued work may still use passes the stream to drain (or waits for its own event) first.
+template <class T, bool Pinned = false> struct HsBuf {
+    T* p = nullptr; size_t cap = 0;
+    HsBuf() = default;
+    HsBuf(const HsBuf&) = delete; HsBuf& operator=(const HsBuf&) = delete;
+    HsBuf(HsBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    HsBuf& operator=(HsBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~HsBuf() { release(); }
+    void release() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+    // room for `count` elements; the contents do not survive a regrow, and a failed one leaves the buffer empty
+    hipError_t grow(size_t count)
+    {
+        if (count <= cap) return hipSuccess;
+        release();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, count * sizeof(T));
+        if (e != hipSuccess) p = nullptr; else cap = count;
+        return e;
+    }
+    hipError_t grow(size_t count, hipStream_t drain)          // ... after everything enqueued on `drain` has finished
+    {
+        if (count <= cap) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(drain);
+        return e != hipSuccess ? e : grow(count);
+    }
+    operator T*() const { return p; }
+};
+template <class T> using HsPinned = HsBuf<T, true>;
+
+// level-0 frames of a host-pointer call in HBM (d_in), and the camera's frames as uploaded, before PreProcessImg on the device (d_raw)
+struct HsFrameStaging { HsBuf<uint8_t> d_in, d_raw; };
+// uRight / depth / best distance of the stereo matcher: three arrays that grow on one count
+struct HsStereoOut {
+    HsBuf<float> ur, depth; HsBuf<int32_t> bd;
+    hipError_t grow(size_t entries, hipStream_t drain)
+    {
+        if (entries <= ur.cap && entries <= depth.cap && entries <= bd.cap) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(drain);
+        if (e == hipSuccess) e = ur.grow(entries);
+        if (e == hipSuccess) e = depth.grow(entries);
+        if (e == hipSuccess) e = bd.grow(entries);
+        return e;
+    }
+};
 
 struct hs_orb {
     hs_orb_params p;
@@ -36,79 +82,77 @@ struct hs_orb {
     // ORBExtractor ctor tables (ORBExtractor.cpp:86-118)
     std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
     std::vector<int> quota;
-    // geometry currently configured
-    int w = 0, h = 0, batch_cap = 0;
-    std::vector<HsLevel> lv;
+    std::vector<HsLevel> lv;           // the levels of the last configure() attempt
     std::vector<HsLevel> lv_n;         // the same levels with the NARROW FAST work items (grp_cells / ngroups / item_begin differ); device copy at d_lv + nlevels
-    int total_cells = 0, max_wcell = 1, max_hcell = 1;
-    int fast_items = 0;                // FAST work items per image (HsLevel::item_begin)
-    int fast_items_n = 0;              // narrow items per image; 0 = no narrow list (a cell wider than the narrow tile)
-    uint64_t cand_img_stride = 0;      // candidate entries per image
-    int sel_img_stride = 0;            // selection entries per image
-    int max_kp = 0;
-    // device memory
-    HsLevel* d_lv = nullptr;
-    HsFastItem* d_fast_items = nullptr;
-    HsFastItem* d_fast_items_n = nullptr;
-    uint32_t* d_fast_ovf = nullptr;
-    uint8_t* d_pyr = nullptr; size_t pyr_bytes = 0;
-    int16_t* d_tables = nullptr;
-    uint8_t* d_qt_tabs = nullptr;      // geometric-key tables of the count-domain quadtree (hs_quadtree_build_tables)
-    // round 4: the FAST kernel computes the candidates' geometric keys and leaves their histogram + the best candidate per deepest cell in global
-    // memory (HsFastQt, HsLevel::qt_hist_off): u16 key tables, the per-level records, the two arrays ([batch][stride]; all zero between calls:
-    // the quadtree kernel zeroes what it consumes)
-    uint16_t* d_qkeys = nullptr; HsFastQt* d_fast_qt = nullptr;
-    uint32_t* d_qhist = nullptr; unsigned long long* d_qbest = nullptr; uint32_t qhist_stride = 0, qbest_stride = 0;
+    // Everything configure() builds for one frame size and batch capacity.  free_geometry() is `geo = Geometry{}`: the buffers free themselves and
+    // w = h = batch_cap = 0 says that nothing is configured.
+    struct Geometry {
+        int w = 0, h = 0, batch_cap = 0;
+        int total_cells = 0, max_wcell = 1, max_hcell = 1;
+        int fast_items = 0;                // FAST work items per image (HsLevel::item_begin)
+        int fast_items_n = 0;              // narrow items per image; 0 = no narrow list (a cell wider than the narrow tile)
+        uint64_t cand_img_stride = 0;      // candidate entries per image
+        int sel_img_stride = 0;            // selection entries per image
+        int max_kp = 0;
+        HsBuf<HsFastItem> d_fast_items, d_fast_items_n;
+        HsBuf<uint32_t> d_fast_ovf;
+        HsBuf<uint8_t> d_pyr;
+        HsBuf<int16_t> d_tables;
+        HsBuf<uint8_t> d_qt_tabs;          // geometric-key tables of the count-domain quadtree (hs_quadtree_build_tables)
+        // round 4: the FAST kernel computes the candidates' geometric keys and leaves their histogram + the best candidate per deepest cell in global
+        // memory (HsFastQt, HsLevel::qt_hist_off): u16 key tables, the per-level records, the two arrays ([batch][stride]; all zero between calls:
+        // the quadtree kernel zeroes what it consumes)
+        HsBuf<uint16_t> d_qkeys; HsBuf<HsFastQt> d_fast_qt;
+        HsBuf<uint32_t> d_qhist; HsBuf<unsigned long long> d_qbest; uint32_t qhist_stride = 0, qbest_stride = 0;
+        HsBuf<uint8_t> d_qt_rects;         // qt_large: batch_cap * nlevels * hs_quadtree_large_scratch_bytes()
+        bool keys_dirty = false;           // a keyed call was enqueued and did not reach its end (any error return of run_extract): d_qhist / d_qbest may hold stale keys -> zeroed before the next call
+        HsBuf<uint8_t> d_pyr_tabs;         // tile / row records of the two-level pyramid kernel (hs_pyramid_build_tables)
+        std::vector<HsPyrFuse> pyr_fuse;   // [level]: kernel argument of the pair (level, level + 1) when it is fused
+        std::vector<HsPyrChain> pyr_deep;  // [level]: the small-batch plan — chains as long as the LDS allows (8 levels: all seven in ONE launch); valid = 0 where none starts
+        std::vector<HsPyrChain> pyr_chain; // [level]: kernel argument of the chain launch that starts at this level (HsLevel::chain_n levels)
+        HsBuf<uint2> d_cand; HsBuf<uint32_t> d_pts_xy, d_pts_sk; HsBuf<uint16_t> d_pt_node;
+        HsBuf<int32_t> d_cand_count, d_sel_count, d_cell_count;
+        HsBuf<uint32_t> d_sel;
+        HsBuf<uint16_t> d_sel_perm;        // spatial order of every level's selection (describe stage)
+    } geo;
+    HsBuf<HsLevel> d_lv;               // [2][HS_MAX_LEVELS]: lv, then lv_n
+    HsBuf<uint16_t> d_taps;
     int fast_keys_levels = HS_MAX_LEVELS;   // HS_FAST_KEYS_LEVELS (read once; tuning): only the levels 0 .. n-1 get keys
     int fast_keys_max_batch = 16;      // HS_FAST_KEYS_MAX_BATCH (read once): calls of more frames than this run without the keys (see run_extract)
     bool qt_large = false;             // a level's quota + 8 exceeds HS_QT_MAX_NODES (up to HS_QT_LARGE_NODES): the quadtree kernel's large-list instance, rectangles in d_qt_rects
-    uint8_t* d_qt_rects = nullptr;     // qt_large: batch_cap * nlevels * hs_quadtree_large_scratch_bytes()
     bool qt_small_ok = false;          // every level's list (quota + 8 nodes) fits the quadtree kernel's small instance (two workgroups per CU; HS_QT_SMALL=0 switches it off, read once)
-    bool keys_dirty = false;           // a keyed call was enqueued and did not reach its end (any error return of run_extract): d_qhist / d_qbest may hold stale keys -> zeroed before the next call
     bool fast_keys = true;             // HS_FAST_KEYS=0 (read once): the quadtree kernel gathers the candidates and computes the keys itself (the scheme until round 3)
     bool keep_points = false;          // hs_orb_set_debug(h, 1): the quadtree kernel also gathers the candidates into the dense point arrays (hs_orb_debug_candidates reads them)
-    uint8_t* d_pyr_tabs = nullptr;     // tile / row records of the two-level pyramid kernel (hs_pyramid_build_tables)
-    std::vector<HsPyrFuse> pyr_fuse;   // [level]: kernel argument of the pair (level, level + 1) when it is fused
-    std::vector<HsPyrChain> pyr_deep;  // [level]: the small-batch plan — chains as long as the LDS allows (8 levels: all seven in ONE launch); valid = 0 where none starts
     int deep_rows = 8;                 // HS_PYRAMID_DEEP_ROWS (read once): rows of the LAST level per tile in the small-batch plan (a workgroup's stages are a dependent
                                        // sequence whose length goes with the rows per wave: more, flatter tiles shorten the launch although their halo rows cost more work)
     int deep_max_batch = 2;            // HS_PYRAMID_DEEP_MAX (read once): calls of at most this many frames use the small-batch plan (0 = never)
-    std::vector<HsPyrChain> pyr_chain; // [level]: kernel argument of the chain launch that starts at this level (HsLevel::chain_n levels)
     int pyr_tbx_max = 0;               // HS_PYRAMID_TBX_MAX (read once): cap on the level-B tile width of the two-level kernel (experiment: lane utilisation against time)
     int chain_mode = -1;               // HS_PYRAMID_CHAIN (read once): -1 = a three-level chain for the tail of an odd number of levels, 0 = never, 2 = chains for every fused pair too (parity tests)
-    uint2* d_cand = nullptr; uint32_t *d_pts_xy = nullptr, *d_pts_sk = nullptr; uint16_t* d_pt_node = nullptr;
-    int32_t *d_cand_count = nullptr, *d_sel_count = nullptr, *d_cell_count = nullptr;
-    uint32_t* d_sel = nullptr;
-    uint16_t* d_sel_perm = nullptr;    // spatial order of every level's selection (describe stage)
-    uint16_t* d_taps = nullptr;
-    // staging for the host-pointer entry points
-    uint8_t* d_in = nullptr; size_t in_bytes = 0; size_t in_pitch = 0;
-    uint8_t* d_raw = nullptr; size_t raw_bytes = 0;      // hs_orb_extract_camera_batch: the camera's frames as uploaded (before PreProcessImg on the device)
-    hs_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr; int32_t* d_n = nullptr; int out_cap = 0, out_batch = 0;
-    float *d_ur = nullptr, *d_depth = nullptr; int32_t* d_bd = nullptr; size_t st_entries = 0;
-    int32_t* d_strip_count = nullptr; void* d_strip_list = nullptr; size_t strip_count_entries = 0, strip_list_entries = 0;
+    // staging for the host-pointer entry points (regrown behind a drained `stream`)
+    HsFrameStaging in;
+    HsBuf<uint8_t> d_out;              // one block [counts | keypoints | descriptors] (out_layout), so that the results come back in ONE device-to-host copy
+    HsStereoOut st;
+    HsBuf<int32_t> d_strip_count; HsBuf<HsStripEntry> d_strip_list;      // two capacities: the counters (pairs * strips) and the lists (pairs * strips * cap) grow independently
     // persistent staging of hs_stereo_match (host-pointer call): device keypoints / descriptors / counts and one pinned host block
-    hs_keypoint* d_sm_kps = nullptr; uint8_t* d_sm_desc = nullptr; int32_t* d_sm_n = nullptr; int sm_cap = 0;
-    uint8_t* h_pin = nullptr; size_t pin_bytes = 0;
+    HsBuf<hs_keypoint> d_sm_kps; HsBuf<uint8_t> d_sm_desc; HsBuf<int32_t> d_sm_n;
+    HsPinned<uint8_t> h_pin;
     // hs_orb_extract_batch (host-pointer call): one pinned block the three outputs come back into
-    uint8_t* h_pin_out = nullptr; size_t pin_out_bytes = 0;
+    HsPinned<uint8_t> h_pin_out;
     int last_batch = 0; HsImg0 last_img0{};
     int last_pyr_launches = 0;         // kernel launches the pyramid stage of the last call really enqueued (hs_launch_pyramid's return value)
     int last_stereo_launches = 2;      // launches of stage 4 in the last stereo call: strips + match (run_stereo) or match only (the front end with the strips inside the describe launch)
     // where the last host-pointer extraction (hs_orb_extract[_batch], hs_orb_wait) left its results on the DEVICE: what hs_frame_publish keeps
     const hs_keypoint* pub_kps = nullptr; const uint8_t* pub_desc = nullptr; int pub_cap = 0, pub_batch = 0;
     // grow-only scratch arena of the host-pointer entry points (HsStage, hs_internal.h)
-    uint8_t* d_scratch = nullptr; size_t scratch_bytes = 0;
+    HsBuf<uint8_t> d_scratch;
     // pipelined host ingest (hs_orb_submit_batch / hs_orb_wait): two staging slots, a copy-in and a copy-out stream next to the compute stream
     struct IngestSlot {
-        uint8_t* d_in = nullptr; size_t in_bytes = 0;          // frames of the batch in HBM
-        uint8_t* d_raw = nullptr; size_t raw_bytes = 0;        // hs_orb_submit_camera_batch: the camera's frames as uploaded (before PreProcessImg)
-        uint8_t* d_out = nullptr; size_t out_bytes = 0;        // [counts | keypoints | descriptors | uRight | depth] in HBM
-        uint8_t* h_out = nullptr; size_t h_out_bytes = 0;      // the same block in page-locked host memory
+        HsFrameStaging in;                 // frames of the batch in HBM (regrown while the slot is idle: nothing to wait for)
+        HsBuf<uint8_t> d_out;              // [counts | keypoints | descriptors | uRight | depth] in HBM (out_layout)
+        HsPinned<uint8_t> h_out;           // the same block in page-locked host memory
         hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_out = nullptr;
         int32_t ticket = 0; bool busy = false;
         int batch = 0, pairs = 0, cap = 0;
-        size_t off_k = 0, off_d = 0, off_u = 0, off_z = 0, used = 0;
     } slot[2];
     hipStream_t s_in = nullptr, s_out = nullptr;
     int32_t next_ticket = 1;
@@ -135,32 +179,15 @@ void mark(hs_orb* h, int stage, hipStream_t s)
     h->prof_stage.push_back(stage);
 }
 
-void free_geometry(hs_orb* h)
-{
-    hipFree(h->d_pyr); h->d_pyr = nullptr;
-    hipFree(h->d_tables); h->d_tables = nullptr;
-    hipFree(h->d_pyr_tabs); h->d_pyr_tabs = nullptr; h->pyr_fuse.clear(); h->pyr_chain.clear(); h->pyr_deep.clear();
-    hipFree(h->d_qt_tabs); h->d_qt_tabs = nullptr;
-    hipFree(h->d_qkeys); h->d_qkeys = nullptr; hipFree(h->d_fast_qt); h->d_fast_qt = nullptr;
-    hipFree(h->d_qhist); h->d_qhist = nullptr; hipFree(h->d_qbest); h->d_qbest = nullptr; h->qhist_stride = h->qbest_stride = 0; h->keys_dirty = false;
-    hipFree(h->d_fast_items); h->d_fast_items = nullptr;
-    hipFree(h->d_fast_items_n); h->d_fast_items_n = nullptr; h->fast_items_n = 0;
-    hipFree(h->d_fast_ovf); h->d_fast_ovf = nullptr;
-    hipFree(h->d_qt_rects); h->d_qt_rects = nullptr;
-    hipFree(h->d_cand); hipFree(h->d_pts_xy); hipFree(h->d_pts_sk); hipFree(h->d_pt_node); hipFree(h->d_cell_count);
-    h->d_cand = nullptr; h->d_pts_xy = h->d_pts_sk = nullptr; h->d_pt_node = nullptr; h->d_cell_count = nullptr;
-    hipFree(h->d_cand_count); hipFree(h->d_sel_count); h->d_cand_count = h->d_sel_count = nullptr;
-    hipFree(h->d_sel); h->d_sel = nullptr;
-    hipFree(h->d_sel_perm); h->d_sel_perm = nullptr;
-    // nothing is configured any more: a failed configure() must not leave a geometry that the early exit would accept
-    h->w = h->h = h->batch_cap = 0; h->max_kp = 0; h->total_cells = 0; h->fast_items = 0;
-}
+// nothing is configured any more (w = h = batch_cap = 0) and the buffers of the geometry are freed: a failed configure() must not leave a
+// geometry that the early exit would accept
+void free_geometry(hs_orb* h) { h->geo = hs_orb::Geometry{}; }
 
 // (Re)build per-level geometry, tables and workspace for batches of `batch` frames of w x h.
 int configure_impl(hs_orb* h, int w, int hh, int batch);
 int configure(hs_orb* h, int w, int hh, int batch)
 {
-    if (w == h->w && hh == h->h && batch <= h->batch_cap) return HS_OK;
+    if (w == h->geo.w && hh == h->geo.h && batch <= h->geo.batch_cap) return HS_OK;
     if (w < 1 || hh < 1 || w > 16384 || hh > 16384 || batch < 1 || batch > 65535)
         return hs_fail(h, HS_ERR_INVALID, "image size / batch out of range");
     const int rc = configure_impl(h, w, hh, batch);
@@ -171,6 +198,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
 {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_geometry(h);                  // also un-configures: every failure return below leaves w = h = batch_cap = 0
+    hs_orb::Geometry& g = h->geo;
     const int L = h->p.nlevels;
     h->lv.assign(L, HsLevel{});
     std::vector<int16_t> tables;
@@ -246,9 +274,9 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         }
     }
     pyr_per_img = (pyr_per_img + 255) & ~(size_t)255;
-    h->max_wcell = h->max_hcell = 1;
-    for (int l = 0; l < L; l++) { h->max_wcell = std::max(h->max_wcell, h->lv[l].wcell); h->max_hcell = std::max(h->max_hcell, h->lv[l].hcell); }
-    h->total_cells = cells; h->fast_items = items; h->cand_img_stride = cand; h->sel_img_stride = sel; h->max_kp = sel;
+    g.max_wcell = g.max_hcell = 1;
+    for (int l = 0; l < L; l++) { g.max_wcell = std::max(g.max_wcell, h->lv[l].wcell); g.max_hcell = std::max(g.max_hcell, h->lv[l].hcell); }
+    g.total_cells = cells; g.fast_items = items; g.cand_img_stride = cand; g.sel_img_stride = sel; g.max_kp = sel;
     // Order of the FAST work items of an image: the REDUCED levels first, deepest level first, level 0 last.  An item of a reduced level
     // costs 2-3 times an item of level 0 (the same number of pixels, denser corners), and the persistent FAST kernel walks the items in this
     // order: with the cheap, uniform level-0 items at the end of every queue the tail of the launch — waves finishing their last item while
@@ -264,36 +292,36 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     };
     order_items(h->lv);
 
-    HIP_TRY(h, hipMalloc(&h->d_pyr, std::max<size_t>(pyr_per_img * batch, 256)));
-    HIP_TRY(h, hipMalloc(&h->d_tables, std::max<size_t>(tables.size() * sizeof(int16_t), 256)));
-    if (!tables.empty()) HIP_TRY(h, hipMemcpy(h->d_tables, tables.data(), tables.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, g.d_pyr.grow(std::max<size_t>(pyr_per_img * batch, 256)));
+    HIP_TRY(h, g.d_tables.grow(std::max<size_t>(tables.size(), 256 / sizeof(int16_t))));
+    if (!tables.empty()) HIP_TRY(h, hipMemcpy(g.d_tables, tables.data(), tables.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     const size_t ce = std::max<uint64_t>(cand * batch, 64);
-    HIP_TRY(h, hipMalloc(&h->d_cand, ce * 8));
-    HIP_TRY(h, hipMalloc(&h->d_pts_xy, ce * 4));
-    HIP_TRY(h, hipMalloc(&h->d_pts_sk, ce * 4));
-    HIP_TRY(h, hipMalloc(&h->d_pt_node, ce * 2));
-    if (h->qt_large) HIP_TRY(h, hipMalloc(&h->d_qt_rects, (size_t)batch * L * hs_quadtree_large_scratch_bytes()));
-    HIP_TRY(h, hipMalloc(&h->d_cell_count, std::max<size_t>((size_t)cells * batch * 4, 64)));
-    HIP_TRY(h, hipMalloc(&h->d_cand_count, (size_t)batch * L * 4));
-    HIP_TRY(h, hipMalloc(&h->d_sel_count, (size_t)batch * L * 4));
-    HIP_TRY(h, hipMalloc(&h->d_sel, std::max<size_t>((size_t)sel * batch * 12, 64)));
-    HIP_TRY(h, hipMalloc(&h->d_sel_perm, std::max<size_t>((size_t)sel * batch * 2, 64)));
+    HIP_TRY(h, g.d_cand.grow(ce));
+    HIP_TRY(h, g.d_pts_xy.grow(ce));
+    HIP_TRY(h, g.d_pts_sk.grow(ce));
+    HIP_TRY(h, g.d_pt_node.grow(ce));
+    if (h->qt_large) HIP_TRY(h, g.d_qt_rects.grow((size_t)batch * L * hs_quadtree_large_scratch_bytes()));
+    HIP_TRY(h, g.d_cell_count.grow(std::max<size_t>((size_t)cells * batch, 64 / 4)));
+    HIP_TRY(h, g.d_cand_count.grow((size_t)batch * L));
+    HIP_TRY(h, g.d_sel_count.grow((size_t)batch * L));
+    HIP_TRY(h, g.d_sel.grow(std::max<size_t>((size_t)sel * batch * 3, 64 / 4)));          // 12 bytes per selection entry
+    HIP_TRY(h, g.d_sel_perm.grow(std::max<size_t>((size_t)sel * batch, 64 / 2)));
     for (int l = 0; l < L; l++) {
         HsLevel& V = h->lv[l];
         V.img_stride = pyr_per_img;
-        V.base = l > 0 ? h->d_pyr + pyr_off[l] : nullptr;
+        V.base = l > 0 ? g.d_pyr + pyr_off[l] : nullptr;
         if (l > 0) {
-            V.xofs = h->d_tables + tab_off[4 * l]; V.ialpha = h->d_tables + tab_off[4 * l + 1];
-            V.yofs = h->d_tables + tab_off[4 * l + 2]; V.ibeta = h->d_tables + tab_off[4 * l + 3];
+            V.xofs = g.d_tables + tab_off[4 * l]; V.ialpha = g.d_tables + tab_off[4 * l + 1];
+            V.yofs = g.d_tables + tab_off[4 * l + 2]; V.ibeta = g.d_tables + tab_off[4 * l + 3];
         }
     }
     {   // geometric-key tables of the quadtree kernel
         std::vector<uint8_t> qblob;
         std::vector<size_t> xo(L, 0), yo2(L, 0); std::vector<char> has(L, 0);
         for (int l = 0; l < L; l++) has[l] = hs_quadtree_build_tables(h->lv[l], qblob, xo[l], yo2[l]) ? 1 : 0;
-        HIP_TRY(h, hipMalloc(&h->d_qt_tabs, std::max<size_t>(qblob.size() + 16, 256)));
-        if (!qblob.empty()) HIP_TRY(h, hipMemcpy(h->d_qt_tabs, qblob.data(), qblob.size(), hipMemcpyHostToDevice));
-        for (int l = 0; l < L; l++) if (has[l]) { h->lv[l].qt_xtab = h->d_qt_tabs + xo[l]; h->lv[l].qt_ytab = h->d_qt_tabs + yo2[l]; }
+        HIP_TRY(h, g.d_qt_tabs.grow(std::max<size_t>(qblob.size() + 16, 256)));
+        if (!qblob.empty()) HIP_TRY(h, hipMemcpy(g.d_qt_tabs, qblob.data(), qblob.size(), hipMemcpyHostToDevice));
+        for (int l = 0; l < L; l++) if (has[l]) { h->lv[l].qt_xtab = g.d_qt_tabs + xo[l]; h->lv[l].qt_ytab = g.d_qt_tabs + yo2[l]; }
         // the FAST kernel's side of the same keys (HsFastQt): u16 tables  xkey[x] = root(x) << 2 DH | spread(xtab[x]),  ykey[y] = spread(ytab[y]) << 1,
         // padded by 512 entries, and this level's place in the per-image histogram / best-candidate arrays
         auto spread = [](uint32_t v) { v = (v | (v << 4)) & 0x0F0Fu; v = (v | (v << 2)) & 0x3333u; v = (v | (v << 1)) & 0x5555u; return v; };
@@ -319,18 +347,18 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
             hoff += (uint32_t)(ncell / 2); boff += (uint32_t)ncell;
             fq[l].hist_off = V.qt_hist_off; fq[l].best_off = V.qt_best_off; fq[l].enabled = 1;
         }
-        h->qhist_stride = hoff; h->qbest_stride = boff;
-        HIP_TRY(h, hipMalloc(&h->d_qkeys, std::max<size_t>(keys.size() * 2 + 16, 256)));
-        if (!keys.empty()) HIP_TRY(h, hipMemcpy(h->d_qkeys, keys.data(), keys.size() * 2, hipMemcpyHostToDevice));
-        for (int l = 0; l < L; l++) if (fq[l].enabled) { fq[l].xkey = h->d_qkeys + kx[l]; fq[l].ykey = h->d_qkeys + ky[l]; }
-        HIP_TRY(h, hipMalloc(&h->d_fast_qt, sizeof(HsFastQt) * HS_MAX_LEVELS));
-        HIP_TRY(h, hipMemcpy(h->d_fast_qt, fq.data(), sizeof(HsFastQt) * L, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(&h->d_qhist, std::max<size_t>((size_t)hoff * batch * 4, 256)));
-        HIP_TRY(h, hipMalloc(&h->d_qbest, std::max<size_t>((size_t)boff * batch * 8, 256)));
+        g.qhist_stride = hoff; g.qbest_stride = boff;
+        HIP_TRY(h, g.d_qkeys.grow(std::max<size_t>(keys.size() + 16 / 2, 256 / 2)));
+        if (!keys.empty()) HIP_TRY(h, hipMemcpy(g.d_qkeys, keys.data(), keys.size() * 2, hipMemcpyHostToDevice));
+        for (int l = 0; l < L; l++) if (fq[l].enabled) { fq[l].xkey = g.d_qkeys + kx[l]; fq[l].ykey = g.d_qkeys + ky[l]; }
+        HIP_TRY(h, g.d_fast_qt.grow(HS_MAX_LEVELS));
+        HIP_TRY(h, hipMemcpy(g.d_fast_qt, fq.data(), sizeof(HsFastQt) * L, hipMemcpyHostToDevice));
+        HIP_TRY(h, g.d_qhist.grow(std::max<size_t>((size_t)hoff * batch, 256 / 4)));
+        HIP_TRY(h, g.d_qbest.grow(std::max<size_t>((size_t)boff * batch, 256 / 8)));
         // (on the handle's stream: hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which the handle's non-blocking
         //  streams are not ordered with — a memset that lands after the first kernels would wipe what they wrote)
-        HIP_TRY(h, hipMemsetAsync(h->d_qhist, 0, std::max<size_t>((size_t)hoff * batch * 4, 256), h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_qbest, 0, std::max<size_t>((size_t)boff * batch * 8, 256), h->stream));
+        HIP_TRY(h, hipMemsetAsync(g.d_qhist, 0, std::max<size_t>((size_t)hoff * batch * 4, 256), h->stream));
+        HIP_TRY(h, hipMemsetAsync(g.d_qbest, 0, std::max<size_t>((size_t)boff * batch * 8, 256), h->stream));
     }
     {   // which level pairs the fused pyramid kernel can produce (decided on the host copies of the tables)
         std::vector<const int16_t*> xt(L, nullptr), yo(L, nullptr);
@@ -340,17 +368,17 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
         std::vector<const int16_t*> ib(L, nullptr);
         for (int l = 1; l < L; l++) ib[l] = tables.data() + tab_off[4 * l + 3];
         std::vector<uint64_t> blob;
-        hs_pyramid_build_tables(h->lv.data(), L, xt.data(), yo.data(), ib.data(), blob, h->pyr_fuse);
+        hs_pyramid_build_tables(h->lv.data(), L, xt.data(), yo.data(), ib.data(), blob, g.pyr_fuse);
         // chains: the last three levels in one launch when the number of levels to make is odd (8 levels: (1,2) (3,4) (5,6,7))
-        h->pyr_chain.assign(L, HsPyrChain{});
+        g.pyr_chain.assign(L, HsPyrChain{});
         for (int l = 0; l < L; l++) h->lv[l].chain_n = 0;
         if (!h->no_fuse && h->chain_mode != 0) {
             if (h->chain_mode == 2) {
                 for (int l = 1; l + 1 < L; l += 2) {
                     int n = (l + 3 == L) ? 3 : 2;
-                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, h->pyr_chain[l]);
-                    if (!h->pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(h->lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, h->pyr_chain[l]);
-                    if (h->pyr_chain[l].valid) { h->lv[l].chain_n = h->pyr_chain[l].nstage; if (h->pyr_chain[l].nstage == 3) l++; }
+                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
+                    if (!g.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(h->lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
+                    if (g.pyr_chain[l].valid) { h->lv[l].chain_n = g.pyr_chain[l].nstage; if (g.pyr_chain[l].nstage == 3) l++; }
                 }
             } else if (const char* plan = getenv("HS_PYRAMID_PLAN")) {      // tuning knob: explicit chain lengths from level 1, e.g. "2,3,2" (1 = a single level, 2 = the two-level kernel unless HS_PYRAMID_CHAIN2=1)
                 const bool chain2 = getenv("HS_PYRAMID_CHAIN2") && atoi(getenv("HS_PYRAMID_CHAIN2")) != 0;
@@ -358,8 +386,8 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
                 for (const char* q = plan; *q && l < L; ) {
                     const int n = std::min(atoi(q), L - l);
                     if (n >= 3 || (n == 2 && (chain2 || !(l & 1)))) {       // (the two-level kernel is planned for pairs that start on an odd level)
-                        hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, h->pyr_chain[l], HS_PYR_DEEP_LDS, 0);
-                        if (h->pyr_chain[l].valid) h->lv[l].chain_n = n;
+                        hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l], HS_PYR_DEEP_LDS, 0);
+                        if (g.pyr_chain[l].valid) h->lv[l].chain_n = n;
                     }
                     if (n == 1) h->lv[l].fuse_tbx = 0;
                     l += std::max(n, 1);
@@ -368,38 +396,38 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
                 }
             } else if (L >= 4 && ((L - 1) & 1)) {
                 const int l = L - 3;
-                hs_pyramid_plan_chain(h->lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, h->pyr_chain[l]);
-                if (h->pyr_chain[l].valid) h->lv[l].chain_n = 3;
+                hs_pyramid_plan_chain(h->lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
+                if (g.pyr_chain[l].valid) h->lv[l].chain_n = 3;
             }
         }
         // the small-batch plan: a launch of few frames lasts as long as one workgroup lives and costs ~5 us whatever it does, so the dependent
         // launches are what counts — greedy: from level 1, the longest chain that fits HS_PYR_DEEP_LDS, then the next (1080p: ONE launch for levels 1-7)
-        h->pyr_deep.assign(L, HsPyrChain{});
+        g.pyr_deep.assign(L, HsPyrChain{});
         if (!h->no_fuse && h->deep_max_batch > 0) {
             for (int l = 1; l + 1 < L;) {
                 int took = 0;
                 for (int n = std::min(HS_PYR_CHAIN_MAX, L - l); n >= 2 && !took; n--) {
-                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, h->pyr_deep[l], HS_PYR_DEEP_LDS, h->deep_rows);
-                    if (h->pyr_deep[l].valid) took = n;
+                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_deep[l], HS_PYR_DEEP_LDS, h->deep_rows);
+                    if (g.pyr_deep[l].valid) took = n;
                 }
                 l += took ? took : 1;
             }
         }
-        HIP_TRY(h, hipMalloc(&h->d_pyr_tabs, std::max<size_t>(blob.size() * 8, 256)));
-        if (!blob.empty()) HIP_TRY(h, hipMemcpy(h->d_pyr_tabs, blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(h, g.d_pyr_tabs.grow(std::max<size_t>(blob.size() * 8, 256)));
+        if (!blob.empty()) HIP_TRY(h, hipMemcpy(g.d_pyr_tabs, blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
         for (int which = 0; which < 2; which++)
-        for (HsPyrChain& C : (which ? h->pyr_deep : h->pyr_chain)) {                  // blob offsets -> device pointers
+        for (HsPyrChain& C : (which ? g.pyr_deep : g.pyr_chain)) {                  // blob offsets -> device pointers
             if (!C.valid) continue;
             for (int i = 0; i < C.nstage; i++) {
                 HsPyrStage& S = C.st[i];
-                S.rows = reinterpret_cast<const HsPyrRow*>(h->d_pyr_tabs + (uintptr_t)S.rows);
-                S.tx = reinterpret_cast<const HsPyrStageX*>(h->d_pyr_tabs + (uintptr_t)S.tx); S.ty = reinterpret_cast<const HsPyrStageY*>(h->d_pyr_tabs + (uintptr_t)S.ty);
+                S.rows = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)S.rows);
+                S.tx = reinterpret_cast<const HsPyrStageX*>(g.d_pyr_tabs + (uintptr_t)S.tx); S.ty = reinterpret_cast<const HsPyrStageY*>(g.d_pyr_tabs + (uintptr_t)S.ty);
             }
         }
-        for (HsPyrFuse& F : h->pyr_fuse) {                    // blob offsets -> device pointers
+        for (HsPyrFuse& F : g.pyr_fuse) {                    // blob offsets -> device pointers
             if (!F.valid) continue;
-            F.rowA = reinterpret_cast<const HsPyrRow*>(h->d_pyr_tabs + (uintptr_t)F.rowA); F.rowB = reinterpret_cast<const HsPyrRow*>(h->d_pyr_tabs + (uintptr_t)F.rowB);
-            F.xt = reinterpret_cast<const HsPyrXTile*>(h->d_pyr_tabs + (uintptr_t)F.xt); F.yt = reinterpret_cast<const HsPyrYTile*>(h->d_pyr_tabs + (uintptr_t)F.yt);
+            F.rowA = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)F.rowA); F.rowB = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)F.rowB);
+            F.xt = reinterpret_cast<const HsPyrXTile*>(g.d_pyr_tabs + (uintptr_t)F.xt); F.yt = reinterpret_cast<const HsPyrYTile*>(g.d_pyr_tabs + (uintptr_t)F.yt);
         }
     }
     // the same levels with NARROW work items (tiles of 32 dwords: <= 119 px of interior per item), for the launches of small batches: the list
@@ -414,13 +442,13 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
             V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 5);
             V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
         }
-        h->fast_items_n = order_items(h->lv_n);
+        g.fast_items_n = order_items(h->lv_n);
     }
     HIP_TRY(h, hipMemcpy(h->d_lv, h->lv.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_lv + L, h->lv_n.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
     {
         bool items_fit = true;                                 // every item against the tile the kernel stages it into (hs_fast_item_fits: columns, score-tile column, cells)
-        auto upload_items = [&](const std::vector<HsLevel>& lv, int n_items, HsFastItem** d_out, int lc) -> hipError_t {
+        auto upload_items = [&](const std::vector<HsLevel>& lv, int n_items, HsBuf<HsFastItem>& d_out, int lc) -> hipError_t {
             std::vector<HsFastItem> fi(std::max(n_items, 1));
             hs_fast_build_items(lv.data(), L, fi.data());
             for (int i = 0; i < n_items; i++) items_fit = items_fit && hs_fast_item_fits(fi[i], lc);
@@ -435,79 +463,60 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
                 std::vector<HsFastItem> t(fi.begin(), fi.begin() + n_red);
                 for (int i = 0; i < n_red; i++) fi[i] = t[key[i].second];
             }
-            hipError_t e = hipMalloc(d_out, fi.size() * sizeof(HsFastItem));
+            hipError_t e = d_out.grow(fi.size());
             if (e != hipSuccess) return e;
-            return hipMemcpy(*d_out, fi.data(), fi.size() * sizeof(HsFastItem), hipMemcpyHostToDevice);
+            return hipMemcpy(d_out, fi.data(), fi.size() * sizeof(HsFastItem), hipMemcpyHostToDevice);
         };
-        HIP_TRY(h, upload_items(h->lv, items, &h->d_fast_items, 6));
-        if (h->fast_items_n > 0) HIP_TRY(h, upload_items(h->lv_n, h->fast_items_n, &h->d_fast_items_n, 5));
+        HIP_TRY(h, upload_items(h->lv, items, g.d_fast_items, 6));
+        if (g.fast_items_n > 0) HIP_TRY(h, upload_items(h->lv_n, g.fast_items_n, g.d_fast_items_n, 5));
         if (!items_fit) return hs_fail(h, HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused");
-        HIP_TRY(h, hipMalloc(&h->d_fast_ovf, std::max<size_t>(hs_fast_overflow_bytes(h->max_hcell, std::max(items, h->fast_items_n) * batch, h->fast_knobs), 256)));
-        HIP_TRY(h, hipMemsetAsync(h->d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream));       // all four work-queue counter sets start at zero (stream-ordered before the first launch)
+        HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(g.max_hcell, std::max(items, g.fast_items_n) * batch, h->fast_knobs), 256) / 4));      // (a multiple of 4 bytes)
+        HIP_TRY(h, hipMemsetAsync(g.d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream));       // all four work-queue counter sets start at zero (stream-ordered before the first launch)
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));     // the memsets above have landed whatever stream the caller's launches will use (configuration is rare: it allocates)
-    h->w = w; h->h = hh; h->batch_cap = batch;      // configured only now
+    g.w = w; g.h = hh; g.batch_cap = batch;      // configured only now
     return HS_OK;
 }
 
+inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }      // a tuning knob of the environment, read once per handle
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-int ensure_pinned(hs_orb* h, uint8_t** p, size_t* have, size_t need)
+// The result block of a host-pointer extraction, on the device and in pinned host memory: [counts | keypoints | descriptors] of `batch` images
+// of `cap` entries and, for a stereo ticket, [uRight | depth] of `pairs` left images.  Every piece starts on a multiple of 256 bytes.
+struct OutLayout { size_t off_k, off_d, off_u, off_z, bytes; };
+OutLayout out_layout(int batch, int cap, int pairs)
 {
-    if (need <= *have) return HS_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (*p) hipHostFree(*p);
-    *p = nullptr; *have = 0;
-    HIP_TRY(h, hipHostMalloc((void**)p, need, hipHostMallocDefault));
-    *have = need;
-    return HS_OK;
+    OutLayout o;
+    o.off_k = pad256((size_t)batch * 4);
+    o.off_d = o.off_k + pad256((size_t)batch * cap * sizeof(hs_keypoint));
+    const size_t desc = (size_t)batch * cap * HS_DESC_BYTES, ur = (size_t)pairs * cap * 4;
+    o.off_u = o.off_z = o.bytes = o.off_d + desc;
+    if (pairs > 0) { o.off_u = o.off_d + pad256(desc); o.off_z = o.off_u + pad256(ur); o.bytes = o.off_z + ur; }
+    return o;
 }
 
-int ensure_outputs(hs_orb* h, int batch, int cap)
+// A pinned result block goes to the caller's [batch][cap] arrays: only the entries that exist are copied (the counts clamped to [0, cap0], the
+// capacity the block was laid out for); the rest of the caller's arrays is left untouched.  uRight / depth belong to the first `pairs` images.
+void scatter_results(const uint8_t* blk, const OutLayout& o, int batch, int cap0, int pairs, hs_keypoint* kps, uint8_t* desc, int32_t* n, int cap, float* uRight, float* depth)
 {
-    if (batch <= h->out_batch && cap == h->out_cap) return HS_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(h->d_n);                     // one block: [counts | keypoints | descriptors], so that the results come back in ONE device-to-host copy
-    batch = std::max(batch, h->out_batch);
-    h->d_kps = nullptr; h->d_desc = nullptr; h->d_n = nullptr; h->out_batch = 0; h->out_cap = 0;
-    const size_t nb = pad256((size_t)batch * 4), kb = pad256((size_t)batch * cap * sizeof(hs_keypoint)), db = (size_t)batch * cap * HS_DESC_BYTES;
-    uint8_t* blk = nullptr;
-    HIP_TRY(h, hipMalloc(&blk, nb + kb + db));
-    h->d_n = reinterpret_cast<int32_t*>(blk); h->d_kps = reinterpret_cast<hs_keypoint*>(blk + nb); h->d_desc = blk + nb + kb;
-    h->out_batch = batch; h->out_cap = cap;
-    return HS_OK;
+    memcpy(n, blk, (size_t)batch * 4);
+    for (int i = 0; i < batch; i++) {
+        const size_t cnt = (size_t)std::min(std::max(n[i], 0), cap0);
+        memcpy(kps + (size_t)i * cap, blk + o.off_k + (size_t)i * cap0 * sizeof(hs_keypoint), cnt * sizeof(hs_keypoint));
+        memcpy(desc + (size_t)i * cap * HS_DESC_BYTES, blk + o.off_d + (size_t)i * cap0 * HS_DESC_BYTES, cnt * HS_DESC_BYTES);
+        if (i < pairs) {
+            memcpy(uRight + (size_t)i * cap, blk + o.off_u + (size_t)i * cap0 * 4, cnt * 4);
+            memcpy(depth + (size_t)i * cap, blk + o.off_z + (size_t)i * cap0 * 4, cnt * 4);
+        }
+    }
 }
 
 int ensure_stereo_strips(hs_orb* h, int pairs, int cap, int n_rows)
 {
-    // two capacities: the counters (pairs * strips) and the lists (pairs * strips * cap) grow independently
     if (n_rows > 65536) return hs_fail(h, HS_ERR_INVALID, "stereo: more than 65536 image rows");      // k_stereo_strips keeps one counter per 32 rows in LDS
-    const size_t need_count = (size_t)pairs * hs_stereo_strips(n_rows), need_list = need_count * (size_t)cap;
-    if (need_count <= h->strip_count_entries && need_list <= h->strip_list_entries) return HS_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (need_count > h->strip_count_entries) {
-        hipFree(h->d_strip_count); h->d_strip_count = nullptr; h->strip_count_entries = 0;
-        HIP_TRY(h, hipMalloc(&h->d_strip_count, need_count * 4));
-        h->strip_count_entries = need_count;
-    }
-    if (need_list > h->strip_list_entries) {
-        hipFree(h->d_strip_list); h->d_strip_list = nullptr; h->strip_list_entries = 0;
-        HIP_TRY(h, hipMalloc(&h->d_strip_list, need_list * HS_STRIP_ENTRY_BYTES));
-        h->strip_list_entries = need_list;
-    }
-    return HS_OK;
-}
-
-int ensure_stereo_scratch(hs_orb* h, size_t entries)
-{
-    if (entries <= h->st_entries) return HS_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(h->d_ur); hipFree(h->d_depth); hipFree(h->d_bd);
-    h->d_ur = h->d_depth = nullptr; h->d_bd = nullptr;
-    HIP_TRY(h, hipMalloc(&h->d_ur, entries * 4));
-    HIP_TRY(h, hipMalloc(&h->d_depth, entries * 4));
-    HIP_TRY(h, hipMalloc(&h->d_bd, entries * 4));
-    h->st_entries = entries;
+    const size_t need_count = (size_t)pairs * hs_stereo_strips(n_rows);
+    HIP_TRY(h, h->d_strip_count.grow(need_count, h->stream));
+    HIP_TRY(h, h->d_strip_list.grow(need_count * (size_t)cap, h->stream));
     return HS_OK;
 }
 
@@ -515,6 +524,7 @@ int ensure_stereo_scratch(hs_orb* h, size_t entries)
 int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, const HsStripFuse* sf = nullptr)
 {
     const int L = h->p.nlevels;
+    hs_orb::Geometry& g = h->geo;
     // Level 0 needs no pyramid.  For one or two LARGE frames the chain of launches is latency-bound (dependent pyramid launches, a FAST launch
     // whose duration is its slowest work item, the level-0 quadtree workgroup — 0.11 ms for a 4000 x 3000 frame): level 0's FAST + quadtree run
     // on a second stream BESIDE the pyramid and the other levels' FAST + quadtree, joined before the describe stage.  Same kernels, same
@@ -527,40 +537,40 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     // resident single-wave workgroups), so it gets the NARROW items — twice as many, half as long; measured at 1080p (pairs per call: narrow / wide pairs/s): 1: 9 949 / 8 403,
     // 2: 16 029 / 15 642, 4: 23 004 / 22 660, 8: 32 657 / 33 240, 16: 40 917 / 41 507 — from ~18 k items on the wide ones win (fewer, fuller tiles).  HS_FAST_COLS = 32 / 64 forces one list, HS_FAST_NARROW_MAX moves the threshold.
     const int narrow_max = h->fast_knobs.narrow_max > 0 ? h->fast_knobs.narrow_max : 18000;
-    const bool narrow = h->fast_items_n > 0 && (h->fast_knobs.cols == 32 || (h->fast_knobs.cols != 64 && (long long)h->fast_items_n * batch <= narrow_max));
+    const bool narrow = g.fast_items_n > 0 && (h->fast_knobs.cols == 32 || (h->fast_knobs.cols != 64 && (long long)g.fast_items_n * batch <= narrow_max));
     // Keys by batch as well: the FAST kernel's two global atomics per candidate cost it 5 % at 16 pairs per call (0.162 -> 0.170 ms) and buy the
     // quadtree launch 4 us there (its 256 workgroups fill the chip either way); at one pair per call they cost 1 us and buy 10 (35.1 -> 24.8 us: the
     // level-0 workgroup no longer gathers 5 000 records on one CU).  Both arrays are zero between calls whatever the mode, so the mode may change per call.
-    const HsPyrChain* const deep = (batch <= h->deep_max_batch && !h->pyr_deep.empty()) ? h->pyr_deep.data() : nullptr;      // the pyramid's small-batch plan
-    const bool use_keys = h->fast_keys && h->d_fast_qt != nullptr && batch <= h->fast_keys_max_batch;
+    const HsPyrChain* const deep = (batch <= h->deep_max_batch && !g.pyr_deep.empty()) ? g.pyr_deep.data() : nullptr;      // the pyramid's small-batch plan
+    const bool use_keys = h->fast_keys && g.d_fast_qt.p != nullptr && batch <= h->fast_keys_max_batch;
     // d_qhist / d_qbest are all zero between calls (the quadtree kernel zeroes what it consumes).  A call that fails anywhere between the keyed FAST
     // launch and its end — an event / stream call of the split path, a later launch — breaks that: the flag makes the NEXT call start from zeroed arrays.
-    if (h->keys_dirty) {
+    if (g.keys_dirty) {
         HIP_TRY(h, hipDeviceSynchronize());
-        if (h->d_qhist) HIP_TRY(h, hipMemsetAsync(h->d_qhist, 0, (size_t)h->qhist_stride * h->batch_cap * 4, s));
-        if (h->d_qbest) HIP_TRY(h, hipMemsetAsync(h->d_qbest, 0, (size_t)h->qbest_stride * h->batch_cap * 8, s));
+        if (g.d_qhist) HIP_TRY(h, hipMemsetAsync(g.d_qhist, 0, (size_t)g.qhist_stride * g.batch_cap * 4, s));
+        if (g.d_qbest) HIP_TRY(h, hipMemsetAsync(g.d_qbest, 0, (size_t)g.qbest_stride * g.batch_cap * 8, s));
         HIP_TRY(h, hipStreamSynchronize(s));
-        h->keys_dirty = false;
+        g.keys_dirty = false;
     }
-    if (use_keys) h->keys_dirty = true;                          // cleared at the end of a call that enqueued everything without error
+    if (use_keys) g.keys_dirty = true;                          // cleared at the end of a call that enqueued everything without error
     const std::vector<HsLevel>& lvh = narrow ? h->lv_n : h->lv;
     const HsLevel* const d_lv = h->d_lv + (narrow ? L : 0);
-    const HsFastItem* const d_items = narrow ? h->d_fast_items_n : h->d_fast_items;
-    const int n_items = narrow ? h->fast_items_n : h->fast_items, lc = narrow ? 5 : 6;
+    const HsFastItem* const d_items = narrow ? g.d_fast_items_n.p : g.d_fast_items.p;
+    const int n_items = narrow ? g.fast_items_n : g.fast_items, lc = narrow ? 5 : 6;
     const int items0 = lvh[0].ngroups * lvh[0].nrows, first0 = lvh[0].item_begin;      // work items of level 0: the LAST items0 of the item list
-    const bool split = !h->prof && L > 1 && items0 > 0 && items0 < n_items && (h->split_mode == 1 || (h->split_mode < 0 && batch <= 2 && (size_t)h->w * (size_t)h->h * (size_t)batch >= 6000000));
+    const bool split = !h->prof && L > 1 && items0 > 0 && items0 < n_items && (h->split_mode == 1 || (h->split_mode < 0 && batch <= 2 && (size_t)g.w * (size_t)g.h * (size_t)batch >= 6000000));
     auto fast = [&](int item_first, int item_count, int spill_slot, hipStream_t st) -> int {
         // launch N uses work-queue counter set N & 3 and relies on launch N - 2 having zeroed it: the epoch advances only when a launch was
         // enqueued without error; after a failed launch all sets are zeroed again so that the next one starts from a known state
-        const bool launched = hs_launch_fast(d_lv, d_items, L, img0, batch, h->total_cells, n_items, h->p.fast_threshold,
-                                             h->d_cand, h->d_cell_count, h->cand_img_stride, h->max_wcell, h->max_hcell, h->d_fast_ovf, h->fast_epoch, h->fast_knobs,
-                                             item_first, item_count, spill_slot, lc, use_keys ? h->d_fast_qt : nullptr, h->d_qhist, h->d_qbest, h->qhist_stride, h->qbest_stride, st);
+        const bool launched = hs_launch_fast(d_lv, d_items, L, img0, batch, g.total_cells, n_items, h->p.fast_threshold,
+                                             g.d_cand, g.d_cell_count, g.cand_img_stride, g.max_wcell, g.max_hcell, g.d_fast_ovf, h->fast_epoch, h->fast_knobs,
+                                             item_first, item_count, spill_slot, lc, use_keys ? g.d_fast_qt.p : nullptr, g.d_qhist, g.d_qbest, g.qhist_stride, g.qbest_stride, st);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             (void)hipDeviceSynchronize();
-            (void)hipMemsetAsync(h->d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream);
-            if (h->d_qhist) (void)hipMemsetAsync(h->d_qhist, 0, (size_t)h->qhist_stride * h->batch_cap * 4, h->stream);      // a launch that died half-way may have left keys behind
-            if (h->d_qbest) (void)hipMemsetAsync(h->d_qbest, 0, (size_t)h->qbest_stride * h->batch_cap * 8, h->stream);
+            (void)hipMemsetAsync(g.d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream);
+            if (g.d_qhist) (void)hipMemsetAsync(g.d_qhist, 0, (size_t)g.qhist_stride * g.batch_cap * 4, h->stream);      // a launch that died half-way may have left keys behind
+            if (g.d_qbest) (void)hipMemsetAsync(g.d_qbest, 0, (size_t)g.qbest_stride * g.batch_cap * 8, h->stream);
             (void)hipStreamSynchronize(h->stream);
             return hs_fail(h, HS_ERR_HIP, std::string("FAST launch: ") + hipGetErrorString(e));
         }
@@ -568,10 +578,10 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         return HS_OK;
     };
     auto quadtree = [&](int level_first, int level_count, hipStream_t st) {
-        hs_launch_quadtree(d_lv, L, batch, h->total_cells, h->d_cand, h->d_cell_count, h->cand_img_stride,
-                           h->d_pts_xy, h->d_pts_sk, h->d_pt_node, h->d_cand_count, h->d_sel, h->d_sel_count, h->sel_img_stride, h->d_sel_perm, h->qt_point_domain ? 1 : 0,
-                           level_first, level_count, use_keys ? h->d_qhist : nullptr, h->d_qbest, h->qhist_stride, h->qbest_stride, h->keep_points ? 1 : 0,
-                           h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0), h->d_qt_rects, st);
+        hs_launch_quadtree(d_lv, L, batch, g.total_cells, g.d_cand, g.d_cell_count, g.cand_img_stride,
+                           g.d_pts_xy, g.d_pts_sk, g.d_pt_node, g.d_cand_count, g.d_sel, g.d_sel_count, g.sel_img_stride, g.d_sel_perm, h->qt_point_domain ? 1 : 0,
+                           level_first, level_count, use_keys ? g.d_qhist.p : nullptr, g.d_qbest, g.qhist_stride, g.qbest_stride, h->keep_points ? 1 : 0,
+                           h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0), g.d_qt_rects, st);
     };
     if (split) {
         if (!h->s_aux) {
@@ -585,14 +595,14 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         if (rc != HS_OK) return rc;
         quadtree(0, 1, h->s_aux);
         HIP_TRY(h, hipEventRecord(h->ev_sjoin, h->s_aux));
-        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), h->pyr_fuse.data(), h->pyr_chain.data(), L, img0, batch, s, deep);
+        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
         rc = fast(0, n_items - items0, 0, s);
         if (rc != HS_OK) return rc;
         quadtree(1, L - 1, s);
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_sjoin, 0));
     } else {
         mark(h, 0, s);
-        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), h->pyr_fuse.data(), h->pyr_chain.data(), L, img0, batch, s, deep);
+        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
         mark(h, 1, s);
         const int rc = fast(0, n_items, 0, s);
         if (rc != HS_OK) return rc;
@@ -600,24 +610,12 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         quadtree(0, L, s);
     }
     mark(h, 3, s);
-    hs_launch_describe(h->d_lv, L, img0, batch, h->d_sel, h->d_sel_count, h->d_sel_perm, h->sel_img_stride, h->max_kp,
+    hs_launch_describe(h->d_lv, L, img0, batch, g.d_sel, g.d_sel_count, g.d_sel_perm, g.sel_img_stride, g.max_kp,
                        h->d_taps, out, s, h->fast_taps, sf ? *sf : HsStripFuse{});
     mark(h, -1, s);
     HIP_TRY(h, hipGetLastError());
-    h->keys_dirty = false;
+    g.keys_dirty = false;
     h->last_batch = batch; h->last_img0 = img0;
-    return HS_OK;
-}
-
-// the grow-only device scratch arena behind hs_orb_scratch_of() (HsStage, hs_internal.h, lays the host-pointer entry points' pieces out in it)
-int scratch_claim(hs_orb* h, size_t total)
-{
-    if (total > h->scratch_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        hipFree(h->d_scratch); h->d_scratch = nullptr; h->scratch_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_scratch, total));
-        h->scratch_bytes = total;
-    }
     return HS_OK;
 }
 
@@ -630,30 +628,52 @@ void stage_frame(HsStage& st, const hs_frame_view* F, DevFrame* o)
     st.temp(&o->cell, hs_frame_grid_bytes(std::max(F->n, 1)));
 }
 
-void run_stereo(hs_orb* h, const hs_keypoint* kL, const uint8_t* dL, const int32_t* nL, const hs_keypoint* kR, const uint8_t* dR,
+// Stage 4.  `binned`: the strips were binned by an extra workgroup of the describe launch (HsStripFuse, the stereo front end): one launch less.
+// (Round 4 also built the median rejection into the matcher — each pair's last workgroup, found with a ticket counter,
+// the three result arrays written through with agent-scope atomic stores so that no L2 write-back is needed: bit-exact, but the write-through
+// stores cost more than the launch they save: 0.056 against 0.022 + 0.006 ms per 16 pairs, 10.0 against 4.8 + 4.8 us for one pair.  Dropped.)
+void run_stereo(hs_orb* h, bool binned, const hs_keypoint* kL, const uint8_t* dL, const int32_t* nL, const hs_keypoint* kR, const uint8_t* dR,
                 const int32_t* nR, int pairs, int cap, const hs_stereo_params& sp, float* ur, float* depth, hipStream_t s)
 {
     mark(h, 4, s);
-    h->last_stereo_launches = 2;
-    hs_launch_stereo(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->d_bd, h->d_strip_count, h->d_strip_list, s);
+    h->last_stereo_launches = binned ? 1 : 2;
+    if (binned) hs_launch_stereo_match_only(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, s);
+    else hs_launch_stereo(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, s);
     mark(h, 5, s);
-    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
+    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->st.bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
     mark(h, -1, s);
 }
 
-// the stereo front end's matcher: the strips were binned by an extra workgroup of the describe launch (HsStripFuse): two launches where
-// run_stereo needs three.  (Round 4 also built the median rejection into the matcher — each pair's last workgroup, found with a ticket counter,
-// the three result arrays written through with agent-scope atomic stores so that no L2 write-back is needed: bit-exact, but the write-through
-// stores cost more than the launch they save: 0.056 against 0.022 + 0.006 ms per 16 pairs, 10.0 against 4.8 + 4.8 us for one pair.  Dropped.)
-void run_stereo_fused(hs_orb* h, const hs_keypoint* kL, const uint8_t* dL, const int32_t* nL, const hs_keypoint* kR, const uint8_t* dR,
-                      const int32_t* nR, int pairs, int cap, const hs_stereo_params& sp, float* ur, float* depth, hipStream_t s)
+// the stereo front end on a configured handle whose stereo buffers are large enough: extraction of the left and the right frames in ONE
+// launch sequence (out.split of each), then the matcher.  HS_STEREO_FUSE (default): the describe launch also bins the right keypoints into the matcher's strips
+int run_stereo_frontend(hs_orb* h, HsImg0 img0, HsOut out, const hs_stereo_params& sp, float* ur, float* depth, hipStream_t s)
 {
-    mark(h, 4, s);
-    h->last_stereo_launches = 1;
-    hs_launch_stereo_match_only(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->d_bd, h->d_strip_count, h->d_strip_list, s);
-    mark(h, 5, s);
-    hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->d_bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
-    mark(h, -1, s);
+    const int pairs = out.split;
+    const HsStripFuse sf{ 1, sp.n_rows, hs_stereo_strips(sp.n_rows), 0, sp.size_ref, h->d_strip_count, h->d_strip_list };
+    const int rc = run_extract(h, img0, 2 * pairs, out, s, h->stereo_fuse ? &sf : nullptr);
+    if (rc != HS_OK) return rc;
+    run_stereo(h, h->stereo_fuse, out.kps, out.desc, out.n, out.kps2, out.desc2, out.n2, pairs, out.cap, sp, ur, depth, s);
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+// The two-lane split of a batch (hs_orb_set_lanes(2), count >= 2): the first half runs on the handle and the caller's stream, the second half on the
+// child handle's own stream, fenced by the fork / join events.  body(lane, first, count, stream) does the unsplit work of `count` items from `first`.
+template <class Body> int run_lanes(hs_orb* h, hipStream_t s, int count, Body body)
+{
+    hs_orb* const child = h->lane2;
+    const int c0 = count / 2;
+    child->prof = h->prof;
+    HIP_TRY(h, hipEventRecord(h->ev_fork, s));
+    HIP_TRY(h, hipStreamWaitEvent(child->stream, h->ev_fork, 0));
+    int rc = body(h, 0, c0, s);
+    if (rc == HS_OK) {
+        rc = body(child, c0, count - c0, child->stream);
+        if (rc != HS_OK) h->err = child->err;
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_join, child->stream));
+    HIP_TRY(h, hipStreamWaitEvent(s, h->ev_join, 0));
+    return rc;
 }
 
 } // namespace
@@ -669,24 +689,29 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
     int deep_launches = 0, longest = 0, lds = 0;
     for (int l = 1; l < L; l++) {
         deep_launches++;
-        if (l < (int)h->pyr_deep.size() && h->pyr_deep[l].valid) {
-            const HsPyrChain& C = h->pyr_deep[l];
+        if (l < (int)h->geo.pyr_deep.size() && h->geo.pyr_deep[l].valid) {
+            const HsPyrChain& C = h->geo.pyr_deep[l];
             if (C.nstage > longest) { longest = C.nstage; lds = C.x_bytes + C.h_rows * 512; }
             l += C.nstage - 1;
         } else if (h->lv[l].chain_n > 0 && l + h->lv[l].chain_n <= L) l += h->lv[l].chain_n - 1;
         else if (h->lv[l].fuse_tbx > 0 && l + 1 < L) l++;
     }
-    out[1] = L > 1 ? deep_launches : 0; out[2] = h->fast_items; out[3] = h->fast_items_n;
+    out[1] = L > 1 ? deep_launches : 0; out[2] = h->geo.fast_items; out[3] = h->geo.fast_items_n;
     for (int l = 0; l < L; l++) out[4] += h->lv[l].qt_hist_off != 0xFFFFFFFFu;
     out[5] = longest; out[6] = lds;
-    if (L > 1 && !h->pyr_deep.empty() && h->pyr_deep[1].valid) out[7] = h->pyr_deep[1].grid_x * h->pyr_deep[1].grid_y;
+    if (L > 1 && !h->geo.pyr_deep.empty() && h->geo.pyr_deep[1].valid) out[7] = h->geo.pyr_deep[1].grid_x * h->geo.pyr_deep[1].grid_y;
 }
 
 // accessors for the other translation units of the library (declared in hs_internal.h)
 void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; }
 int hs_orb_device_of(const hs_orb* h) { return h ? h->device : 0; }
 hipStream_t hs_orb_stream_of(const hs_orb* h) { return h ? h->stream : nullptr; }
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes) { return scratch_claim(h, bytes) == HS_OK ? h->d_scratch : nullptr; }
+// (the grow-only arena that HsStage, hs_internal.h, lays the host-pointer entry points' pieces out in)
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes)
+{
+    const auto claim = [&]() -> int { HIP_TRY(h, h->d_scratch.grow(bytes, h->stream)); return HS_OK; };
+    return claim() == HS_OK ? h->d_scratch.p : nullptr;
+}
 
 extern "C" {
 
@@ -736,18 +761,18 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     hs_orb* h = new hs_orb();
     h->p = *p; h->device = device;
     h->fast_knobs = hs_fast_read_knobs();
-    { const char* e = getenv("HS_PYRAMID_NO_FUSE"); h->no_fuse = e && atoi(e) != 0; }
-    { const char* e = getenv("HS_STEREO_FUSE"); h->stereo_fuse = !(e && atoi(e) == 0); }
-    { const char* e = getenv("HS_FAST_KEYS"); h->fast_keys = !(e && atoi(e) == 0); }
-    { const char* e = getenv("HS_FAST_KEYS_LEVELS"); if (e && atoi(e) > 0) h->fast_keys_levels = atoi(e); }
-    { const char* e = getenv("HS_FAST_KEYS_MAX_BATCH"); if (e && atoi(e) >= 0) h->fast_keys_max_batch = atoi(e); }
-    { const char* e = getenv("HS_FAST_ORDER"); h->fast_order = e ? atoi(e) : 1; }
-    { const char* e = getenv("HS_PYRAMID_CHAIN"); h->chain_mode = e ? atoi(e) : -1; }
-    { const char* e = getenv("HS_PYRAMID_TBX_MAX"); if (e) h->pyr_tbx_max = atoi(e); }
-    { const char* e = getenv("HS_PYRAMID_DEEP_MAX"); if (e) h->deep_max_batch = atoi(e); }
-    { const char* e = getenv("HS_PYRAMID_DEEP_ROWS"); if (e && atoi(e) >= 2) h->deep_rows = atoi(e); }
-    { const char* e = getenv("HS_QT_POINT_DOMAIN"); h->qt_point_domain = e && atoi(e) != 0; }
-    { const char* e = getenv("HS_EXTRACT_SPLIT"); h->split_mode = e ? (atoi(e) != 0 ? 1 : 0) : -1; }
+    h->no_fuse = env_int("HS_PYRAMID_NO_FUSE", 0) != 0;
+    h->stereo_fuse = env_int("HS_STEREO_FUSE", 1) != 0;
+    h->fast_keys = env_int("HS_FAST_KEYS", 1) != 0;
+    { const int v = env_int("HS_FAST_KEYS_LEVELS", 0); if (v > 0) h->fast_keys_levels = v; }
+    { const int v = env_int("HS_FAST_KEYS_MAX_BATCH", -1); if (v >= 0) h->fast_keys_max_batch = v; }
+    h->fast_order = env_int("HS_FAST_ORDER", 1);
+    h->chain_mode = env_int("HS_PYRAMID_CHAIN", -1);
+    h->pyr_tbx_max = env_int("HS_PYRAMID_TBX_MAX", h->pyr_tbx_max);
+    h->deep_max_batch = env_int("HS_PYRAMID_DEEP_MAX", h->deep_max_batch);
+    { const int v = env_int("HS_PYRAMID_DEEP_ROWS", 0); if (v >= 2) h->deep_rows = v; }
+    h->qt_point_domain = env_int("HS_QT_POINT_DOMAIN", 0) != 0;
+    { const int v = env_int("HS_EXTRACT_SPLIT", INT_MIN); h->split_mode = v == INT_MIN ? -1 : (v != 0 ? 1 : 0); }
     bool zero = true; for (int k = 0; k < 7; k++) zero = zero && p->blur_taps[k] == 0;
     static const uint16_t def[7] = { 18, 34, 49, 55, 49, 34, 18 };
     for (int k = 0; k < 7; k++) h->taps[k] = zero ? def[k] : p->blur_taps[k];
@@ -773,12 +798,12 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     // ... and only on request (HS_QT_SMALL=1, read once): measured at 32 / 64 pairs per call the two-per-CU instance is SLOWER (quadtree 0.0631 against 0.0606 ms,
     // 0.1198 against 0.1117): without the points in LDS every sweep goes through L2, which costs a workgroup more than sharing the CU buys.  Kept as a parity /
     // tuning variant (tests/test_gpu_parity.py runs it).
-    { const char* e = getenv("HS_QT_SMALL"); if (!e || atoi(e) == 0) h->qt_small_ok = false; }
+    if (env_int("HS_QT_SMALL", 0) == 0) h->qt_small_ok = false;
 
     if (hipSetDevice(device) != hipSuccess) { delete h; return HS_ERR_NO_DEVICE; }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->d_lv, sizeof(HsLevel) * 2 * HS_MAX_LEVELS) != hipSuccess ||
-        hipMalloc(&h->d_taps, 16) != hipSuccess ||
+        h->d_lv.grow(2 * HS_MAX_LEVELS) != hipSuccess ||
+        h->d_taps.grow(8) != hipSuccess ||
         hipMemcpy(h->d_taps, h->taps, 14, hipMemcpyHostToDevice) != hipSuccess) {
         hs_orb_destroy(h);
         return HS_ERR_HIP;
@@ -811,19 +836,11 @@ static void orb_destroy_now(hs_orb* h)
     if (h->s_aux) { hipStreamSynchronize(h->s_aux); hipStreamDestroy(h->s_aux); }
     if (h->ev_sfork) hipEventDestroy(h->ev_sfork);
     if (h->ev_sjoin) hipEventDestroy(h->ev_sjoin);
+    // every stream is drained before anything is freed; the buffers themselves go with the handle (HsBuf's destructor, in `delete h` below)
     if (h->stream) hipStreamSynchronize(h->stream);
-    free_geometry(h);
-    hipFree(h->d_lv); hipFree(h->d_taps); hipFree(h->d_in); hipFree(h->d_raw);
-    hipFree(h->d_n);                     // the output block (counts, keypoints, descriptors)
-    hipFree(h->d_ur); hipFree(h->d_depth); hipFree(h->d_bd); hipFree(h->d_scratch); hipFree(h->d_strip_count); hipFree(h->d_strip_list);
-    hipFree(h->d_sm_kps); hipFree(h->d_sm_desc); hipFree(h->d_sm_n);
-    if (h->h_pin) hipHostFree(h->h_pin);
-    if (h->h_pin_out) hipHostFree(h->h_pin_out);
     if (h->s_in) hipStreamSynchronize(h->s_in);
     if (h->s_out) hipStreamSynchronize(h->s_out);
     for (auto& sl : h->slot) {
-        hipFree(sl.d_in); hipFree(sl.d_raw); hipFree(sl.d_out);
-        if (sl.h_out) hipHostFree(sl.h_out);
         if (sl.ev_in) hipEventDestroy(sl.ev_in);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
         if (sl.ev_out) hipEventDestroy(sl.ev_out);
@@ -861,7 +878,7 @@ int hs_orb_max_keypoints(const hs_orb* h)
     // 4*nIni nodes of the unconditional first pass.  nIni depends on the frame; assume the widest supported.
     int n = 0;
     for (int l = 0; l < h->p.nlevels; l++) n += std::max(h->quota[l] + 4, 4 * 8 + 4);
-    return std::max(n, h->max_kp);          // a configured geometry (hs_orb_reserve / a previous extract) with more than 8 root nodes per level needs more
+    return std::max(n, h->geo.max_kp);          // a configured geometry (hs_orb_reserve / a previous extract) with more than 8 root nodes per level needs more
 }
 
 int hs_orb_reserve(hs_orb* h, int w, int h_px, int batch)
@@ -881,102 +898,99 @@ int hs_orb_extract_batch_device(hs_orb* h, const uint8_t* d_imgs, int batch, int
     if (((uintptr_t)d_desc & 15) != 0 || (((uintptr_t)d_kps | (uintptr_t)d_n) & 3) != 0)
         return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores; hs_record_offsets pads for it), keypoints and counts 4");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->lane2 && batch >= 2) {      // two lanes: the second half runs on the child handle's stream, fenced by fork / join events
-        hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-        const int b0 = batch / 2, b1 = batch - b0;
-        h->lane2->prof = h->prof;
-        HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-        HIP_TRY(h, hipStreamWaitEvent(h->lane2->stream, h->ev_fork, 0));
-        hs_orb* child = h->lane2; h->lane2 = nullptr;          // the recursive calls below must not split again
-        int rc = hs_orb_extract_batch_device(h, d_imgs, b0, w, h_px, row_stride, image_stride, d_kps, d_desc, d_n, cap, s);
-        if (rc == HS_OK) {
-            rc = hs_orb_extract_batch_device(child, d_imgs + (size_t)b0 * image_stride, b1, w, h_px, row_stride, image_stride,
-                                             d_kps + (size_t)b0 * cap, d_desc + (size_t)b0 * cap * HS_DESC_BYTES, d_n + b0, cap, child->stream);
-            if (rc != HS_OK) h->err = child->err;
-        }
-        h->lane2 = child;
-        HIP_TRY(h, hipEventRecord(h->ev_join, child->stream));
-        HIP_TRY(h, hipStreamWaitEvent(s, h->ev_join, 0));
-        return rc;
-    }
-    int rc = configure(h, w, h_px, batch);
-    if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    HsImg0 img0{ d_imgs, d_imgs, batch, (uint64_t)row_stride, (uint64_t)image_stride };
-    HsOut out{ d_kps, d_desc, d_n, d_kps, d_desc, d_n, batch, cap };
-    return run_extract(h, img0, batch, out, s);
+    const auto body = [&](hs_orb* q, int first, int count, hipStream_t qs) -> int {
+        int rc = configure(q, w, h_px, count);
+        if (rc != HS_OK) return rc;
+        if (cap < q->geo.max_kp) return hs_fail(q, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+        const uint8_t* const imgs = d_imgs + (size_t)first * image_stride;
+        hs_keypoint* const k = d_kps + (size_t)first * cap; uint8_t* const d = d_desc + (size_t)first * cap * HS_DESC_BYTES;
+        HsImg0 img0{ imgs, imgs, count, (uint64_t)row_stride, (uint64_t)image_stride };
+        HsOut out{ k, d, d_n + first, k, d, d_n + first, count, cap };
+        return run_extract(q, img0, count, out, qs);
+    };
+    return h->lane2 && batch >= 2 ? run_lanes(h, s, batch, body) : body(h, 0, batch, s);
 }
 
-// the host-pointer extraction, shared by hs_orb_extract_batch (grey frames) and hs_orb_extract_camera_batch (pp != nullptr: the frames are what the camera
-// delivers — 1 / 3 / 4 channels at its own size — and ImageProcessing::PreProcessImg runs on the device between the upload and the pyramid)
 namespace {
+// Frames that come as host pointers, grey (pp == nullptr: w x h IS the level-0 size) or as the camera delivers them (pp: 1 / 3 / 4 channels at the
+// camera's own size; ImageProcessing::PreProcessImg runs on the device between the upload and the pyramid): the sizes of their staging copies
+struct FramePlan {
+    int w, h, gw, gh;                      // the frames as they come; the grey level 0
+    size_t pitch, per_img;                 // level-0 frames in HsFrameStaging::d_in: rows padded to a multiple of 64 bytes
+    size_t row_bytes, rpitch, raw_img;     // what is uploaded: a row, and (camera frames, in d_raw) rows packed to a multiple of 4 bytes
+};
+int plan_frames(hs_orb* h, int w, int h_px, const hs_preprocess_params* pp, FramePlan* u)
+{
+    u->w = u->gw = w; u->h = u->gh = h_px;
+    if (pp) hs_preprocess_out_size(w, h_px, pp->scale, &u->gw, &u->gh);
+    if (u->gw < 1 || u->gh < 1) return hs_fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
+    u->pitch = ((size_t)u->gw + 63) & ~(size_t)63; u->per_img = u->pitch * u->gh;
+    u->row_bytes = (size_t)w * (pp ? pp->channels : 1);
+    u->rpitch = pp ? (u->row_bytes + 3) & ~(size_t)3 : 0; u->raw_img = u->rpitch * h_px;
+    return HS_OK;
+}
+
+// grows the staging pair for `batch` frames (`drain`: the stream to drain before a regrow; nullptr: the pair is idle) and enqueues the uploads on
+// the copy stream `s`.  The frames cross PCIe as they are, once.  Pageable frames go through the runtime's own staging path (measured: packing the
+// rows into a pinned buffer on the calling thread first is SLOWER — one core copies 2 MB frames at ~10 GB/s, the runtime's staged copy moves them
+// at more than twice that); page-locked frames (hs_host_alloc) go by DMA at link speed and the call returns at once.
+// `linear`: a frame whose rows are contiguous may go as ONE linear copy.  The synchronous calls say yes; the ingest path says no: measured with
+// pageable 1080p frames, two tickets in flight, the linear copy holds the submitting thread longer than the 2-D one (9 130 against 10 250 pairs/s).
+int upload_frames(hs_orb* h, HsFrameStaging& st, const hipStream_t* drain, const FramePlan& u, bool camera, const uint8_t* const* imgs, int batch, size_t stride, bool linear, hipStream_t s)
+{
+    HIP_TRY(h, drain ? st.d_in.grow(u.per_img * batch, *drain) : st.d_in.grow(u.per_img * batch));
+    if (camera) HIP_TRY(h, drain ? st.d_raw.grow(u.raw_img * batch, *drain) : st.d_raw.grow(u.raw_img * batch));
+    uint8_t* const dst = camera ? st.d_raw.p : st.d_in.p;
+    const size_t dp = camera ? u.rpitch : u.pitch, di = camera ? u.raw_img : u.per_img;
+    for (int i = 0; i < batch; i++) {
+        // a frame whose rows are as far apart as the staging copy's (width a multiple of 64, no padding: 1920 x 1080) is ONE linear copy
+        if (linear && stride == dp && u.row_bytes == dp) HIP_TRY(h, hipMemcpyAsync(dst + di * i, imgs[i], di, hipMemcpyHostToDevice, s));
+        else HIP_TRY(h, hipMemcpy2DAsync(dst + di * i, dp, imgs[i], stride, u.row_bytes, u.h, hipMemcpyHostToDevice, s));      // (rows with padding: the last row's padding need not exist in the caller's buffer)
+    }
+    return HS_OK;
+}
+
+// camera scale + grey on the compute stream `s`, from the uploaded frames into the level-0 frames
+int preprocess_frames(hs_orb* h, const HsFrameStaging& st, const FramePlan& u, const hs_preprocess_params& pp, int batch, hipStream_t s)
+{
+    hs_launch_preprocess(st.d_raw, u.w, u.h, u.rpitch, u.raw_img, pp.channels, pp.rgb, pp.scale, st.d_in, u.gw, u.gh, u.pitch, u.per_img, 1, batch, s);
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+// the host-pointer extraction, shared by hs_orb_extract_batch (grey frames) and hs_orb_extract_camera_batch (pp != nullptr)
 int extract_host_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int w, int h_px, size_t stride, const hs_preprocess_params* pp,
                         hs_keypoint* kps, uint8_t* desc, int cap, int32_t* n, uint8_t* grey_out)
 {
     HIP_TRY(h, hipSetDevice(h->device));
     h->pub_kps = nullptr; h->pub_desc = nullptr; h->pub_batch = 0;
-    int gw = w, gh = h_px;                                   // size of the grey level 0
-    if (pp) hs_preprocess_out_size(w, h_px, pp->scale, &gw, &gh);
-    if (gw < 1 || gh < 1) return hs_fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
-    int rc = configure(h, gw, gh, batch);
+    FramePlan u;
+    int rc = plan_frames(h, w, h_px, pp, &u);
+    if (rc == HS_OK) rc = configure(h, u.gw, u.gh, batch);
     if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
-    const size_t pitch = ((size_t)gw + 63) & ~(size_t)63, per_img = pitch * gh;
-    if (per_img * batch > h->in_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        hipFree(h->d_in); h->d_in = nullptr;
-        HIP_TRY(h, hipMalloc(&h->d_in, per_img * batch));
-        h->in_bytes = per_img * batch;
-    }
-    rc = ensure_outputs(h, batch, cap);
-    if (rc != HS_OK) return rc;
+    if (cap < h->geo.max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
     hipStream_t s = h->stream;
+    const OutLayout o = out_layout(batch, cap, 0);
+    HIP_TRY(h, h->d_out.grow(o.bytes, s));
     for (int i = 0; i < batch; i++) if (!imgs[i]) return hs_fail(h, HS_ERR_INVALID, "null image in batch");
-    if (!pp) {
-        // Frames: the runtime's own pageable-memory path (measured: packing the rows into a pinned buffer on the calling thread first is SLOWER —
-        // one core copies 2 MB frames at ~10 GB/s, the runtime's staged copy moves them at more than twice that)
-        for (int i = 0; i < batch; i++) {
-            // a frame whose rows are as far apart as the staging copy's (width a multiple of 64, no padding: 1920 x 1080) is ONE linear copy
-            if (stride == pitch && (size_t)w == pitch) HIP_TRY(h, hipMemcpyAsync(h->d_in + per_img * i, imgs[i], per_img, hipMemcpyHostToDevice, s));      // (rows with padding: the last row's padding need not exist in the caller's buffer)
-            else HIP_TRY(h, hipMemcpy2DAsync(h->d_in + per_img * i, pitch, imgs[i], stride, w, h_px, hipMemcpyHostToDevice, s));
-        }
-    } else {
-        // the camera's frames cross PCIe as they are (once), rows packed to a multiple of 4 bytes; PreProcessImg runs between the copy and the pyramid
-        const size_t row_bytes = (size_t)w * pp->channels, rpitch = (row_bytes + 3) & ~(size_t)3, raw_img = rpitch * h_px;
-        if (raw_img * batch > h->raw_bytes) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            hipFree(h->d_raw); h->d_raw = nullptr; h->raw_bytes = 0;
-            HIP_TRY(h, hipMalloc(&h->d_raw, raw_img * batch));
-            h->raw_bytes = raw_img * batch;
-        }
-        for (int i = 0; i < batch; i++) {
-            if (stride == rpitch && row_bytes == rpitch) HIP_TRY(h, hipMemcpyAsync(h->d_raw + raw_img * i, imgs[i], raw_img, hipMemcpyHostToDevice, s));
-            else HIP_TRY(h, hipMemcpy2DAsync(h->d_raw + raw_img * i, rpitch, imgs[i], stride, row_bytes, h_px, hipMemcpyHostToDevice, s));
-        }
-        hs_launch_preprocess(h->d_raw, w, h_px, rpitch, raw_img, pp->channels, pp->rgb, pp->scale, h->d_in, gw, gh, pitch, per_img, 1, batch, s);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HsImg0 img0{ h->d_in, h->d_in, batch, (uint64_t)pitch, (uint64_t)per_img };
-    HsOut out{ h->d_kps, h->d_desc, h->d_n, h->d_kps, h->d_desc, h->d_n, batch, cap };
+    rc = upload_frames(h, h->in, &s, u, pp != nullptr, imgs, batch, stride, true, s);
+    if (rc == HS_OK && pp) rc = preprocess_frames(h, h->in, u, *pp, batch, s);
+    if (rc != HS_OK) return rc;
+    int32_t* const d_n = reinterpret_cast<int32_t*>(h->d_out.p);
+    hs_keypoint* const d_kps = reinterpret_cast<hs_keypoint*>(h->d_out + o.off_k); uint8_t* const d_desc = h->d_out + o.off_d;
+    HsImg0 img0{ h->in.d_in, h->in.d_in, batch, (uint64_t)u.pitch, (uint64_t)u.per_img };
+    HsOut out{ d_kps, d_desc, d_n, d_kps, d_desc, d_n, batch, cap };
     rc = run_extract(h, img0, batch, out, s);
     if (rc != HS_OK) return rc;
-    // counts, keypoints and descriptors live in one device block (ensure_outputs): one copy into pinned memory, then the used part goes to the caller
-    const size_t nb = pad256((size_t)h->out_batch * 4), kb = pad256((size_t)h->out_batch * cap * sizeof(hs_keypoint));
-    const size_t out_bytes = nb + kb + (size_t)batch * cap * HS_DESC_BYTES;
-    rc = ensure_pinned(h, &h->h_pin_out, &h->pin_out_bytes, out_bytes);
-    if (rc != HS_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->h_pin_out, h->d_n, out_bytes, hipMemcpyDeviceToHost, s));
+    // counts, keypoints and descriptors live in one device block: one copy into pinned memory, then the used part goes to the caller
+    HIP_TRY(h, h->h_pin_out.grow(o.bytes, s));
+    HIP_TRY(h, hipMemcpyAsync(h->h_pin_out, h->d_out, o.bytes, hipMemcpyDeviceToHost, s));
     // the grey frame the reference keeps beside the features (track_data.image = mImGray, ImageProcessing.cpp:60,108): tight rows, on request
-    if (grey_out) HIP_TRY(h, hipMemcpy2DAsync(grey_out, (size_t)gw, h->d_in, pitch, (size_t)gw, (size_t)gh * batch, hipMemcpyDeviceToHost, s));
+    if (grey_out) HIP_TRY(h, hipMemcpy2DAsync(grey_out, (size_t)u.gw, h->in.d_in, u.pitch, (size_t)u.gw, (size_t)u.gh * batch, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    memcpy(n, h->h_pin_out, (size_t)batch * 4);
-    for (int i = 0; i < batch; i++) {            // only the keypoints that exist are copied; the rest of the caller's arrays is left untouched
-        const size_t cnt = (size_t)std::min(std::max(n[i], 0), cap);
-        memcpy(kps + (size_t)i * cap, h->h_pin_out + nb + (size_t)i * cap * sizeof(hs_keypoint), cnt * sizeof(hs_keypoint));
-        memcpy(desc + (size_t)i * cap * HS_DESC_BYTES, h->h_pin_out + nb + kb + (size_t)i * cap * HS_DESC_BYTES, cnt * HS_DESC_BYTES);
-    }
-    h->pub_kps = h->d_kps; h->pub_desc = h->d_desc; h->pub_cap = cap; h->pub_batch = batch;
+    scatter_results(h->h_pin_out, o, batch, cap, 0, kps, desc, n, cap, nullptr, nullptr);
+    h->pub_kps = d_kps; h->pub_desc = d_desc; h->pub_cap = cap; h->pub_batch = batch;
     return HS_OK;
 }
 }  // namespace
@@ -1052,14 +1066,45 @@ int hs_stereo_match_batch_device(hs_orb* h, const hs_keypoint* d_kpsL, const uin
         pairs < 1 || pairs > 65535 || cap < 1 || cap > 65535)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_stereo_scratch(h, (size_t)pairs * cap);
-    if (rc == HS_OK) rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
+    HIP_TRY(h, h->st.grow((size_t)pairs * cap, h->stream));
+    const int rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    run_stereo(h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, *sp, d_uRight, d_depth, s);
+    run_stereo(h, false, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, *sp, d_uRight, d_depth, s);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
+
+namespace {
+// What the two single-pair stereo calls share.  The head: the handle's pinned block of `front` bytes + counts + [2][cap] results, and the matcher's buffers
+int stereo_pair_buffers(hs_orb* h, size_t front, int cap, int n_rows)
+{
+    HIP_TRY(h, h->h_pin.grow(std::max<size_t>(front + 16 + 2 * (size_t)cap * 4, 1 << 18), h->stream));
+    HIP_TRY(h, h->d_sm_n.grow(2));
+    HIP_TRY(h, h->st.grow((size_t)cap, h->stream));
+    return ensure_stereo_strips(h, 1, cap, n_rows);
+}
+// The tail: the counts go up through the pinned block (at `front`), the matcher runs on one pair of `cap` entries (behind the frames' `ready` events
+// when the keypoints come from the frame cache) and uRight / depth of the nL left keypoints come back through the pinned block
+int stereo_pair_tail(hs_orb* h, size_t front, int nL, int nR, const hs_keypoint* kL, const uint8_t* dL, const hs_keypoint* kR, const uint8_t* dR, int cap,
+                     const hs_stereo_params& sp, hipEvent_t readyL, hipEvent_t readyR, float* uRight, float* depth)
+{
+    hipStream_t s = h->stream;
+    int32_t* pn = reinterpret_cast<int32_t*>(h->h_pin + front); float* pout = reinterpret_cast<float*>(h->h_pin + front + 16);
+    pn[0] = nL; pn[1] = nR;
+    HIP_TRY(h, hipMemcpyAsync(h->d_sm_n, pn, 8, hipMemcpyHostToDevice, s));
+    if (readyL) HIP_TRY(h, hipStreamWaitEvent(s, readyL, 0));
+    if (readyR) HIP_TRY(h, hipStreamWaitEvent(s, readyR, 0));
+    run_stereo(h, false, kL, dL, h->d_sm_n, kR, dR, h->d_sm_n + 1, 1, cap, sp, h->st.ur, h->st.depth, s);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(pout, h->st.ur, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(pout + cap, h->st.depth, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    memcpy(uRight, pout, (size_t)nL * 4);
+    memcpy(depth, pout + cap, (size_t)nL * 4);
+    return HS_OK;
+}
+}  // namespace
 
 int hs_stereo_match(hs_orb* h, const hs_keypoint* kpsL, const uint8_t* descL, int nL,
                     const hs_keypoint* kpsR, const uint8_t* descR, int nR,
@@ -1074,39 +1119,21 @@ int hs_stereo_match(hs_orb* h, const hs_keypoint* kpsL, const uint8_t* descL, in
     hipStream_t s = h->stream;
     // persistent staging (grow-only): no allocation on the steady-state path.  Inputs go through one pinned block so that the five
     // H2D copies are real asynchronous DMAs; outputs come back into the same block.
-    if (cap > h->sm_cap) {
-        HIP_TRY(h, hipStreamSynchronize(s));
-        hipFree(h->d_sm_kps); hipFree(h->d_sm_desc); hipFree(h->d_sm_n); h->d_sm_kps = nullptr; h->d_sm_desc = nullptr; h->d_sm_n = nullptr; h->sm_cap = 0;
-        const int grow = std::max(cap, 2048);
-        HIP_TRY(h, hipMalloc(&h->d_sm_kps, (size_t)2 * grow * sizeof(hs_keypoint)));
-        HIP_TRY(h, hipMalloc(&h->d_sm_desc, (size_t)2 * grow * HS_DESC_BYTES));
-        HIP_TRY(h, hipMalloc(&h->d_sm_n, 8));
-        h->sm_cap = grow;
-    }
+    const size_t room = (size_t)2 * std::max(cap, 2048);      // left at [0, cap), right at [cap, 2 cap)
+    HIP_TRY(h, h->d_sm_kps.grow(room, s));
+    HIP_TRY(h, h->d_sm_desc.grow(room * HS_DESC_BYTES, s));
     const size_t kb = (size_t)cap * sizeof(hs_keypoint), db = (size_t)cap * HS_DESC_BYTES;
-    const size_t pin_need = 2 * kb + 2 * db + 16 + 2 * (size_t)cap * 4;
-    int rc = ensure_pinned(h, &h->h_pin, &h->pin_bytes, std::max<size_t>(pin_need, 1 << 18));
-    if (rc == HS_OK) rc = ensure_stereo_scratch(h, (size_t)cap);
-    if (rc == HS_OK) rc = ensure_stereo_strips(h, 1, cap, sp->n_rows);
+    const int rc = stereo_pair_buffers(h, 2 * kb + 2 * db, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
-    hs_keypoint* dk = h->d_sm_kps; uint8_t* dd = h->d_sm_desc; int32_t* dn = h->d_sm_n;
-    uint8_t* pk = h->h_pin; uint8_t* pd = pk + 2 * kb; int32_t* pn = reinterpret_cast<int32_t*>(pd + 2 * db); float* pout = reinterpret_cast<float*>(pd + 2 * db + 16);
+    hs_keypoint* dk = h->d_sm_kps; uint8_t* dd = h->d_sm_desc;
+    uint8_t* pk = h->h_pin; uint8_t* pd = pk + 2 * kb;
     memcpy(pk, kpsL, (size_t)nL * sizeof(hs_keypoint));
     if (nR) memcpy(pk + kb, kpsR, (size_t)nR * sizeof(hs_keypoint));
     memcpy(pd, descL, (size_t)nL * 32);
     if (nR) memcpy(pd + db, descR, (size_t)nR * 32);
-    pn[0] = nL; pn[1] = nR;
-    HIP_TRY(h, hipMemcpyAsync(dk, pk, 2 * kb, hipMemcpyHostToDevice, s));                 // left at [0, cap), right at [cap, 2 cap)
+    HIP_TRY(h, hipMemcpyAsync(dk, pk, 2 * kb, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(dd, pd, 2 * db, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dn, pn, 8, hipMemcpyHostToDevice, s));
-    run_stereo(h, dk, dd, dn, dk + cap, dd + (size_t)cap * 32, dn + 1, 1, cap, *sp, h->d_ur, h->d_depth, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(pout, h->d_ur, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(pout + cap, h->d_depth, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    memcpy(uRight, pout, (size_t)nL * 4);
-    memcpy(depth, pout + cap, (size_t)nL * 4);
-    return HS_OK;
+    return stereo_pair_tail(h, 2 * kb + 2 * db, nL, nR, dk, dd, dk + cap, dd + (size_t)cap * 32, cap, *sp, nullptr, nullptr, uRight, depth);
 }
 
 int hs_stereo_frontend_batch_device(hs_orb* h, const uint8_t* d_left, const uint8_t* d_right, int pairs,
@@ -1124,48 +1151,21 @@ int hs_stereo_frontend_batch_device(hs_orb* h, const uint8_t* d_left, const uint
     if ((((uintptr_t)d_descL | (uintptr_t)d_descR) & 15) != 0 || (((uintptr_t)d_kpsL | (uintptr_t)d_kpsR | (uintptr_t)d_nL | (uintptr_t)d_nR | (uintptr_t)d_uRight | (uintptr_t)d_depth) & 3) != 0)
         return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores), everything else 4");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->lane2 && pairs >= 2) {      // two lanes: each handles half of the pairs end to end (extract L+R, match) on its own stream
-        hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-        const int p0 = pairs / 2, p1 = pairs - p0;
-        h->lane2->prof = h->prof;
-        HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-        HIP_TRY(h, hipStreamWaitEvent(h->lane2->stream, h->ev_fork, 0));
-        hs_orb* child = h->lane2; h->lane2 = nullptr;
-        int rc = hs_stereo_frontend_batch_device(h, d_left, d_right, p0, w, h_px, row_stride, image_stride, d_kpsL, d_descL, d_nL,
-                                                 d_kpsR, d_descR, d_nR, cap, sp, d_uRight, d_depth, s);
-        if (rc == HS_OK) {
-            const size_t io = (size_t)p0 * image_stride, ko = (size_t)p0 * cap;
-            rc = hs_stereo_frontend_batch_device(child, d_left + io, d_right + io, p1, w, h_px, row_stride, image_stride,
-                                                 d_kpsL + ko, d_descL + ko * HS_DESC_BYTES, d_nL + p0, d_kpsR + ko, d_descR + ko * HS_DESC_BYTES, d_nR + p0,
-                                                 cap, sp, d_uRight + ko, d_depth + ko, child->stream);
-            if (rc != HS_OK) h->err = child->err;
-        }
-        h->lane2 = child;
-        HIP_TRY(h, hipEventRecord(h->ev_join, child->stream));
-        HIP_TRY(h, hipStreamWaitEvent(s, h->ev_join, 0));
-        return rc;
-    }
-    int rc = configure(h, w, h_px, 2 * pairs);
-    if (rc != HS_OK) return rc;
-    if (cap < h->max_kp) return hs_fail(h, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
-    rc = ensure_stereo_scratch(h, (size_t)pairs * cap);
-    if (rc == HS_OK) rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
-    if (rc != HS_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    HsImg0 img0{ d_left, d_right, pairs, (uint64_t)row_stride, (uint64_t)image_stride };
-    HsOut out{ d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap };
-    if (h->stereo_fuse) {
-        const HsStripFuse sf{ 1, sp->n_rows, hs_stereo_strips(sp->n_rows), 0, sp->size_ref, h->d_strip_count, reinterpret_cast<HsStripEntry*>(h->d_strip_list) };
-        rc = run_extract(h, img0, 2 * pairs, out, s, &sf);
+    const auto body = [&](hs_orb* q, int first, int count, hipStream_t qs) -> int {
+        int rc = configure(q, w, h_px, 2 * count);
         if (rc != HS_OK) return rc;
-        run_stereo_fused(h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, *sp, d_uRight, d_depth, s);
-    } else {
-        rc = run_extract(h, img0, 2 * pairs, out, s);
+        if (cap < q->geo.max_kp) return hs_fail(q, HS_ERR_CAPACITY, "cap < keypoints this frame size can produce; see hs_orb_max_keypoints");
+        HIP_TRY(q, q->st.grow((size_t)count * cap, q->stream));
+        rc = ensure_stereo_strips(q, count, cap, sp->n_rows);
         if (rc != HS_OK) return rc;
-        run_stereo(h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, *sp, d_uRight, d_depth, s);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+        const size_t io = (size_t)first * image_stride, ko = (size_t)first * cap;
+        HsImg0 img0{ d_left + io, d_right + io, count, (uint64_t)row_stride, (uint64_t)image_stride };
+        HsOut out{ d_kpsL + ko, d_descL + ko * HS_DESC_BYTES, d_nL + first, d_kpsR + ko, d_descR + ko * HS_DESC_BYTES, d_nR + first, count, cap };
+        return run_stereo_frontend(q, img0, out, *sp, d_uRight + ko, d_depth + ko, qs);
+    };
+    // two lanes: each handles half of the pairs end to end (extract L+R, match) on its own stream
+    return h->lane2 && pairs >= 2 ? run_lanes(h, s, pairs, body) : body(h, 0, pairs, s);
 }
 
 /* ---- pipelined host ingest ----
@@ -1187,9 +1187,9 @@ void hs_host_free(void* p) { if (p) (void)hipHostFree(p); }
 static int submit_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int src_w, int src_h, size_t stride, const hs_preprocess_params* pp, const hs_stereo_params* sp, int32_t* ticket)
 {
     for (int i = 0; i < batch; i++) if (!imgs[i]) return hs_fail(h, HS_ERR_INVALID, "null image in batch");
-    int w = src_w, h_px = src_h;
-    if (pp) hs_preprocess_out_size(src_w, src_h, pp->scale, &w, &h_px);
-    if (w < 1 || h_px < 1) return hs_fail(h, HS_ERR_INVALID, "the camera scale reduces the frame to nothing (cv::resize asserts on an empty size)");
+    FramePlan u;
+    int rc = plan_frames(h, src_w, src_h, pp, &u);
+    if (rc != HS_OK) return rc;
     *ticket = 0;
     h->pub_kps = nullptr; h->pub_desc = nullptr; h->pub_batch = 0;      // a slot's device block may be rewritten from here on
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1205,90 +1205,48 @@ static int submit_frames(hs_orb* h, const uint8_t* const* imgs, int batch, int s
         HIP_TRY(h, hipEventCreateWithFlags(&sl->ev_done, hipEventDisableTiming));
         HIP_TRY(h, hipEventCreateWithFlags(&sl->ev_out, hipEventDisableTiming));
     }
-    if (!(w == h->w && h_px == h->h && batch <= h->batch_cap)) {      // a new geometry rebuilds the shared workspace: nothing may be in flight on it
+    if (!(u.gw == h->geo.w && u.gh == h->geo.h && batch <= h->geo.batch_cap)) {      // a new geometry rebuilds the shared workspace: nothing may be in flight on it
         HIP_TRY(h, hipStreamSynchronize(h->s_in)); HIP_TRY(h, hipStreamSynchronize(h->s_out));
     }
-    int rc = configure(h, w, h_px, batch);
+    rc = configure(h, u.gw, u.gh, batch);
     if (rc != HS_OK) return rc;
-    const int cap = h->max_kp, pairs = sp ? batch / 2 : 0;
+    const int cap = h->geo.max_kp, pairs = sp ? batch / 2 : 0;
     if (cap < 1) return hs_fail(h, HS_ERR_INVALID, "this frame size yields no keypoints");
-    const size_t pitch = ((size_t)w + 63) & ~(size_t)63, per_img = pitch * h_px;
-    if (per_img * batch > sl->in_bytes) {
-        hipFree(sl->d_in); sl->d_in = nullptr; sl->in_bytes = 0;           // the slot is idle: its last batch was waited for
-        HIP_TRY(h, hipMalloc(&sl->d_in, per_img * batch));
-        sl->in_bytes = per_img * batch;
-    }
-    const size_t raw_row = pp ? (size_t)src_w * pp->channels : 0, rpitch = (raw_row + 3) & ~(size_t)3, raw_img = rpitch * src_h;      // the camera's frames as uploaded
-    if (pp && raw_img * batch > sl->raw_bytes) {
-        hipFree(sl->d_raw); sl->d_raw = nullptr; sl->raw_bytes = 0;
-        HIP_TRY(h, hipMalloc(&sl->d_raw, raw_img * batch));
-        sl->raw_bytes = raw_img * batch;
-    }
-    sl->off_k = pad256((size_t)batch * 4);
-    sl->off_d = sl->off_k + pad256((size_t)batch * cap * sizeof(hs_keypoint));
-    sl->off_u = sl->off_d + pad256((size_t)batch * cap * HS_DESC_BYTES);
-    sl->off_z = sl->off_u + pad256((size_t)std::max(pairs, 1) * cap * 4);
-    sl->used = sl->off_z + pad256((size_t)std::max(pairs, 1) * cap * 4);
-    if (sl->used > sl->out_bytes) {
-        hipFree(sl->d_out); sl->d_out = nullptr; sl->out_bytes = 0;
-        HIP_TRY(h, hipMalloc(&sl->d_out, sl->used));
-        sl->out_bytes = sl->used;
-    }
-    if (sl->used > sl->h_out_bytes) {
-        if (sl->h_out) hipHostFree(sl->h_out);
-        sl->h_out = nullptr; sl->h_out_bytes = 0;
-        HIP_TRY(h, hipHostMalloc((void**)&sl->h_out, sl->used, hipHostMallocDefault));
-        sl->h_out_bytes = sl->used;
-    }
+    const OutLayout o = out_layout(batch, cap, pairs);
+    HIP_TRY(h, sl->d_out.grow(o.bytes));             // the slot is idle: its last batch was waited for
+    HIP_TRY(h, sl->h_out.grow(o.bytes));
     if (sp) {
-        rc = ensure_stereo_scratch(h, (size_t)pairs * cap);
-        if (rc == HS_OK) rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
+        HIP_TRY(h, h->st.grow((size_t)pairs * cap, h->stream));
+        rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
         if (rc != HS_OK) return rc;
     }
     // From here on work is ENQUEUED that targets the slot's buffers: whatever fails below, the three streams are drained before the call returns,
     // so that a slot handed out again (it stays !busy) is never written by a copy or a kernel of the failed attempt.
     auto enqueue = [&]() -> int {
-    // copy-in stream: page-locked frames (hs_host_alloc) go by DMA at link speed and the call returns at once; pageable frames go through the
-    // runtime's staging path (the call returns when they are staged) — either way the compute stream keeps running the previous batch
-    for (int i = 0; i < batch; i++) {
-        if (pp) HIP_TRY(h, hipMemcpy2DAsync(sl->d_raw + raw_img * i, rpitch, imgs[i], stride, raw_row, src_h, hipMemcpyHostToDevice, h->s_in));
-        else HIP_TRY(h, hipMemcpy2DAsync(sl->d_in + per_img * i, pitch, imgs[i], stride, w, h_px, hipMemcpyHostToDevice, h->s_in));
-    }
+    // copy-in stream: the compute stream keeps running the previous batch meanwhile
+    rc = upload_frames(h, sl->in, nullptr, u, pp != nullptr, imgs, batch, stride, false, h->s_in);
+    if (rc != HS_OK) return rc;
     HIP_TRY(h, hipEventRecord(sl->ev_in, h->s_in));
     hipStream_t s = h->stream;
     HIP_TRY(h, hipStreamWaitEvent(s, sl->ev_in, 0));
-    if (pp) {      // camera scale + grey on the compute stream, into the slot's level-0 frames
-        hs_launch_preprocess(sl->d_raw, src_w, src_h, rpitch, raw_img, pp->channels, pp->rgb, pp->scale, sl->d_in, w, h_px, pitch, per_img, 1, batch, s);
-        HIP_TRY(h, hipGetLastError());
-    }
-    int32_t* d_n = reinterpret_cast<int32_t*>(sl->d_out);
-    hs_keypoint* d_k = reinterpret_cast<hs_keypoint*>(sl->d_out + sl->off_k);
-    uint8_t* d_d = sl->d_out + sl->off_d;
+    if (pp) { rc = preprocess_frames(h, sl->in, u, *pp, batch, s); if (rc != HS_OK) return rc; }
+    int32_t* d_n = reinterpret_cast<int32_t*>(sl->d_out.p);
+    hs_keypoint* d_k = reinterpret_cast<hs_keypoint*>(sl->d_out + o.off_k);
+    uint8_t* d_d = sl->d_out + o.off_d;
+    const uint8_t* const d_in = sl->in.d_in;
     if (sp) {      // images [0, pairs) are the left frames, [pairs, 2 pairs) the right ones (hs_stereo_frontend_batch_device's layout)
-        HsImg0 img0{ sl->d_in, sl->d_in + per_img * pairs, pairs, (uint64_t)pitch, (uint64_t)per_img };
+        HsImg0 img0{ d_in, d_in + u.per_img * pairs, pairs, (uint64_t)u.pitch, (uint64_t)u.per_img };
         HsOut out{ d_k, d_d, d_n, d_k + (size_t)pairs * cap, d_d + (size_t)pairs * cap * HS_DESC_BYTES, d_n + pairs, pairs, cap };
-        if (h->stereo_fuse) {
-            const HsStripFuse sf{ 1, sp->n_rows, hs_stereo_strips(sp->n_rows), 0, sp->size_ref, h->d_strip_count, reinterpret_cast<HsStripEntry*>(h->d_strip_list) };
-            rc = run_extract(h, img0, batch, out, s, &sf);
-            if (rc != HS_OK) return rc;
-            run_stereo_fused(h, out.kps, out.desc, out.n, out.kps2, out.desc2, out.n2, pairs, cap, *sp,
-                             reinterpret_cast<float*>(sl->d_out + sl->off_u), reinterpret_cast<float*>(sl->d_out + sl->off_z), s);
-        } else {
-            rc = run_extract(h, img0, batch, out, s);
-            if (rc != HS_OK) return rc;
-            run_stereo(h, out.kps, out.desc, out.n, out.kps2, out.desc2, out.n2, pairs, cap, *sp,
-                       reinterpret_cast<float*>(sl->d_out + sl->off_u), reinterpret_cast<float*>(sl->d_out + sl->off_z), s);
-        }
-        HIP_TRY(h, hipGetLastError());
+        rc = run_stereo_frontend(h, img0, out, *sp, reinterpret_cast<float*>(sl->d_out + o.off_u), reinterpret_cast<float*>(sl->d_out + o.off_z), s);
     } else {
-        HsImg0 img0{ sl->d_in, sl->d_in, batch, (uint64_t)pitch, (uint64_t)per_img };
+        HsImg0 img0{ d_in, d_in, batch, (uint64_t)u.pitch, (uint64_t)u.per_img };
         HsOut out{ d_k, d_d, d_n, d_k, d_d, d_n, batch, cap };
         rc = run_extract(h, img0, batch, out, s);
-        if (rc != HS_OK) return rc;
     }
+    if (rc != HS_OK) return rc;
     HIP_TRY(h, hipEventRecord(sl->ev_done, s));
     HIP_TRY(h, hipStreamWaitEvent(h->s_out, sl->ev_done, 0));
-    HIP_TRY(h, hipMemcpyAsync(sl->h_out, sl->d_out, sl->used, hipMemcpyDeviceToHost, h->s_out));
+    HIP_TRY(h, hipMemcpyAsync(sl->h_out, sl->d_out, o.bytes, hipMemcpyDeviceToHost, h->s_out));
     HIP_TRY(h, hipEventRecord(sl->ev_out, h->s_out));
     return HS_OK;
     };
@@ -1341,21 +1299,11 @@ int hs_orb_wait(hs_orb* h, int32_t ticket, hs_keypoint* kps, uint8_t* desc, int3
             return hs_fail(h, HS_ERR_HIP, std::string("hipEventSynchronize(ticket): ") + hipGetErrorString(e));
         }
     }
-    const int B = sl->batch, c0 = sl->cap;
-    memcpy(n, sl->h_out, (size_t)B * 4);
-    for (int i = 0; i < B; i++) {            // only the keypoints that exist are copied, into the caller's [batch][cap] layout
-        const size_t cnt = (size_t)std::min(std::max(n[i], 0), c0);
-        memcpy(kps + (size_t)i * cap, sl->h_out + sl->off_k + (size_t)i * c0 * sizeof(hs_keypoint), cnt * sizeof(hs_keypoint));
-        memcpy(desc + (size_t)i * cap * HS_DESC_BYTES, sl->h_out + sl->off_d + (size_t)i * c0 * HS_DESC_BYTES, cnt * HS_DESC_BYTES);
-    }
-    for (int i = 0; i < sl->pairs; i++) {
-        const size_t cnt = (size_t)std::min(std::max(n[i], 0), c0);
-        memcpy(uRight + (size_t)i * cap, sl->h_out + sl->off_u + (size_t)i * c0 * 4, cnt * 4);
-        memcpy(depth + (size_t)i * cap, sl->h_out + sl->off_z + (size_t)i * c0 * 4, cnt * 4);
-    }
+    const OutLayout o = out_layout(sl->batch, sl->cap, sl->pairs);
+    scatter_results(sl->h_out, o, sl->batch, sl->cap, sl->pairs, kps, desc, n, cap, uRight, depth);
     sl->busy = false;
     // (the slot's device block stays as it is until the slot is handed to another hs_orb_submit_batch)
-    h->pub_kps = reinterpret_cast<const hs_keypoint*>(sl->d_out + sl->off_k); h->pub_desc = sl->d_out + sl->off_d; h->pub_cap = c0; h->pub_batch = B;
+    h->pub_kps = reinterpret_cast<const hs_keypoint*>(sl->d_out + o.off_k); h->pub_desc = sl->d_out + o.off_d; h->pub_cap = sl->cap; h->pub_batch = sl->batch;
     return HS_OK;
 }
 
@@ -1421,8 +1369,8 @@ namespace {
 constexpr int HS_FRAME_SLOTS = 16;
 struct FrameSlot {
     uint64_t token = 0, stamp = 0;     // token 0 = empty
-    int n = 0, cap = 0, readers = 0;
-    hs_keypoint* d_kps = nullptr; uint8_t* d_desc = nullptr;
+    int n = 0, readers = 0;
+    HsBuf<hs_keypoint> d_kps; HsBuf<uint8_t> d_desc;   // regrown behind `ready`; leaked with the cache at process exit (HsBuf's destructor never runs there)
     std::vector<hs_keypoint> h_kps;
     hipEvent_t ready = nullptr;        // recorded behind the copy that filled the slot
 };
@@ -1471,13 +1419,11 @@ int hs_frame_publish(hs_orb* h, int image, const hs_keypoint* kps, int n, hs_fra
     }
     struct Unreserve { FrameSlot* s; ~Unreserve() { if (s) { std::lock_guard<std::mutex> g(g_frames_mu); s->readers = 0; } } } unreserve{sl};      // failure paths: the slot is empty (token 0) and free again
     if (!sl->ready) HIP_TRY(h, hipEventCreateWithFlags(&sl->ready, hipEventDisableTiming));
-    if (n > sl->cap) {
+    if ((size_t)n > sl->d_kps.cap) {
         HIP_TRY(h, hipEventSynchronize(sl->ready));      // (a never-recorded event is complete)
-        hipFree(sl->d_kps); hipFree(sl->d_desc); sl->d_kps = nullptr; sl->d_desc = nullptr; sl->cap = 0;
-        const int grow = std::max(n, 2048);
-        HIP_TRY(h, hipMalloc(&sl->d_kps, (size_t)grow * sizeof(hs_keypoint)));
-        HIP_TRY(h, hipMalloc(&sl->d_desc, (size_t)grow * HS_DESC_BYTES));
-        sl->cap = grow;
+        const size_t room = (size_t)std::max(n, 2048);
+        HIP_TRY(h, sl->d_kps.grow(room));
+        HIP_TRY(h, sl->d_desc.grow(room * HS_DESC_BYTES));
     }
     hipStream_t s = h->stream;
     HIP_TRY(h, hipStreamWaitEvent(s, sl->ready, 0));     // the copy that filled the slot last time (another handle's stream) comes first
@@ -1532,7 +1478,7 @@ int hs_frame_cache_clear(int device)
         (void)hipSetDevice(device);
         for (FrameSlot& sl : c->slot) {
             if (sl.ready) { (void)hipEventSynchronize(sl.ready); (void)hipEventDestroy(sl.ready); }
-            (void)hipFree(sl.d_kps); (void)hipFree(sl.d_desc);
+            sl.d_kps.release(); sl.d_desc.release();
         }
         if (cur >= 0) (void)hipSetDevice(cur);
         delete c;
@@ -1595,26 +1541,9 @@ int hs_stereo_match_frames(hs_orb* h, hs_frame_token left, hs_frame_token right,
     guard.b = &R;
     HIP_TRY(h, hipSetDevice(h->device));
     const int nL = L.n, nR = R.n, cap = std::max(nL, nR);
-    hipStream_t s = h->stream;
-    if (!h->d_sm_n) HIP_TRY(h, hipMalloc(&h->d_sm_n, 8));
-    const size_t pin_need = 16 + 2 * (size_t)cap * 4;
-    int rc = ensure_pinned(h, &h->h_pin, &h->pin_bytes, std::max<size_t>(pin_need, 1 << 18));
-    if (rc == HS_OK) rc = ensure_stereo_scratch(h, (size_t)cap);
-    if (rc == HS_OK) rc = ensure_stereo_strips(h, 1, cap, sp->n_rows);
+    const int rc = stereo_pair_buffers(h, 0, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
-    int32_t* pn = reinterpret_cast<int32_t*>(h->h_pin); float* pout = reinterpret_cast<float*>(h->h_pin + 16);
-    pn[0] = nL; pn[1] = nR;
-    HIP_TRY(h, hipMemcpyAsync(h->d_sm_n, pn, 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipStreamWaitEvent(s, L.ready, 0));
-    HIP_TRY(h, hipStreamWaitEvent(s, R.ready, 0));
-    run_stereo(h, L.d_kps, L.d_desc, h->d_sm_n, R.d_kps, R.d_desc, h->d_sm_n + 1, 1, cap, *sp, h->d_ur, h->d_depth, s);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(pout, h->d_ur, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(pout + cap, h->d_depth, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    memcpy(uRight, pout, (size_t)nL * 4);
-    memcpy(depth, pout + cap, (size_t)nL * 4);
-    return HS_OK;
+    return stereo_pair_tail(h, 0, nL, nR, L.d_kps, L.d_desc, R.d_kps, R.d_desc, cap, *sp, L.ready, R.ready, uRight, depth);
 }
 
 int hs_frame_grid(hs_orb* h, const hs_frame_view* F, int8_t* cell_xy)
@@ -1940,7 +1869,7 @@ int hs_orb_stage_launches(const hs_orb* h, int stage)
     if (stage == 0) {
         if (h->last_pyr_launches > 0) return h->last_pyr_launches;      // counted by the launcher itself: a per-level fallback (caller-frame alignment, no big LDS) is included
         if (h->lv.empty()) return std::max(h->p.nlevels - 1, 0);
-        if (h->last_batch > 0 && h->last_batch <= h->deep_max_batch && !h->pyr_deep.empty()) { int32_t o[8]; hs_debug_plan_summary(h, o); return o[1]; }
+        if (h->last_batch > 0 && h->last_batch <= h->deep_max_batch && !h->geo.pyr_deep.empty()) { int32_t o[8]; hs_debug_plan_summary(h, o); return o[1]; }
         return hs_pyramid_launch_count(h->lv.data(), h->p.nlevels);
     }
     return stage == 4 ? h->last_stereo_launches : 1;
@@ -2052,14 +1981,14 @@ int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int c
     HIP_TRY(h, hipDeviceSynchronize());
     const HsLevel& V = h->lv[level];
     int32_t cnt = 0;
-    HIP_TRY(h, hipMemcpy(&cnt, h->d_cand_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(&cnt, h->geo.d_cand_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     cnt = std::min(cnt, V.cand_cap);
     *n = cnt;
     if (cnt > cap) return hs_fail(h, HS_ERR_CAPACITY, "more candidates than buffer");
     std::vector<uint32_t> xy(cnt), sk(cnt);
     if (cnt) {
-        HIP_TRY(h, hipMemcpy(xy.data(), h->d_pts_xy + (size_t)image * h->cand_img_stride + V.cand_off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(sk.data(), h->d_pts_sk + (size_t)image * h->cand_img_stride + V.cand_off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(xy.data(), h->geo.d_pts_xy + (size_t)image * h->geo.cand_img_stride + V.cand_off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(sk.data(), h->geo.d_pts_sk + (size_t)image * h->geo.cand_img_stride + V.cand_off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     }
     for (int i = 0; i < cnt; i++) { xys[3 * i] = xy[i] & 0xFFFF; xys[3 * i + 1] = xy[i] >> 16; xys[3 * i + 2] = sk[i] >> 24; }
     return HS_OK;
@@ -2073,10 +2002,10 @@ int hs_orb_debug_selected(hs_orb* h, int image, int level, int32_t* xys, int cap
     HIP_TRY(h, hipDeviceSynchronize());
     const HsLevel& V = h->lv[level];
     int32_t cnt = 0;
-    HIP_TRY(h, hipMemcpy(&cnt, h->d_sel_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(&cnt, h->geo.d_sel_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     *n = cnt;
     if (cnt > cap) return hs_fail(h, HS_ERR_CAPACITY, "more keypoints than buffer");
-    if (cnt) HIP_TRY(h, hipMemcpy(xys, h->d_sel + ((size_t)image * h->sel_img_stride + V.sel_off) * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost));
+    if (cnt) HIP_TRY(h, hipMemcpy(xys, h->geo.d_sel + ((size_t)image * h->geo.sel_img_stride + V.sel_off) * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost));
     return HS_OK;
 }
 

@@ -21,6 +21,7 @@ void hs_orb_borrow(hs_orb* h, int delta);      // hs_api.hip (internal: what hs_
 
 extern "C" long hip_stub_launches();
 extern "C" void hip_stub_zero_device();
+extern "C" void hip_stub_counters(unsigned long long* out /*[14]*/);       // hip_stub.cpp: live allocations, calls and bytes of allocations / copies / memsets, launches and their digest
 void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/);        // hs_api.hip: launches of the pyramid's two plans, item counts (host-side facts of the last configuration)
 
 #define CHECK(c) do { if (!(c)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
@@ -28,11 +29,24 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/);        // hs_
 static std::mt19937_64 rng;
 static int rnd(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }
 
+// what the host code asked of the runtime so far, as one line: two commits that claim the same behaviour print the same figures
+static void print_counters(const char* where)
+{
+    unsigned long long c[14]; hip_stub_counters(c);
+    printf("%s: live device %llu pinned %llu | hipMalloc %llu calls %llu B | hipHostMalloc %llu calls %llu B | H2D %llu calls %llu B | D2H %llu calls %llu B | memset %llu calls %llu B | launches %llu digest %016llx\n",
+           where, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12], c[13]);
+}
+// live "device" and pinned allocations: a handle that was destroyed must have given back everything it took
+struct Live { unsigned long long dev, pin; };
+static Live live_now() { unsigned long long c[14]; hip_stub_counters(c); return Live{ c[0], c[1] }; }
+static bool same_live(const Live& a) { const Live b = live_now(); if (a.dev != b.dev || a.pin != b.pin) printf("live allocations: device %llu -> %llu, pinned %llu -> %llu\n", a.dev, b.dev, a.pin, b.pin); return a.dev == b.dev && a.pin == b.pin; }
+
 static int geometry_case(int w, int h, int nfeat, float scale, int levels, int cell, int batch, bool exercise)
 {
     hs_orb_params p; hs_orb_default_params(&p);
     p.nfeatures = nfeat; p.scale_factor = scale; p.nlevels = levels; p.cell_px = cell;
     hs_orb* ex = nullptr;
+    const Live before = live_now();
     int st = hs_orb_create(&p, 0, &ex);
     if (st != HS_OK) return 0;                                   // rejected parameter combinations (quota > LDS list, ...) are fine: no crash is the point
     st = hs_orb_reserve(ex, w, h, batch);
@@ -93,6 +107,7 @@ static int geometry_case(int w, int h, int nfeat, float scale, int levels, int c
         }
     }
     hs_orb_destroy(ex);
+    if (!same_live(before)) { printf("hs_orb_destroy left allocations behind (%dx%d, batch %d)\n", w, h, batch); return -1; }
     return ok;
 }
 
@@ -151,6 +166,7 @@ static int staged_sweep(int rounds)
 {
     hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300;
     hs_orb *ex = nullptr, *h = nullptr;                          // ex extracts and publishes frames, h is the ONE handle of the sweep
+    const Live before = live_now();
     CHECK(hs_orb_create(&p, 0, &ex) == HS_OK && hs_orb_create(&p, 0, &h) == HS_OK);
     const int w = 320, hh = 240;
     const std::vector<uint8_t> img = rand_bytes((size_t)w * hh);
@@ -250,7 +266,8 @@ static int staged_sweep(int rounds)
         }
     }
     hs_orb_destroy(ex); hs_orb_destroy(h);
-    CHECK(hs_frame_cache_clear(0) == HS_OK);
+    CHECK(hs_frame_cache_clear(0) == HS_OK);                     // (the published frames belong to the cache, not to a handle)
+    CHECK(same_live(before));
     return calls > 0 ? 0 : 1;
 }
 
@@ -294,6 +311,7 @@ int main(int argc, char** argv)
     }
     unsetenv("HS_PYRAMID_PLAN"); unsetenv("HS_PYRAMID_CHAIN"); unsetenv("HS_PYRAMID_DEEP_MAX");
     CHECK(accepted > tried / 2);
+    print_counters("HOST SANITIZE COUNTERS after the geometry sweep");       // (everything up to here is single-threaded: the same for every run of a commit)
 
     // ---- a handle outliving its communicators: hs_orb_destroy and the last borrower's release race on two threads; exactly one of them frees
     // the handle (ASan: a double free or a leak fails the run), in either order and with several borrowers
@@ -374,7 +392,7 @@ int main(int argc, char** argv)
             }
         };
         std::thread t1(publisher, ex, 1000), t2(publisher, ex2, 5000);
-        std::thread t3([&] { std::vector<hs_keypoint> kk(nk); while (!stop.load()) { for (int i = 0; i < nk; i++) kk[i] = hs_keypoint{ 1000.f + (float)(rng() % 400), (float)i, 31.f, 0.f, 1.f, 0 }; hs_frame_token t = 0; (void)hs_frame_find(0, kk.data(), 1 + (int)(rng() % nk), &t); } });
+        std::thread t3([&] { std::mt19937_64 rng(seed + 3) /* its own: the main generator stays what the seed made it */; std::vector<hs_keypoint> kk(nk); while (!stop.load()) { for (int i = 0; i < nk; i++) kk[i] = hs_keypoint{ 1000.f + (float)(rng() % 400), (float)i, 31.f, 0.f, 1.f, 0 }; hs_frame_token t = 0; (void)hs_frame_find(0, kk.data(), 1 + (int)(rng() % nk), &t); } });
         std::thread t4([&] {
             hs_frame_view G = F; std::vector<int32_t> mi2(lm.size()); std::vector<float> md2(lm.size()); int32_t nm2 = 0;
             while (!stop.load()) {
@@ -389,6 +407,7 @@ int main(int argc, char** argv)
         CHECK(hs_frame_info(0, latest.load(), &ninfo) != HS_OK);
     }
 
+    print_counters("HOST SANITIZE COUNTERS after the threaded frame-cache section (varies from run to run)");
     CHECK(staged_sweep(12) == 0);
 
     // ---- vocabulary files: valid round trips, then truncations and random corruptions of both formats
@@ -430,7 +449,8 @@ int main(int argc, char** argv)
         } else { CHECK(a == nullptr && hs_vocab_last_error()[0] != 0); refused++; }
     }
     unlink(ptxt.c_str()); unlink(pbin.c_str()); unlink(pbad_t.c_str()); unlink(pbad_b.c_str()); rmdir(dir);
-    printf("HOST SANITIZE OK seed %llu: %d of %d geometries configured, %ld kernel launches issued into the stub, %d corrupted vocabularies refused, %d still well-formed\n",
+    printf("HOST SANITIZE OK seed %llu: %d of %d geometries configured, %ld kernel launches issued into the stub, %d corrupted vocabularies refused, %d still well-formed; ",
            (unsigned long long)seed, accepted, tried, hip_stub_launches(), refused, loaded);
+    print_counters("totals");
     return 0;
 }
