@@ -13,13 +13,10 @@
 // merge walk disappears.  Inside a node the reference scans side 2 in ascending index order and the first minimum wins: the candidate key is
 // dist<<32 | side-2 index, which makes the bucket's internal order irrelevant.  Features whose word weight is not positive are left out of the
 // feature vector, as in DBoW2 (`if (w > 0) fv.addFeature(nid, i)`).
-#include "hs_internal.h"
+#include "hs_match_device.h"
 #include <algorithm>
-#include <cfloat>
 #include <vector>
 
-#define BOW_NO_KEY 0x7FFFFFFFFFFFFFFFull
-#define BOW_NO_DIST 0x7FFFFFFF
 #define BOW_MAX_GROUPS 8192
 
 struct hs_vocab_dev {
@@ -34,16 +31,14 @@ struct BowTree { const int32_t* cb; const int32_t* cc; const uint8_t* desc; cons
 // DBoW2 transform of one descriptor: word (leaf) and the node passed at level nid_level (0 = root when nid_level <= 0)
 __device__ __forceinline__ void bow_descend(const BowTree& T, const uint8_t* f32, int& leaf, int& nid)
 {
-    const unsigned long long* f = reinterpret_cast<const unsigned long long*>(f32);
-    const unsigned long long f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+    const Desc256 f = desc_load(f32);
     int final_id = 0, level = 0; nid = 0;
     do {
         ++level;
         const int cb = T.cb[final_id], cc = T.cc[final_id];
         int best = 0x7FFFFFFF;
         for (int c = cb; c < cb + cc; c++) {
-            const unsigned long long* d = reinterpret_cast<const unsigned long long*>(T.desc + (size_t)c * 32);
-            const int dist = __popcll(f0 ^ d[0]) + __popcll(f1 ^ d[1]) + __popcll(f2 ^ d[2]) + __popcll(f3 ^ d[3]);
+            const int dist = hamming256(f, desc_load(T.desc + (size_t)c * 32));
             if (dist < best) { best = dist; final_id = c; }      // strict: the first minimum wins
         }
         if (level == T.nid_level) nid = final_id;
@@ -90,33 +85,13 @@ __global__ __launch_bounds__(1024) void k_records_buckets(const uint8_t* __restr
     const int PER = (groups + 1023) / 1024;
     uint32_t sum = 0;
     for (int k = 0; k < PER; k++) { const int g = tid * PER + k; if (g < groups) sum += cnt[g]; }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += v; }
-    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const uint32_t x = s_wave[w]; if (w < (tid >> 6)) base += x; total += x; }
-    uint32_t run = base + incl - sum;
+    uint32_t total, run = block_scan_excl(sum, s_wave, total);
     int32_t* st = start + (size_t)r * (groups + 1);
     for (int k = 0; k < PER; k++) { const int g = tid * PER + k; if (g < groups) { const uint32_t c = cnt[g]; st[g] = (int32_t)run; cnt[g] = run; run += c; } }
     if (tid == 0) st[groups] = (int32_t)total;
     __syncthreads();
     uint16_t* it = items + (size_t)r * cap;
     for (int i = tid; i < n; i += 1024) { const int g = fg[i]; if (g >= 0) it[atomicAdd(&cnt[g], 1u)] = (uint16_t)i; }
-}
-
-__device__ __forceinline__ void bow_wave_best2(unsigned long long& best, int& second)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long ob = __shfl_xor(best, s, 64);
-        const int os = __shfl_xor(second, s, 64);
-        const int worse = max((int)(best >> 32), (int)(ob >> 32));
-        best = min(best, ob);
-        second = min(min(second, os), worse);
-    }
 }
 
 // blockIdx.x = group, blockIdx.y = peer record: every side-1 feature of the group against the peer's features of the same group
@@ -134,22 +109,15 @@ __global__ __launch_bounds__(256) void k_records_bow_match(const uint8_t* __rest
     const uint8_t* d1 = recs + (size_t)rank * stride + off_desc; const uint8_t* d2 = recs + (size_t)peer * stride + off_desc;
     for (int p = p0 + wv; p < p1; p += 4) {
         const int i1 = it1[p];
-        const unsigned long long* a = reinterpret_cast<const unsigned long long*>(d1 + (size_t)i1 * 32);
-        const unsigned long long a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-        unsigned long long best = BOW_NO_KEY; int second = BOW_NO_DIST;
+        const Desc256 a = desc_load(d1 + (size_t)i1 * 32);
+        unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
         for (int q = q0 + lane; q < q1; q += 64) {
             const int i2 = it2[q];
-            const unsigned long long* b = reinterpret_cast<const unsigned long long*>(d2 + (size_t)i2 * 32);
-            const int d = __popcll(a0 ^ b[0]) + __popcll(a1 ^ b[1]) + __popcll(a2 ^ b[2]) + __popcll(a3 ^ b[3]);
-            const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)i2;      // ascending side-2 index breaks ties, like the reference's scan
-            if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-            else second = min(second, d);
+            const int d = hamming256(a, desc_load(d2 + (size_t)i2 * 32));
+            best2_take(best, second, ((unsigned long long)d << 32) | (unsigned)i2, d);        // ascending side-2 index breaks ties, like the reference's scan
         }
-        bow_wave_best2(best, second);
-        if (lane == 0 && best != BOW_NO_KEY) {
-            const float bd1 = (float)(int)(best >> 32), bd2 = second == BOW_NO_DIST ? FLT_MAX : (float)second;
-            if (bd1 < score_threshold && bd1 < __fmul_rn(ratio, bd2)) match12[(size_t)peer * cap + i1] = (int)(best & 0xFFFFFFFFu);
-        }
+        wave_best2(best, second);
+        if (lane == 0 && best != HS_NO_KEY && bow_accept(best, second, score_threshold, ratio)) match12[(size_t)peer * cap + i1] = (int)(best & 0xFFFFFFFFu);
     }
 }
 
@@ -169,27 +137,11 @@ __global__ __launch_bounds__(1024) void k_records_rotation(const uint8_t* __rest
     if (tid < 30) hist[tid] = 0;
     if (tid == 0) total = 0;
     __syncthreads();
-    auto bin_of = [&](int i) {
-        float rot = __fsub_rn(k2[m[i]].angle, k1[i].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        const int b = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        return b == 30 ? 0 : b;
-    };
+    auto bin_of = [&](int i) { return rot_bin(k2[m[i]].angle, k1[i].angle); };
     if (check_rotation) {
         for (int i = tid; i < n; i += 1024) if (m[i] >= 0) { const int b = bin_of(i); if (b >= 0 && b < 30) atomicAdd(&hist[b], 1); }
         __syncthreads();
-        if (tid == 0) {   // ComputeThreeMaxima
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            ind[0] = i1; ind[1] = i2; ind[2] = i3;
-        }
+        if (tid == 0) three_maxima(hist, ind);
         __syncthreads();
     }
     int kept = 0;
@@ -211,11 +163,6 @@ __global__ __launch_bounds__(1024) void k_records_rotation(const uint8_t* __rest
 // order-dependent, so neither is a tree.
 #define BOWV_MAX 16384
 #define BOWV_PAD 0xFFFFFFFFFFFFFFFFull
-__device__ __forceinline__ double bowv_lane(double x, int j)
-{
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)__double_as_longlong(x), j), hi = __builtin_amdgcn_readlane((unsigned)(__double_as_longlong(x) >> 32), j);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 __global__ __launch_bounds__(1024) void k_bow_vector(const int32_t* __restrict__ word, const float* __restrict__ weight, const int32_t* __restrict__ d_n, int n_max, int N /*power of two >= n_max, >= 64*/,
                                                      int32_t* out_word, double* out_value, int32_t* out_m)
@@ -246,15 +193,7 @@ __global__ __launch_bounds__(1024) void k_bow_vector(const int32_t* __restrict__
     auto is_head = [&](int p) { return p < N && bowv_keys[p] != BOWV_PAD && (p == 0 || (bowv_keys[p] >> 32) != (bowv_keys[p - 1] >> 32)); };
     uint32_t heads = 0;
     for (int k = 0; k < PER; k++) heads += is_head(p0 + k) ? 1u : 0u;
-    uint32_t incl = heads;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-    if (lane == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const uint32_t x = s_wave[w]; if (w < (tid >> 6)) base += x; total += x; }
-    uint32_t rank = base + incl - heads;
+    uint32_t total, rank = block_scan_excl(heads, s_wave, total);
     for (int k = 0; k < PER; k++) {
         const int p = p0 + k;
         if (!is_head(p)) continue;
@@ -274,7 +213,7 @@ __global__ __launch_bounds__(1024) void k_bow_vector(const int32_t* __restrict__
         for (int b = 0; b < m; b += 64) {
             const int cnt = min(64, m - b);
             const double v = lane < cnt ? fabs(out_value[b + lane]) : 0.0;
-            for (int j = 0; j < cnt; j++) norm = __dadd_rn(norm, bowv_lane(v, j));
+            for (int j = 0; j < cnt; j++) norm = __dadd_rn(norm, lane_read(v, j));
         }
         if (tid == 0) { s_norm = norm; *out_m = m; }
     }
@@ -290,6 +229,15 @@ BowTree tree_of(const hs_vocab_dev* v)
     T.nid_level = v->levels - v->levelsup;
     return T;
 }
+}
+
+// hs_bow_transform's launcher (hs_internal.h): a vocabulary the caller staged array by array, node ids as flat indices
+void hs_launch_bow_transform(int n, const uint8_t* d_desc, const int32_t* d_cb, const int32_t* d_cc, const uint8_t* d_ndesc, const int32_t* d_word,
+                             const float* d_weight, int levels, int levelsup, int32_t* d_out_word, float* d_out_weight, int32_t* d_out_node, hipStream_t s)
+{
+    if (n <= 0) return;
+    const BowTree T{d_cb, d_cc, d_ndesc, d_word, d_weight, nullptr, nullptr, levels - levelsup};
+    hipLaunchKernelGGL(k_bow_transform_dev, dim3((n + 255) / 256), dim3(256), 0, s, T, d_desc, (const int32_t*)nullptr, n, d_out_word, d_out_weight, d_out_node);
 }
 
 // ---- host side (declared in include/hyslam_amd.h); error text goes through hs_api.hip's handle via hs_set_error (hs_internal.h)

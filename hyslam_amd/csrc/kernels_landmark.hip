@@ -18,7 +18,7 @@
 // their order, so they are added strictly left to right: every lane walks the chunk's terms in lane order (readlane) onto a running sum carried
 // from the previous chunk.  The rounding of every step is DESIGN.md D8.  It runs after the descriptor kernels on the same stream and reads their
 // best[] for the scatter.
-#include "hs_internal.h"
+#include "hs_match_device.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -30,20 +30,6 @@
 // the wave's earlier LDS accesses are done before its next ones (all lanes): compiler barrier + lgkmcnt(0)
 #define LM_WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                                 __builtin_amdgcn_s_waitcnt(0xc07f); } while (0)
-
-struct LmDesc { unsigned long long w[4]; };
-
-__device__ __forceinline__ LmDesc lm_load(const uint8_t* __restrict__ desc, long long j)
-{
-    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(desc + j * 32);
-    const ulonglong2 a = p[0], b = p[1];
-    return LmDesc{{a.x, a.y, b.x, b.y}};
-}
-
-__device__ __forceinline__ int lm_dist(const LmDesc& a, const LmDesc& b)
-{
-    return __popcll(a.w[0] ^ b.w[0]) + __popcll(a.w[1] ^ b.w[1]) + __popcll(a.w[2] ^ b.w[2]) + __popcll(a.w[3] ^ b.w[3]);
-}
 
 __device__ __forceinline__ void lm_write(int i, int n, int best, int median, int32_t* __restrict__ best_idx, int32_t* __restrict__ best_median)
 {
@@ -62,17 +48,14 @@ __global__ __launch_bounds__(256) void k_landmark_small(const int64_t* __restric
     const long long nn = e - o;
     if (nn > LM_SMALL) return;                                           // k_landmark_large's
     const int n = __builtin_amdgcn_readfirstlane(nn > 0 ? (int)nn : 0);
-    LmDesc mine{{0, 0, 0, 0}};
-    if (lane < n) mine = lm_load(desc, o + lane);
+    Desc256 mine{{0, 0, 0, 0}};
+    if (lane < n) mine = desc_load(desc + (o + lane) * 32);
     const int k = (n - 1) >> 1;                                          // (size_t)(0.5*(N-1)), N >= 1
     int best = 0, best_med = 0x7fffffff;
     for (int r = 0; r < n; r++) {
-        LmDesc row;
-        for (int w = 0; w < 4; w++) {
-            const unsigned wl = __builtin_amdgcn_readlane((unsigned)mine.w[w], r), wh = __builtin_amdgcn_readlane((unsigned)(mine.w[w] >> 32), r);
-            row.w[w] = ((unsigned long long)wh << 32) | wl;
-        }
-        const int d = lane < n ? lm_dist(row, mine) : 0x7fff;            // lanes beyond N never count
+        Desc256 row;
+        for (int w = 0; w < 4; w++) row.w[w] = lane_read(mine.w[w], r);
+        const int d = lane < n ? hamming256(row, mine) : 0x7fff;           // lanes beyond N never count
         // smallest v in [0, 256] with count(d <= v) >= k + 1
         int lo = 0, hi = 256;
 #pragma unroll
@@ -104,8 +87,8 @@ __global__ __launch_bounds__(64 * LM_LARGE_WAVES) void k_landmark_large(const in
             reinterpret_cast<int4*>(h)[lane] = make_int4(0, 0, 0, 0);
             if (lane == 0) h[256] = 0;
             LM_WAVE_LDS_SYNC();
-            const LmDesc row = lm_load(desc, o + r);
-            for (int j = lane; j < n; j += 64) atomicAdd(&h[lm_dist(row, lm_load(desc, o + j))], 1);
+            const Desc256 row = desc_load(desc + (o + r) * 32);
+            for (int j = lane; j < n; j += 64) atomicAdd(&h[hamming256(row, desc_load(desc + (o + j) * 32))], 1);
             LM_WAVE_LDS_SYNC();
             // lane l owns bins 4l .. 4l+3; the first lane whose inclusive prefix exceeds k holds the median (bin 256 if none does)
             const int4 b = reinterpret_cast<const int4*>(h)[lane];
@@ -170,8 +153,6 @@ __device__ __forceinline__ float lm_feature_size(const hs_lm_obs& ob)
     return __double2float_rn(lm_norm3(__fsub_rn(xr, xl), __fsub_rn(yr, yl), __fsub_rn(z, z)));
 }
 
-__device__ __forceinline__ float lm_lane(float x, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); }
-
 struct LmEntryArgs {
     hs_lm_entry_params prm;
     int L;
@@ -212,9 +193,9 @@ __global__ __launch_bounds__(256) void k_landmark_entries(LmEntryArgs a)
             sz = lm_feature_size(ob);
         }
         for (int j = 0; j < cnt; j++) {                                 // observation order; never a tree
-            nx = __fadd_rn(lm_lane(tx, j), nx); ny = __fadd_rn(lm_lane(ty, j), ny); nz = __fadd_rn(lm_lane(tz, j), nz);
-            mean = __fadd_rn(mean, lm_lane(dist, j));
-            const float sj = lm_lane(sz, j);
+            nx = __fadd_rn(lane_read(tx, j), nx); ny = __fadd_rn(lane_read(ty, j), ny); nz = __fadd_rn(lane_read(tz, j), nz);
+            mean = __fadd_rn(mean, lane_read(dist, j));
+            const float sj = lane_read(sz, j);
             if (sj > 0.0f) { size = __fadd_rn(size, sj); npos++; }      // (:298-301)
         }
     }

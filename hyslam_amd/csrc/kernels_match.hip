@@ -16,17 +16,8 @@
 //   dist<<32 | cellx<<22 | celly<<16 | keypoint index;
 // the second-best distance is order independent (second smallest of the multiset).
 // cv::Mat products in the reference are OpenCV gemm calls (float data, double accumulation, one rounding): restated in fp64.
-#include "hs_internal.h"
-#include <cfloat>
+#include "hs_match_device.h"
 #include <cstddef>
-
-#define GRID_COLS 64   // FRAME_GRID_COLS, src/core/Frame.h
-#define GRID_ROWS 48
-
-// (int) of an integral float (a floor / ceil / round result) as the reference's x86-64 build converts it (cvttss2si): NaN or a value outside the
-// int range gives INT_MIN.  C++ leaves that conversion undefined; a plain cast here is v_cvt_i32_f32, which clamps to INT_MAX and maps NaN to 0, so
-// a huge or infinite search radius would scan the whole grid where the reference finds nothing.
-__device__ __forceinline__ int cvt_i32(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u; }
 
 struct HsFrameDev {            // hs_frame_view with device pointers
     float Rcw[9], tcw[3], Ow[3];
@@ -67,15 +58,7 @@ __global__ __launch_bounds__(1024) void k_frame_grid_lists(int n, const int8_t* 
     uint32_t loc[PER], sum = 0;
 #pragma unroll
     for (int k = 0; k < PER; k++) { const int c = tid * PER + k; loc[k] = c < NC ? cnt[c] : 0; sum += loc[k]; }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += v; }
-    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const uint32_t x = s_wave[w]; if (w < (tid >> 6)) base += x; total += x; }
-    uint32_t run = base + incl - sum;
+    uint32_t total, run = block_scan_excl(sum, s_wave, total);
 #pragma unroll
     for (int k = 0; k < PER; k++) { const int c = tid * PER + k; if (c < NC) { cell_start[c] = (int32_t)run; cnt[c] = run; run += loc[k]; } }
     if (tid == 0) cell_start[NC] = (int32_t)total;
@@ -122,26 +105,16 @@ __device__ __forceinline__ bool cam_project(const HsFrameDev& F, const float* Pc
     return PcZ > 0.0f && u >= F.min_x && u <= F.max_x && v >= F.min_y && v <= F.max_y;
 }
 
-__device__ __forceinline__ int hamming256(const unsigned long long* a, const unsigned long long* b)
+// landMarkSizePixels of a landmark in frame F (projects with F's OWN pose — also in the Sim3 variants, KeyFrame.cc:258-279)
+__device__ __forceinline__ float landmark_size_px(const HsFrameDev& F, const hs_landmark& lm)
 {
-    return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
+    if (lm.assoc_kp >= 0) return F.kps[lm.assoc_kp].size;
+    const float half = __fdiv_rn(lm.size, 2.0f);
+    float ul, vl, url, u2, v2, ur2;
+    project(F, __fsub_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], ul, vl, url);
+    project(F, __fadd_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], u2, v2, ur2);
+    return __fsub_rn(u2, ul);
 }
-
-// wave-wide merge of (best key, second-best distance)
-__device__ __forceinline__ void wave_best2(unsigned long long& best, int& second)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        unsigned long long ob = __shfl_xor(best, s, 64);
-        int os = __shfl_xor(second, s, 64);
-        int db = (int)(best >> 32), dob = (int)(ob >> 32);
-        int worse = max(db, dob);          // distance of whichever best loses (0x7FFFFFFF when a side is empty)
-        best = min(best, ob);
-        second = min(min(second, os), worse);
-    }
-}
-#define NO_KEY 0x7FFFFFFFFFFFFFFFull
-#define NO_DIST 0x7FFFFFFF
 
 struct HsProjDev : hs_proj_params { float cos_view_angle; };   // cosf(max_view_angle), evaluated on the host like the reference does
 
@@ -195,29 +168,13 @@ __global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const h
         if (!(dot > (double)pp.cos_view_angle)) ok = false;
     }
     if (ok) {
-        // landMarkSizePixels
-        float sizePx;
-        if (lm.assoc_kp >= 0) sizePx = F.kps[lm.assoc_kp].size;
-        else {
-            const float half = __fdiv_rn(lm.size, 2.0f);
-            float ul, vl, url, u2, v2, ur2;
-            project(F, __fsub_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], ul, vl, url);
-            project(F, __fadd_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], u2, v2, ur2);
-            sizePx = __fsub_rn(u2, ul);
-        }
+        const float sizePx = landmark_size_px(F, lm);
         const float r = __fdiv_rn(__fmul_rn(pp.th, sizePx), F.size_ref);
-        // GetFeaturesInAreaNEW cell range (with its early returns)
-        const float invW = (float)GRID_COLS / (F.max_x - F.min_x), invH = (float)GRID_ROWS / (F.max_y - F.min_y);
-        const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW))));
-        const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW))));
-        const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH))));
-        const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH))));
-        const bool any = !(minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0);
+        const GridRange g = grid_range(F.min_x, F.max_x, F.min_y, F.max_y, u, v, r);          // GetFeaturesInAreaNEW
         const float smin = __fmul_rn(pp.frac_smaller, sizePx), smax = __fmul_rn(pp.frac_larger, sizePx);
         const bool stereo = pp.use_stereo && F.sensor != 0;
-        const unsigned long long* dl = reinterpret_cast<const unsigned long long*>(lm.desc);
-        const unsigned long long l0 = dl[0], l1 = dl[1], l2 = dl[2], l3 = dl[3];
-        unsigned long long best = NO_KEY; int second = NO_DIST;
+        const Desc256 dl = desc_load(lm.desc);
+        unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
         // candidates: the keypoints of the grid cells [minCX,maxCX] x [minCY,maxCY] (GetFeaturesInAreaNEW); a row of cells is one
         // contiguous span of the cell lists.  Without lists (cell_start == nullptr) every keypoint is tested against the cell range.
         auto consider = [&](int i, int cx, int cy) {
@@ -236,32 +193,28 @@ __global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const h
                 const float stereo_factor = urv > 0.f ? 1.30f : 1.00f;
                 if (!(__fdiv_rn(err, sigma) < __fmul_rn(stereo_factor, pp.reproj_threshold))) return;
             }
-            const unsigned long long* dk = reinterpret_cast<const unsigned long long*>(F.desc + (size_t)i * 32);
-            const int d = __popcll(l0 ^ dk[0]) + __popcll(l1 ^ dk[1]) + __popcll(l2 ^ dk[2]) + __popcll(l3 ^ dk[3]);
-            const unsigned long long key = ((unsigned long long)d << 32) | ((unsigned long long)cx << 22) | ((unsigned long long)cy << 16) | (unsigned)i;
-            if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-            else second = min(second, d);
+            const int d = hamming256(dl, desc_load(F.desc + (size_t)i * 32));
+            best2_take(best, second, ((unsigned long long)d << 32) | ((unsigned long long)cx << 22) | ((unsigned long long)cy << 16) | (unsigned)i, d);
         };
-        if (any && F.cell_start) {
-            for (int cy = minCY; cy <= maxCY; cy++) {
-                const int a = hs_cload<int32_t>(F.cell_start + cy * GRID_COLS + minCX), b = hs_cload<int32_t>(F.cell_start + cy * GRID_COLS + maxCX + 1);
+        if (!g.empty && F.cell_start) {
+            for (int cy = g.minCY; cy <= g.maxCY; cy++) {
+                const int a = hs_cload<int32_t>(F.cell_start + cy * GRID_COLS + g.minCX), b = hs_cload<int32_t>(F.cell_start + cy * GRID_COLS + g.maxCX + 1);
                 for (int t = a + lane; t < b; t += 64) {
                     const int i = F.cell_items[t];
                     consider(i, F.cell[2 * i], cy);
                 }
             }
-        } else if (any) {
+        } else if (!g.empty) {
             for (int i = lane; i < F.n; i += 64) {
                 const int cx = F.cell[2 * i], cy = F.cell[2 * i + 1];
-                if (cx < minCX || cx > maxCX || cy < minCY || cy > maxCY) continue;           // also drops cx == -1
+                if (cx < g.minCX || cx > g.maxCX || cy < g.minCY || cy > g.maxCY) continue;   // also drops cx == -1
                 consider(i, cx, cy);
             }
         }
         wave_best2(best, second);
-        if (best != NO_KEY) {                                                                   // BestScoreCriterion accept rule
+        if (best != HS_NO_KEY) {                                                                   // BestScoreCriterion accept rule
             const float bestDist = (float)(int)(best >> 32);
-            const float bestDist2 = second == NO_DIST ? FLT_MAX : (float)second;
-            if (bestDist <= pp.score_threshold && !(bestDist > __fmul_rn(pp.second_best_ratio, bestDist2))) {
+            if (bestDist <= pp.score_threshold && !(bestDist > __fmul_rn(pp.second_best_ratio, second_as_float(second)))) {
                 out_idx = (int)(best & 0xFFFF); out_dist = bestDist;
             }
         }
@@ -290,12 +243,7 @@ __global__ __launch_bounds__(1024) void k_rotation_filter(int n, int32_t* __rest
         for (int i = tid; i < n; i += 1024) if (match[i] >= 0) atomicMax(&winner[match[i]], i);
     }
     __syncthreads();
-    auto bin_of = [&](int i) {
-        float rot = __fsub_rn(angle_prev[i], kps_curr[match[i]].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        int b = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        return b == 30 ? 0 : b;
-    };
+    auto bin_of = [&](int i) { return rot_bin(angle_prev[i], kps_curr[match[i]].angle); };
     for (int i = tid; i < n; i += 1024) {
         if (match[i] < 0) continue;
         if (dedupe && winner[match[i]] != i) continue;
@@ -303,18 +251,7 @@ __global__ __launch_bounds__(1024) void k_rotation_filter(int n, int32_t* __rest
         if (b >= 0 && b < 30) atomicAdd(&hist[b], 1);
     }
     __syncthreads();
-    if (tid == 0) {   // ComputeThreeMaxima
-        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-            else if (s > max3) { max3 = s; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-        ind[0] = i1; ind[1] = i2; ind[2] = i3;
-    }
+    if (tid == 0) three_maxima(hist, ind);
     __syncthreads();
     int kept = 0;
     for (int i = tid; i < n; i += 1024) {
@@ -364,8 +301,8 @@ __global__ __launch_bounds__(256) void k_bow_match(const int32_t* __restrict__ p
     for (int p = p0 + wv; p < p1; p += 4) {
         const int i1 = idx1[p];
         if (keep1 && !keep1[i1]) continue;                                   // PreviouslyMatchedIndexCriterion
-        const unsigned long long* d1 = reinterpret_cast<const unsigned long long*>(desc1 + (size_t)i1 * 32);
-        unsigned long long best = NO_KEY; int second = NO_DIST;
+        const Desc256 d1 = desc_load(desc1 + (size_t)i1 * 32);
+        unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
         float ea = 0.f, eb = 0.f, ec = 0.f;
         if (epi.on) {   // epipolar line of kp1 in image 2: l = x1' F12 (MatchCriteria.cpp:661-663)
             const float x1 = kps1[i1].x, y1 = kps1[i1].y;
@@ -386,16 +323,11 @@ __global__ __launch_bounds__(256) void k_bow_match(const int32_t* __restrict__ p
                 const float sigma2 = __fmul_rn(epi.sigma_ref, __fmul_rn(sf, sf));
                 if (!((double)dsqr < __dmul_rn(3.84, (double)sigma2))) continue;
             }
-            const int d = hamming256(d1, reinterpret_cast<const unsigned long long*>(desc2 + (size_t)i2 * 32));
-            const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)(q - q0);     // list order breaks ties
-            if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-            else second = min(second, d);
+            const int d = hamming256(d1, desc_load(desc2 + (size_t)i2 * 32));
+            best2_take(best, second, ((unsigned long long)d << 32) | (unsigned)(q - q0), d);           // list order breaks ties
         }
         wave_best2(best, second);
-        if (lane == 0 && best != NO_KEY) {
-            const float bd1 = (float)(int)(best >> 32), bd2 = second == NO_DIST ? FLT_MAX : (float)second;
-            if (bd1 < score_threshold && bd1 < __fmul_rn(ratio, bd2)) match12[i1] = idx2[q0 + (int)(best & 0xFFFFFFFFu)];
-        }
+        if (lane == 0 && best != HS_NO_KEY && bow_accept(best, second, score_threshold, ratio)) match12[i1] = idx2[q0 + (int)(best & 0xFFFFFFFFu)];
     }
 }
 
@@ -417,25 +349,20 @@ __global__ __launch_bounds__(64) void k_bow_match_exclusive(const int32_t* __res
     for (int p = p0; p < p1; p++) {
         const int i1 = idx1[p];
         if (keep1 && !keep1[i1]) continue;                                   // !pMP1 || pMP1->isBad() (:985-990)
-        const unsigned long long* d1 = reinterpret_cast<const unsigned long long*>(desc1 + (size_t)i1 * 32);
-        unsigned long long best = NO_KEY; int second = NO_DIST;
+        const Desc256 d1 = desc_load(desc1 + (size_t)i1 * 32);
+        unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
         for (int q = q0 + lane; q < q1; q += 64) {
             const int i2 = idx2[q];
             if (keep2 && !keep2[i2]) continue;
             if (__hip_atomic_load(&taken2[i2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;      // vbMatched2[idx2] (:999)
-            const int d = hamming256(d1, reinterpret_cast<const unsigned long long*>(desc2 + (size_t)i2 * 32));
-            const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)(q - q0);     // list order breaks ties
-            if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-            else second = min(second, d);
+            const int d = hamming256(d1, desc_load(desc2 + (size_t)i2 * 32));
+            best2_take(best, second, ((unsigned long long)d << 32) | (unsigned)(q - q0), d);           // list order breaks ties
         }
         wave_best2(best, second);                                            // every lane holds the result
-        if (best != NO_KEY) {
-            const float bd1 = (float)(int)(best >> 32), bd2 = second == NO_DIST ? FLT_MAX : (float)second;
-            if (bd1 < score_threshold && bd1 < __fmul_rn(ratio, bd2)) {
-                const int i2 = idx2[q0 + (int)(best & 0xFFFFFFFFu)];
-                if (lane == 0) { match12[i1] = i2; __hip_atomic_store(&taken2[i2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-                __builtin_amdgcn_s_waitcnt(0x0f70);                          // vmcnt(0): the flag is in L2 before the next feature's loads
-            }
+        if (best != HS_NO_KEY && bow_accept(best, second, score_threshold, ratio)) {
+            const int i2 = idx2[q0 + (int)(best & 0xFFFFFFFFu)];
+            if (lane == 0) { match12[i1] = i2; __hip_atomic_store(&taken2[i2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            __builtin_amdgcn_s_waitcnt(0x0f70);                              // vmcnt(0): the flag is in L2 before the next feature's loads
         }
     }
 }
@@ -445,21 +372,17 @@ __device__ __forceinline__ void knn2_wave(const uint8_t* __restrict__ q, int i, 
                                           int32_t* __restrict__ best_idx, int32_t* __restrict__ best_dist, int32_t* __restrict__ second_dist)
 {
     const int lane = threadIdx.x & 63;
-    const unsigned long long* dq = reinterpret_cast<const unsigned long long*>(q + (size_t)i * 32);
-    const unsigned long long a0 = dq[0], a1 = dq[1], a2 = dq[2], a3 = dq[3];
-    unsigned long long best = NO_KEY; int second = NO_DIST;
+    const Desc256 dq = desc_load(q + (size_t)i * 32);
+    unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
     for (int j = lane; j < nt; j += 64) {
-        const unsigned long long* dt = reinterpret_cast<const unsigned long long*>(t + (size_t)j * 32);
-        const int d = __popcll(a0 ^ dt[0]) + __popcll(a1 ^ dt[1]) + __popcll(a2 ^ dt[2]) + __popcll(a3 ^ dt[3]);
-        const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)j;
-        if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-        else second = min(second, d);
+        const int d = hamming256(dq, desc_load(t + (size_t)j * 32));
+        best2_take(best, second, ((unsigned long long)d << 32) | (unsigned)j, d);
     }
     wave_best2(best, second);
     if (lane == 0) {
-        best_idx[i] = best == NO_KEY ? -1 : (int)(best & 0xFFFFFFFFu);
-        best_dist[i] = best == NO_KEY ? -1 : (int)(best >> 32);
-        second_dist[i] = second == NO_DIST ? -1 : second;
+        best_idx[i] = best == HS_NO_KEY ? -1 : (int)(best & 0xFFFFFFFFu);
+        best_dist[i] = best == HS_NO_KEY ? -1 : (int)(best >> 32);
+        second_dist[i] = second == HS_NO_DIST ? -1 : second;
     }
 }
 
@@ -487,39 +410,23 @@ __global__ __launch_bounds__(256) void k_knn2_records(const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------- legacy loop-closing matchers (FeatureMatcher.cc:628-934)
-// landMarkSizePixels of a landmark in frame F (projects with F's OWN pose — also in the Sim3 variants, KeyFrame.cc:258-279)
-__device__ __forceinline__ float landmark_size_px(const HsFrameDev& F, const hs_landmark& lm)
-{
-    if (lm.assoc_kp >= 0) return F.kps[lm.assoc_kp].size;
-    const float half = __fdiv_rn(lm.size, 2.0f);
-    float ul, vl, url, u2, v2, ur2;
-    project(F, __fsub_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], ul, vl, url);
-    project(F, __fadd_rn(lm.pos[0], half), lm.pos[1], lm.pos[2], u2, v2, ur2);
-    return __fsub_rn(u2, ul);
-}
 // best Hamming over GetFeaturesInArea(u, v, r) in the reference's candidate order (first minimum wins), skipping keypoints whose bit is set in
-// `taken` (LDS bitmask, may be null).  Wave-wide; returns the key dist<<32 | cellx<<22 | celly<<16 | idx or NO_KEY.
+// `taken` (LDS bitmask, may be null).  Wave-wide; returns the key dist<<32 | cellx<<22 | celly<<16 | idx or HS_NO_KEY.
 __device__ __forceinline__ unsigned long long best_in_area(const HsFrameDev& F, float u, float v, float r, const uint8_t* desc32, const uint32_t* taken)
 {
     const int lane = threadIdx.x & 63;
-    const float invW = (float)GRID_COLS / (F.max_x - F.min_x), invH = (float)GRID_ROWS / (F.max_y - F.min_y);
-    const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, F.min_x), r), invW))));
-    const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, F.min_x), r), invW))));
-    const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, F.min_y), r), invH))));
-    const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, F.min_y), r), invH))));
-    unsigned long long best = NO_KEY;
-    if (minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0) return best;
-    const unsigned long long* dl = reinterpret_cast<const unsigned long long*>(desc32);
-    const unsigned long long l0 = dl[0], l1 = dl[1], l2 = dl[2], l3 = dl[3];
-    for (int cy = minCY; cy <= maxCY; cy++) {
-        const int a = F.cell_start[cy * GRID_COLS + minCX], b = F.cell_start[cy * GRID_COLS + maxCX + 1];
+    const GridRange g = grid_range(F.min_x, F.max_x, F.min_y, F.max_y, u, v, r);
+    unsigned long long best = HS_NO_KEY;
+    if (g.empty) return best;
+    const Desc256 dl = desc_load(desc32);
+    for (int cy = g.minCY; cy <= g.maxCY; cy++) {
+        const int a = F.cell_start[cy * GRID_COLS + g.minCX], b = F.cell_start[cy * GRID_COLS + g.maxCX + 1];
         for (int t = a + lane; t < b; t += 64) {
             const int i = F.cell_items[t];
             const hs_keypoint kp = F.kps[i];
             if (!(fabsf(__fsub_rn(kp.x, u)) < r && fabsf(__fsub_rn(kp.y, v)) < r)) continue;
             if (taken && ((taken[i >> 5] >> (i & 31)) & 1u)) continue;
-            const unsigned long long* dk = reinterpret_cast<const unsigned long long*>(F.desc + (size_t)i * 32);
-            const int d = __popcll(l0 ^ dk[0]) + __popcll(l1 ^ dk[1]) + __popcll(l2 ^ dk[2]) + __popcll(l3 ^ dk[3]);
+            const int d = hamming256(dl, desc_load(F.desc + (size_t)i * 32));
             const unsigned long long key = ((unsigned long long)d << 32) | ((unsigned long long)F.cell[2 * i] << 22) | ((unsigned long long)cy << 16) | (unsigned)i;
             best = min(best, key);
         }
@@ -575,7 +482,7 @@ __global__ __launch_bounds__(64) void k_sim3_assign(HsFrameDev F, const hs_landm
         int out = -1;
         if (r >= 0.f) {                                                      // a negative or NaN radius finds no candidate in the reference either
             const unsigned long long best = best_in_area(F, geo[3 * li], geo[3 * li + 1], r, lms[li].desc, taken);
-            if (best != NO_KEY && (float)(int)(best >> 32) <= th_low) {
+            if (best != HS_NO_KEY && (float)(int)(best >> 32) <= th_low) {
                 out = (int)(best & 0xFFFF);
                 if (lane == 0) { taken[out >> 5] |= 1u << (out & 31); kp_matched[out] = 1; }
                 n++;
@@ -608,7 +515,7 @@ __global__ __launch_bounds__(256) void k_sim3_direction(HsFrameDev Fsrc, HsFrame
             if (!(d3 < lm.min_dist || d3 > lm.max_dist)) {
                 const float radius = __fdiv_rn(__fmul_rn(th, landmark_size_px(Fdst, lm)), Fdst.size_ref);
                 const unsigned long long best = best_in_area(Fdst, u, v, radius, lm.desc, nullptr);
-                if (best != NO_KEY && (float)(int)(best >> 32) <= th_high) res = (int)(best & 0xFFFF);
+                if (best != HS_NO_KEY && (float)(int)(best >> 32) <= th_high) res = (int)(best & 0xFFFF);
             }
         }
     }
@@ -639,10 +546,7 @@ void hs_launch_frame_grid(const hs_frame_view& F, const hs_keypoint* d_kps, int8
     }
 }
 
-void hs_launch_search_projection(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR,
-                                 const int32_t* d_obs, const int8_t* d_cell, const hs_landmark* d_lms, int L, const hs_proj_params& pp,
-                                 int32_t* d_match_idx, float* d_match_dist, int32_t* d_winner, float* d_prev_angle_scratch,
-                                 int32_t* d_n_matches, hipStream_t s)
+static HsFrameDev frame_dev(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR, const int32_t* d_obs, const int8_t* d_cell)
 {
     HsFrameDev D{};
     for (int i = 0; i < 9; i++) D.Rcw[i] = F.Rcw[i];
@@ -654,6 +558,15 @@ void hs_launch_search_projection(const hs_frame_view& F, const hs_keypoint* d_kp
         const int32_t* start = grid_lists_start(const_cast<int8_t*>(d_cell), F.n);
         D.cell_start = start; D.cell_items = reinterpret_cast<const uint16_t*>(start + GRID_ROWS * GRID_COLS + 1);
     }
+    return D;
+}
+
+void hs_launch_search_projection(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR,
+                                 const int32_t* d_obs, const int8_t* d_cell, const hs_landmark* d_lms, int L, const hs_proj_params& pp,
+                                 int32_t* d_match_idx, float* d_match_dist, int32_t* d_winner, float* d_prev_angle_scratch,
+                                 int32_t* d_n_matches, hipStream_t s)
+{
+    const HsFrameDev D = frame_dev(F, d_kps, d_desc, d_uR, d_obs, d_cell);
     HsProjDev P; static_cast<hs_proj_params&>(P) = pp; P.cos_view_angle = cosf(pp.max_view_angle);
     hipLaunchKernelGGL(k_search_projection, dim3((L + 3) / 4), dim3(256), 0, s, D, d_lms, L, P, d_match_idx, d_match_dist);
     if (pp.first_wins) {
@@ -739,21 +652,6 @@ void hs_launch_knn2(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int3
     hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, s, d_q, nq, d_t, nt, d_bi, d_bd, d_sd);
 }
 
-static HsFrameDev frame_dev(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR, const int32_t* d_obs, const int8_t* d_cell)
-{
-    HsFrameDev D{};
-    for (int i = 0; i < 9; i++) D.Rcw[i] = F.Rcw[i];
-    for (int i = 0; i < 3; i++) { D.tcw[i] = F.tcw[i]; D.Ow[i] = F.Ow[i]; }
-    D.fx = F.fx; D.fy = F.fy; D.cx = F.cx; D.cy = F.cy; D.mbf = F.mbf; D.sensor = F.sensor;
-    D.min_x = F.min_x; D.max_x = F.max_x; D.min_y = F.min_y; D.max_y = F.max_y; D.size_ref = F.size_ref; D.n = F.n;
-    D.kps = d_kps; D.desc = d_desc; D.uR = d_uR; D.kp_lm_obs = d_obs; D.cell = d_cell;
-    if (F.n > 0) {
-        const int32_t* start = grid_lists_start(const_cast<int8_t*>(d_cell), F.n);
-        D.cell_start = start; D.cell_items = reinterpret_cast<const uint16_t*>(start + GRID_ROWS * GRID_COLS + 1);
-    }
-    return D;
-}
-
 void hs_launch_sim3_projection(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const int8_t* d_cell,
                                const float* R9, const float* t3, const float* Ow3, const hs_landmark* d_lms, int L, float th, float th_low,
                                float* d_geo, uint8_t* d_kp_matched, int32_t* d_match_idx, int32_t* d_n_matches, hipStream_t s)
@@ -786,40 +684,6 @@ void hs_launch_knn2_records(const uint8_t* d_recs, size_t stride, int world, int
     hipLaunchKernelGGL(k_knn2_records, dim3((cap + 3) / 4, world), dim3(256), 0, s, d_recs, stride, rank, cap, off_desc, d_bi, d_bd, d_sd);
 }
 
-// DBoW2 transform: one lane per descriptor walks the tree (k children x L levels Hamming distances; the tree is L2-resident)
-__global__ __launch_bounds__(256) void k_bow_transform(int n, const uint8_t* __restrict__ desc, const int32_t* __restrict__ child_begin,
-                                                       const int32_t* __restrict__ child_count, const uint8_t* __restrict__ ndesc,
-                                                       const int32_t* __restrict__ nword, const float* __restrict__ nweight, int levels, int levelsup,
-                                                       int32_t* __restrict__ word_id, float* __restrict__ weight, int32_t* __restrict__ node_id)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long* f = reinterpret_cast<const unsigned long long*>(desc + (size_t)i * 32);
-    const unsigned long long f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
-    const int nid_level = levels - levelsup;
-    int final_id = 0, level = 0, nid = 0;
-    do {
-        ++level;
-        const int cb = child_begin[final_id], cc = child_count[final_id];
-        int best = 0x7FFFFFFF;
-        for (int c = cb; c < cb + cc; c++) {
-            const unsigned long long* d = reinterpret_cast<const unsigned long long*>(ndesc + (size_t)c * 32);
-            const int dist = __popcll(f0 ^ d[0]) + __popcll(f1 ^ d[1]) + __popcll(f2 ^ d[2]) + __popcll(f3 ^ d[3]);
-            if (dist < best) { best = dist; final_id = c; }      // strict: the first minimum wins
-        }
-        if (level == nid_level) nid = final_id;
-    } while (child_count[final_id] != 0 && level < 64);
-    word_id[i] = nword[final_id]; weight[i] = nweight[final_id]; node_id[i] = nid;
-}
-
-void hs_launch_bow_transform(int n, const uint8_t* d_desc, const int32_t* d_cb, const int32_t* d_cc, const uint8_t* d_ndesc, const int32_t* d_word,
-                             const float* d_weight, int levels, int levelsup, int32_t* d_out_word, float* d_out_weight, int32_t* d_out_node, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, s, n, d_desc, d_cb, d_cc, d_ndesc, d_word, d_weight, levels, levelsup,
-                       d_out_word, d_out_weight, d_out_node);
-}
-
 // SearchForInitialization: ONE workgroup, sequential over frame-1 keypoints, parallel inside each step.
 // owner[i2] = frame-1 index currently matched to frame-2 keypoint i2 (-1 none), odist[i2] = its distance (global scratch, L2-resident).
 __global__ __launch_bounds__(1024) void k_search_init(HsFrameDev F2, const uint8_t* __restrict__ desc1, int n1, const float* __restrict__ prev_xy,
@@ -830,44 +694,32 @@ __global__ __launch_bounds__(1024) void k_search_init(HsFrameDev F2, const uint8
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int i = tid; i < F2.n; i += 1024) { owner[i] = -1; odist[i] = -1; }
     __syncthreads();
-    const float invW = (float)GRID_COLS / (F2.max_x - F2.min_x), invH = (float)GRID_ROWS / (F2.max_y - F2.min_y);
     const float r = window;
     for (int i1 = 0; i1 < n1; i1++) {
         const float x = prev_xy[2 * i1], y = prev_xy[2 * i1 + 1];
-        const int minCX = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F2.min_x), r), invW))));
-        const int maxCX = min(GRID_COLS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F2.min_x), r), invW))));
-        const int minCY = max(0, cvt_i32(floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F2.min_y), r), invH))));
-        const int maxCY = min(GRID_ROWS - 1, cvt_i32(ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F2.min_y), r), invH))));
-        unsigned long long best = NO_KEY; int second = NO_DIST;
-        if (!(minCX >= GRID_COLS || maxCX < 0 || minCY >= GRID_ROWS || maxCY < 0)) {
-            const unsigned long long* d1 = reinterpret_cast<const unsigned long long*>(desc1 + (size_t)i1 * 32);
-            const unsigned long long a0 = d1[0], a1 = d1[1], a2 = d1[2], a3 = d1[3];
+        const GridRange g = grid_range(F2.min_x, F2.max_x, F2.min_y, F2.max_y, x, y, r);
+        unsigned long long best = HS_NO_KEY; int second = HS_NO_DIST;
+        if (!g.empty) {
+            const Desc256 d1 = desc_load(desc1 + (size_t)i1 * 32);
             for (int i2 = tid; i2 < F2.n; i2 += 1024) {
                 const int cx = F2.cell[2 * i2], cy = F2.cell[2 * i2 + 1];
-                if (cx < minCX || cx > maxCX || cy < minCY || cy > maxCY) continue;
+                if (cx < g.minCX || cx > g.maxCX || cy < g.minCY || cy > g.maxCY) continue;
                 const hs_keypoint kp = F2.kps[i2];
                 if (!(fabsf(__fsub_rn(kp.x, x)) < r && fabsf(__fsub_rn(kp.y, y)) < r)) continue;
-                const unsigned long long* dk = reinterpret_cast<const unsigned long long*>(F2.desc + (size_t)i2 * 32);
-                const int d = __popcll(a0 ^ dk[0]) + __popcll(a1 ^ dk[1]) + __popcll(a2 ^ dk[2]) + __popcll(a3 ^ dk[3]);
+                const int d = hamming256(d1, desc_load(F2.desc + (size_t)i2 * 32));
                 const int dp = odist[i2];
                 if (dp >= 0 && !(d < dp)) continue;                         // MonoInitScoreExceedsPrevious
-                const unsigned long long key = ((unsigned long long)d << 32) | ((unsigned long long)cx << 22) | ((unsigned long long)cy << 16) | (unsigned)i2;
-                if (key < best) { second = min(second, (int)(best >> 32)); best = key; }
-                else second = min(second, d);
+                best2_take(best, second, ((unsigned long long)d << 32) | ((unsigned long long)cx << 22) | ((unsigned long long)cy << 16) | (unsigned)i2, d);
             }
         }
         wave_best2(best, second);
         if (lane == 0) { s_best[wv] = best; s_second[wv] = second; }
         __syncthreads();
         if (tid == 0) {
-            unsigned long long b = NO_KEY; int s2 = NO_DIST;
-            for (int w = 0; w < 16; w++) {
-                const unsigned long long ob = s_best[w]; const int os = s_second[w];
-                const int worse = max((int)(b >> 32), (int)(ob >> 32));
-                b = min(b, ob); s2 = min(min(s2, os), worse);
-            }
-            if (b != NO_KEY) {                                               // MonoInitBestScore accept rule
-                const float bd = (float)(int)(b >> 32), bd2 = s2 == NO_DIST ? FLT_MAX : (float)s2;
+            unsigned long long b = HS_NO_KEY; int s2 = HS_NO_DIST;
+            for (int w = 0; w < 16; w++) best2_merge(b, s2, s_best[w], s_second[w]);
+            if (b != HS_NO_KEY) {                                               // MonoInitBestScore accept rule
+                const float bd = (float)(int)(b >> 32), bd2 = second_as_float(s2);
                 if (bd <= th_low && bd < __fmul_rn(bd2, nnratio)) { const int i2 = (int)(b & 0xFFFF); owner[i2] = i1; odist[i2] = (int)(b >> 32); }
             }
         }

@@ -17,7 +17,7 @@
 // Arithmetic: L1Scoring::score adds `fabs(vi - wi) - fabs(vi) - fabs(wi)` per shared word in ascending word order in double, from 0.0, and returns
 // -s / 2.0; compiled with -ffp-contract=off and written with __dsub_rn / __dadd_rn so that nothing fuses.  The sum is ordered: the hits of a 64-entry
 // chunk are COMPACTED (a ballot, then one readlane per hit in lane order = word order), so lanes without a hit add nothing at all.
-#include "hs_internal.h"
+#include "hs_match_device.h"
 #include <algorithm>
 #include <cmath>
 #include <climits>
@@ -37,12 +37,6 @@ __global__ __launch_bounds__(256) void k_place_scatter(const int32_t* __restrict
     if (i >= qm) return;
     const int w = qw[i];
     if ((unsigned)w < (unsigned)n_words) dense[w] = set ? qv[i] : 0.0;
-}
-
-__device__ __forceinline__ double pl_lane(double x, int j)
-{
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)__double_as_longlong(x), j), hi = __builtin_amdgcn_readlane((unsigned)(__double_as_longlong(x) >> 32), j);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 // one wavefront per slot
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(256) void k_place_score(const int32_t* __restrict__
         while (m) {                                                             // the chunk's hits, in lane order = ascending word order
             const int j = __builtin_ctzll(m);
             m &= m - 1;
-            s = __dadd_rn(s, pl_lane(term, j));
+            s = __dadd_rn(s, lane_read(term, j));
         }
     }
     if (lane != 0) return;

@@ -224,6 +224,31 @@ def test_transform_on_edge_trees(matcher, edge_trees):
                 assert (dw[seen:] == PATTERN).all() and (dwt[seen:] == PATTERN).all() and (dnd[seen:] == PATTERN).all(), tag + (count, "beyond the count")
 
 
+def test_host_and_device_transform_agree_across_the_block_boundary(matcher, edge_trees):
+    """hs_bow_transform runs the device-vocabulary kernel (k_bow_transform_dev, 256 descriptors per block) with a tree that has neither groups nor
+    reported ids: on every edge tree without orig_id, n = 1, 255, 256, 257 descriptors give the same word, weight and node arrays through
+    hs_bow_transform and hs_bow_transform_device, and both equal the numpy reference's"""
+    stream = hipmem.Stream()
+    sizes = (1, 255, 256, 257)
+    seen_trees = 0
+    for e, vocs in edge_trees:
+        t = e["tree"]
+        if t["orig_id"] is not None:
+            continue
+        seen_trees += 1
+        desc = np.ascontiguousarray(np.resize(e["desc"], (max(sizes), 32)))     # the tree's own descriptors, repeated
+        for levelsup, voc in vocs.items():
+            pw, pwt, pnd = ref_bow.bow_transform(t, desc, levelsup)               # per descriptor: a prefix is the shorter call's reference
+            for n in sizes:
+                d_desc = hipmem.DevBuf.from_numpy(desc[:n])
+                gw, gwt, gnd = host_transform(matcher, t, desc[:n], levelsup)
+                dw, dwt, dnd = device_transform(matcher, voc, d_desc, n, None, stream)
+                tag = (e["name"], levelsup, n)
+                assert np.array_equal(gw, dw) and np.array_equal(gwt.view(np.uint32), dwt) and np.array_equal(gnd, dnd), tag
+                assert np.array_equal(gw, pw[:n]) and np.array_equal(gwt.view(np.uint32), pwt.view(np.uint32)[:n]) and np.array_equal(gnd, pnd[:n]), tag + ("numpy reference",)
+    assert seen_trees >= 4
+
+
 def test_transform_refusals(matcher):
     """trees that are not forward-linked, a root without children, missing arrays: HS_ERR_INVALID from hs_bow_transform and hs_vocab_upload"""
     e = next(iter(scenes.vocab_edge_trees(3)))
