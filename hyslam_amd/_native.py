@@ -4,6 +4,7 @@ There is no CPU fallback: if the HIP library is missing or cannot be loaded this
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -47,6 +48,24 @@ class LmEntryParams(C.Structure):
 
     def __init__(self, max_dist_factor=2.0, min_dist_factor=0.5):
         super().__init__(max_dist_factor, min_dist_factor)
+
+
+# hs_kf_table (include/hyslam_amd.h): the observation table of the key-frame graph entry points; host or device pointers
+class KfTable(C.Structure):
+    _fields_ = [("L", C.c_int32), ("n_kf", C.c_int32), ("lm_obs_offsets", C.c_void_p), ("lm_obs_kf", C.c_void_p), ("lm_obs_octave", C.c_void_p),
+                ("lm_bad", C.c_void_p), ("lm_nobs", C.c_void_p), ("kf_bad", C.c_void_p), ("kf_id", C.c_void_p)]
+
+
+def _header_constant(name):
+    """the value of `#define name <integer>` in include/hyslam_amd.h: the header is the one place that states it"""
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hyslam_amd.h")) as f:
+        m = re.search(r"^#define[ \t]+%s[ \t]+(\d+)[ \t]*$" % name, f.read(), re.M)
+    if not m:
+        raise ImportError("include/hyslam_amd.h does not define " + name)
+    return int(m.group(1))
+
+
+HS_KF_LDS_SLOTS, HS_KF_SORT_PASS = _header_constant("HS_KF_LDS_SLOTS"), _header_constant("HS_KF_SORT_PASS")
 
 
 class FrameView(C.Structure):
@@ -96,6 +115,7 @@ EXPORTS = [
     "hs_vocab_upload", "hs_vocab_dev_destroy", "hs_vocab_dev_groups", "hs_bow_transform_device", "hs_records_bow_match_device", "hs_bow_transform", "hs_hamming_knn2", "hs_hamming_knn2_device",
     "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device", "hs_landmark_best_descriptors", "hs_landmark_best_descriptors_device",
     "hs_landmark_update_entries", "hs_landmark_update_entries_device",
+    "hs_kf_votes", "hs_kf_votes_device", "hs_kf_redundancy", "hs_kf_redundancy_device",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -222,6 +242,10 @@ def lib():
     L.hs_landmark_best_descriptors_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_landmark_update_entries.argtypes = [vp, vp, C.c_int] + [vp] * 13
     L.hs_landmark_update_entries_device.argtypes = [vp, vp, C.c_int] + [vp] * 15 + [C.c_int, vp]
+    L.hs_kf_votes.argtypes = [vp, C.POINTER(KfTable), C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.hs_kf_votes_device.argtypes = L.hs_kf_votes.argtypes + [vp]
+    L.hs_kf_redundancy.argtypes = [vp, C.POINTER(KfTable), C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp, vp, vp]
+    L.hs_kf_redundancy_device.argtypes = L.hs_kf_redundancy.argtypes + [vp]
     L.hs_bow_vector.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_bow_vector_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.hs_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]

@@ -297,7 +297,7 @@ void hs_launch_search_init(const hs_frame_view& F2, const hs_keypoint* d_kps2, c
                            const hs_keypoint* d_kps1, const uint8_t* d_desc1, int n1, const float* d_prev_xy, float window, float th_low, float nnratio,
                            int32_t* d_owner, int32_t* d_odist, float* d_angle_scratch, int32_t* d_self_scratch, int32_t* d_n_matches, hipStream_t s);
 
-// ---- host entry points that work on a handle (hs_api.hip, kernels_landmark.hip, kernels_bow.hip, kernels_place.hip, hs_comm.hip) ----
+// ---- host entry points that work on a handle (hs_api.hip, kernels_landmark.hip, kernels_bow.hip, kernels_place.hip, hs_kfgraph.hip, hs_comm.hip) ----
 // hs_orb is opaque outside hs_api.hip; the other translation units reach it through these four accessors (defined in hs_api.hip).
 void hs_set_error(hs_orb* h, const char* msg);
 int hs_orb_device_of(const hs_orb* h);

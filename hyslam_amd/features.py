@@ -628,6 +628,93 @@ class FeatureMatcher:
                                                           *[p(out[k]) for k in ("normal", "min_dist", "max_dist", "mean_dist", "size", "best", "median", "flags")]))
         return out
 
+    @staticmethod
+    def _kf_table(table):
+        """the observation table of the key-frame graph calls -> (_native.KfTable, the arrays it points into).  `table`: a dict with kf_bad, kf_id
+        [n_kf], lm_bad, lm_nobs [L] (each optional: zeros / the CSR lengths) and the landmarks' observations either as `observations`, a list per
+        landmark of (slot, octave) rows in ascending slot order, or as CSR lm_obs_offsets [L+1] + lm_obs_kf + lm_obs_octave (octave optional)."""
+        if "observations" in table:
+            rows = [np.asarray(o, np.int32).reshape(-1, 2) for o in table["observations"]]
+            off = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=off[1:])
+            flat = np.concatenate(rows) if rows else np.zeros((0, 2), np.int32)
+            kf, octv = np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
+        else:
+            off = np.ascontiguousarray(table["lm_obs_offsets"], np.int64).reshape(-1)
+            kf = np.ascontiguousarray(table["lm_obs_kf"], np.int32).reshape(-1)
+            octv = np.ascontiguousarray(table["lm_obs_octave"], np.int32).reshape(-1) if table.get("lm_obs_octave") is not None else np.zeros(len(kf), np.int32)
+            if len(off) < 1 or off[-1] > len(kf) or len(octv) != len(kf):
+                raise ValueError("lm_obs_offsets[L] exceeds the number of observations")
+        L = len(off) - 1
+        lm_bad = np.ascontiguousarray(table["lm_bad"], np.uint8).reshape(-1) if table.get("lm_bad") is not None else np.zeros(L, np.uint8)
+        lm_nobs = np.ascontiguousarray(table["lm_nobs"], np.int32).reshape(-1) if table.get("lm_nobs") is not None else np.diff(off).astype(np.int32)
+        if table.get("kf_id") is not None:
+            kf_id = np.ascontiguousarray(table["kf_id"], np.int64).reshape(-1)
+        else:
+            kf_id = np.arange(int(table["n_kf"]) if "n_kf" in table else (int(kf.max()) + 1 if len(kf) else 0), dtype=np.int64)
+        kf_bad = np.ascontiguousarray(table["kf_bad"], np.uint8).reshape(-1) if table.get("kf_bad") is not None else np.zeros(len(kf_id), np.uint8)
+        if len(lm_bad) != L or len(lm_nobs) != L or len(kf_bad) != len(kf_id):
+            raise ValueError("the per-landmark / per-key-frame arrays do not match the table")
+        keep = (off, kf, octv, lm_bad, lm_nobs, kf_bad, kf_id)
+        return N.KfTable(L, len(kf_id), *[a.ctypes.data for a in keep]), keep
+
+    def KeyFrameVotes(self, table, queries=None, q_offsets=None, q_lm=None, self_id=None, count_bad_kf=False, th=15, cap=10, weights=True):
+        """The key-frame counter of CovisNode::UpdateConnections (src/core/CovisibilityGraph.cpp:42-124; count_bad_kf=False, self_id = the node's
+        mnId) or TrackLocalMap::UpdateLocalKeyFrames (src/slam/tracking/TrackLocalMap.cpp:80-123; count_bad_kf=True) for a batch of queries, and what
+        the reference derives from it.  `table`: see _kf_table.  Queries: either `queries`, a list of landmark-index arrays, or CSR `q_offsets`
+        [Q+1] + `q_lm`.  `self_id` [Q] (None: nothing excluded).  Returns a dict: weights (Q, n_kf) (None with weights=False), max_slot, max_count,
+        n_ordered [Q], ordered_slot, ordered_weight (Q, cap): the entries with count >= th (or the single maximum) by descending weight, then
+        descending slot; rows padded with -1 / 0; n_ordered holds the full length.  With cap=10 a row is a `neigh` row of PlaceRecognizer."""
+        T, keep = self._kf_table(table)
+        qoff, ql = self._csr(queries, q_offsets, q_lm, np.int32, (), "query")
+        Q = len(qoff) - 1
+        sid = None if self_id is None else np.ascontiguousarray(self_id, np.int64).reshape(-1)
+        if sid is not None and len(sid) != Q:
+            raise ValueError("self_id must have one entry per query")
+        out = dict(weights=np.zeros((Q, T.n_kf), np.int32) if weights else None, max_slot=np.zeros(Q, np.int32), max_count=np.zeros(Q, np.int32),
+                   ordered_slot=np.zeros((Q, cap), np.int32), ordered_weight=np.zeros((Q, cap), np.int32), n_ordered=np.zeros(Q, np.int32))
+        ex = self._ex
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_kf_votes(ex._h, C.byref(T), Q, p(qoff), p(ql), p(sid), int(bool(count_bad_kf)), int(th), p(out["weights"]),
+                                           p(out["max_slot"]), p(out["max_count"]), p(out["ordered_slot"]), p(out["ordered_weight"]), int(cap),
+                                           p(out["n_ordered"])))
+        return out
+
+    def KeyFrameRedundancy(self, table, cand_slot, cand_th_depth, items=None, cand_offsets=None, item_lm=None, item_octave=None, item_depth=None,
+                           is_mono=False, th_obs=3, frac_redundant=0.9):
+        """KeyFrameCuller::run's verdict (src/slam/mapping/KeyFrameCuller.cpp:33-86) for every candidate against ONE snapshot of the map (`table`,
+        see _kf_table): a pure function of the snapshot — SetBadKeyFrame on a culled candidate changes the map, so cull the first candidate with
+        cull = 1, regather and ask again for those behind it.  Candidates: slot and mThDepth, and their keypoints that hold a landmark either as
+        `items`, a list per candidate of (landmark, octave, depth) rows, or as CSR `cand_offsets` [C+1] + item_lm + item_octave + item_depth.
+        Returns a dict of n_mps, n_redundant (int32 [C]) and cull (uint8 [C])."""
+        T, keep = self._kf_table(table)
+        slot = np.ascontiguousarray(cand_slot, np.int32).reshape(-1)
+        thd = np.ascontiguousarray(cand_th_depth, np.float32).reshape(-1)
+        if items is not None:
+            if cand_offsets is not None or item_lm is not None:
+                raise ValueError("pass either the items list or cand_offsets + item arrays")
+            rows = [np.asarray(r, np.float64).reshape(-1, 3) for r in items]
+            coff = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=coff[1:])
+            flat = np.concatenate(rows) if rows else np.zeros((0, 3))
+            ilm, ioct, idep = (np.ascontiguousarray(flat[:, 0], np.int32), np.ascontiguousarray(flat[:, 1], np.int32), np.ascontiguousarray(flat[:, 2], np.float32))
+        else:
+            coff = np.ascontiguousarray(cand_offsets, np.int64).reshape(-1)
+            ilm = np.ascontiguousarray(item_lm, np.int32).reshape(-1)
+            ioct = np.ascontiguousarray(item_octave, np.int32).reshape(-1)
+            idep = np.ascontiguousarray(item_depth, np.float32).reshape(-1) if item_depth is not None else np.zeros(len(ilm), np.float32)
+            if len(coff) < 1 or coff[-1] > len(ilm) or len(ioct) != len(ilm) or len(idep) != len(ilm):
+                raise ValueError("cand_offsets[C] exceeds the number of items")
+        Cn = len(coff) - 1
+        if len(slot) != Cn or len(thd) != Cn:
+            raise ValueError("cand_slot, cand_th_depth and the items must describe the same number of candidates")
+        out = dict(n_mps=np.zeros(Cn, np.int32), n_redundant=np.zeros(Cn, np.int32), cull=np.zeros(Cn, np.uint8))
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_kf_redundancy(ex._h, C.byref(T), Cn, p(slot), p(thd), p(coff), p(ilm), p(ioct), p(idep), int(bool(is_mono)),
+                                                int(th_obs), float(frac_redundant), p(out["n_mps"]), p(out["n_redundant"]), p(out["cull"])))
+        return out
+
 
 class ORBVocabulary:
     """HYSLAM::ORBVocabulary::transform (src/features/low_level/ORBVocabulary.cpp:31-42) over a flat vocabulary tree

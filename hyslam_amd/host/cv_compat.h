@@ -153,6 +153,7 @@ public:
     bool Protected() { return n_protected > 0; }
     bool IsInKeyFrame(KeyFrame* pKF) { return in_keyframes.count(pKF) > 0 || mObservations.count(pKF) > 0; }
     int GetIndexInKeyFrame(KeyFrame* pKF) { auto it = mObservations.find(pKF); return it == mObservations.end() ? -1 : (int)it->second; }      // MapPoint.cc:124-131
+    std::map<KeyFrame*, size_t> GetObservations() { return mObservations; }                                                                   // MapPoint.cc:86-89
     // test set-up (the reference fills these through Map / MapPointDB)
     cv::Mat mWorldPos = cv::Mat(3, 1, CV_32F), mNormalVector = cv::Mat(3, 1, CV_32F);
     FeatureDescriptor mDescriptor; int nObs = 0; float size = 0, mfMinDistance = 0, mfMaxDistance = 0; bool mbBad = false; int n_protected = 0;
@@ -239,6 +240,11 @@ public:
     const Camera& getCamera() const { return camera; }
     const FeatureViews& getViews() const { return views; }
     const LandMarkMatches& getLandMarkMatches() { return matches; }
+    std::set<MapPoint*> GetMapPoints() { std::set<MapPoint*> s; for (const auto& kv : matches) if (kv.second) s.insert(kv.second); return s; }                         // the landmarks of `matches` (KeyFrame::GetMapPoints)
+    bool isBad() { return mbBad; }
+    long unsigned int mnId = 0;
+    float mThDepth = 0;
+    bool mbBad = false;                // test set-up (the reference sets it in Map::SetBadKeyFrame)
     Camera camera;
     DBoW2::FeatureVector mFeatVec;
     float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;

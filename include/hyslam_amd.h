@@ -543,6 +543,87 @@ int  hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* para
                                        int32_t* d_best, int32_t* d_median, int32_t* d_flags,
                                        hs_landmark* d_lms, const int32_t* d_lm_index, int n_lms, void* stream);
 
+/* ---- key-frame graph: everything the reference answers by walking "which key frames see these landmarks?" — CovisNode::UpdateConnections
+ * (src/core/CovisibilityGraph.cpp:42-124), TrackLocalMap::UpdateLocalKeyFrames (src/slam/tracking/TrackLocalMap.cpp:80-123) and KeyFrameCuller::run
+ * (src/slam/mapping/KeyFrameCuller.cpp:21-93) — over ONE observation table, for a batch.  Integer arithmetic only: every output is identical to the
+ * reference's, not merely close.
+ * Containers the reference orders by KeyFrame* address become ARRAY ORDER: key frames are numbered by slot 0 .. n_kf-1, passed in
+ * ascending address order.  The table (host pointers for the host forms, device pointers for the `_device` forms; the struct itself is host memory):
+ *   lm_obs_offsets [L+1] int64   CSR over the landmarks' observations: non-decreasing, [0] >= 0 (the host forms check: HS_ERR_INVALID)
+ *   lm_obs_kf      []    int32   slot of each observation, ascending within a landmark (the order of its std::map<KeyFrame*, size_t>)
+ *   lm_obs_octave  []    int32   views.keypt(idx).octave of that observation          (hs_kf_redundancy only; hs_kf_votes ignores it)
+ *   lm_bad         [L]   u8      MapPoint::isBad()
+ *   lm_nobs        [L]   int32   MapPoint::Observations() — counts a stereo observation twice, so it is NOT the CSR length (hs_kf_redundancy only)
+ *   kf_bad         [n_kf] u8     KeyFrame::isBad()                                    (hs_kf_votes only)
+ *   kf_id          [n_kf] int64  KeyFrame::mnId                                       (hs_kf_votes only)
+ * The host forms also refuse a landmark index or slot outside the table (HS_ERR_INVALID, no output touched); the device forms check nothing, their
+ * kernels skip such an entry. */
+typedef struct hs_kf_table {
+    int32_t L, n_kf;
+    const int64_t* lm_obs_offsets;
+    const int32_t* lm_obs_kf;
+    const int32_t* lm_obs_octave;
+    const uint8_t* lm_bad;
+    const int32_t* lm_nobs;
+    const uint8_t* kf_bad;
+    const int64_t* kf_id;
+} hs_kf_table;
+
+/* hs_kf_votes keeps a query's counters in LDS while n_kf <= HS_KF_LDS_SLOTS; beyond it they are a row of global memory updated with device atomics
+ * (integer adds: both paths are exact).  An ordered list of up to HS_KF_SORT_PASS entries is sorted from LDS in one pass; a longer one is ranked
+ * straight from the counters: correct for any length up to n_kf, at n_ordered * n_kf counter reads per query (with all of 12 288 key frames
+ * listed about 12 ms on an MI355X, with 12 289 about 23 ms; profiles/README.md). */
+#define HS_KF_LDS_SLOTS 12288
+#define HS_KF_SORT_PASS 1024
+
+/* The counter of UpdateConnections / UpdateLocalKeyFrames and what the reference derives from it, for Q queries.  Query q votes with the landmarks
+ * q_lm[q_offsets[q] .. q_offsets[q+1]) (a CSR like the table's; pKF->GetMapPoints() for covisibility, the frame's matched landmarks for the local
+ * map; a landmark listed twice counts twice — a std::set caller never lists one twice).  A bad landmark contributes nothing (:55,
+ * TrackLocalMap.cpp:88).  q_self_id [Q] (may be NULL = none): observations by a key frame whose kf_id equals it are not counted (:63 compares mnId,
+ * not the address, so EVERY slot carrying that id is left out); -1 excludes none.  count_bad_kf = 0 is covisibility (:65-68): a bad key frame is
+ * not counted and never appears.  count_bad_kf = 1 is UpdateLocalKeyFrames: a bad key frame is counted into `weights`, but skipped when the maximum
+ * is chosen (TrackLocalMap.cpp:113) and left out of the ordered list.  th: the connection threshold (15, :82).  Per query:
+ *   weights [Q][n_kf] int32 (may be NULL)   the counter, 0 = not in the map: mConnectedKeyFrameWeights.  For local_key_frames the caller tests
+ *                                           `> 0` AND !isBad(): with count_bad_kf = 1 a bad key frame carries its count here, and the reference skips it
+ *                                           before local_key_frames.insert (TrackLocalMap.cpp:113-122)
+ *   max_slot [Q], max_count [Q]             pKFmax / nmax of `if (count > nmax)` on the walk over ascending slots: the LOWEST slot among equal
+ *                                           maxima; -1 / 0 when nothing (that is not bad) was counted — the reference returns without touching the node
+ *   ordered_slot [Q][cap], ordered_weight [Q][cap], n_ordered [Q]
+ *                                           the entries with count >= th or, when there is none, the single (nmax, pKFmax) entry (:100-104), in the
+ *                                           order of sort(vPairs) + push_front (:106-113): descending weight and, among equal weights, DESCENDING
+ *                                           slot.  n_ordered always holds the full length; the first min(n_ordered, cap) entries are written and the
+ *                                           rest of the row is filled with -1 / 0.  Truncation is not an error: GetBestCovisibilityKeyFrames(N) is the
+ *                                           first N entries, and with cap = 10 a row is a `neigh` row of hs_place_query_*.  cap = 0: no list wanted.
+ * The symmetric_updates of :96,103 — what the CovisGraph applies to the OTHER nodes — are exactly the ordered entries (slot, weight).
+ * hs_kf_votes: host pointers, staged through the handle's scratch, synchronous.  hs_kf_votes_device: `T` holds device pointers, every array is in HBM
+ * of the handle's device, enqueued on `stream` (NULL = the handle's own) without synchronising, nothing checked; beyond HS_KF_LDS_SLOTS key frames
+ * the d_weights rows ARE the counters and d_weights must not be NULL.  The handle's one-stream-at-a-time rule applies (see
+ * hs_orb_extract_batch_device). */
+int  hs_kf_votes(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* q_offsets, const int32_t* q_lm, const int64_t* q_self_id,
+                 int count_bad_kf, int th, int32_t* weights, int32_t* max_slot, int32_t* max_count,
+                 int32_t* ordered_slot, int32_t* ordered_weight, int cap, int32_t* n_ordered);
+int  hs_kf_votes_device(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* d_q_offsets, const int32_t* d_q_lm, const int64_t* d_q_self_id,
+                        int count_bad_kf, int th, int32_t* d_weights, int32_t* d_max_slot, int32_t* d_max_count,
+                        int32_t* d_ordered_slot, int32_t* d_ordered_weight, int cap, int32_t* d_n_ordered, void* stream);
+
+/* KeyFrameCuller::run's verdict (:33-86) for C candidate key frames, each against the SAME snapshot of the map.  Candidate c is the key frame in
+ * slot cand_slot[c] with mThDepth cand_th_depth[c]; its keypoints that hold a landmark are the items [cand_offsets[c] .. cand_offsets[c+1]):
+ * item_lm (landmark index), item_octave (KFviews.keypt(i).octave), item_depth (KFviews.depth(i); read only when is_mono = 0).  Per item, as :39-81:
+ * a bad landmark is skipped; when not mono an item with depth > th_depth || depth < 0 is skipped; nMPs counts the rest; when lm_nobs > th_obs the
+ * landmark's observations with slot != cand_slot and octave <= item octave + 1 are counted, and the landmark is redundant when they reach th_obs
+ * (the reference's early `break` changes nothing).  n_mps [C], n_redundant [C], cull [C] u8 = n_redundant > frac_redundant * n_mps evaluated as C++
+ * does (:86): the int converted to float, one float product.  th_obs = 3 and frac_redundant = 0.9f are KeyFrameCullerParameters' defaults.
+ * The call is a PURE FUNCTION OF THE SNAPSHOT.  The sequential part of the reference is not in it: SetBadKeyFrame on a culled candidate erases its
+ * observations, can turn landmarks bad (MapPointDB.cpp:39-75) and may be refused (Map.cc:153-159), all of which changes the verdict of the candidates
+ * after it.  The caller culls the first candidate with cull = 1, regathers the table and asks again for the candidates behind it
+ * (hyslam_amd/host/HipKeyFrameGraph.h does).  Host / device forms as hs_kf_votes. */
+int  hs_kf_redundancy(hs_orb* h, const hs_kf_table* T, int C, const int32_t* cand_slot, const float* cand_th_depth, const int64_t* cand_offsets,
+                      const int32_t* item_lm, const int32_t* item_octave, const float* item_depth, int is_mono, int th_obs, float frac_redundant,
+                      int32_t* n_mps, int32_t* n_redundant, uint8_t* cull);
+int  hs_kf_redundancy_device(hs_orb* h, const hs_kf_table* T, int C, const int32_t* d_cand_slot, const float* d_cand_th_depth,
+                             const int64_t* d_cand_offsets, const int32_t* d_item_lm, const int32_t* d_item_octave, const float* d_item_depth,
+                             int is_mono, int th_obs, float frac_redundant, int32_t* d_n_mps, int32_t* d_n_redundant, uint8_t* d_cull, void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the

@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
@@ -54,7 +54,7 @@ def compile_mode(ref, host_dir, mode, tmp):
     for d, _, _ in os.walk(os.path.join(ref, "src")):
         inc.append("-I" + d)
     tu = os.path.join(tmp, "tu_%s.cpp" % mode)
-    body = "".join('#include "%s"\n' % h for h in HEADERS)
+    body = "".join('#include "%s"\n' % h for h in HEADERS) + "#include <Map.h>\n#include <MappingDataStructs.h>\n"
     flags = ["-DHYSLAM_AMD_WITH_HYSLAM"]
     first = []
     if mode == "unpatched":
@@ -80,7 +80,10 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    const std::vector<HYSLAM::HipLandmarkEntries::Result> ent = lme.updateEntries(lin); cv::Mat nrm = ent[0].normal.clone();\n"
              "    HYSLAM::HipPlaceRecognizer pr(1000); HYSLAM::KeyFrame* pkf = nullptr; HYSLAM::Frame* pf = nullptr; pr.add(pkf); pr.erase(pkf);\n"
              "    const std::vector<HYSLAM::KeyFrame*> lc = pr.detectLoopCandidates(pkf, 0.01f); const std::set<HYSLAM::KeyFrame*> rc = pr.relocalizationCandidateSet(pf);\n"
-             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size();\n}\n")
+             "    HYSLAM::HipKeyFrameGraph kg; HYSLAM::Map* pmap = nullptr; HYSLAM::KeyFrameCullerParameters kcp;\n"
+             "    const HYSLAM::HipKeyFrameGraph::Connections con = kg.updateConnections(pkf); const HYSLAM::HipKeyFrameGraph::Votes vo = kg.localKeyFrameVotes(*pf);\n"
+             "    const std::vector<HYSLAM::KeyFrame*> gone = kg.cullRedundant(pkf, pmap, kcp);\n"
+             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size();\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
           ["-I" + os.path.join(ROOT, "tests", "cpp", "thirdparty_stubs"), "-I" + host_dir, "-I" + os.path.join(ROOT, "include"), tu]
