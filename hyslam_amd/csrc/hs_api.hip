@@ -3,7 +3,7 @@
 // paths), the host-computed tables (scale factors, per-level quotas, resize coefficients) and the launch
 // sequence.  The whole extraction of a batch is GPU-resident: pyramid -> FAST/NMS cells -> quadtree
 // distribution -> blur+orientation+rBRIEF, 10 kernel launches for an 8-level pyramid regardless of batch size.
-#include "hs_internal.h"
+#include "hs_plan.h"
 #include <atomic>
 #include <climits>
 #include <cmath>
@@ -70,24 +70,23 @@ struct hs_orb {
     hipStream_t stream = nullptr;
     std::string err;
     uint16_t taps[7];
+    HsKnobs knobs{};                   // the handle's HS_* environment knobs, read once in hs_orb_create (read_knobs has the table); split_mode is also set by hs_orb_set_split
     HsFastKnobs fast_knobs{};          // HS_FAST_* environment knobs, read once in hs_orb_create
     uint32_t fast_epoch = 0;           // FAST launches on this workspace so far (selects the work-queue counter set)
-    int split_mode = -1;               // HS_EXTRACT_SPLIT (read once): 1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, -1 = for small batches
     hipStream_t s_aux = nullptr; hipEvent_t ev_sfork = nullptr, ev_sjoin = nullptr;      // the second launch sequence of the split and its fences
-    bool qt_point_domain = false;      // HS_QT_POINT_DOMAIN=1 (read once): the quadtree's general point-domain passes only (parity tests of the fallback)
-    int fast_order = 1;                // HS_FAST_ORDER (read once): order of the FAST work items of an image: 1 = reduced levels deepest first, level 0 last; 0 = level 0 first (the order until round 3); 2 = reduced levels interleaved, level 0 last
-    bool stereo_fuse = true;           // HS_STEREO_FUSE=0 (read once): the stereo front end with a separate k_stereo_strips launch instead of the strips binned by an extra workgroup of the describe launch
-    bool no_fuse = false;              // HS_PYRAMID_NO_FUSE=1 (read once): one pyramid level per launch (parity tests of the unfused kernel)
     bool fast_taps = false;            // every tap fits a byte and the 16-bit row sums cannot saturate
     // ORBExtractor ctor tables (ORBExtractor.cpp:86-118)
     std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
     std::vector<int> quota;
-    std::vector<HsLevel> lv;           // the levels of the last configure() attempt
-    std::vector<HsLevel> lv_n;         // the same levels with the NARROW FAST work items (grp_cells / ngroups / item_begin differ); device copy at d_lv + nlevels
-    // Everything configure() builds for one frame size and batch capacity.  free_geometry() is `geo = Geometry{}`: the buffers free themselves and
-    // w = h = batch_cap = 0 says that nothing is configured.
+    // Everything configure() builds for one frame size and batch capacity, and what the last call left behind that only holds for them.
+    // free_geometry() is `geo = Geometry{}`: the buffers free themselves and w = h = batch_cap = 0 says that nothing is configured.
     struct Geometry {
         int w = 0, h = 0, batch_cap = 0;
+        uint64_t plan_digest = 0;          // HsPlan::digest of the plan this geometry was made from (hs_debug_plan_digest)
+        std::vector<HsLevel> lv;           // the levels, host copy of d_lv (empty: no plan since the last reset)
+        std::vector<HsLevel> lv_n;         // the same levels with the NARROW FAST work items (grp_cells / ngroups / item_begin differ); device copy at d_lv + nlevels
+        int last_batch = 0; HsImg0 last_img0{};      // the last extraction on this geometry: frames and where level 0 was (the hs_orb_debug_* readers)
+        int last_pyr_launches = 0;         // kernel launches the pyramid stage of the last call really enqueued (hs_launch_pyramid's return value); 0 = no call yet
         int total_cells = 0, max_wcell = 1, max_hcell = 1;
         int fast_items = 0;                // FAST work items per image (HsLevel::item_begin)
         int fast_items_n = 0;              // narrow items per image; 0 = no narrow list (a cell wider than the narrow tile)
@@ -117,17 +116,9 @@ struct hs_orb {
     } geo;
     HsBuf<HsLevel> d_lv;               // [2][HS_MAX_LEVELS]: lv, then lv_n
     HsBuf<uint16_t> d_taps;
-    int fast_keys_levels = HS_MAX_LEVELS;   // HS_FAST_KEYS_LEVELS (read once; tuning): only the levels 0 .. n-1 get keys
-    int fast_keys_max_batch = 16;      // HS_FAST_KEYS_MAX_BATCH (read once): calls of more frames than this run without the keys (see run_extract)
     bool qt_large = false;             // a level's quota + 8 exceeds HS_QT_MAX_NODES (up to HS_QT_LARGE_NODES): the quadtree kernel's large-list instance, rectangles in d_qt_rects
-    bool qt_small_ok = false;          // every level's list (quota + 8 nodes) fits the quadtree kernel's small instance (two workgroups per CU; HS_QT_SMALL=0 switches it off, read once)
-    bool fast_keys = true;             // HS_FAST_KEYS=0 (read once): the quadtree kernel gathers the candidates and computes the keys itself (the scheme until round 3)
+    bool qt_small_ok = false;          // HS_QT_SMALL=1 and every level's list (quota + 8 nodes) fits the quadtree kernel's small instance (two workgroups per CU)
     bool keep_points = false;          // hs_orb_set_debug(h, 1): the quadtree kernel also gathers the candidates into the dense point arrays (hs_orb_debug_candidates reads them)
-    int deep_rows = 8;                 // HS_PYRAMID_DEEP_ROWS (read once): rows of the LAST level per tile in the small-batch plan (a workgroup's stages are a dependent
-                                       // sequence whose length goes with the rows per wave: more, flatter tiles shorten the launch although their halo rows cost more work)
-    int deep_max_batch = 2;            // HS_PYRAMID_DEEP_MAX (read once): calls of at most this many frames use the small-batch plan (0 = never)
-    int pyr_tbx_max = 0;               // HS_PYRAMID_TBX_MAX (read once): cap on the level-B tile width of the two-level kernel (experiment: lane utilisation against time)
-    int chain_mode = -1;               // HS_PYRAMID_CHAIN (read once): -1 = a three-level chain for the tail of an odd number of levels, 0 = never, 2 = chains for every fused pair too (parity tests)
     // staging for the host-pointer entry points (regrown behind a drained `stream`)
     HsFrameStaging in;
     HsBuf<uint8_t> d_out;              // one block [counts | keypoints | descriptors] (out_layout), so that the results come back in ONE device-to-host copy
@@ -138,8 +129,7 @@ struct hs_orb {
     HsPinned<uint8_t> h_pin;
     // hs_orb_extract_batch (host-pointer call): one pinned block the three outputs come back into
     HsPinned<uint8_t> h_pin_out;
-    int last_batch = 0; HsImg0 last_img0{};
-    int last_pyr_launches = 0;         // kernel launches the pyramid stage of the last call really enqueued (hs_launch_pyramid's return value)
+    // (the two below outlive a reconfiguration: the matcher has no geometry, and the published results live in d_out / a slot's block, not in the workspace)
     int last_stereo_launches = 2;      // launches of stage 4 in the last stereo call: strips + match (run_stereo) or match only (the front end with the strips inside the describe launch)
     // where the last host-pointer extraction (hs_orb_extract[_batch], hs_orb_wait) left its results on the DEVICE: what hs_frame_publish keeps
     const hs_keypoint* pub_kps = nullptr; const uint8_t* pub_desc = nullptr; int pub_cap = 0, pub_batch = 0;
@@ -167,8 +157,6 @@ struct hs_orb {
 namespace {
 
 inline int cv_round_f(float v) { return (int)nearbyintf(v); }           // cvRound: round half to even
-inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
-inline short sat_short(float v) { int i = cv_round_f(v); return (short)(i < -32768 ? -32768 : (i > 32767 ? 32767 : i)); }
 
 // record "stage `stage` starts here" (stage -1 closes the previous one) when profiling is on
 void mark(hs_orb* h, int stage, hipStream_t s)
@@ -183,7 +171,45 @@ void mark(hs_orb* h, int stage, hipStream_t s)
 // geometry that the early exit would accept
 void free_geometry(hs_orb* h) { h->geo = hs_orb::Geometry{}; }
 
-// (Re)build per-level geometry, tables and workspace for batches of `batch` frames of w x h.
+// The plan's pointer fields hold byte offsets (hs_plan.h); these turn them into addresses, in one place per buffer.  "None" is decided by
+// what the record is, never by a zero offset: level 1 sits at offset 0 of an image's pyramid while base == nullptr means level 0.
+template <class T> void relocate(T*& p, const void* base) { p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + reinterpret_cast<uintptr_t>(p)); }
+void relocate_levels(std::vector<HsLevel>& lv, const hs_orb::Geometry& g)
+{
+    for (size_t l = 0; l < lv.size(); l++) {
+        HsLevel& V = lv[l];
+        if (l > 0) { relocate(V.base, g.d_pyr.p); relocate(V.xofs, g.d_tables.p); relocate(V.ialpha, g.d_tables.p); relocate(V.yofs, g.d_tables.p); relocate(V.ibeta, g.d_tables.p); }
+        if (V.qt_ytab) { relocate(V.qt_xtab, g.d_qt_tabs.p); relocate(V.qt_ytab, g.d_qt_tabs.p); }      // (the y table follows the x table: its offset is never 0)
+    }
+}
+void relocate_pyramid(hs_orb::Geometry& g)
+{
+    for (std::vector<HsPyrChain>* plan : { &g.pyr_chain, &g.pyr_deep })
+        for (size_t l = 0; l < plan->size(); l++) {
+            HsPyrChain& C = (*plan)[l];
+            if (!C.valid) continue;
+            if (l > 1) relocate(C.sbase, g.d_pyr.p);                // a chain that starts at level 1 reads the caller's frames
+            for (int i = 0; i < C.nstage; i++) {
+                HsPyrStage& S = C.st[i];
+                relocate(S.base, g.d_pyr.p); relocate(S.xt, g.d_tables.p);
+                relocate(S.rows, g.d_pyr_tabs.p); relocate(S.tx, g.d_pyr_tabs.p); relocate(S.ty, g.d_pyr_tabs.p);
+            }
+        }
+    for (size_t l = 0; l < g.pyr_fuse.size(); l++) {
+        HsPyrFuse& F = g.pyr_fuse[l];
+        if (!F.valid) continue;
+        if (l > 1) relocate(F.sbase, g.d_pyr.p);
+        relocate(F.abase, g.d_pyr.p); relocate(F.bbase, g.d_pyr.p); relocate(F.xtA, g.d_tables.p); relocate(F.xtB, g.d_tables.p);
+        relocate(F.rowA, g.d_pyr_tabs.p); relocate(F.rowB, g.d_pyr_tabs.p); relocate(F.xt, g.d_pyr_tabs.p); relocate(F.yt, g.d_pyr_tabs.p);
+    }
+}
+template <class T, class V> hipError_t upload(const HsBuf<T>& d, const std::vector<V>& v)
+{
+    return v.empty() ? hipSuccess : hipMemcpy(d.p, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice);
+}
+
+// (Re)build per-level geometry, tables and workspace for batches of `batch` frames of w x h: plan on the host (hs_plan.hip), then allocate
+// from the plan's sizes, upload its arrays and turn its offsets into addresses.
 int configure_impl(hs_orb* h, int w, int hh, int batch);
 int configure(hs_orb* h, int w, int hh, int batch)
 {
@@ -200,285 +226,115 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     free_geometry(h);                  // also un-configures: every failure return below leaves w = h = batch_cap = 0
     hs_orb::Geometry& g = h->geo;
     const int L = h->p.nlevels;
-    h->lv.assign(L, HsLevel{});
-    std::vector<int16_t> tables;
-    std::vector<size_t> tab_off(L * 4, 0);
-    size_t pyr_per_img = 0; uint64_t cand = 0; int sel = 0, cells = 0, items = 0;
-    std::vector<size_t> pyr_off(L, 0);
-    for (int l = 0; l < L; l++) {
-        HsLevel& V = h->lv[l];
-        V.w = cv_round_f((float)w * h->inv_scale[l]);          // ORBExtractor.cpp:568-569
-        V.h = cv_round_f((float)hh * h->inv_scale[l]);
-        if (V.w < 1 || V.h < 1) return hs_fail(h, HS_ERR_INVALID, "pyramid level collapses to zero size");
-        V.pitch = (V.w + 63) & ~63;
-        if (l > 0) { pyr_off[l] = pyr_per_img; pyr_per_img += (size_t)V.pitch * V.h; }
-        // cell grid, ORBExtractor.cpp:413-428
-        const int minB = HS_BORDER, maxBX = V.w - HS_BORDER, maxBY = V.h - HS_BORDER;
-        const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
-        const float W = (float)h->p.cell_px;
-        V.ncols = width > 0 ? (int)(width / W) : 0;
-        V.nrows = height > 0 ? (int)(height / W) : 0;
-        if (V.ncols < 1 || V.nrows < 1) { V.ncols = V.nrows = 0; V.wcell = V.hcell = 0; }   // reference: division by zero (UB); no keypoints here
-        else { V.wcell = (int)ceilf(width / V.ncols); V.hcell = (int)ceilf(height / V.nrows); }
-        if (V.wcell > hs_fast_max_cell_w(6) || V.hcell > HS_MAX_CELL_H)
-            return hs_fail(h, HS_ERR_INVALID, "FAST cell wider than 247 px or taller than 125 px is not supported");
-        V.cell_begin = cells; cells += V.ncols * V.nrows;
-        V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 6);
-        V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
-        V.item_begin = items; items += V.ngroups * V.nrows;
-        V.inv_wcell = V.wcell > 0 ? (65536 + V.wcell - 1) / V.wcell : 0;
-        V.inv_wcell1 = V.wcell > 0 ? (65536 + V.wcell) / (V.wcell + 1) : 0;
-        // quadtree, ORBExtractor.cpp:183-185
-        V.qt_w = maxBX - minB; V.qt_h = maxBY - minB;
-        V.n_ini = (V.qt_w > 0 && V.qt_h > 0) ? (int)roundf((float)V.qt_w / (float)V.qt_h) : 0;
-        if (V.ncols > 0 && V.n_ini < 1) return hs_fail(h, HS_ERR_INVALID, "aspect ratio w/h < 0.5 is undefined behaviour in the reference (nIni == 0)");
-        if (V.ncols < 1) V.n_ini = 0;      // a level without a FAST cell has no keypoints (D4) and no tree: its aspect ratio refuses nothing (until round 6 a 560 x 33 level 7 did: 528 roots)
-        if (V.n_ini > (h->qt_large ? HS_QT_LARGE_NODES : HS_QT_MAX_NODES) / 4) return hs_fail(h, HS_ERR_INVALID, "aspect ratio too wide");
-        V.hx = V.n_ini > 0 ? (float)V.qt_w / V.n_ini : 1.f;
-        V.quota = h->quota[l];
-        V.cand_cap = V.ncols * V.nrows * hs_cell_cap(V.wcell, V.hcell);
-        V.cand_off = cand; cand += (uint64_t)((V.cand_cap + 3) & ~3);
-        V.sel_cap = std::max(V.quota + 4, 4 * V.n_ini + 4);
-        V.sel_off = sel; sel += V.sel_cap;
-        V.scale = h->scale[l];
-        V.kp_size = (float)(int)(31 * h->scale[l]);              // ORBExtractor.cpp:478
-        // cv::resize tables (OpenCV 3.4 resize.cpp, INTER_LINEAR, 8U fixed point) from level l-1
-        if (l > 0) {
-            const int sw = h->lv[l - 1].w, sh = h->lv[l - 1].h;
-            const double scale_x = 1. / ((double)V.w / sw), scale_y = 1. / ((double)V.h / sh);
-            int xmax = V.w;
-            auto grow = [&](size_t n) { size_t o = (tables.size() + 3) & ~(size_t)3; tables.resize(o + n); return o; };   // 8-byte aligned
-            size_t o0 = grow(4 * (size_t)V.w);   // x table: {sx, a0, a1, 0} per output column
-            size_t o1 = o0;
-            size_t o2 = grow(V.h);               // yofs
-            size_t o3 = grow(2 * (size_t)V.h);   // ibeta
-            for (int dx = 0; dx < V.w; dx++) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = cv_floor_f(fx); fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx + 1 >= sw) { xmax = std::min(xmax, dx); if (sx >= sw - 1) { fx = 0; sx = sw - 1; } }
-                tables[o0 + 4 * dx] = (int16_t)sx;
-                tables[o0 + 4 * dx + 1] = sat_short((1.f - fx) * 2048);
-                tables[o0 + 4 * dx + 2] = sat_short(fx * 2048);
-                tables[o0 + 4 * dx + 3] = 0;
-            }
-            for (int dy = 0; dy < V.h; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = cv_floor_f(fy); fy -= sy;
-                tables[o2 + dy] = (int16_t)std::max(-32768, std::min(32767, sy));
-                tables[o3 + 2 * dy] = sat_short((1.f - fy) * 2048);
-                tables[o3 + 2 * dy + 1] = sat_short(fy * 2048);
-            }
-            V.xmax = xmax;
-            tab_off[4 * l] = o0; tab_off[4 * l + 1] = o1; tab_off[4 * l + 2] = o2; tab_off[4 * l + 3] = o3;
-        }
-    }
-    pyr_per_img = (pyr_per_img + 255) & ~(size_t)255;
-    g.max_wcell = g.max_hcell = 1;
-    for (int l = 0; l < L; l++) { g.max_wcell = std::max(g.max_wcell, h->lv[l].wcell); g.max_hcell = std::max(g.max_hcell, h->lv[l].hcell); }
-    g.total_cells = cells; g.fast_items = items; g.cand_img_stride = cand; g.sel_img_stride = sel; g.max_kp = sel;
-    // Order of the FAST work items of an image: the REDUCED levels first, deepest level first, level 0 last.  An item of a reduced level
-    // costs 2-3 times an item of level 0 (the same number of pixels, denser corners), and the persistent FAST kernel walks the items in this
-    // order: with the cheap, uniform level-0 items at the end of every queue the tail of the launch — waves finishing their last item while
-    // the queues are empty — is short (a 32-frame launch spent ~17 % more per frame than a 128-frame launch with the expensive items last).
-    auto order_items = [&](std::vector<HsLevel>& lv) {
-        int pos = 0;
-        if (h->fast_order == 0) { for (int l = 0; l < L; l++) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; } }
-        else {
-            for (int l = L - 1; l >= 1; l--) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; }
-            lv[0].item_begin = pos; pos += lv[0].ngroups * lv[0].nrows;
-        }
-        return pos;
-    };
-    order_items(h->lv);
+    HsPlan P; std::string refusal;
+    const HsPlanInput in{ &h->p, h->inv_scale.data(), h->scale.data(), h->quota.data(), &h->knobs, &h->fast_knobs, h->qt_large, w, hh };
+    const int rc = hs_plan_geometry(in, P, refusal);
+    if (rc != HS_OK) return hs_fail(h, rc, refusal);
+    g.total_cells = P.total_cells; g.max_wcell = P.max_wcell; g.max_hcell = P.max_hcell; g.fast_items = P.fast_items; g.fast_items_n = P.fast_items_n;
+    g.cand_img_stride = P.cand_img_stride; g.sel_img_stride = P.sel_img_stride; g.max_kp = P.max_kp;
+    g.qhist_stride = P.qhist_stride; g.qbest_stride = P.qbest_stride; g.plan_digest = P.digest;
+    g.lv = std::move(P.lv); g.lv_n = std::move(P.lv_n);
+    g.pyr_fuse = std::move(P.pyr_fuse); g.pyr_chain = std::move(P.pyr_chain); g.pyr_deep = std::move(P.pyr_deep);
 
-    HIP_TRY(h, g.d_pyr.grow(std::max<size_t>(pyr_per_img * batch, 256)));
-    HIP_TRY(h, g.d_tables.grow(std::max<size_t>(tables.size(), 256 / sizeof(int16_t))));
-    if (!tables.empty()) HIP_TRY(h, hipMemcpy(g.d_tables, tables.data(), tables.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-    const size_t ce = std::max<uint64_t>(cand * batch, 64);
+    // ---- allocate: every size is the plan's per-image figure times `batch`, with a floor that keeps an empty buffer addressable
+    HIP_TRY(h, g.d_pyr.grow(std::max<size_t>(P.pyr_per_img * batch, 256)));
+    HIP_TRY(h, g.d_tables.grow(std::max<size_t>(P.tables.size(), 256 / sizeof(int16_t))));
+    const size_t ce = std::max<uint64_t>(g.cand_img_stride * batch, 64);
     HIP_TRY(h, g.d_cand.grow(ce));
     HIP_TRY(h, g.d_pts_xy.grow(ce));
     HIP_TRY(h, g.d_pts_sk.grow(ce));
     HIP_TRY(h, g.d_pt_node.grow(ce));
     if (h->qt_large) HIP_TRY(h, g.d_qt_rects.grow((size_t)batch * L * hs_quadtree_large_scratch_bytes()));
-    HIP_TRY(h, g.d_cell_count.grow(std::max<size_t>((size_t)cells * batch, 64 / 4)));
+    HIP_TRY(h, g.d_cell_count.grow(std::max<size_t>((size_t)g.total_cells * batch, 64 / 4)));
     HIP_TRY(h, g.d_cand_count.grow((size_t)batch * L));
     HIP_TRY(h, g.d_sel_count.grow((size_t)batch * L));
-    HIP_TRY(h, g.d_sel.grow(std::max<size_t>((size_t)sel * batch * 3, 64 / 4)));          // 12 bytes per selection entry
-    HIP_TRY(h, g.d_sel_perm.grow(std::max<size_t>((size_t)sel * batch, 64 / 2)));
-    for (int l = 0; l < L; l++) {
-        HsLevel& V = h->lv[l];
-        V.img_stride = pyr_per_img;
-        V.base = l > 0 ? g.d_pyr + pyr_off[l] : nullptr;
-        if (l > 0) {
-            V.xofs = g.d_tables + tab_off[4 * l]; V.ialpha = g.d_tables + tab_off[4 * l + 1];
-            V.yofs = g.d_tables + tab_off[4 * l + 2]; V.ibeta = g.d_tables + tab_off[4 * l + 3];
-        }
-    }
-    {   // geometric-key tables of the quadtree kernel
-        std::vector<uint8_t> qblob;
-        std::vector<size_t> xo(L, 0), yo2(L, 0); std::vector<char> has(L, 0);
-        for (int l = 0; l < L; l++) has[l] = hs_quadtree_build_tables(h->lv[l], qblob, xo[l], yo2[l]) ? 1 : 0;
-        HIP_TRY(h, g.d_qt_tabs.grow(std::max<size_t>(qblob.size() + 16, 256)));
-        if (!qblob.empty()) HIP_TRY(h, hipMemcpy(g.d_qt_tabs, qblob.data(), qblob.size(), hipMemcpyHostToDevice));
-        for (int l = 0; l < L; l++) if (has[l]) { h->lv[l].qt_xtab = g.d_qt_tabs + xo[l]; h->lv[l].qt_ytab = g.d_qt_tabs + yo2[l]; }
-        // the FAST kernel's side of the same keys (HsFastQt): u16 tables  xkey[x] = root(x) << 2 DH | spread(xtab[x]),  ykey[y] = spread(ytab[y]) << 1,
-        // padded by 512 entries, and this level's place in the per-image histogram / best-candidate arrays
-        auto spread = [](uint32_t v) { v = (v | (v << 4)) & 0x0F0Fu; v = (v | (v << 2)) & 0x3333u; v = (v | (v << 1)) & 0x5555u; return v; };
-        std::vector<uint16_t> keys; std::vector<HsFastQt> fq(L, HsFastQt{});
-        std::vector<size_t> kx(L, 0), ky(L, 0);
-        uint32_t hoff = 0, boff = 0;
-        for (int l = 0; l < L; l++) {
-            HsLevel& V = h->lv[l];
-            V.qt_hist_off = V.qt_best_off = 0xFFFFFFFFu;
-            // (HS_FAST_KEYS_LEVELS: only levels 0 .. n-1.  Measured at one 1080p pair per call, quadtree us for n = 0 / 1 / 2 / 3 / 8: 35.1 / 32.6 /
-            // 31.4 / 30.8 / 24.8 — every level's workgroup is about as long as level 0's, the fixed block-wide steps dominate — so it is all or nothing.)
-            if (!has[l] || !h->fast_keys || l >= h->fast_keys_levels) continue;
-            const int DH = V.n_ini <= 2 ? 6 : 5, ncell = V.n_ini << (2 * DH);
-            kx[l] = keys.size(); keys.resize(keys.size() + (size_t)V.qt_w + 1 + 512, 0);
-            for (int x = 0; x <= V.qt_w; x++) {
-                int r = 0;
-                for (int i = 1; i < V.n_ini; i++) r += x >= V.qt_rbound[i];
-                keys[kx[l] + x] = (uint16_t)(((uint32_t)r << (2 * DH)) | spread(qblob[xo[l] + x]));
-            }
-            ky[l] = keys.size(); keys.resize(keys.size() + (size_t)V.qt_h + 1 + 512, 0);
-            for (int y = 0; y <= V.qt_h; y++) keys[ky[l] + y] = (uint16_t)(spread(qblob[yo2[l] + y]) << 1);
-            V.qt_hist_off = hoff; V.qt_best_off = boff;
-            hoff += (uint32_t)(ncell / 2); boff += (uint32_t)ncell;
-            fq[l].hist_off = V.qt_hist_off; fq[l].best_off = V.qt_best_off; fq[l].enabled = 1;
-        }
-        g.qhist_stride = hoff; g.qbest_stride = boff;
-        HIP_TRY(h, g.d_qkeys.grow(std::max<size_t>(keys.size() + 16 / 2, 256 / 2)));
-        if (!keys.empty()) HIP_TRY(h, hipMemcpy(g.d_qkeys, keys.data(), keys.size() * 2, hipMemcpyHostToDevice));
-        for (int l = 0; l < L; l++) if (fq[l].enabled) { fq[l].xkey = g.d_qkeys + kx[l]; fq[l].ykey = g.d_qkeys + ky[l]; }
-        HIP_TRY(h, g.d_fast_qt.grow(HS_MAX_LEVELS));
-        HIP_TRY(h, hipMemcpy(g.d_fast_qt, fq.data(), sizeof(HsFastQt) * L, hipMemcpyHostToDevice));
-        HIP_TRY(h, g.d_qhist.grow(std::max<size_t>((size_t)hoff * batch, 256 / 4)));
-        HIP_TRY(h, g.d_qbest.grow(std::max<size_t>((size_t)boff * batch, 256 / 8)));
-        // (on the handle's stream: hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which the handle's non-blocking
-        //  streams are not ordered with — a memset that lands after the first kernels would wipe what they wrote)
-        HIP_TRY(h, hipMemsetAsync(g.d_qhist, 0, std::max<size_t>((size_t)hoff * batch * 4, 256), h->stream));
-        HIP_TRY(h, hipMemsetAsync(g.d_qbest, 0, std::max<size_t>((size_t)boff * batch * 8, 256), h->stream));
-    }
-    {   // which level pairs the fused pyramid kernel can produce (decided on the host copies of the tables)
-        std::vector<const int16_t*> xt(L, nullptr), yo(L, nullptr);
-        for (int l = 1; l < L; l++) { xt[l] = tables.data() + tab_off[4 * l]; yo[l] = tables.data() + tab_off[4 * l + 2]; }
-        hs_pyramid_plan_fusion(h->lv.data(), L, xt.data(), yo.data(), h->pyr_tbx_max);
-        if (h->no_fuse) for (int l = 0; l < L; l++) h->lv[l].fuse_tbx = 0;
-        std::vector<const int16_t*> ib(L, nullptr);
-        for (int l = 1; l < L; l++) ib[l] = tables.data() + tab_off[4 * l + 3];
-        std::vector<uint64_t> blob;
-        hs_pyramid_build_tables(h->lv.data(), L, xt.data(), yo.data(), ib.data(), blob, g.pyr_fuse);
-        // chains: the last three levels in one launch when the number of levels to make is odd (8 levels: (1,2) (3,4) (5,6,7))
-        g.pyr_chain.assign(L, HsPyrChain{});
-        for (int l = 0; l < L; l++) h->lv[l].chain_n = 0;
-        if (!h->no_fuse && h->chain_mode != 0) {
-            if (h->chain_mode == 2) {
-                for (int l = 1; l + 1 < L; l += 2) {
-                    int n = (l + 3 == L) ? 3 : 2;
-                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
-                    if (!g.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(h->lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
-                    if (g.pyr_chain[l].valid) { h->lv[l].chain_n = g.pyr_chain[l].nstage; if (g.pyr_chain[l].nstage == 3) l++; }
-                }
-            } else if (const char* plan = getenv("HS_PYRAMID_PLAN")) {      // tuning knob: explicit chain lengths from level 1, e.g. "2,3,2" (1 = a single level, 2 = the two-level kernel unless HS_PYRAMID_CHAIN2=1)
-                const bool chain2 = getenv("HS_PYRAMID_CHAIN2") && atoi(getenv("HS_PYRAMID_CHAIN2")) != 0;
-                int l = 1;
-                for (const char* q = plan; *q && l < L; ) {
-                    const int n = std::min(atoi(q), L - l);
-                    if (n >= 3 || (n == 2 && (chain2 || !(l & 1)))) {       // (the two-level kernel is planned for pairs that start on an odd level)
-                        hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l], HS_PYR_DEEP_LDS, 0);
-                        if (g.pyr_chain[l].valid) h->lv[l].chain_n = n;
-                    }
-                    if (n == 1) h->lv[l].fuse_tbx = 0;
-                    l += std::max(n, 1);
-                    while (*q && *q != ',') q++;
-                    if (*q == ',') q++;
-                }
-            } else if (L >= 4 && ((L - 1) & 1)) {
-                const int l = L - 3;
-                hs_pyramid_plan_chain(h->lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, g.pyr_chain[l]);
-                if (g.pyr_chain[l].valid) h->lv[l].chain_n = 3;
-            }
-        }
-        // the small-batch plan: a launch of few frames lasts as long as one workgroup lives and costs ~5 us whatever it does, so the dependent
-        // launches are what counts — greedy: from level 1, the longest chain that fits HS_PYR_DEEP_LDS, then the next (1080p: ONE launch for levels 1-7)
-        g.pyr_deep.assign(L, HsPyrChain{});
-        if (!h->no_fuse && h->deep_max_batch > 0) {
-            for (int l = 1; l + 1 < L;) {
-                int took = 0;
-                for (int n = std::min(HS_PYR_CHAIN_MAX, L - l); n >= 2 && !took; n--) {
-                    hs_pyramid_plan_chain(h->lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, g.pyr_deep[l], HS_PYR_DEEP_LDS, h->deep_rows);
-                    if (g.pyr_deep[l].valid) took = n;
-                }
-                l += took ? took : 1;
-            }
-        }
-        HIP_TRY(h, g.d_pyr_tabs.grow(std::max<size_t>(blob.size() * 8, 256)));
-        if (!blob.empty()) HIP_TRY(h, hipMemcpy(g.d_pyr_tabs, blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
-        for (int which = 0; which < 2; which++)
-        for (HsPyrChain& C : (which ? g.pyr_deep : g.pyr_chain)) {                  // blob offsets -> device pointers
-            if (!C.valid) continue;
-            for (int i = 0; i < C.nstage; i++) {
-                HsPyrStage& S = C.st[i];
-                S.rows = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)S.rows);
-                S.tx = reinterpret_cast<const HsPyrStageX*>(g.d_pyr_tabs + (uintptr_t)S.tx); S.ty = reinterpret_cast<const HsPyrStageY*>(g.d_pyr_tabs + (uintptr_t)S.ty);
-            }
-        }
-        for (HsPyrFuse& F : g.pyr_fuse) {                    // blob offsets -> device pointers
-            if (!F.valid) continue;
-            F.rowA = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)F.rowA); F.rowB = reinterpret_cast<const HsPyrRow*>(g.d_pyr_tabs + (uintptr_t)F.rowB);
-            F.xt = reinterpret_cast<const HsPyrXTile*>(g.d_pyr_tabs + (uintptr_t)F.xt); F.yt = reinterpret_cast<const HsPyrYTile*>(g.d_pyr_tabs + (uintptr_t)F.yt);
-        }
-    }
-    // the same levels with NARROW work items (tiles of 32 dwords: <= 119 px of interior per item), for the launches of small batches: the list
-    // differs in the grouping of the cells only, so everything downstream of the FAST kernel (the quadtree's gather) reads the grouping it was
-    // launched with from ITS copy of the level array (d_lv + L)
-    h->lv_n = h->lv;
-    bool narrow_ok = h->fast_knobs.cols != 64;
-    for (int l = 0; l < L; l++) if (h->lv[l].wcell > hs_fast_max_cell_w(5)) narrow_ok = false;
-    if (narrow_ok) {
-        for (int l = 0; l < L; l++) {
-            HsLevel& V = h->lv_n[l];
-            V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 5);
-            V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
-        }
-        g.fast_items_n = order_items(h->lv_n);
-    }
-    HIP_TRY(h, hipMemcpy(h->d_lv, h->lv.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_lv + L, h->lv_n.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
-    {
-        bool items_fit = true;                                 // every item against the tile the kernel stages it into (hs_fast_item_fits: columns, score-tile column, cells)
-        auto upload_items = [&](const std::vector<HsLevel>& lv, int n_items, HsBuf<HsFastItem>& d_out, int lc) -> hipError_t {
-            std::vector<HsFastItem> fi(std::max(n_items, 1));
-            hs_fast_build_items(lv.data(), L, fi.data());
-            for (int i = 0; i < n_items; i++) items_fit = items_fit && hs_fast_item_fits(fi[i], lc);
-            if (h->fast_order == 2 && L > 2) {                 // experiment: the reduced levels interleaved in proportion (every stretch of the list has the same mix of levels), level 0 last
-                const int n_red = lv[0].item_begin;
-                std::vector<std::pair<double, int>> key(n_red);
-                for (int l = 1; l < L; l++) {
-                    const int n = lv[l].ngroups * lv[l].nrows;
-                    for (int k = 0; k < n; k++) key[lv[l].item_begin + k] = { (k + 0.5) / n, lv[l].item_begin + k };
-                }
-                std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
-                std::vector<HsFastItem> t(fi.begin(), fi.begin() + n_red);
-                for (int i = 0; i < n_red; i++) fi[i] = t[key[i].second];
-            }
-            hipError_t e = d_out.grow(fi.size());
-            if (e != hipSuccess) return e;
-            return hipMemcpy(d_out, fi.data(), fi.size() * sizeof(HsFastItem), hipMemcpyHostToDevice);
-        };
-        HIP_TRY(h, upload_items(h->lv, items, g.d_fast_items, 6));
-        if (g.fast_items_n > 0) HIP_TRY(h, upload_items(h->lv_n, g.fast_items_n, g.d_fast_items_n, 5));
-        if (!items_fit) return hs_fail(h, HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused");
-        HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(g.max_hcell, std::max(items, g.fast_items_n) * batch, h->fast_knobs), 256) / 4));      // (a multiple of 4 bytes)
-        HIP_TRY(h, hipMemsetAsync(g.d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream));       // all four work-queue counter sets start at zero (stream-ordered before the first launch)
-    }
+    HIP_TRY(h, g.d_sel.grow(std::max<size_t>((size_t)g.sel_img_stride * batch * 3, 64 / 4)));          // 12 bytes per selection entry
+    HIP_TRY(h, g.d_sel_perm.grow(std::max<size_t>((size_t)g.sel_img_stride * batch, 64 / 2)));
+    HIP_TRY(h, g.d_qt_tabs.grow(std::max<size_t>(P.qt_tabs.size() + 16, 256)));
+    HIP_TRY(h, g.d_qkeys.grow(std::max<size_t>(P.qkeys.size() + 16 / 2, 256 / 2)));
+    HIP_TRY(h, g.d_fast_qt.grow(HS_MAX_LEVELS));
+    HIP_TRY(h, g.d_qhist.grow(std::max<size_t>((size_t)g.qhist_stride * batch, 256 / 4)));
+    HIP_TRY(h, g.d_qbest.grow(std::max<size_t>((size_t)g.qbest_stride * batch, 256 / 8)));
+    HIP_TRY(h, g.d_pyr_tabs.grow(std::max<size_t>(P.pyr_tabs.size() * 8, 256)));
+    HIP_TRY(h, g.d_fast_items.grow(P.items.size()));
+    HIP_TRY(h, g.d_fast_items_n.grow(P.items_n.size()));
+    HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(g.max_hcell, std::max(g.fast_items, g.fast_items_n) * batch, h->fast_knobs), 256) / 4));      // (a multiple of 4 bytes)
+
+    // ---- offsets -> addresses.  The FAST items were built by the plan from the levels' offsets (hs_fast_build_items copies HsLevel::base), so
+    // they are relocated here by HsFastItem::level rather than rebuilt from the relocated levels.
+    relocate_levels(g.lv, g); relocate_levels(g.lv_n, g);
+    relocate_pyramid(g);
+    for (size_t l = 0; l < P.fast_qt.size(); l++) if (P.fast_qt[l].enabled) { relocate(P.fast_qt[l].xkey, g.d_qkeys.p); relocate(P.fast_qt[l].ykey, g.d_qkeys.p); }
+    for (std::vector<HsFastItem>* items : { &P.items, &P.items_n })
+        for (HsFastItem& it : *items) if (it.level > 0) relocate(it.base, g.d_pyr.p);
+
+    // ---- upload
+    HIP_TRY(h, upload(g.d_tables, P.tables));
+    HIP_TRY(h, upload(g.d_qt_tabs, P.qt_tabs));
+    HIP_TRY(h, upload(g.d_qkeys, P.qkeys));
+    HIP_TRY(h, upload(g.d_fast_qt, P.fast_qt));
+    HIP_TRY(h, upload(g.d_pyr_tabs, P.pyr_tabs));
+    HIP_TRY(h, hipMemcpy(h->d_lv, g.lv.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_lv + L, g.lv_n.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
+    HIP_TRY(h, upload(g.d_fast_items, P.items));
+    HIP_TRY(h, upload(g.d_fast_items_n, P.items_n));
+
+    // ---- what the kernels expect to find zero (on the handle's stream: hipMemset on device memory is asynchronous to the host and runs on the NULL
+    // stream, which the handle's non-blocking streams are not ordered with — a memset that lands after the first kernels would wipe what they wrote)
+    HIP_TRY(h, hipMemsetAsync(g.d_qhist, 0, std::max<size_t>((size_t)g.qhist_stride * batch * 4, 256), h->stream));
+    HIP_TRY(h, hipMemsetAsync(g.d_qbest, 0, std::max<size_t>((size_t)g.qbest_stride * batch * 8, 256), h->stream));
+    HIP_TRY(h, hipMemsetAsync(g.d_fast_ovf, 0, 4 * HS_FAST_QUEUE_DWORDS * 4, h->stream));       // all four work-queue counter sets start at zero (stream-ordered before the first launch)
     HIP_TRY(h, hipStreamSynchronize(h->stream));     // the memsets above have landed whatever stream the caller's launches will use (configuration is rare: it allocates)
     g.w = w; g.h = hh; g.batch_cap = batch;      // configured only now
     return HS_OK;
 }
 
-inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }      // a tuning knob of the environment, read once per handle
+// The handle's knobs of the environment: name, default, how the value is taken, meaning.  read_knobs is their only reader and runs once, in
+// hs_orb_create (a second lane's handle reads them again at its own creation).  INTEGRATION.md has the users' table of every HS_* variable.
+enum KnobRule { K_ANY, K_FLAG /*v != 0*/, K_POSITIVE /*v > 0, else the default*/, K_NONNEG /*v >= 0, else the default*/, K_MIN2 /*v >= 2, else the default*/,
+                K_TRISTATE /*unset (or INT_MIN) = -1, else v != 0*/ };
+struct KnobRow { const char* name; int HsKnobs::* field; int def; KnobRule rule; const char* meaning; };
+const KnobRow KNOBS[] = {
+    { "HS_PYRAMID_NO_FUSE",     &HsKnobs::no_fuse,             0,             K_FLAG,     "one pyramid level per launch (parity tests of the unfused kernel)" },
+    { "HS_PYRAMID_CHAIN",       &HsKnobs::chain_mode,          -1,            K_ANY,      "-1 = a three-level chain for the tail of an odd number of levels, 0 = never, 2 = chains for every fused pair too (parity tests)" },
+    { "HS_PYRAMID_CHAIN2",      &HsKnobs::pyr_chain2,          0,             K_FLAG,     "HS_PYRAMID_PLAN: a 2 is a two-level chain launch, not the two-level kernel" },
+    { "HS_PYRAMID_TBX_MAX",     &HsKnobs::pyr_tbx_max,         0,             K_ANY,      "cap on the level-B tile width of the two-level kernel (experiment: lane utilisation against time)" },
+    { "HS_PYRAMID_DEEP_MAX",    &HsKnobs::deep_max_batch,      2,             K_ANY,      "calls of at most this many frames use the small-batch plan (0 = never)" },
+    // (a workgroup's stages are a dependent sequence whose length goes with the rows per wave: more, flatter tiles shorten the launch although their halo rows cost more work)
+    { "HS_PYRAMID_DEEP_ROWS",   &HsKnobs::deep_rows,           8,             K_MIN2,     "rows of the LAST level per tile in the small-batch plan" },
+    { "HS_FAST_ORDER",          &HsKnobs::fast_order,          1,             K_ANY,      "order of an image's FAST work items: 1 = reduced levels deepest first, level 0 last; 0 = level 0 first (the order until round 3); 2 = reduced levels interleaved, level 0 last" },
+    { "HS_FAST_KEYS",           &HsKnobs::fast_keys,           1,             K_FLAG,     "0: the quadtree kernel gathers the candidates and computes the keys itself (the scheme until round 3)" },
+    { "HS_FAST_KEYS_LEVELS",    &HsKnobs::fast_keys_levels,    HS_MAX_LEVELS, K_POSITIVE, "only the levels 0 .. n-1 get keys (tuning)" },
+    { "HS_FAST_KEYS_MAX_BATCH", &HsKnobs::fast_keys_max_batch, 16,            K_NONNEG,   "calls of more frames than this run without the keys (see run_extract)" },
+    { "HS_QT_POINT_DOMAIN",     &HsKnobs::qt_point_domain,     0,             K_FLAG,     "the quadtree's general point-domain passes only (parity tests of the fallback)" },
+    // (measured at 32 / 64 pairs per call the two-per-CU instance is SLOWER (quadtree 0.0631 against 0.0606 ms, 0.1198 against 0.1117): without the points in LDS every
+    //  sweep goes through L2, which costs a workgroup more than sharing the CU buys.  Kept as a parity / tuning variant: tests/test_gpu_parity.py runs it.)
+    { "HS_QT_SMALL",            &HsKnobs::qt_small,            0,             K_FLAG,     "the quadtree kernel's small instance (two workgroups per CU) where every level's list fits it" },
+    { "HS_STEREO_FUSE",         &HsKnobs::stereo_fuse,         1,             K_FLAG,     "0: the stereo front end with a separate k_stereo_strips launch instead of the strips binned by an extra workgroup of the describe launch" },
+    { "HS_EXTRACT_SPLIT",       &HsKnobs::split_mode,          -1,            K_TRISTATE, "1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, unset = for small batches (hs_orb_set_split overrides)" },
+};
+HsKnobs read_knobs()
+{
+    HsKnobs k{};
+    for (const KnobRow& r : KNOBS) {
+        int& dst = k.*r.field;
+        dst = r.def;
+        const char* e = getenv(r.name);
+        if (!e) continue;
+        const int v = atoi(e);
+        switch (r.rule) {
+        case K_ANY: dst = v; break;
+        case K_FLAG: dst = v != 0; break;
+        case K_POSITIVE: if (v > 0) dst = v; break;
+        case K_NONNEG: if (v >= 0) dst = v; break;
+        case K_MIN2: if (v >= 2) dst = v; break;
+        case K_TRISTATE: dst = v == INT_MIN ? -1 : (v != 0 ? 1 : 0); break;
+        }
+    }
+    // HS_PYRAMID_PLAN (tuning): explicit chain lengths from level 1, e.g. "2,3,2"; parsed by the plan (hs_plan.hip: plan_pyramid)
+    if (const char* e = getenv("HS_PYRAMID_PLAN")) { k.pyr_plan_set = true; k.pyr_plan = e; }
+    return k;
+}
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The result block of a host-pointer extraction, on the device and in pinned host memory: [counts | keypoints | descriptors] of `batch` images
@@ -541,8 +397,8 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     // Keys by batch as well: the FAST kernel's two global atomics per candidate cost it 5 % at 16 pairs per call (0.162 -> 0.170 ms) and buy the
     // quadtree launch 4 us there (its 256 workgroups fill the chip either way); at one pair per call they cost 1 us and buy 10 (35.1 -> 24.8 us: the
     // level-0 workgroup no longer gathers 5 000 records on one CU).  Both arrays are zero between calls whatever the mode, so the mode may change per call.
-    const HsPyrChain* const deep = (batch <= h->deep_max_batch && !g.pyr_deep.empty()) ? g.pyr_deep.data() : nullptr;      // the pyramid's small-batch plan
-    const bool use_keys = h->fast_keys && g.d_fast_qt.p != nullptr && batch <= h->fast_keys_max_batch;
+    const HsPyrChain* const deep = (batch <= h->knobs.deep_max_batch && !g.pyr_deep.empty()) ? g.pyr_deep.data() : nullptr;      // the pyramid's small-batch plan
+    const bool use_keys = h->knobs.fast_keys && g.d_fast_qt.p != nullptr && batch <= h->knobs.fast_keys_max_batch;
     // d_qhist / d_qbest are all zero between calls (the quadtree kernel zeroes what it consumes).  A call that fails anywhere between the keyed FAST
     // launch and its end — an event / stream call of the split path, a later launch — breaks that: the flag makes the NEXT call start from zeroed arrays.
     if (g.keys_dirty) {
@@ -553,12 +409,12 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         g.keys_dirty = false;
     }
     if (use_keys) g.keys_dirty = true;                          // cleared at the end of a call that enqueued everything without error
-    const std::vector<HsLevel>& lvh = narrow ? h->lv_n : h->lv;
+    const std::vector<HsLevel>& lvh = narrow ? h->geo.lv_n : h->geo.lv;
     const HsLevel* const d_lv = h->d_lv + (narrow ? L : 0);
     const HsFastItem* const d_items = narrow ? g.d_fast_items_n.p : g.d_fast_items.p;
     const int n_items = narrow ? g.fast_items_n : g.fast_items, lc = narrow ? 5 : 6;
     const int items0 = lvh[0].ngroups * lvh[0].nrows, first0 = lvh[0].item_begin;      // work items of level 0: the LAST items0 of the item list
-    const bool split = !h->prof && L > 1 && items0 > 0 && items0 < n_items && (h->split_mode == 1 || (h->split_mode < 0 && batch <= 2 && (size_t)g.w * (size_t)g.h * (size_t)batch >= 6000000));
+    const bool split = !h->prof && L > 1 && items0 > 0 && items0 < n_items && (h->knobs.split_mode == 1 || (h->knobs.split_mode < 0 && batch <= 2 && (size_t)g.w * (size_t)g.h * (size_t)batch >= 6000000));
     auto fast = [&](int item_first, int item_count, int spill_slot, hipStream_t st) -> int {
         // launch N uses work-queue counter set N & 3 and relies on launch N - 2 having zeroed it: the epoch advances only when a launch was
         // enqueued without error; after a failed launch all sets are zeroed again so that the next one starts from a known state
@@ -579,7 +435,7 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     };
     auto quadtree = [&](int level_first, int level_count, hipStream_t st) {
         hs_launch_quadtree(d_lv, L, batch, g.total_cells, g.d_cand, g.d_cell_count, g.cand_img_stride,
-                           g.d_pts_xy, g.d_pts_sk, g.d_pt_node, g.d_cand_count, g.d_sel, g.d_sel_count, g.sel_img_stride, g.d_sel_perm, h->qt_point_domain ? 1 : 0,
+                           g.d_pts_xy, g.d_pts_sk, g.d_pt_node, g.d_cand_count, g.d_sel, g.d_sel_count, g.sel_img_stride, g.d_sel_perm, h->knobs.qt_point_domain ? 1 : 0,
                            level_first, level_count, use_keys ? g.d_qhist.p : nullptr, g.d_qbest, g.qhist_stride, g.qbest_stride, h->keep_points ? 1 : 0,
                            h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0), g.d_qt_rects, st);
     };
@@ -595,14 +451,14 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         if (rc != HS_OK) return rc;
         quadtree(0, 1, h->s_aux);
         HIP_TRY(h, hipEventRecord(h->ev_sjoin, h->s_aux));
-        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
+        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
         rc = fast(0, n_items - items0, 0, s);
         if (rc != HS_OK) return rc;
         quadtree(1, L - 1, s);
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_sjoin, 0));
     } else {
         mark(h, 0, s);
-        h->last_pyr_launches = hs_launch_pyramid(h->d_lv, h->lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
+        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
         mark(h, 1, s);
         const int rc = fast(0, n_items, 0, s);
         if (rc != HS_OK) return rc;
@@ -615,7 +471,7 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     mark(h, -1, s);
     HIP_TRY(h, hipGetLastError());
     g.keys_dirty = false;
-    h->last_batch = batch; h->last_img0 = img0;
+    h->geo.last_batch = batch; h->geo.last_img0 = img0;
     return HS_OK;
 }
 
@@ -650,9 +506,9 @@ int run_stereo_frontend(hs_orb* h, HsImg0 img0, HsOut out, const hs_stereo_param
 {
     const int pairs = out.split;
     const HsStripFuse sf{ 1, sp.n_rows, hs_stereo_strips(sp.n_rows), 0, sp.size_ref, h->d_strip_count, h->d_strip_list };
-    const int rc = run_extract(h, img0, 2 * pairs, out, s, h->stereo_fuse ? &sf : nullptr);
+    const int rc = run_extract(h, img0, 2 * pairs, out, s, h->knobs.stereo_fuse ? &sf : nullptr);
     if (rc != HS_OK) return rc;
-    run_stereo(h, h->stereo_fuse, out.kps, out.desc, out.n, out.kps2, out.desc2, out.n2, pairs, out.cap, sp, ur, depth, s);
+    run_stereo(h, h->knobs.stereo_fuse, out.kps, out.desc, out.n, out.kps2, out.desc2, out.n2, pairs, out.cap, sp, ur, depth, s);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -683,9 +539,9 @@ template <class Body> int run_lanes(hs_orb* h, hipStream_t s, int count, Body bo
 void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
 {
     for (int i = 0; i < 8; i++) out[i] = 0;
-    if (!h || h->lv.empty()) return;
+    if (!h || h->geo.lv.empty()) return;
     const int L = h->p.nlevels;
-    out[0] = hs_pyramid_launch_count(h->lv.data(), L);
+    out[0] = hs_pyramid_launch_count(h->geo.lv.data(), L);
     int deep_launches = 0, longest = 0, lds = 0;
     for (int l = 1; l < L; l++) {
         deep_launches++;
@@ -693,14 +549,16 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
             const HsPyrChain& C = h->geo.pyr_deep[l];
             if (C.nstage > longest) { longest = C.nstage; lds = C.x_bytes + C.h_rows * 512; }
             l += C.nstage - 1;
-        } else if (h->lv[l].chain_n > 0 && l + h->lv[l].chain_n <= L) l += h->lv[l].chain_n - 1;
-        else if (h->lv[l].fuse_tbx > 0 && l + 1 < L) l++;
+        } else if (h->geo.lv[l].chain_n > 0 && l + h->geo.lv[l].chain_n <= L) l += h->geo.lv[l].chain_n - 1;
+        else if (h->geo.lv[l].fuse_tbx > 0 && l + 1 < L) l++;
     }
     out[1] = L > 1 ? deep_launches : 0; out[2] = h->geo.fast_items; out[3] = h->geo.fast_items_n;
-    for (int l = 0; l < L; l++) out[4] += h->lv[l].qt_hist_off != 0xFFFFFFFFu;
+    for (int l = 0; l < L; l++) out[4] += h->geo.lv[l].qt_hist_off != 0xFFFFFFFFu;
     out[5] = longest; out[6] = lds;
     if (L > 1 && !h->geo.pyr_deep.empty() && h->geo.pyr_deep[1].valid) out[7] = h->geo.pyr_deep[1].grid_x * h->geo.pyr_deep[1].grid_y;
 }
+// the digest of the plan the current configuration was made from (hs_plan_digest); 0 = nothing is configured
+uint64_t hs_debug_plan_digest(const hs_orb* h) { return h && h->geo.w > 0 ? h->geo.plan_digest : 0; }
 
 // accessors for the other translation units of the library (declared in hs_internal.h)
 void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; }
@@ -761,18 +619,7 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     hs_orb* h = new hs_orb();
     h->p = *p; h->device = device;
     h->fast_knobs = hs_fast_read_knobs();
-    h->no_fuse = env_int("HS_PYRAMID_NO_FUSE", 0) != 0;
-    h->stereo_fuse = env_int("HS_STEREO_FUSE", 1) != 0;
-    h->fast_keys = env_int("HS_FAST_KEYS", 1) != 0;
-    { const int v = env_int("HS_FAST_KEYS_LEVELS", 0); if (v > 0) h->fast_keys_levels = v; }
-    { const int v = env_int("HS_FAST_KEYS_MAX_BATCH", -1); if (v >= 0) h->fast_keys_max_batch = v; }
-    h->fast_order = env_int("HS_FAST_ORDER", 1);
-    h->chain_mode = env_int("HS_PYRAMID_CHAIN", -1);
-    h->pyr_tbx_max = env_int("HS_PYRAMID_TBX_MAX", h->pyr_tbx_max);
-    h->deep_max_batch = env_int("HS_PYRAMID_DEEP_MAX", h->deep_max_batch);
-    { const int v = env_int("HS_PYRAMID_DEEP_ROWS", 0); if (v >= 2) h->deep_rows = v; }
-    h->qt_point_domain = env_int("HS_QT_POINT_DOMAIN", 0) != 0;
-    { const int v = env_int("HS_EXTRACT_SPLIT", INT_MIN); h->split_mode = v == INT_MIN ? -1 : (v != 0 ? 1 : 0); }
+    h->knobs = read_knobs();
     bool zero = true; for (int k = 0; k < 7; k++) zero = zero && p->blur_taps[k] == 0;
     static const uint16_t def[7] = { 18, 34, 49, 55, 49, 34, 18 };
     for (int k = 0; k < 7; k++) h->taps[k] = zero ? def[k] : p->blur_taps[k];
@@ -795,10 +642,7 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     for (int l = 0; l < L; l++) if (h->quota[l] + 8 > HS_QT_MAX_NODES) h->qt_large = true;
     h->qt_small_ok = true;
     for (int l = 0; l < L; l++) if (h->quota[l] + 8 > hs_quadtree_small_nodes()) h->qt_small_ok = false;
-    // ... and only on request (HS_QT_SMALL=1, read once): measured at 32 / 64 pairs per call the two-per-CU instance is SLOWER (quadtree 0.0631 against 0.0606 ms,
-    // 0.1198 against 0.1117): without the points in LDS every sweep goes through L2, which costs a workgroup more than sharing the CU buys.  Kept as a parity /
-    // tuning variant (tests/test_gpu_parity.py runs it).
-    if (env_int("HS_QT_SMALL", 0) == 0) h->qt_small_ok = false;
+    if (!h->knobs.qt_small) h->qt_small_ok = false;      // ... and only on request (HS_QT_SMALL, see read_knobs)
 
     if (hipSetDevice(device) != hipSuccess) { delete h; return HS_ERR_NO_DEVICE; }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1864,13 +1708,15 @@ int hs_debug_stream_copy(hs_orb* h, void* d_dst, const void* d_src, size_t bytes
 int hs_orb_stage_launches(const hs_orb* h, int stage)
 {
     // launches per stage OF THE LAST CALL on the handle (what hs_orb_profile_end's per-stage times are divided by): the pyramid's plan depends on the
-    // batch (calls of <= deep_max_batch frames run the small-batch plan: one launch at 1080p instead of three), the stereo stage on the entry point
+    // batch (calls of <= deep_max_batch frames run the small-batch plan: one launch at 1080p instead of three), the stereo stage on the entry point.
+    // Between a (re)configuration and the next call: the planned count of the CURRENT geometry's standard plan (the last call's figures go with
+    // the geometry they were counted on).  Per lane: a second lane (hs_orb_set_lanes) enqueues as many launches again on its own stream.
     if (!h || stage < 0 || stage >= HS_NUM_STAGES) return 0;
     if (stage == 0) {
-        if (h->last_pyr_launches > 0) return h->last_pyr_launches;      // counted by the launcher itself: a per-level fallback (caller-frame alignment, no big LDS) is included
-        if (h->lv.empty()) return std::max(h->p.nlevels - 1, 0);
-        if (h->last_batch > 0 && h->last_batch <= h->deep_max_batch && !h->geo.pyr_deep.empty()) { int32_t o[8]; hs_debug_plan_summary(h, o); return o[1]; }
-        return hs_pyramid_launch_count(h->lv.data(), h->p.nlevels);
+        if (h->geo.last_pyr_launches > 0) return h->geo.last_pyr_launches;      // counted by the launcher itself: a per-level fallback (caller-frame alignment, no big LDS) is included
+        if (h->geo.lv.empty()) return std::max(h->p.nlevels - 1, 0);
+        if (h->geo.last_batch > 0 && h->geo.last_batch <= h->knobs.deep_max_batch && !h->geo.pyr_deep.empty()) { int32_t o[8]; hs_debug_plan_summary(h, o); return o[1]; }
+        return hs_pyramid_launch_count(h->geo.lv.data(), h->p.nlevels);
     }
     return stage == 4 ? h->last_stereo_launches : 1;
 }
@@ -1933,8 +1779,8 @@ int hs_orb_set_split(hs_orb* h, int mode)
 {
     if (!h) return HS_ERR_INVALID;
     if (mode < -1 || mode > 1) return hs_fail(h, HS_ERR_INVALID, "split mode must be -1 (auto), 0 or 1");
-    h->split_mode = mode;
-    if (h->lane2) h->lane2->split_mode = mode;
+    h->knobs.split_mode = mode;
+    if (h->lane2) h->lane2->knobs.split_mode = mode;
     return HS_OK;
 }
 
@@ -1949,15 +1795,15 @@ int hs_orb_synchronize(hs_orb* h, void* stream)
 int hs_orb_debug_level(hs_orb* h, int image, int level, uint8_t* out, size_t cap_bytes, int32_t* lw, int32_t* lh)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!out || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!out || image < 0 || image >= h->geo.last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    const HsLevel& V = h->lv[level];
+    const HsLevel& V = h->geo.lv[level];
     if ((size_t)V.w * V.h > cap_bytes) return hs_fail(h, HS_ERR_CAPACITY, "level larger than buffer");
     if (lw) *lw = V.w;
     if (lh) *lh = V.h;
     const uint8_t* src; size_t pitch;
-    if (level == 0) { src = hs_img0_ptr(h->last_img0, image); pitch = h->last_img0.row_stride; }
+    if (level == 0) { src = hs_img0_ptr(h->geo.last_img0, image); pitch = h->geo.last_img0.row_stride; }
     else { src = V.base + (size_t)image * V.img_stride; pitch = V.pitch; }
     HIP_TRY(h, hipMemcpy2D(out, V.w, src, pitch, V.w, V.h, hipMemcpyDeviceToHost));
     return HS_OK;
@@ -1974,12 +1820,12 @@ int hs_orb_set_debug(hs_orb* h, int on)
 int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int cap, int32_t* n)
 {
     if (!h) return HS_ERR_INVALID;
-    if (h->fast_keys && h->last_batch <= h->fast_keys_max_batch && !h->keep_points)
+    if (h->knobs.fast_keys && h->geo.last_batch <= h->knobs.fast_keys_max_batch && !h->keep_points)
         return hs_fail(h, HS_ERR_INVALID, "hs_orb_debug_candidates: call hs_orb_set_debug(h, 1) before the extraction (the candidates are only gathered into a dense list in debug mode)");
-    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!xys || !n || image < 0 || image >= h->geo.last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    const HsLevel& V = h->lv[level];
+    const HsLevel& V = h->geo.lv[level];
     int32_t cnt = 0;
     HIP_TRY(h, hipMemcpy(&cnt, h->geo.d_cand_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     cnt = std::min(cnt, V.cand_cap);
@@ -1997,10 +1843,10 @@ int hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int c
 int hs_orb_debug_selected(hs_orb* h, int image, int level, int32_t* xys, int cap, int32_t* n)
 {
     if (!h) return HS_ERR_INVALID;
-    if (!xys || !n || image < 0 || image >= h->last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!xys || !n || image < 0 || image >= h->geo.last_batch || level < 0 || level >= h->p.nlevels) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    const HsLevel& V = h->lv[level];
+    const HsLevel& V = h->geo.lv[level];
     int32_t cnt = 0;
     HIP_TRY(h, hipMemcpy(&cnt, h->geo.d_sel_count + image * h->p.nlevels + level, 4, hipMemcpyDeviceToHost));
     *n = cnt;

@@ -1,0 +1,57 @@
+// hs_plan.h — the extractor's configuration as a pure host computation (hs_plan.hip): everything hs_orb_reserve decides for one frame size,
+// without a HIP call and without the handle.  hs_api.hip allocates from the plan's sizes, uploads its arrays and turns its offsets into pointers.
+#pragma once
+#include "hs_internal.h"
+
+// The handle's tuning / parity-test knobs of the environment, read ONCE per handle by read_knobs (hs_api.hip: the table of names, defaults and
+// meanings is there; INTEGRATION.md lists them for users).  Flags are 0 / 1.  HsFastKnobs (kernels_fast.hip) and HS_PYRAMID_NW8
+// (kernels_pyramid.hip) are read where they are used.
+struct HsKnobs {
+    int no_fuse, stereo_fuse, fast_keys, fast_keys_levels, fast_keys_max_batch, fast_order;
+    int chain_mode, pyr_chain2, pyr_tbx_max, deep_max_batch, deep_rows;
+    int qt_point_domain, qt_small, split_mode;
+    bool pyr_plan_set = false;         // HS_PYRAMID_PLAN is in the environment (an empty string is a plan too: no chain at all)
+    std::string pyr_plan;
+};
+
+// What the plan is made from: the extractor's parameters, its constructor tables (ORBExtractor.cpp:86-118), the knobs and the frame size.
+struct HsPlanInput {
+    const hs_orb_params* p;
+    const float* inv_scale; const float* scale; const int* quota;      // [nlevels]
+    const HsKnobs* knobs; const HsFastKnobs* fast_knobs;
+    bool qt_large;
+    int w, h;
+};
+
+// The plan of one frame size, independent of the batch and free of addresses.  Every pointer field of its records holds a BYTE OFFSET into the
+// buffer the field will point into, until hs_api.hip relocates it:
+//   HsLevel::base, HsFastItem::base, HsPyrFuse::{s,a,b}base, HsPyrChain::sbase, HsPyrStage::base   -> one image's pyramid (d_pyr)
+//   HsLevel::{xofs,ialpha,yofs,ibeta}, HsPyrFuse::xtA/xtB, HsPyrStage::xt                          -> tables (d_tables)
+//   HsLevel::qt_xtab/qt_ytab -> qt_tabs;   HsFastQt::xkey/ykey -> qkeys;   HsPyrFuse::row*/xt/yt, HsPyrStage::rows/tx/ty -> pyr_tabs
+// Offset 0 is a valid place (level 1 starts one image's pyramid), so "none" is never told from the field's value: level 0 has no pyramid buffer
+// and no resize tables, a fused pair / chain that starts at level 1 reads the caller's frames (sbase stays nullptr), a level has quadtree
+// tables iff qt_ytab != 0 (the y table follows the x table), a HsFastQt record iff enabled, a pyramid record iff valid.
+struct HsPlan {
+    int w = 0, h = 0;
+    int total_cells = 0, max_wcell = 1, max_hcell = 1, fast_items = 0, fast_items_n = 0;
+    uint64_t cand_img_stride = 0; int sel_img_stride = 0, max_kp = 0;
+    uint32_t qhist_stride = 0, qbest_stride = 0;
+    size_t pyr_per_img = 0;                    // bytes of one image's levels 1.., a multiple of 256
+    std::vector<HsLevel> lv, lv_n;             // the levels with the wide / the narrow FAST work items
+    std::vector<int16_t> tables;               // cv::resize tables of every level >= 1
+    std::vector<uint8_t> qt_tabs;              // geometric-key tables of the count-domain quadtree
+    std::vector<uint16_t> qkeys;               // the FAST kernel's u16 key tables
+    std::vector<HsFastQt> fast_qt;             // [nlevels]
+    std::vector<uint64_t> pyr_tabs;            // tile / row records of the fused and chain pyramid kernels
+    std::vector<HsPyrFuse> pyr_fuse;           // [level]: the pair (level, level + 1) when it is fused
+    std::vector<HsPyrChain> pyr_chain;         // [level]: the chain launch that starts at this level (HsLevel::chain_n levels)
+    std::vector<HsPyrChain> pyr_deep;          // [level]: the small-batch plan; valid = 0 where no chain starts
+    std::vector<HsFastItem> items, items_n;    // one image's FAST work items, wide / narrow (items_n: fast_items_n > 0); at least one record each
+    uint64_t digest = 0;                       // hs_plan_digest of all of the above
+};
+
+// HS_OK and the plan, or the status and the text of a refusal (the plan is then unspecified)
+int hs_plan_geometry(const HsPlanInput& in, HsPlan& out, std::string& err);
+// FNV-1a-style 64-bit hash (xor, multiply by the FNV prime; 8-byte words where possible) over the plan, field by field in the order stated at its definition: equal digests <=> the kernels get the same tables,
+// records and launch geometry
+uint64_t hs_plan_digest(const HsPlan& P);

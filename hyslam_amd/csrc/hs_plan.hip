@@ -1,0 +1,335 @@
+// hs_plan.hip — the extractor's configuration for one frame size as a pure host computation (HsPlan, hs_plan.h): level sizes and cell grid,
+// cv::resize's fixed-point tables, the quadtree's key tables, the pyramid's fusion / chain / small-batch plans, both FAST work-item lists and
+// every per-image size.  No HIP call, no handle: pointer fields hold byte offsets until hs_api.hip has allocated the buffers they point into.
+#include "hs_plan.h"
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+#include <utility>
+
+namespace {
+
+inline int cv_round_f(float v) { return (int)nearbyintf(v); }           // cvRound: round half to even
+inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
+inline short sat_short(float v) { int i = cv_round_f(v); return (short)(i < -32768 ? -32768 : (i > 32767 ? 32767 : i)); }
+
+template <class T> T* at_offset(size_t bytes) { return reinterpret_cast<T*>((uintptr_t)bytes); }
+
+struct Refusal { int code; const char* text; };
+const Refusal OK{ HS_OK, "" };
+
+// Level sizes (ORBExtractor.cpp:568-569), the FAST cell grid (:413-428), the wide work items, the quadtree's inputs (:183-185) and each level's
+// place in one image's pyramid, candidate and selection arrays
+Refusal plan_levels(const HsPlanInput& in, HsPlan& P)
+{
+    const int L = in.p->nlevels;
+    P.lv.assign(L, HsLevel{});
+    size_t pyr_per_img = 0; uint64_t cand = 0; int sel = 0, cells = 0, items = 0;
+    for (int l = 0; l < L; l++) {
+        HsLevel& V = P.lv[l];
+        V.w = cv_round_f((float)in.w * in.inv_scale[l]);          // ORBExtractor.cpp:568-569
+        V.h = cv_round_f((float)in.h * in.inv_scale[l]);
+        if (V.w < 1 || V.h < 1) return { HS_ERR_INVALID, "pyramid level collapses to zero size" };
+        V.pitch = (V.w + 63) & ~63;
+        if (l > 0) { V.base = at_offset<uint8_t>(pyr_per_img); pyr_per_img += (size_t)V.pitch * V.h; }      // (level 1 at offset 0; level 0 is the caller's frame: nullptr)
+        // cell grid, ORBExtractor.cpp:413-428
+        const int minB = HS_BORDER, maxBX = V.w - HS_BORDER, maxBY = V.h - HS_BORDER;
+        const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
+        const float W = (float)in.p->cell_px;
+        V.ncols = width > 0 ? (int)(width / W) : 0;
+        V.nrows = height > 0 ? (int)(height / W) : 0;
+        if (V.ncols < 1 || V.nrows < 1) { V.ncols = V.nrows = 0; V.wcell = V.hcell = 0; }   // reference: division by zero (UB); no keypoints here
+        else { V.wcell = (int)ceilf(width / V.ncols); V.hcell = (int)ceilf(height / V.nrows); }
+        if (V.wcell > hs_fast_max_cell_w(6) || V.hcell > HS_MAX_CELL_H)
+            return { HS_ERR_INVALID, "FAST cell wider than 247 px or taller than 125 px is not supported" };
+        V.cell_begin = cells; cells += V.ncols * V.nrows;
+        V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 6);
+        V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
+        V.item_begin = items; items += V.ngroups * V.nrows;
+        V.inv_wcell = V.wcell > 0 ? (65536 + V.wcell - 1) / V.wcell : 0;
+        V.inv_wcell1 = V.wcell > 0 ? (65536 + V.wcell) / (V.wcell + 1) : 0;
+        // quadtree, ORBExtractor.cpp:183-185
+        V.qt_w = maxBX - minB; V.qt_h = maxBY - minB;
+        V.n_ini = (V.qt_w > 0 && V.qt_h > 0) ? (int)roundf((float)V.qt_w / (float)V.qt_h) : 0;
+        if (V.ncols > 0 && V.n_ini < 1) return { HS_ERR_INVALID, "aspect ratio w/h < 0.5 is undefined behaviour in the reference (nIni == 0)" };
+        if (V.ncols < 1) V.n_ini = 0;      // a level without a FAST cell has no keypoints (D4) and no tree: its aspect ratio refuses nothing (until round 6 a 560 x 33 level 7 did: 528 roots)
+        if (V.n_ini > (in.qt_large ? HS_QT_LARGE_NODES : HS_QT_MAX_NODES) / 4) return { HS_ERR_INVALID, "aspect ratio too wide" };
+        V.hx = V.n_ini > 0 ? (float)V.qt_w / V.n_ini : 1.f;
+        V.quota = in.quota[l];
+        V.cand_cap = V.ncols * V.nrows * hs_cell_cap(V.wcell, V.hcell);
+        V.cand_off = cand; cand += (uint64_t)((V.cand_cap + 3) & ~3);
+        V.sel_cap = std::max(V.quota + 4, 4 * V.n_ini + 4);
+        V.sel_off = sel; sel += V.sel_cap;
+        V.scale = in.scale[l];
+        V.kp_size = (float)(int)(31 * in.scale[l]);              // ORBExtractor.cpp:478
+    }
+    P.pyr_per_img = (pyr_per_img + 255) & ~(size_t)255;
+    for (int l = 0; l < L; l++) {
+        P.lv[l].img_stride = P.pyr_per_img;
+        P.max_wcell = std::max(P.max_wcell, P.lv[l].wcell); P.max_hcell = std::max(P.max_hcell, P.lv[l].hcell);
+    }
+    P.w = in.w; P.h = in.h;
+    P.total_cells = cells; P.fast_items = items; P.cand_img_stride = cand; P.sel_img_stride = sel; P.max_kp = sel;
+    return OK;
+}
+
+// cv::resize tables (OpenCV 3.4 resize.cpp, INTER_LINEAR, 8U fixed point) of every level l >= 1 from level l - 1
+void plan_resize_tables(HsPlan& P)
+{
+    std::vector<int16_t>& tables = P.tables;
+    for (size_t l = 1; l < P.lv.size(); l++) {
+        HsLevel& V = P.lv[l];
+        const int sw = P.lv[l - 1].w, sh = P.lv[l - 1].h;
+        const double scale_x = 1. / ((double)V.w / sw), scale_y = 1. / ((double)V.h / sh);
+        int xmax = V.w;
+        auto grow = [&](size_t n) { size_t o = (tables.size() + 3) & ~(size_t)3; tables.resize(o + n); return o; };   // 8-byte aligned
+        const size_t o0 = grow(4 * (size_t)V.w);   // x table: {sx, a0, a1, 0} per output column (xofs and ialpha are the same table)
+        const size_t o2 = grow(V.h);               // yofs
+        const size_t o3 = grow(2 * (size_t)V.h);   // ibeta
+        for (int dx = 0; dx < V.w; dx++) {
+            float fx = (float)((dx + 0.5) * scale_x - 0.5);
+            int sx = cv_floor_f(fx); fx -= sx;
+            if (sx < 0) { fx = 0; sx = 0; }
+            if (sx + 1 >= sw) { xmax = std::min(xmax, dx); if (sx >= sw - 1) { fx = 0; sx = sw - 1; } }
+            tables[o0 + 4 * dx] = (int16_t)sx;
+            tables[o0 + 4 * dx + 1] = sat_short((1.f - fx) * 2048);
+            tables[o0 + 4 * dx + 2] = sat_short(fx * 2048);
+            tables[o0 + 4 * dx + 3] = 0;
+        }
+        for (int dy = 0; dy < V.h; dy++) {
+            float fy = (float)((dy + 0.5) * scale_y - 0.5);
+            int sy = cv_floor_f(fy); fy -= sy;
+            tables[o2 + dy] = (int16_t)std::max(-32768, std::min(32767, sy));
+            tables[o3 + 2 * dy] = sat_short((1.f - fy) * 2048);
+            tables[o3 + 2 * dy + 1] = sat_short(fy * 2048);
+        }
+        V.xmax = xmax;
+        V.xofs = at_offset<int16_t>(2 * o0); V.ialpha = at_offset<int16_t>(2 * o0);
+        V.yofs = at_offset<int16_t>(2 * o2); V.ibeta = at_offset<int16_t>(2 * o3);
+    }
+}
+
+// Order of the FAST work items of an image: the REDUCED levels first, deepest level first, level 0 last.  An item of a reduced level
+// costs 2-3 times an item of level 0 (the same number of pixels, denser corners), and the persistent FAST kernel walks the items in this
+// order: with the cheap, uniform level-0 items at the end of every queue the tail of the launch — waves finishing their last item while
+// the queues are empty — is short (a 32-frame launch spent ~17 % more per frame than a 128-frame launch with the expensive items last).
+int order_items(std::vector<HsLevel>& lv, int fast_order)
+{
+    const int L = (int)lv.size();
+    int pos = 0;
+    if (fast_order == 0) { for (int l = 0; l < L; l++) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; } }
+    else {
+        for (int l = L - 1; l >= 1; l--) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; }
+        lv[0].item_begin = pos; pos += lv[0].ngroups * lv[0].nrows;
+    }
+    return pos;
+}
+
+// Geometric-key tables of the quadtree kernel, and the FAST kernel's side of the same keys (HsFastQt): u16 tables
+// xkey[x] = root(x) << 2 DH | spread(xtab[x]),  ykey[y] = spread(ytab[y]) << 1,  padded by 512 entries, and every level's place in the per-image
+// histogram / best-candidate arrays
+void plan_quadtree_keys(const HsKnobs& k, HsPlan& P)
+{
+    const int L = (int)P.lv.size();
+    std::vector<uint8_t>& qblob = P.qt_tabs;
+    std::vector<size_t> xo(L, 0), yo2(L, 0); std::vector<char> has(L, 0);
+    for (int l = 0; l < L; l++) {
+        has[l] = hs_quadtree_build_tables(P.lv[l], qblob, xo[l], yo2[l]) ? 1 : 0;
+        if (has[l]) { P.lv[l].qt_xtab = at_offset<uint8_t>(xo[l]); P.lv[l].qt_ytab = at_offset<uint8_t>(yo2[l]); }
+    }
+    auto spread = [](uint32_t v) { v = (v | (v << 4)) & 0x0F0Fu; v = (v | (v << 2)) & 0x3333u; v = (v | (v << 1)) & 0x5555u; return v; };
+    std::vector<uint16_t>& keys = P.qkeys;
+    P.fast_qt.assign(L, HsFastQt{});
+    uint32_t hoff = 0, boff = 0;
+    for (int l = 0; l < L; l++) {
+        HsLevel& V = P.lv[l];
+        V.qt_hist_off = V.qt_best_off = 0xFFFFFFFFu;
+        // (HS_FAST_KEYS_LEVELS: only levels 0 .. n-1.  Measured at one 1080p pair per call, quadtree us for n = 0 / 1 / 2 / 3 / 8: 35.1 / 32.6 /
+        // 31.4 / 30.8 / 24.8 — every level's workgroup is about as long as level 0's, the fixed block-wide steps dominate — so it is all or nothing.)
+        if (!has[l] || !k.fast_keys || l >= k.fast_keys_levels) continue;
+        const int DH = V.n_ini <= 2 ? 6 : 5, ncell = V.n_ini << (2 * DH);
+        const size_t kx = keys.size(); keys.resize(kx + (size_t)V.qt_w + 1 + 512, 0);
+        for (int x = 0; x <= V.qt_w; x++) {
+            int r = 0;
+            for (int i = 1; i < V.n_ini; i++) r += x >= V.qt_rbound[i];
+            keys[kx + x] = (uint16_t)(((uint32_t)r << (2 * DH)) | spread(qblob[xo[l] + x]));
+        }
+        const size_t ky = keys.size(); keys.resize(ky + (size_t)V.qt_h + 1 + 512, 0);
+        for (int y = 0; y <= V.qt_h; y++) keys[ky + y] = (uint16_t)(spread(qblob[yo2[l] + y]) << 1);
+        V.qt_hist_off = hoff; V.qt_best_off = boff;
+        hoff += (uint32_t)(ncell / 2); boff += (uint32_t)ncell;
+        HsFastQt& Q = P.fast_qt[l];
+        Q.xkey = at_offset<uint16_t>(2 * kx); Q.ykey = at_offset<uint16_t>(2 * ky);
+        Q.hist_off = V.qt_hist_off; Q.best_off = V.qt_best_off; Q.enabled = 1;
+    }
+    P.qhist_stride = hoff; P.qbest_stride = boff;
+}
+
+// Which launches make the pyramid: the fused level pairs (decided on the host copies of the resize tables), the chains of the standard plan
+// and the small-batch plan.  The planners copy the levels' offsets into their records and append their tile tables to P.pyr_tabs.
+void plan_pyramid(const HsKnobs& k, HsPlan& P)
+{
+    const int L = (int)P.lv.size();
+    std::vector<HsLevel>& lv = P.lv;
+    std::vector<const int16_t*> xt(L, nullptr), yo(L, nullptr), ib(L, nullptr);
+    for (int l = 1; l < L; l++) {
+        const uint8_t* const t = reinterpret_cast<const uint8_t*>(P.tables.data());
+        xt[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].xofs); yo[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].yofs);
+        ib[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].ibeta);
+    }
+    hs_pyramid_plan_fusion(lv.data(), L, xt.data(), yo.data(), k.pyr_tbx_max);
+    if (k.no_fuse) for (int l = 0; l < L; l++) lv[l].fuse_tbx = 0;
+    std::vector<uint64_t>& blob = P.pyr_tabs;
+    hs_pyramid_build_tables(lv.data(), L, xt.data(), yo.data(), ib.data(), blob, P.pyr_fuse);
+    // chains: the last three levels in one launch when the number of levels to make is odd (8 levels: (1,2) (3,4) (5,6,7))
+    P.pyr_chain.assign(L, HsPyrChain{});
+    for (int l = 0; l < L; l++) lv[l].chain_n = 0;
+    if (!k.no_fuse && k.chain_mode != 0) {
+        if (k.chain_mode == 2) {
+            for (int l = 1; l + 1 < L; l += 2) {
+                int n = (l + 3 == L) ? 3 : 2;
+                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
+                if (!P.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
+                if (P.pyr_chain[l].valid) { lv[l].chain_n = P.pyr_chain[l].nstage; if (P.pyr_chain[l].nstage == 3) l++; }
+            }
+        } else if (k.pyr_plan_set) {      // tuning knob HS_PYRAMID_PLAN: explicit chain lengths from level 1, e.g. "2,3,2" (1 = a single level, 2 = the two-level kernel unless HS_PYRAMID_CHAIN2=1)
+            const bool chain2 = k.pyr_chain2 != 0;
+            int l = 1;
+            for (const char* q = k.pyr_plan.c_str(); *q && l < L; ) {
+                const int n = std::min(atoi(q), L - l);
+                if (n >= 3 || (n == 2 && (chain2 || !(l & 1)))) {       // (the two-level kernel is planned for pairs that start on an odd level)
+                    hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], HS_PYR_DEEP_LDS, 0);
+                    if (P.pyr_chain[l].valid) lv[l].chain_n = n;
+                }
+                if (n == 1) lv[l].fuse_tbx = 0;
+                l += std::max(n, 1);
+                while (*q && *q != ',') q++;
+                if (*q == ',') q++;
+            }
+        } else if (L >= 4 && ((L - 1) & 1)) {
+            const int l = L - 3;
+            hs_pyramid_plan_chain(lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
+            if (P.pyr_chain[l].valid) lv[l].chain_n = 3;
+        }
+    }
+    // the small-batch plan: a launch of few frames lasts as long as one workgroup lives and costs ~5 us whatever it does, so the dependent
+    // launches are what counts — greedy: from level 1, the longest chain that fits HS_PYR_DEEP_LDS, then the next (1080p: ONE launch for levels 1-7)
+    P.pyr_deep.assign(L, HsPyrChain{});
+    if (!k.no_fuse && k.deep_max_batch > 0) {
+        for (int l = 1; l + 1 < L;) {
+            int took = 0;
+            for (int n = std::min(HS_PYR_CHAIN_MAX, L - l); n >= 2 && !took; n--) {
+                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_deep[l], HS_PYR_DEEP_LDS, k.deep_rows);
+                if (P.pyr_deep[l].valid) took = n;
+            }
+            l += took ? took : 1;
+        }
+    }
+}
+
+// Both FAST work-item lists.  The narrow list: the same levels with NARROW work items (tiles of 32 dwords: <= 119 px of interior per item), for
+// the launches of small batches: it differs in the grouping of the cells only, so everything downstream of the FAST kernel (the quadtree's
+// gather) reads the grouping it was launched with from ITS copy of the level array (lv_n).  Built last: hs_fast_build_items copies
+// HsLevel::base (here: the level's offset), and the narrow levels are a copy of the finished wide ones.
+Refusal plan_fast_items(const HsKnobs& k, const HsFastKnobs& fk, HsPlan& P)
+{
+    const int L = (int)P.lv.size();
+    P.lv_n = P.lv;
+    bool narrow_ok = fk.cols != 64;
+    for (int l = 0; l < L; l++) if (P.lv[l].wcell > hs_fast_max_cell_w(5)) narrow_ok = false;
+    if (narrow_ok) {
+        for (int l = 0; l < L; l++) {
+            HsLevel& V = P.lv_n[l];
+            V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 5);
+            V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
+        }
+        P.fast_items_n = order_items(P.lv_n, k.fast_order);
+    }
+    bool items_fit = true;                                 // every item against the tile the kernel stages it into (hs_fast_item_fits: columns, score-tile column, cells)
+    auto build = [&](const std::vector<HsLevel>& lv, int n_items, std::vector<HsFastItem>& fi, int lc) {
+        fi.assign(std::max(n_items, 1), HsFastItem{});
+        hs_fast_build_items(lv.data(), L, fi.data());
+        for (int i = 0; i < n_items; i++) items_fit = items_fit && hs_fast_item_fits(fi[i], lc);
+        if (k.fast_order == 2 && L > 2) {                  // experiment: the reduced levels interleaved in proportion (every stretch of the list has the same mix of levels), level 0 last
+            const int n_red = lv[0].item_begin;
+            std::vector<std::pair<double, int>> key(n_red);
+            for (int l = 1; l < L; l++) {
+                const int n = lv[l].ngroups * lv[l].nrows;
+                for (int j = 0; j < n; j++) key[lv[l].item_begin + j] = { (j + 0.5) / n, lv[l].item_begin + j };
+            }
+            std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
+            std::vector<HsFastItem> t(fi.begin(), fi.begin() + n_red);
+            for (int i = 0; i < n_red; i++) fi[i] = t[key[i].second];
+        }
+    };
+    build(P.lv, P.fast_items, P.items, 6);
+    if (P.fast_items_n > 0) build(P.lv_n, P.fast_items_n, P.items_n, 5);
+    if (!items_fit) return { HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused" };
+    return OK;
+}
+
+struct Fnv {
+    uint64_t v = 0xcbf29ce484222325ull;
+    // FNV-1a's xor-then-multiply step, over 8-byte words where there are that many and over bytes for the rest: one multiply per word keeps the
+    // pass over the plan's tables (a few hundred KB at 1080p) far below the time the allocations take
+    void bytes(const void* p, size_t n)
+    {
+        const uint8_t* b = static_cast<const uint8_t*>(p);
+        for (; n >= 8; n -= 8, b += 8) { uint64_t w; memcpy(&w, b, 8); v ^= w; v *= 0x100000001b3ull; }
+        for (; n > 0; n--, b++) { v ^= *b; v *= 0x100000001b3ull; }
+    }
+    template <class T> void val(const T& x) { static_assert(std::is_arithmetic<T>::value, "fields only: a record may have padding"); bytes(&x, sizeof(T)); }
+    void off(const void* p) { val((uint64_t)(uintptr_t)p); }            // a pointer field of the plan: its byte offset
+    template <class T> void vec(const std::vector<T>& x) { val((uint64_t)x.size()); if (!x.empty()) bytes(x.data(), x.size() * sizeof(T)); }
+};
+
+void hash_level(Fnv& H, const HsLevel& V)          // every field in declaration order (the record has padding after `quota`)
+{
+    H.val(V.w); H.val(V.h); H.val(V.pitch); H.val(V._r0); H.val(V.img_stride); H.off(V.base);
+    H.val(V.ncols); H.val(V.nrows); H.val(V.wcell); H.val(V.hcell); H.val(V.cell_begin);
+    H.val(V.grp_cells); H.val(V.ngroups); H.val(V.item_begin); H.val(V.inv_wcell); H.val(V.inv_wcell1);
+    H.val(V.qt_w); H.val(V.qt_h); H.val(V.n_ini); H.val(V.hx); H.val(V.quota);
+    H.off(V.qt_xtab); H.off(V.qt_ytab); for (int i = 0; i < 8; i++) H.val(V.qt_rbound[i]);
+    H.val(V.qt_hist_off); H.val(V.qt_best_off); H.val(V.cand_cap); H.val(V.sel_cap); H.val(V.cand_off); H.val(V.sel_off);
+    H.val(V.xmax); H.off(V.xofs); H.off(V.ialpha); H.off(V.yofs); H.off(V.ibeta); H.val(V.scale); H.val(V.kp_size);
+    H.val(V.fuse_tbx); H.val(V.fuse_ar); H.val(V.fuse_sr); H.val(V.fuse_pitch); H.val(V.chain_n); H.val(V._r1);
+}
+
+// the records below are hashed as bytes: no padding (the sizes are the sums of their fields), and every one starts from a zero-initialised
+// record (HsFastQt{}, HsPyrFuse{}, HsPyrChain{} by the planners, memset in hs_fast_build_items)
+static_assert(sizeof(HsFastQt) == 32 && sizeof(HsPyrFuse) == 152 && sizeof(HsPyrStage) == 64 && sizeof(HsPyrChain) == 56 + 64 * HS_PYR_CHAIN_MAX && sizeof(HsFastItem) == 64,
+              "hs_plan_digest hashes these records as bytes: a record that gains padding must be hashed field by field");
+
+} // namespace
+
+int hs_plan_geometry(const HsPlanInput& in, HsPlan& P, std::string& err)
+{
+    P = HsPlan{};
+    Refusal r = plan_levels(in, P);
+    if (r.code == HS_OK) {
+        plan_resize_tables(P);
+        order_items(P.lv, in.knobs->fast_order);
+        plan_quadtree_keys(*in.knobs, P);
+        plan_pyramid(*in.knobs, P);
+        r = plan_fast_items(*in.knobs, *in.fast_knobs, P);      // last: the items and the narrow levels copy what the steps above left in the levels
+    }
+    if (r.code != HS_OK) { err = r.text; return r.code; }
+    P.digest = hs_plan_digest(P);
+    return HS_OK;
+}
+
+// Order: the scalars (w, h, total_cells, max_wcell, max_hcell, fast_items, fast_items_n, cand_img_stride, sel_img_stride, max_kp, qhist_stride,
+// qbest_stride, pyr_per_img), the wide levels, the narrow levels, the resize tables, the quadtree blob, the key table, the HsFastQt records,
+// the pyramid blob, pyr_fuse, pyr_chain, pyr_deep, the wide items, the narrow items.  Arrays are preceded by their length.
+uint64_t hs_plan_digest(const HsPlan& P)
+{
+    Fnv H;
+    H.val(P.w); H.val(P.h); H.val(P.total_cells); H.val(P.max_wcell); H.val(P.max_hcell); H.val(P.fast_items); H.val(P.fast_items_n);
+    H.val(P.cand_img_stride); H.val(P.sel_img_stride); H.val(P.max_kp); H.val(P.qhist_stride); H.val(P.qbest_stride); H.val((uint64_t)P.pyr_per_img);
+    for (const std::vector<HsLevel>* lv : { &P.lv, &P.lv_n }) { H.val((uint64_t)lv->size()); for (const HsLevel& V : *lv) hash_level(H, V); }
+    H.vec(P.tables); H.vec(P.qt_tabs); H.vec(P.qkeys); H.vec(P.fast_qt); H.vec(P.pyr_tabs);
+    H.vec(P.pyr_fuse); H.vec(P.pyr_chain); H.vec(P.pyr_deep);
+    H.vec(P.items); H.vec(P.items_n);
+    return H.v;
+}

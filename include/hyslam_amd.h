@@ -678,7 +678,10 @@ int  hs_comm_allgather_records(hs_comm* c, const void* d_record, void* d_gathere
  * end:   synchronise, write the summed milliseconds per stage into ms[6] and the number of launches of each
  *        stage into launches[6] (pyramid counts one launch per call although it is nlevels-1 kernels), stop collecting. */
 #define HS_NUM_STAGES 6
-/* kernel launches that stage `stage` issues per call (the pyramid is several launches, the stereo match two) */
+/* kernel launches that stage `stage` issued in the last call on the handle (the pyramid is several launches, the stereo match two).  The figure
+ * is PER LANE: with hs_orb_set_lanes(h, 2) the second lane enqueues as many again on its own stream.  Between a (re)configuration —
+ * hs_orb_reserve, or a call with another frame size or a larger batch — and the next call, stage 0 reports the planned count of the
+ * configured geometry's standard plan. */
 int  hs_orb_stage_launches(const hs_orb* h, int stage);
 int  hs_orb_profile_begin(hs_orb* h);
 int  hs_orb_profile_pause(hs_orb* h);

@@ -22,6 +22,7 @@ void hs_orb_borrow(hs_orb* h, int delta);      // hs_api.hip (internal: what hs_
 extern "C" long hip_stub_launches();
 extern "C" void hip_stub_zero_device();
 extern "C" void hip_stub_counters(unsigned long long* out /*[14]*/);       // hip_stub.cpp: live allocations, calls and bytes of allocations / copies / memsets, launches and their digest
+uint64_t hs_debug_plan_digest(const hs_orb* h);                           // hs_api.hip: FNV-style 64-bit digest of the pointer-free plan of the current configuration (hs_plan.h)
 void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/);        // hs_api.hip: launches of the pyramid's two plans, item counts (host-side facts of the last configuration)
 
 #define CHECK(c) do { if (!(c)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
@@ -273,14 +274,18 @@ static int staged_sweep(int rounds)
 
 int main(int argc, char** argv)
 {
-    if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels]: the host-side plan of a geometry
+    if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels [cell]]: the host-side plan of a geometry, or its refusal
         hs_orb_params p; hs_orb_default_params(&p);
         p.nfeatures = argc > 4 ? atoi(argv[4]) : 2000; if (argc > 5) p.scale_factor = (float)atof(argv[5]); if (argc > 6) p.nlevels = atoi(argv[6]);
+        if (argc > 7) p.cell_px = atoi(argv[7]);
         hs_orb* ex = nullptr;
-        CHECK(hs_orb_create(&p, 0, &ex) == HS_OK && hs_orb_reserve(ex, atoi(argv[2]), atoi(argv[3]), 2) == HS_OK);
+        CHECK(hs_orb_create(&p, 0, &ex) == HS_OK);
+        const int rc = hs_orb_reserve(ex, atoi(argv[2]), atoi(argv[3]), 2);
+        if (rc != HS_OK) { printf("refused: status %d: %s\n", rc, hs_orb_last_error(ex)); hs_orb_destroy(ex); return 0; }
         int32_t s[8]; hs_debug_plan_summary(ex, s);
         printf("pyramid launches: standard plan %d, small-batch plan %d (longest chain %d levels, %d B of LDS, %d workgroups per frame); FAST items per frame: %d wide, %d narrow; levels with quadtree keys: %d\n",
                s[0], s[1], s[5], s[6], s[7], s[2], s[3], s[4]);
+        printf("plan digest: %016llx\n", (unsigned long long)hs_debug_plan_digest(ex));
         hs_orb_destroy(ex);
         return 0;
     }

@@ -122,3 +122,28 @@ def test_one_handle_grows_reuses_and_splits(gpu):
     n, k, d, u, z = ex.wait(ex.submit_batch([small]))
     assert u is None and z is None and same_features(k[0, :n[0]], d[0, :n[0]], ok0, od0)
     first_call_again("after the mono ticket")
+
+
+def test_reconfiguration_resets_what_the_last_call_left(gpu):
+    """Between a (re)configuration and the next call the handle reports the planned pyramid launches of the CURRENT geometry, not the count of the
+    last call on the previous one; a refused geometry leaves a handle that extracts as a fresh one does."""
+    s = HS.FeatureExtractorSettings(nFeatures=NF)
+    img = synth_image(21, W1, H1)
+    fresh = HS.ORBExtractor(s)
+    fk, fd = fresh.extract_batch([img])
+    assert len(fk[0]) > 200
+
+    planned = HS.ORBExtractor(s)
+    planned.reserve(W0, H0, 1)
+
+    ex = HS.ORBExtractor(s)
+    k, d = ex.extract_batch([img])
+    assert same_features(k[0], d[0], fk[0], fd[0])
+    ex.reserve(W0, H0, 1)
+    assert ex.pyramid_launches() == planned.pyramid_launches()
+
+    with pytest.raises(N.HsError) as e:
+        ex.reserve(100, 400, 1)                      # aspect below 0.5: refused by the plan
+    assert e.value.status == N.HS_ERR_INVALID
+    k, d = ex.extract_batch([img])
+    assert same_features(k[0], d[0], fk[0], fd[0])

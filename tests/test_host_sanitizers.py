@@ -4,6 +4,7 @@ hyslam_amd/csrc compiled host-only (`hipcc --cuda-host-only`: no device code) an
 hs_orb_reserve / the host-pointer entry points (planners, table builders, workspace sizing, staging, the ingest tickets) and feeds the vocabulary
 loaders truncated and corrupted files.  Any sanitizer report aborts the driver.  (GPU AddressSanitizer is not available on this pool; the oracle has
 its own sanitizer test, tests/test_oracle_sanitizers.py.)"""
+import json
 import os
 import shutil
 import subprocess
@@ -37,3 +38,22 @@ def test_small_batch_pyramid_plan_is_one_launch_at_1080p():
     r = subprocess.run([EXE, "plan", "1920", "1080"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "standard plan 3, small-batch plan 1 (longest chain 7 levels" in r.stdout, r.stdout
+
+
+def test_plan_digests_and_refusals_match_the_recorded_ones():
+    """the pure host plan (hyslam_amd/csrc/hs_plan.hip) against tests/golden/plan_digests.json: for every recorded geometry and knob setting the
+    summary line and the digest of the pointer-free plan — every table, record and offset the kernels get — or the refusal's status and text"""
+    build()
+    with open(os.path.join(ROOT, "tests", "golden", "plan_digests.json")) as f:
+        cases = json.load(f)["cases"]
+    assert len(cases) == 14 + 2 * 16 + 3
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("HS_")}
+    for c in cases:
+        r = subprocess.run([EXE, "plan"] + c["args"], env=dict(clean, **c["env"]), capture_output=True, text=True, timeout=300)
+        what = (c["args"], c["env"], r.stdout + r.stderr[-2000:])
+        assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, what
+        lines = r.stdout.strip().split("\n")
+        if "refused" in c:
+            assert lines == ["refused: status %d: %s" % (c["refused"]["status"], c["refused"]["error"])], what
+        else:
+            assert lines == [c["summary"], "plan digest: " + c["digest"]], what
