@@ -108,7 +108,13 @@ int  hs_orb_extract_batch(hs_orb* h, const uint8_t* const* imgs, int batch, int 
 typedef struct hs_preprocess_params { int32_t channels; int32_t rgb; float scale; int32_t _pad; } hs_preprocess_params;
 void hs_preprocess_size(int w, int h_px, float scale, int32_t* ow, int32_t* oh);
 /* device frames (image i at d_src + i * image_stride, rows `row_stride` bytes apart, channels interleaved) -> device grey frames of the scaled size;
- * asynchronous on `stream` (the handle's own when 0).  Only the ow x oh pixels of every grey frame are written. */
+ * asynchronous on `stream` (the handle's own when 0).  Only the ow x oh pixels of every grey frame are written.
+ * Layout: d_src, d_grey and all four strides may have ANY alignment (a source whose base and strides are multiples of 4 is read with dword loads, any
+ * other with byte loads; grey rows are stored as dwords where they fall on one and as bytes elsewhere, never past column ow, so grey_row_stride == ow
+ * is allowed).  Rows and images must not overlap.
+ * Refused with HS_ERR_INVALID, nothing enqueued and nothing written, the handle stays usable — here and in the two camera-batch calls below:
+ * pp->channels other than 1, 3 and 4; pp->scale outside (0, 16]; a scaled size (hs_preprocess_size) that is empty; row_stride < w * pp->channels;
+ * w or h_px above 32768.  hs_preprocess_device also refuses a scaled size above 16384 either way, grey_row_stride < ow, w or h_px < 1 and batch < 1. */
 int  hs_preprocess_device(hs_orb* h, const uint8_t* d_src, int w, int h_px, size_t row_stride, size_t image_stride, int batch, const hs_preprocess_params* pp,
                           uint8_t* d_grey, size_t grey_row_stride, size_t grey_image_stride, void* stream);
 /* ProcessMonoImage / ProcessStereoImage's `PreProcessImg(...)` + `(*extractor)(mImGray, ...)` in one call (ImageProcessing.cpp:44,55 / :76-77,82-83): `batch`

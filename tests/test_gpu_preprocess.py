@@ -8,18 +8,9 @@ import hipmem
 import oracle
 import hyslam_amd as HS
 from hyslam_amd.synth import synth_image
+from preprocess_cases import colour_frame
 
 pytestmark = pytest.mark.gpu
-
-
-def colour_frame(seed, w, h, cn):
-    """a structured grey scene per channel (different seeds: the channels differ), so that the grey result has corners"""
-    if cn == 1:
-        return synth_image(seed, w, h)
-    chans = [synth_image(seed + 7 * k, w, h) for k in range(3)]
-    if cn == 4:
-        chans.append(np.full((h, w), 200, np.uint8))
-    return np.ascontiguousarray(np.stack(chans, axis=2))
 
 
 @pytest.mark.parametrize("cn", [1, 3, 4])

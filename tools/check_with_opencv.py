@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Run on a machine WITH OpenCV (ideally 3.4.x): compares a dump of tools/dump_boundaries.py with cv2 at the four boundaries.
-usage: python tools/check_with_opencv.py oracle_boundaries.npz        (needs only numpy + cv2)"""
+usage: python tools/check_with_opencv.py oracle_boundaries.npz        (needs only numpy + cv2)
+
+Not yet covered by the dump (PreProcessImg answers that rest on an assumption about OpenCV 3.4; both CPU references agree on them and
+tests/test_preprocess_ref.py pins them by hand, tests/preprocess_cases.py holds the frames):
+  * the scales next to 0.5 (nextafter(0.5f, 0) and nextafter(0.5f, 1)) take the bilinear path, not INTER_AREA's 2x2 fast path
+  * a scale other than 1 that leaves the size unchanged (0.999 on 67 x 35) is a plain copy
+  * a trailing partial block of the 2x2 area path is the float mean of the samples that exist, rounded half to even (2 and 3 give 2)"""
 import sys
 
 import cv2
