@@ -66,6 +66,13 @@ def _header_constant(name):
 
 
 HS_KF_LDS_SLOTS, HS_KF_SORT_PASS = _header_constant("HS_KF_LDS_SLOTS"), _header_constant("HS_KF_SORT_PASS")
+HS_LOCAL_POINTS_BLOCK = _header_constant("HS_LOCAL_POINTS_BLOCK")
+
+
+# hs_local_map_out (include/hyslam_amd.h): the device outputs of hs_local_map_search_device
+class LocalMapOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("weights", "max_slot", "max_count", "local", "n_local", "frame_remove", "sel", "n_sel", "lms", "match_idx",
+                                          "match_dist", "n_matches")]
 
 
 class FrameView(C.Structure):
@@ -116,6 +123,8 @@ EXPORTS = [
     "hs_record_bytes", "hs_record_offsets", "hs_records_knn2_device", "hs_landmark_best_descriptors", "hs_landmark_best_descriptors_device",
     "hs_landmark_update_entries", "hs_landmark_update_entries_device",
     "hs_kf_votes", "hs_kf_votes_device", "hs_kf_redundancy", "hs_kf_redundancy_device",
+    "hs_local_keyframes", "hs_local_keyframes_device", "hs_local_points", "hs_local_points_device", "hs_local_points_work_bytes",
+    "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -246,6 +255,15 @@ def lib():
     L.hs_kf_votes_device.argtypes = L.hs_kf_votes.argtypes + [vp]
     L.hs_kf_redundancy.argtypes = [vp, C.POINTER(KfTable), C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp, vp, vp]
     L.hs_kf_redundancy_device.argtypes = L.hs_kf_redundancy.argtypes + [vp]
+    L.hs_local_keyframes.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    L.hs_local_keyframes_device.argtypes = L.hs_local_keyframes.argtypes + [vp]
+    L.hs_local_points.argtypes = [vp, C.POINTER(KfTable), vp, vp, C.c_int, vp, vp, C.c_int, vp]
+    L.hs_local_points_device.argtypes = L.hs_local_points.argtypes + [vp, vp]
+    L.hs_landmark_gather_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hs_local_map_search_device.argtypes = [vp, C.POINTER(KfTable), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameView), vp,
+                                             C.POINTER(ProjParams), C.c_int, C.POINTER(LocalMapOut), vp, vp]
+    for f in (L.hs_local_points_work_bytes, L.hs_local_map_work_bytes):
+        f.argtypes, f.restype = [C.c_int], C.c_size_t
     L.hs_bow_vector.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_bow_vector_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.hs_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]

@@ -297,7 +297,17 @@ void hs_launch_search_init(const hs_frame_view& F2, const hs_keypoint* d_kps2, c
                            const hs_keypoint* d_kps1, const uint8_t* d_desc1, int n1, const float* d_prev_xy, float window, float th_low, float nnratio,
                            int32_t* d_owner, int32_t* d_odist, float* d_angle_scratch, int32_t* d_self_scratch, int32_t* d_n_matches, hipStream_t s);
 
-// ---- host entry points that work on a handle (hs_api.hip, kernels_landmark.hip, kernels_bow.hip, kernels_place.hip, hs_kfgraph.hip, hs_comm.hip) ----
+// ---- the local map (kernels_localmap.hip; entry points in hs_localmap.hip).  d_work of hs_launch_local_points: hs_local_points_flag_bytes(L) flag bytes,
+// then one int32 per block of HS_LOCAL_POINTS_BLOCK landmarks
+void hs_launch_local_keyframes(int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
+                               int n_max, int n_neighbor, uint8_t* d_local, int32_t* d_n_local, hipStream_t s);
+size_t hs_local_points_flag_bytes(int L);
+void hs_launch_local_points(const hs_kf_table& T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
+                            int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, hipStream_t s);
+void hs_launch_landmark_gather(const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out, hipStream_t s);
+void hs_launch_local_map_query(int n_assoc, int64_t* d_q_off, hipStream_t s);
+
+// ---- host entry points that work on a handle (hs_api.hip, kernels_landmark.hip, kernels_bow.hip, kernels_place.hip, hs_kfgraph.hip, hs_localmap.hip, hs_comm.hip) ----
 // hs_orb is opaque outside hs_api.hip; the other translation units reach it through these four accessors (defined in hs_api.hip).
 void hs_set_error(hs_orb* h, const char* msg);
 int hs_orb_device_of(const hs_orb* h);
@@ -311,6 +321,20 @@ inline int hs_fail(hs_orb* h, int code, const std::string& msg) { hs_set_error(h
 // thread does not report it again through hipGetLastError()
 #define HIP_TRY(h, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); \
     return hs_fail(h, HS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
+
+// argument checks of the host forms over an observation table (hs_kfgraph.hip, hs_localmap.hip): a CSR of `n` rows has offsets[0] >= 0 and is
+// non-decreasing; every index lies in [lo, limit)
+inline bool hs_csr_ok(const int64_t* off, int n)
+{
+    if (off[0] < 0) return false;
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
+    return true;
+}
+inline bool hs_index_range_ok(const int32_t* v, size_t n, int lo, int limit)
+{
+    for (size_t i = 0; i < n; i++) if (v[i] < lo || v[i] >= limit) return false;
+    return true;
+}
 
 #define HS_STAGE_MAX_PIECES 17      // the largest user: bow_host (hs_api.hip)
 // bytes claimed past the last piece.  Unmeasured headroom: nobody has shown that anything needs it, nor that nothing does.

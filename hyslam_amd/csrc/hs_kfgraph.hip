@@ -194,19 +194,6 @@ static void launch_votes(const KfVoteArgs& a, int Q, hipStream_t s)
     else hipLaunchKernelGGL(k_kf_votes<false>, dim3(Q), dim3(KF_VOTE_THREADS), 0, s, a);
 }
 
-// a CSR of `n` rows: offsets[0] >= 0, non-decreasing
-static bool kf_csr_ok(const int64_t* off, int n)
-{
-    if (off[0] < 0) return false;
-    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
-    return true;
-}
-static bool kf_in_range(const int32_t* v, size_t n, int limit)
-{
-    for (size_t i = 0; i < n; i++) if ((unsigned)v[i] >= (unsigned)limit) return false;
-    return true;
-}
-
 extern "C" {
 
 int hs_kf_votes_device(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* d_q_offsets, const int32_t* d_q_lm, const int64_t* d_q_self_id,
@@ -239,10 +226,10 @@ int hs_kf_votes(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* q_offsets
     if (!T->lm_obs_offsets || !q_offsets || !max_slot || !max_count || !n_ordered || (cap > 0 && (!ordered_slot || !ordered_weight)) ||
         (n_kf > 0 && (!T->kf_bad || !T->kf_id)) || (L > 0 && !T->lm_bad))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (!kf_csr_ok(T->lm_obs_offsets, L) || !kf_csr_ok(q_offsets, Q)) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing");
+    if (!hs_csr_ok(T->lm_obs_offsets, L) || !hs_csr_ok(q_offsets, Q)) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing");
     const size_t n_obs = (size_t)T->lm_obs_offsets[L], n_q = (size_t)q_offsets[Q];
     if ((n_obs > 0 && !T->lm_obs_kf) || (n_q > 0 && !q_lm)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (!kf_in_range(T->lm_obs_kf, n_obs, n_kf) || !kf_in_range(q_lm, n_q, L)) return hs_fail(h, HS_ERR_INVALID, "a key-frame slot or landmark index outside the table");
+    if (!hs_index_range_ok(T->lm_obs_kf, n_obs, 0, n_kf) || !hs_index_range_ok(q_lm, n_q, 0, L)) return hs_fail(h, HS_ERR_INVALID, "a key-frame slot or landmark index outside the table");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     HsStage st(h);
     KfVoteArgs a{L, n_kf, count_bad_kf ? 1 : 0, th, cap, 0};
@@ -295,11 +282,11 @@ int hs_kf_redundancy(hs_orb* h, const hs_kf_table* T, int C, const int32_t* cand
     const int L = T->L;
     if (!T->lm_obs_offsets || !cand_slot || !cand_th_depth || !cand_offsets || !n_mps || !n_redundant || !cull || (L > 0 && (!T->lm_bad || !T->lm_nobs)))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (!kf_csr_ok(T->lm_obs_offsets, L) || !kf_csr_ok(cand_offsets, C)) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing");
+    if (!hs_csr_ok(T->lm_obs_offsets, L) || !hs_csr_ok(cand_offsets, C)) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing");
     const size_t n_obs = (size_t)T->lm_obs_offsets[L], n_it = (size_t)cand_offsets[C];
     if ((n_obs > 0 && (!T->lm_obs_kf || !T->lm_obs_octave)) || (n_it > 0 && (!item_lm || !item_octave || (!is_mono && !item_depth))))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (!kf_in_range(item_lm, n_it, L)) return hs_fail(h, HS_ERR_INVALID, "a landmark index outside the table");
+    if (!hs_index_range_ok(item_lm, n_it, 0, L)) return hs_fail(h, HS_ERR_INVALID, "a landmark index outside the table");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     HsStage st(h);
     KfRedArgs a{L, is_mono ? 1 : 0, th_obs, frac_redundant};

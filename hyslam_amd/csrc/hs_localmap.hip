@@ -1,0 +1,131 @@
+// hs_localmap.hip — entry points of the local map (include/hyslam_amd.h): hs_local_keyframes(_device), hs_local_points(_device),
+// hs_landmark_gather_device and hs_local_map_search_device, which is the vote of hs_kfgraph.hip, these three and the projection search enqueued on one
+// stream.  The kernels and their launchers are in kernels_localmap.hip.  The host forms check their arguments and stage through HsStage; the device
+// forms take their temporaries from the caller, so nothing here claims the handle's scratch between two launches of a chain.
+#include "hs_internal.h"
+
+namespace {
+size_t lp_blocks(int L) { return ((size_t)std::max(L, 0) + HS_LOCAL_POINTS_BLOCK - 1) / HS_LOCAL_POINTS_BLOCK; }
+const size_t LM_WORK_HEAD = 256;       // hs_local_map_search_device: q_offsets [2] int64, then n_ordered int32, in front of the local-points work
+}  // namespace
+
+extern "C" {
+
+size_t hs_local_points_work_bytes(int L) { return hs_local_points_flag_bytes(L) + ((lp_blocks(L) * sizeof(int32_t) + 255) & ~(size_t)255) + 256; }
+size_t hs_local_map_work_bytes(int L) { return LM_WORK_HEAD + hs_local_points_work_bytes(L); }
+
+int hs_local_keyframes_device(hs_orb* h, int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap,
+                              const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* d_local, int32_t* d_n_local, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (n_kf < 0 || neigh_cap < 0 || !d_n_local || (n_kf > 0 && (!d_weights || !d_kf_bad || !d_parent || !d_local || (neigh_cap > 0 && !d_neigh))))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    hs_launch_local_keyframes(n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local, d_n_local,
+                              stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+int hs_local_keyframes(hs_orb* h, int n_kf, const int32_t* weights, const uint8_t* kf_bad, const int32_t* neigh, int neigh_cap, const int32_t* parent,
+                       int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* local, int32_t* n_local)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (n_kf < 0 || neigh_cap < 0 || !n_local || (n_kf > 0 && (!weights || !kf_bad || !parent || !local || (neigh_cap > 0 && !neigh))))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (n_neighbor_keyframes < 0 || n_neighbor_keyframes > neigh_cap) return hs_fail(h, HS_ERR_INVALID, "n_neighbor_keyframes must be in [0, neigh_cap]");
+    if (!hs_index_range_ok(neigh, (size_t)n_kf * neigh_cap, -1, n_kf) || !hs_index_range_ok(parent, (size_t)n_kf, -1, n_kf))
+        return hs_fail(h, HS_ERR_INVALID, "a neighbour or parent slot outside [-1, n_kf)");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    HsStage st(h);
+    int32_t *d_w, *d_neigh, *d_parent, *d_n;
+    uint8_t *d_bad, *d_local;
+    st.in(&d_w, (size_t)n_kf, weights); st.in(&d_bad, (size_t)n_kf, kf_bad); st.in(&d_neigh, (size_t)n_kf * neigh_cap, neigh); st.in(&d_parent, (size_t)n_kf, parent);
+    st.out(&d_local, (size_t)n_kf, local); st.out(&d_n, 1, n_local);
+    const int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    hs_launch_local_keyframes(n_kf, d_w, d_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local, d_n, st.stream());
+    return st.finish();
+}
+
+int hs_local_points_device(hs_orb* h, const hs_kf_table* T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
+                           int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!T || T->L < 0 || T->n_kf < 0 || n_assoc < 0 || cap < 0 || !d_n_sel || !d_work || (cap > 0 && !d_sel) || (n_assoc > 0 && (!d_frame_lm || !d_frame_remove)) ||
+        (T->L > 0 && (!T->lm_obs_offsets || !T->lm_bad)) || (T->n_kf > 0 && !d_local))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    hs_launch_local_points(*T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, d_work, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+int hs_local_points(hs_orb* h, const hs_kf_table* T, const uint8_t* local, const int32_t* frame_lm, int n_assoc, uint8_t* frame_remove,
+                    int32_t* sel, int cap, int32_t* n_sel)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!T || T->L < 0 || T->n_kf < 0 || n_assoc < 0 || cap < 0 || !n_sel || (cap > 0 && !sel) || (n_assoc > 0 && (!frame_lm || !frame_remove)) ||
+        !T->lm_obs_offsets || (T->L > 0 && !T->lm_bad) || (T->n_kf > 0 && !local))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    const int L = T->L, n_kf = T->n_kf;
+    if (!hs_csr_ok(T->lm_obs_offsets, L)) return hs_fail(h, HS_ERR_INVALID, "offsets must be non-negative and non-decreasing");
+    const size_t n_obs = (size_t)T->lm_obs_offsets[L];
+    if (n_obs > 0 && !T->lm_obs_kf) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (!hs_index_range_ok(T->lm_obs_kf, n_obs, 0, n_kf) || !hs_index_range_ok(frame_lm, (size_t)n_assoc, -1, L))
+        return hs_fail(h, HS_ERR_INVALID, "a key-frame slot or landmark index outside the table");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    HsStage st(h);
+    hs_kf_table D = *T;
+    int64_t* d_off; int32_t *d_kf, *d_flm, *d_sel, *d_n; uint8_t *d_bad, *d_local, *d_rem, *d_work;
+    st.in(&d_off, (size_t)L + 1, T->lm_obs_offsets); st.in(&d_kf, n_obs, T->lm_obs_kf); st.in(&d_bad, (size_t)L, T->lm_bad);
+    st.in(&d_local, (size_t)n_kf, local); st.in(&d_flm, (size_t)n_assoc, frame_lm);
+    st.out(&d_rem, (size_t)n_assoc, frame_remove); st.out(&d_sel, (size_t)cap, sel); st.out(&d_n, 1, n_sel);
+    st.temp(&d_work, hs_local_points_work_bytes(L));
+    const int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    D.lm_obs_offsets = d_off; D.lm_obs_kf = d_kf; D.lm_bad = d_bad;
+    D.lm_obs_octave = nullptr; D.lm_nobs = nullptr; D.kf_bad = nullptr; D.kf_id = nullptr;
+    hs_launch_local_points(D, d_local, d_flm, n_assoc, d_rem, d_sel, cap, d_n, d_work, st.stream());
+    return st.finish();
+}
+
+int hs_landmark_gather_device(hs_orb* h, const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (L < 0 || cap < 0 || !d_n_sel || (cap > 0 && (!d_sel || !d_out)) || (L > 0 && !d_lms) || ((uintptr_t)d_lms & 15) || ((uintptr_t)d_out & 15))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument (d_lms and d_out are 16-byte aligned)");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    hs_launch_landmark_gather(d_lms, L, d_sel, d_n_sel, cap, d_out, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
+
+int hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                               const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
+                               const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!T || !out || !d_work || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
+        !out->frame_remove || !out->sel || !out->n_sel || !out->lms || !out->match_idx || !out->match_dist || !out->n_matches)
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    void* s = stream ? stream : (void*)hs_orb_stream_of(h);
+    int64_t* d_q_off = static_cast<int64_t*>(d_work);
+    int32_t* d_n_ordered = reinterpret_cast<int32_t*>(d_q_off + 2);
+    void* d_lp_work = static_cast<uint8_t*>(d_work) + LM_WORK_HEAD;
+    hs_launch_local_map_query(n_assoc, d_q_off, (hipStream_t)s);
+    // keyframeCounter with the bad key frames in it, pKFmax among those that are not bad; no ordered list (TrackLocalMap.cpp:80-123)
+    int rc = hs_kf_votes_device(h, T, 1, d_q_off, d_frame_lm, nullptr, 1, 1, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, d_n_ordered, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_local_keyframes_device(h, T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes,
+                                   out->local, out->n_local, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_local_points_device(h, T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, d_lp_work, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_landmark_gather_device(h, d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
+    if (rc != HS_OK) return rc;
+    return hs_search_by_projection_device(h, F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
+}
+
+}  // extern "C"

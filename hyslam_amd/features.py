@@ -307,6 +307,37 @@ class ORBExtractor:
                                                                      d_normal, d_min_dist, d_max_dist, d_mean_dist, d_size, d_best, d_median, d_flags,
                                                                      d_lms, d_lm_index, n_lms, stream or None))
 
+    # ---- the local map on device-resident tables (include/hyslam_amd.h): raw device addresses, asynchronous, nothing checked
+    def local_points_work_bytes(self, L):
+        return int(self._lib.hs_local_points_work_bytes(int(L)))
+
+    def local_map_work_bytes(self, L):
+        return int(self._lib.hs_local_map_work_bytes(int(L)))
+
+    def local_keyframes_device(self, n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local,
+                               d_n_local, stream=0):
+        """hs_local_keyframes_device: d_weights int32 [n_kf], d_kf_bad u8 [n_kf], d_neigh int32 [n_kf][neigh_cap], d_parent int32 [n_kf];
+        d_local u8 [n_kf], d_n_local int32 [1]"""
+        N.check(self._h, self._lib.hs_local_keyframes_device(self._h, n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes,
+                                                             n_neighbor_keyframes, d_local, d_n_local, stream or None))
+
+    def local_points_device(self, table, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, d_work, stream=0):
+        """hs_local_points_device: `table` a _native.KfTable of device pointers; d_work: local_points_work_bytes(table.L) bytes"""
+        N.check(self._h, self._lib.hs_local_points_device(self._h, C.byref(table), d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel,
+                                                          d_work, stream or None))
+
+    def landmark_gather_device(self, d_lms, L, d_sel, d_n_sel, cap, d_out, stream=0):
+        """hs_landmark_gather_device: d_out[j] = d_lms[d_sel[j]] (hs_landmark, 16-byte aligned), skip = 1 past *d_n_sel; exactly cap records"""
+        N.check(self._h, self._lib.hs_landmark_gather_device(self._h, d_lms, L, d_sel, d_n_sel, cap, d_out, stream or None))
+
+    def local_map_search_device(self, table, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, frame,
+                                d_lms, proj_params, cap, out, d_work, stream=0):
+        """hs_local_map_search_device: vote, key-frame expansion, landmark selection, gather and projection search on one stream.  `table`:
+        _native.KfTable, `frame`: _native.FrameView, both of device pointers; `out`: _native.LocalMapOut; d_work: local_map_work_bytes(table.L)"""
+        N.check(self._h, self._lib.hs_local_map_search_device(self._h, C.byref(table), d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent,
+                                                              n_max_local_keyframes, n_neighbor_keyframes, C.byref(frame), d_lms, C.byref(proj_params),
+                                                              cap, C.byref(out), d_work, stream or None))
+
     def stereo_match_batch_device(self, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, sp, d_uRight, d_depth, stream=0):
         N.check(self._h, self._lib.hs_stereo_match_batch_device(self._h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap,
                                                                 C.byref(sp), d_uRight, d_depth, stream or None))
@@ -714,6 +745,42 @@ class FeatureMatcher:
         N.check(ex._h, ex._lib.hs_kf_redundancy(ex._h, C.byref(T), Cn, p(slot), p(thd), p(coff), p(ilm), p(ioct), p(idep), int(bool(is_mono)),
                                                 int(th_obs), float(frac_redundant), p(out["n_mps"]), p(out["n_redundant"]), p(out["cull"])))
         return out
+
+    def LocalKeyFrames(self, weights, kf_bad, neigh, parent, n_max_local_keyframes=80, n_neighbor_keyframes=10):
+        """The key-frame expansion of TrackLocalMap::UpdateLocalKeyFrames (src/slam/tracking/TrackLocalMap.cpp:106-156).  weights [n_kf]: a row of
+        KeyFrameVotes(count_bad_kf=True); kf_bad [n_kf]; neigh (n_kf, neigh_cap): each slot's ordered covisibility list padded with -1; parent
+        [n_kf], -1 = none.  The live set is walked in ascending slot order as the reference walks its std::set while inserting; the walk ends at
+        the first visited slot that has a parent.  Returns (local uint8 [n_kf], n_local)."""
+        w = np.ascontiguousarray(weights, np.int32).reshape(-1)
+        n_kf = len(w)
+        bad = np.ascontiguousarray(kf_bad, np.uint8).reshape(-1)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        ng = np.ascontiguousarray(neigh, np.int32).reshape(n_kf, -1) if n_kf else np.zeros((0, 0), np.int32)
+        if len(bad) != n_kf or len(par) != n_kf:
+            raise ValueError("weights, kf_bad, neigh and parent must describe the same number of key frames")
+        local, n_local = np.zeros(n_kf, np.uint8), np.zeros(1, np.int32)
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_local_keyframes(ex._h, n_kf, p(w), p(bad), p(ng), ng.shape[1], p(par), int(n_max_local_keyframes),
+                                                  int(n_neighbor_keyframes), p(local), p(n_local)))
+        return local, int(n_local[0])
+
+    def LocalPoints(self, table, local, frame_lm, cap=None):
+        """TrackLocalMap::UpdateLocalPoints (:166-184) with the filter at the head of SearchLocalPoints (:55-67).  `table`: see _kf_table; local
+        [n_kf]: the set of LocalKeyFrames; frame_lm: the frame's associations as landmark indices, -1 = null.  Returns (frame_remove uint8
+        [n_assoc], sel int32 [cap], n_sel): sel lists in ascending index the landmarks that are not bad, are observed by a local key frame and are
+        not held by the frame through a good association, padded with -1; n_sel is the full count.  cap=None: room for every landmark."""
+        T, keep = self._kf_table(table)
+        loc = np.ascontiguousarray(local, np.uint8).reshape(-1)
+        flm = np.ascontiguousarray(frame_lm, np.int32).reshape(-1)
+        if len(loc) != T.n_kf:
+            raise ValueError("local must have one entry per key frame")
+        cap = T.L if cap is None else int(cap)
+        rem, sel, n_sel = np.zeros(len(flm), np.uint8), np.zeros(cap, np.int32), np.zeros(1, np.int32)
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_local_points(ex._h, C.byref(T), p(loc), p(flm), len(flm), p(rem), p(sel), cap, p(n_sel)))
+        return rem, sel, int(n_sel[0])
 
 
 class ORBVocabulary:

@@ -1,8 +1,11 @@
-// HipKeyFrameGraph.h — the key-frame graph walks of hySLAM over the C ABI (hs_kf_votes, hs_kf_redundancy, include/hyslam_amd.h):
+// HipKeyFrameGraph.h — the key-frame graph walks of hySLAM over the C ABI (hs_kf_votes, hs_kf_redundancy, hs_local_keyframes, hs_local_points,
+// include/hyslam_amd.h):
 //
 //   updateConnections(pKF)            CovisNode::UpdateConnections (src/core/CovisibilityGraph.cpp:42-124): the counter map, the ordered key frames and
 //                                     weights, and the symmetric updates the CovisGraph applies to the other nodes
 //   localKeyFrameVotes(frame)         the vote of TrackLocalMap::UpdateLocalKeyFrames (src/slam/tracking/TrackLocalMap.cpp:80-123)
+//   localMap(frame, map, params)      TrackLocalMap::UpdateLocalMap and the head of SearchLocalPoints (TrackLocalMap.cpp:43-67,80-184): the local key
+//                                     frames, the local landmarks in the order SearchByProjection gets them, the associations to remove
 //   cullRedundant(pKF, map, params)   KeyFrameCuller::run (src/slam/mapping/KeyFrameCuller.cpp:21-93) with the reference's SEQUENCE
 //
 // The adaptor gathers the observation table (landmark -> (key frame, octave)) from the objects, numbers the key frames by ascending address — the
@@ -44,6 +47,15 @@ public:
         std::vector<int> bad_matches;                  // LMids whose landmark isBad(): the reference calls removeLandMarkAssociation on them (:96)
     };
 
+    struct LocalMap {
+        std::set<KeyFrame*> key_frames;                // local_key_frames after UpdateLocalKeyFrames; empty when nothing was counted (the reference
+                                                       // then returns early and keeps the set of the frame before: the caller does the same)
+        std::vector<MapPoint*> map_points;             // v_lmp handed to SearchByProjection (:74): local_map_points in ascending address
+        std::vector<int> bad_matches;                  // LMids whose landmark isBad(): removeLandMarkAssociation (:62, :96)
+        KeyFrame* max_kf = nullptr;                    // pKFmax
+        int max_count = 0;
+    };
+
     // `handle`: any hs_orb on the device to run on; NULL = the calling thread's handle on hip_detail::default_device().  One thread at a time.
     explicit HipKeyFrameGraph(hs_orb* handle = nullptr) : h(handle) {}
 
@@ -79,6 +91,68 @@ public:
         vote(-1, 1, 1, 0);
         for (int s = 0; s < n_kf; s++) if (weights[s] > 0) out.counter[kfs[s]] = weights[s];
         if (max_slot >= 0) { out.max_kf = kfs[max_slot]; out.max_count = max_count; }
+        return out;
+    }
+
+    // `map`: HYSLAM::Map (GetAllKeyFrames, GetAllMapPoints, getBestCovisibilityKeyFrames); `params`: TrackLocalMapParameters (N_max_local_keyframes,
+    // N_neighbor_keyframes).  The table is the whole map: key frames and landmarks numbered by ascending address, KeyFrame::
+    // GetMapPointMatches read through the landmarks' observations (D12).  Three host-form calls; a caller that keeps the table resident chains the
+    // `_device` forms instead (hs_local_map_search_device).
+    template <class MapT, class Params> LocalMap localMap(Frame& frame, MapT* map, const Params& params) {
+        LocalMap out;
+        const int n_neighbor = params.N_neighbor_keyframes > 0 ? (int)params.N_neighbor_keyframes : 0;
+        std::set<MapPoint*> lm_set;
+        for (MapPoint* pMP : map->GetAllMapPoints()) if (pMP) lm_set.insert(pMP);
+        std::vector<int> lmids;
+        std::vector<MapPoint*> held;
+        const LandMarkMatches& matches = frame.getLandMarkMatches();
+        for (auto it = matches.cbegin(); it != matches.cend(); ++it) { lmids.push_back(it->first); held.push_back(it->second); if (it->second) lm_set.insert(it->second); }
+        const std::vector<MapPoint*> lms(lm_set.begin(), lm_set.end());
+        // every key frame the walk can reach: the map's, the observers, and their neighbours and parents
+        std::set<KeyFrame*> reach;
+        for (KeyFrame* pKF : map->GetAllKeyFrames()) if (pKF) reach.insert(pKF);
+        for (MapPoint* pMP : lms) if (!pMP->isBad()) for (const auto& kv : pMP->GetObservations()) reach.insert(kv.first);
+        std::vector<KeyFrame*> todo(reach.begin(), reach.end());
+        std::map<KeyFrame*, std::vector<KeyFrame*>> best;
+        while (!todo.empty()) {
+            KeyFrame* pKF = todo.back(); todo.pop_back();
+            std::vector<KeyFrame*>& row = best[pKF];
+            row = map->getBestCovisibilityKeyFrames(pKF, n_neighbor);
+            if ((int)row.size() > n_neighbor) row.resize((size_t)n_neighbor);
+            for (KeyFrame* q : row) if (q && reach.insert(q).second) todo.push_back(q);
+            KeyFrame* par = pKF->GetParent();
+            if (par && reach.insert(par).second) todo.push_back(par);
+        }
+        const std::vector<KeyFrame*> also(reach.begin(), reach.end());
+        gather(lms, false, &also);
+        const int n_kf = (int)kfs.size();
+        std::unordered_map<MapPoint*, int32_t> index;
+        for (size_t i = 0; i < lms.size(); i++) index[lms[i]] = (int32_t)i;
+        std::vector<int32_t> frame_lm(held.size(), -1);
+        for (size_t i = 0; i < held.size(); i++) if (held[i]) frame_lm[i] = index.at(held[i]);
+        if (n_kf > 0) {
+            vote(-1, 1, 1, 0, &frame_lm);
+            if (max_slot >= 0) { out.max_kf = kfs[max_slot]; out.max_count = max_count; }
+        } else weights.clear();
+        std::vector<int32_t> neigh((size_t)n_kf * n_neighbor, -1), parent((size_t)n_kf, -1);
+        for (int s = 0; s < n_kf; s++) {
+            const std::vector<KeyFrame*>& row = best[kfs[s]];
+            for (size_t k = 0; k < row.size(); k++) if (row[k]) neigh[(size_t)s * n_neighbor + k] = slot_of.at(row[k]);
+            if (KeyFrame* par = kfs[s]->GetParent()) parent[s] = slot_of.at(par);
+        }
+        std::vector<uint8_t> local((size_t)n_kf, 0), remove(frame_lm.size(), 0);
+        std::vector<int32_t> sel(lms.size(), -1);
+        int32_t n_local = 0, n_sel = 0;
+        const hs_kf_table T = table();
+        hs_orb* use = handle();
+        int st = hs_local_keyframes(use, n_kf, weights.data(), kf_bad.data(), neigh.data(), n_neighbor, parent.data(), (int)params.N_max_local_keyframes,
+                                    n_neighbor, local.data(), &n_local);
+        if (st != HS_OK) fail(use, st);
+        st = hs_local_points(use, &T, local.data(), frame_lm.data(), (int)frame_lm.size(), remove.data(), sel.data(), (int)sel.size(), &n_sel);
+        if (st != HS_OK) fail(use, st);
+        for (int s = 0; s < n_kf; s++) if (local[s]) out.key_frames.insert(kfs[s]);
+        for (int32_t j = 0; j < n_sel; j++) out.map_points.push_back(lms[sel[j]]);
+        for (size_t i = 0; i < remove.size(); i++) if (remove[i]) out.bad_matches.push_back(lmids[i]);
         return out;
     }
 
@@ -177,12 +251,13 @@ private:
         T.lm_bad = lm_bad.data(); T.lm_nobs = lm_nobs.data(); T.kf_bad = kf_bad.data(); T.kf_id = kf_id.data();
         return T;
     }
-    // one query over all gathered landmarks
-    void vote(int64_t self, int count_bad_kf, int th, int cap) {
+    // one query: over all gathered landmarks, or over those `only` lists (-1 entries left out)
+    void vote(int64_t self, int count_bad_kf, int th, int cap, const std::vector<int32_t>* only = nullptr) {
         const int n_kf = (int)kfs.size();
-        const int64_t q_off[2] = {0, (int64_t)n_lms};
-        std::vector<int32_t> q_lm((size_t)n_lms);
-        for (int32_t i = 0; i < n_lms; i++) q_lm[i] = i;
+        std::vector<int32_t> q_lm;
+        if (only) { for (int32_t i : *only) if (i >= 0) q_lm.push_back(i); }
+        else { q_lm.resize((size_t)n_lms); for (int32_t i = 0; i < n_lms; i++) q_lm[i] = i; }
+        const int64_t q_off[2] = {0, (int64_t)q_lm.size()};
         weights.assign((size_t)n_kf, 0); ord_slot.assign((size_t)cap + 1, -1); ord_w.assign((size_t)cap + 1, 0);
         const hs_kf_table T = table();
         hs_orb* use = handle();

@@ -242,9 +242,11 @@ public:
     const LandMarkMatches& getLandMarkMatches() { return matches; }
     std::set<MapPoint*> GetMapPoints() { std::set<MapPoint*> s; for (const auto& kv : matches) if (kv.second) s.insert(kv.second); return s; }                         // the landmarks of `matches` (KeyFrame::GetMapPoints)
     bool isBad() { return mbBad; }
+    KeyFrame* GetParent() { return mpParent; }
     long unsigned int mnId = 0;
     float mThDepth = 0;
     bool mbBad = false;                // test set-up (the reference sets it in Map::SetBadKeyFrame)
+    KeyFrame* mpParent = nullptr;      // test set-up (the reference pushes it down from the spanning tree, KeyFrame::setParent)
     Camera camera;
     DBoW2::FeatureVector mFeatVec;
     float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;

@@ -630,6 +630,85 @@ int  hs_kf_redundancy_device(hs_orb* h, const hs_kf_table* T, int C, const int32
                              const int64_t* d_cand_offsets, const int32_t* d_item_lm, const int32_t* d_item_octave, const float* d_item_depth,
                              int is_mono, int th_obs, float frac_redundant, int32_t* d_n_mps, int32_t* d_n_redundant, uint8_t* d_cull, void* stream);
 
+/* ---- the local map: what TrackLocalMap::track (src/slam/tracking/TrackLocalMap.cpp) does between the vote (hs_kf_votes, count_bad_kf = 1) and the
+ * projection search (hs_search_by_projection): the key-frame expansion of UpdateLocalKeyFrames (:126-156), the landmark selection of
+ * UpdateLocalPoints (:166-184) with the filter at the head of SearchLocalPoints (:55-67), and the gather of the selected hs_landmark records.  Over
+ * the same hs_kf_table, in ARRAY ORDER: key frames are slots 0 .. n_kf-1 and landmarks indices 0 .. L-1, both in ascending
+ * address.  Integer and index work: every output is identical to the reference's.  Each stage has a host form (host pointers, staged through the
+ * handle's scratch, synchronous, arguments checked: HS_ERR_INVALID, no output touched) and a `_device` form (device pointers, enqueued on `stream`
+ * (NULL = the handle's own) without synchronising, nothing checked; its kernels skip a slot or index outside the table).  The `_device` forms take
+ * their temporaries from the caller (`d_work`), not from the handle, so a chain of them never waits for the host.  The handle's
+ * one-stream-at-a-time rule applies (see hs_orb_extract_batch_device). */
+
+/* The expansion (:106-156).  weights [n_kf]: a row of hs_kf_votes with count_bad_kf = 1;  kf_bad [n_kf];  neigh [n_kf][neigh_cap]: each slot's
+ * ordered covisibility list = Map::getBestCovisibilityKeyFrames, i.e. the ordered rows of hs_kf_votes, padded with -1;  parent [n_kf]: GetParent(),
+ * -1 = none.  n_max_local_keyframes, n_neighbor_keyframes: TrackLocalMapParameters (80, 10).  The host form refuses n_neighbor_keyframes > neigh_cap
+ * or < 0, and a neigh / parent entry outside [-1, n_kf).  local [n_kf] u8, n_local [1]: the set and its size.  Literally as the reference:
+ *   the set starts as weights > 0 && !kf_bad (:109-123);
+ *   the reference iterates the std::set while inserting into it: the live set is walked in ascending slot order, a slot inserted above the cursor is
+ *   visited later, one inserted below it never;
+ *   at each visited slot: stop if the size of the set is > n_max (strict, the current size; the int is converted to size_t as C++ does, so a
+ *   negative n_max never stops the walk) (:130); among the first n_neighbor entries of the slot's row insert the first that is not bad and look no
+ *   further in that row (:139-147); if the slot has a parent insert it — bad or not — and END THE WHOLE WALK (the `break` at :153 leaves the
+ *   outer loop);
+ *   nothing counted: the set stays empty.
+ * One wave; the next member is found with a ballot over 64-slot words. */
+int  hs_local_keyframes(hs_orb* h, int n_kf, const int32_t* weights, const uint8_t* kf_bad, const int32_t* neigh, int neigh_cap, const int32_t* parent,
+                        int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* local, int32_t* n_local);
+int  hs_local_keyframes_device(hs_orb* h, int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap,
+                               const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* d_local, int32_t* d_n_local,
+                               void* stream);
+
+/* The landmarks of the local map (:166-184 and :55-67).  Of the table only lm_obs_offsets, lm_obs_kf and lm_bad are read.  local [n_kf]: the set of
+ * hs_local_keyframes.  frame_lm [n_assoc]: the frame's associations (getLandMarkMatches()) as landmark indices, -1 = a null entry.
+ *   frame_remove [n_assoc] u8   1 where the associated landmark is bad: the caller calls removeLandMarkAssociation on it (:62)
+ *   sel [cap] int32, n_sel [1]  in ASCENDING landmark index every landmark that is not bad, has at least one observation by a local key frame, and
+ *                               is not held by the frame through an association that is not bad (the erase at :65).  n_sel always holds the full
+ *                               count; the first min(n_sel, cap) indices are written and the rest of sel is -1.  Truncation is not an error.
+ * A landmark with an empty observation range is never selected.  The reference collects KeyFrame::GetMapPointMatches() of the local key frames; the
+ * table lists the MapPoints' observations.  The two are the same relation as long as associations are symmetric (a key frame holds a landmark
+ * exactly when the landmark lists that key frame as an observer), which Map's association calls maintain.
+ * The compaction is deterministic: counts per block of HS_LOCAL_POINTS_BLOCK landmarks, a scan, a scatter; no atomic counter decides a position.
+ * d_work: hs_local_points_work_bytes(L) bytes of device memory, 16-byte aligned, contents irrelevant before and after. */
+#define HS_LOCAL_POINTS_BLOCK 1024
+size_t hs_local_points_work_bytes(int L);
+int  hs_local_points(hs_orb* h, const hs_kf_table* T, const uint8_t* local, const int32_t* frame_lm, int n_assoc, uint8_t* frame_remove,
+                     int32_t* sel, int cap, int32_t* n_sel);
+int  hs_local_points_device(hs_orb* h, const hs_kf_table* T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
+                            int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, void* stream);
+
+/* d_out[j] = d_lms[d_sel[j]] for j < min(*d_n_sel, cap), with assoc_kp = -1 (no selected landmark is held by the frame) and skip = 0.  The records
+ * j in [*d_n_sel, cap) — and one whose index is outside [0, L) — are all zero but for assoc_kp = -1 and skip = 1, so hs_search_by_projection_device
+ * can be enqueued with L = cap and the host never needs to know n_sel, which is read from device memory.  Exactly cap records are written.  d_lms and
+ * d_out are 16-byte aligned (hipMalloc's are): a record moves as five 16-byte loads and stores.  No host form: the gather has no reference semantics
+ * of its own. */
+int  hs_landmark_gather_device(hs_orb* h, const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out,
+                               void* stream);
+
+/* UpdateLocalMap + SearchLocalPoints in one call: hs_kf_votes_device (one query = frame_lm, count_bad_kf = 1), hs_local_keyframes_device,
+ * hs_local_points_device, hs_landmark_gather_device and hs_search_by_projection_device with L = cap, enqueued on one stream, no synchronisation in
+ * between; the result equals making those five calls one after another (it IS those five calls).  T: the map's table;  d_lms [T->L]: its resident
+ * hs_landmark records (hs_landmark_update_entries_device keeps them current);  F, pp: as hs_search_by_projection_device.  cap >= 1.
+ * Every pointer of `out` is device memory and required: */
+typedef struct hs_local_map_out {
+    int32_t* weights;              /* [n_kf]   keyframeCounter, the bad key frames included                                  */
+    int32_t* max_slot;             /* [1]      pKFmax (the reference key frame), -1 = none                                   */
+    int32_t* max_count;            /* [1]                                                                                    */
+    uint8_t* local;                /* [n_kf]   local_key_frames                                                              */
+    int32_t* n_local;              /* [1]                                                                                    */
+    uint8_t* frame_remove;         /* [n_assoc]                                                                              */
+    int32_t* sel;                  /* [cap]    local_map_points as landmark indices, ascending; -1 past n_sel                */
+    int32_t* n_sel;                /* [1]      the full count (may exceed cap)                                               */
+    hs_landmark* lms;              /* [cap]    the gathered records, 16-byte aligned                                         */
+    int32_t* match_idx;            /* [cap]    keypoint matched by landmark sel[j], or -1                                    */
+    float*   match_dist;           /* [cap]                                                                                  */
+    int32_t* n_matches;            /* [1]                                                                                    */
+} hs_local_map_out;
+size_t hs_local_map_work_bytes(int L);
+int  hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                                const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
+                                const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the

@@ -83,7 +83,9 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    HYSLAM::HipKeyFrameGraph kg; HYSLAM::Map* pmap = nullptr; HYSLAM::KeyFrameCullerParameters kcp;\n"
              "    const HYSLAM::HipKeyFrameGraph::Connections con = kg.updateConnections(pkf); const HYSLAM::HipKeyFrameGraph::Votes vo = kg.localKeyFrameVotes(*pf);\n"
              "    const std::vector<HYSLAM::KeyFrame*> gone = kg.cullRedundant(pkf, pmap, kcp);\n"
-             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size();\n}\n")
+             "    struct { int N_max_local_keyframes = 80; int N_neighbor_keyframes = 10; } tlp;   // TrackLocalMapParameters' two fields (its header needs g2o)\n"
+             "    const HYSLAM::HipKeyFrameGraph::LocalMap lmap = kg.localMap(*pf, pmap, tlp);\n"
+             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size() + (int)lmap.map_points.size();\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
           ["-I" + os.path.join(ROOT, "tests", "cpp", "thirdparty_stubs"), "-I" + host_dir, "-I" + os.path.join(ROOT, "include"), tu]
