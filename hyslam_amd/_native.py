@@ -75,6 +75,27 @@ class LocalMapOut(C.Structure):
                                           "match_dist", "n_matches")]
 
 
+# hs_pose_edge / hs_pose_problem / hs_pose_result (include/hyslam_amd.h): the pose-only optimisation
+POSE_EDGE_DTYPE = np.dtype([("Xw", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4"), ("kp", "<i4")])
+POSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", 16), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4")])
+POSE_RESULT_DTYPE = np.dtype([("Tcw_d", "<f8", 16), ("Tcw", "<f4", 16), ("n_edges", "<i4"), ("n_good", "<i4"), ("rounds", "<i4"),
+                              ("lm_iterations", "<i4"), ("lm_trials", "<i4"), ("status", "<i4")])
+HS_POSE_OK, HS_POSE_TOO_FEW, HS_POSE_NONFINITE = 0, 1, 2
+
+
+class PoseEdge(C.Structure):
+    _fields_ = [("Xw", C.c_float * 3), ("u", C.c_float), ("v", C.c_float), ("ur", C.c_float), ("inv_sigma2", C.c_float), ("kp", C.c_int32)]
+
+
+class PoseProblem(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float)]
+
+
+class PoseResult(C.Structure):
+    _fields_ = [("Tcw_d", C.c_double * 16), ("Tcw", C.c_float * 16), ("n_edges", C.c_int32), ("n_good", C.c_int32), ("rounds", C.c_int32),
+                ("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("status", C.c_int32)]
+
+
 class FrameView(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float),
@@ -125,6 +146,7 @@ EXPORTS = [
     "hs_kf_votes", "hs_kf_votes_device", "hs_kf_redundancy", "hs_kf_redundancy_device",
     "hs_local_keyframes", "hs_local_keyframes_device", "hs_local_points", "hs_local_points_device", "hs_local_points_work_bytes",
     "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
+    "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -264,6 +286,10 @@ def lib():
                                              C.POINTER(ProjParams), C.c_int, C.POINTER(LocalMapOut), vp, vp]
     for f in (L.hs_local_points_work_bytes, L.hs_local_map_work_bytes):
         f.argtypes, f.restype = [C.c_int], C.c_size_t
+    L.hs_pose_optimize.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_pose_optimize_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_pose_work_bytes.argtypes, L.hs_pose_work_bytes.restype = [C.c_int, C.c_int64], C.c_size_t
+    L.hs_pose_edges_device.argtypes = [vp, C.POINTER(FrameView), vp, C.c_int, vp, f32, vp, C.c_int, vp, vp, vp]
     L.hs_bow_vector.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_bow_vector_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.hs_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]

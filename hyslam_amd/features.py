@@ -338,6 +338,22 @@ class ORBExtractor:
                                                               n_max_local_keyframes, n_neighbor_keyframes, C.byref(frame), d_lms, C.byref(proj_params),
                                                               cap, C.byref(out), d_work, stream or None))
 
+    # ---- pose-only optimisation on device-resident data (include/hyslam_amd.h): raw device addresses, asynchronous, nothing checked
+    def pose_work_bytes(self, Q, n_edges_total):
+        return int(self._lib.hs_pose_work_bytes(int(Q), int(n_edges_total)))
+
+    def pose_optimize_device(self, Q, d_problems, d_edges, d_outlier, d_results, d_edge_offsets=None, d_n_edges=None, edge_cap=0, d_work=None, stream=0):
+        """hs_pose_optimize_device: d_problems hs_pose_problem [Q], d_edges hs_pose_edge [..] (16-byte aligned), d_outlier u8 [..], d_results
+        hs_pose_result [Q]; exactly one of d_edge_offsets (int64 [Q + 1]) and d_n_edges (int32 [1], Q == 1, with edge_cap)"""
+        N.check(self._h, self._lib.hs_pose_optimize_device(self._h, Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_outlier, d_results,
+                                                           d_work, stream or None))
+
+    def pose_edges_device(self, frame, d_lms, L, d_kp_lm, d_edges, cap, d_n_edges, sigma_ref=1.0, d_work=None, stream=0):
+        """hs_pose_edges_device: `frame` a _native.FrameView of device pointers (kps, uR, n, size_ref are read); d_lms hs_landmark [L]; d_kp_lm int32
+        [frame.n]; d_edges hs_pose_edge [cap] in ascending keypoint index, d_n_edges int32 [1] the full count"""
+        N.check(self._h, self._lib.hs_pose_edges_device(self._h, C.byref(frame), d_lms, L, d_kp_lm, sigma_ref, d_edges, cap, d_n_edges, d_work,
+                                                        stream or None))
+
     def stereo_match_batch_device(self, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, sp, d_uRight, d_depth, stream=0):
         N.check(self._h, self._lib.hs_stereo_match_batch_device(self._h, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap,
                                                                 C.byref(sp), d_uRight, d_depth, stream or None))
@@ -781,6 +797,64 @@ class FeatureMatcher:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         N.check(ex._h, ex._lib.hs_local_points(ex._h, C.byref(T), p(loc), p(flm), len(flm), p(rem), p(sel), cap, p(n_sel)))
         return rem, sel, int(n_sel[0])
+
+
+class Optimizer:
+    """HYSLAM::Optimizer::PoseOptimization (src/optimizers/Optimizer.cc:48-279) on flat arrays: the frame's pose against the landmarks its keypoints
+    hold, four rounds of Levenberg-Marquardt with outlier classification, computed by one HIP launch (include/hyslam_amd.h)."""
+
+    def __init__(self, extractor=None):
+        self._ex = extractor or ORBExtractor()
+
+    @staticmethod
+    def pose_edges(kps, uR, kp_lm, landmarks, size_ref=31.0, sigma_ref=1.0):
+        """The edge list the reference builds at Optimizer.cc:94-188: one _native.POSE_EDGE_DTYPE record per keypoint i with 0 <= kp_lm[i] <
+        len(landmarks), in ascending i.  kps: KP_DTYPE; uR float32 [n] (< 0: monocular); landmarks: LM_DTYPE records or an (L, 3) position array."""
+        kp_lm = np.asarray(kp_lm, np.int32).reshape(-1)
+        pos = landmarks["pos"] if getattr(landmarks, "dtype", None) is not None and landmarks.dtype.names else np.asarray(landmarks, np.float32).reshape(-1, 3)
+        idx = np.nonzero((kp_lm >= 0) & (kp_lm < len(pos)))[0]
+        e = np.zeros(len(idx), N.POSE_EDGE_DTYPE)
+        e["Xw"], e["u"], e["v"], e["kp"] = pos[kp_lm[idx]], kps["x"][idx], kps["y"][idx], idx
+        e["ur"] = np.asarray(uR, np.float32).reshape(-1)[idx]
+        with np.errstate(all="ignore"):
+            s = kps["size"][idx].astype(np.float32) / np.float32(size_ref)             # determineSigma2, in float as the reference
+            e["inv_sigma2"] = np.float32(1.0) / (np.float32(sigma_ref) * (s * s))
+        return e
+
+    def PoseOptimizationBatch(self, poses, cameras, edge_lists):
+        """Q independent problems in one call.  poses: Q float32 4x4 (pFrame->mTcw); cameras: Q of (fx, fy, cx, cy, bf); edge_lists: Q arrays of
+        POSE_EDGE_DTYPE.  Returns (results POSE_RESULT_DTYPE [Q], outlier uint8 arrays per problem — all zero for a problem with fewer than 3 edges,
+        which is not optimised)."""
+        Q = len(poses)
+        prob = np.zeros(Q, N.POSE_PROBLEM_DTYPE)
+        for q in range(Q):
+            prob["Tcw"][q] = np.asarray(poses[q], np.float32).reshape(16)
+            prob["fx"][q], prob["fy"][q], prob["cx"][q], prob["cy"][q], prob["bf"][q] = [np.float32(c) for c in cameras[q]]
+        lists = [np.ascontiguousarray(e, N.POSE_EDGE_DTYPE).reshape(-1) for e in edge_lists]
+        off = np.zeros(Q + 1, np.int64)
+        off[1:] = np.cumsum([len(e) for e in lists])
+        edges = np.concatenate(lists) if Q else np.zeros(0, N.POSE_EDGE_DTYPE)
+        outlier, res = np.zeros(len(edges), np.uint8), np.zeros(Q, N.POSE_RESULT_DTYPE)
+        ex = self._ex
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_pose_optimize(ex._h, Q, p(prob), p(off), p(edges), p(outlier), p(res)))
+        return res, [outlier[off[q]:off[q + 1]] for q in range(Q)]
+
+    def PoseOptimization(self, frame_pose, camera, edges=None, kps=None, uR=None, kp_lm=None, landmarks=None, size_ref=31.0, sigma_ref=1.0):
+        """int Optimizer::PoseOptimization(Frame*).  frame_pose: pFrame->mTcw (4x4); camera: (fx, fy, cx, cy, bf); either `edges` (POSE_EDGE_DTYPE)
+        or the frame's arrays (kps, uR, kp_lm, landmarks) from which pose_edges gathers them.  Returns (Tcw float32 4x4 — the pose handed to SetPose,
+        the input pose when fewer than 3 keypoints hold a landmark; outlier uint8 per KEYPOINT INDEX — 1 where the reference calls
+        setOutlier(i, true); n_good — the return value)."""
+        if edges is None:
+            edges = self.pose_edges(kps, uR, kp_lm, landmarks, size_ref, sigma_ref)
+            n_kp = len(kps)
+        else:
+            edges = np.ascontiguousarray(edges, N.POSE_EDGE_DTYPE).reshape(-1)
+            n_kp = int(edges["kp"].max()) + 1 if len(edges) else 0
+        res, (flags,) = self.PoseOptimizationBatch([frame_pose], [camera], [edges])
+        outlier = np.zeros(n_kp, np.uint8)
+        outlier[edges["kp"]] = flags
+        return res["Tcw"][0].reshape(4, 4).copy(), outlier, int(res["n_good"][0])
 
 
 class ORBVocabulary:

@@ -138,6 +138,9 @@ public:
     float mb() const { return mbf / K.at<float>(0, 0); }
 };
 
+// src/main/ORBSLAM_datastructs.h:34-45 — the parameter block Optimizer::PoseOptimization takes and does not read
+struct optInfo { bool realtime = false; int GBAinterval = 0; int GBAtype = 0; };
+
 class KeyFrame;
 // src/core/MapPoint.h:54-169 (accessors the matchers call)
 class MapPoint {
@@ -179,6 +182,8 @@ struct LandMarkMatches {
         if (other_view >= 0 && other_view != i) views_to_landmarks.erase(other_view);      // the landmark moves to view i
         return 0;
     }
+    bool isOutlier(int i) const { auto it = outliers.find(i); return it != outliers.end() && it->second; }                       // LandMarkMatches.cpp:90-99
+    int setOutlier(int i, bool is_outlier) { auto it = outliers.find(i); if (it == outliers.end()) return -1; it->second = is_outlier; return 0; }   // :100-110
     using const_iterator = LandMarkMatches_t::const_iterator;
     const_iterator begin() const { return views_to_landmarks.begin(); }
     const_iterator end() const { return views_to_landmarks.end(); }
@@ -202,6 +207,8 @@ public:
     MapPoint* hasAssociation(int i) const { return matches.hasAssociation(i); }
     int hasAssociation(MapPoint* pMP) const { return matches.hasAssociation(pMP); }
     int associateLandMark(int i, MapPoint* pMP, bool replace) { return matches.associateLandMark(i, pMP, replace); }
+    bool isOutlier(int i) const { return matches.isOutlier(i); }                                                                    // Frame.h:138-139
+    int setOutlier(int i, bool is_outlier) { return matches.setOutlier(i, is_outlier); }
     std::vector<MapPoint*> replicatemvpMapPoints() const { std::vector<MapPoint*> v(N, nullptr); for (const auto& kv : matches) if (kv.first < N) v[kv.first] = kv.second; return v; }
     const Camera& getCamera() const { return camera; }
     const FeatureViews& getViews() const { return views; }

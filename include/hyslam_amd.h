@@ -709,6 +709,61 @@ int  hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* 
                                 const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
                                 const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream);
 
+/* ================= pose-only optimisation: Optimizer::PoseOptimization (src/optimizers/Optimizer.cc:48-279) =================
+ * One 6-DoF vertex (the frame's pose), one unary reprojection edge per keypoint that holds a landmark, Huber kernels, g2o's Levenberg-Marquardt
+ * (at most 10 iterations of at most 10 trials) in four rounds; after every round each edge is classified against chi2 5.991 (mono) / 7.815 (stereo),
+ * the next round optimises the inliers only and starts again from the INPUT pose, and the kernels come off after the third round.  DESIGN.md 5.11
+ * lists the behaviour item by item.  A call takes Q independent problems (the cameras of a rig, the candidates of a relocalisation): one launch, one
+ * workgroup per problem.  fp64 but for what the reference computes in float; no floating-point atomics: the same call gives the same bytes.
+ *
+ * hs_pose_edge: what Optimizer.cc:105-187 reads for keypoint `kp`.  ur < 0 makes the monocular edge, anything else (NaN included) the stereo edge.
+ * Arrays of edges are 16-byte aligned (hipMalloc's are; the host form stages them). */
+typedef struct hs_pose_edge {
+    float Xw[3];                       /* pMP->GetWorldPos()                                            */
+    float u, v, ur;                    /* kpUn.pt.x, kpUn.pt.y, views.uR(i)                             */
+    float inv_sigma2;                  /* 1 / orbParams().determineSigma2(kpUn.size), computed in float */
+    int32_t kp;                        /* the keypoint index i; carried, not read                       */
+} hs_pose_edge;                        /* 32 bytes */
+typedef struct hs_pose_problem {
+    float Tcw[16];                     /* pFrame->mTcw, row-major 4x4                                   */
+    float fx, fy, cx, cy, bf;          /* Camera::fx() .. cy(), Camera::mbf                             */
+} hs_pose_problem;
+#define HS_POSE_OK 0                   /* hs_pose_result::status: optimised                                                        */
+#define HS_POSE_TOO_FEW 1              /* fewer than 3 edges: nothing ran (the reference returns 0 and leaves pose and flags alone) */
+#define HS_POSE_NONFINITE 2            /* optimised, and the resulting pose holds a NaN or an infinity                              */
+typedef struct hs_pose_result {
+    double Tcw_d[16];                  /* SE3Quat::to_homogeneous_matrix() of the estimate, row-major                  */
+    float  Tcw[16];                    /* the same converted to float: what Converter::toCvMat hands to SetPose        */
+    int32_t n_edges;                   /* nInitialCorrespondences                                                     */
+    int32_t n_good;                    /* the return value: nInitialCorrespondences - nBad of the last round run       */
+    int32_t rounds;                    /* rounds run: 4, or 1 with fewer than 10 edges, or 0                           */
+    int32_t lm_iterations, lm_trials;  /* calls of OptimizationAlgorithmLevenberg::solve / passes of its trial loop    */
+    int32_t status;                    /* HS_POSE_*                                                                    */
+} hs_pose_result;
+/* Problem q owns edges [edge_offsets[q], edge_offsets[q + 1]) and the same range of `outlier` (u8, 1 = outlier: what the reference passes to
+ * pFrame->setOutlier(kp, ...)).  outlier is written for every edge of a problem that ran and NOT TOUCHED for a problem with fewer than 3 edges; for
+ * such a problem status = HS_POSE_TOO_FEW, n_good = 0 and Tcw / Tcw_d carry the input pose (Tcw_d its floats widened), so the next search of a chain
+ * can always read results[q].Tcw:  Rcw = its upper-left 3x3, tcw = its last column, Ow = -Rcw^T tcw (Frame::UpdatePoseMatrices).
+ * Host form: host pointers, synchronous; edge_offsets must be non-negative and non-decreasing, else HS_ERR_INVALID and no output is touched. */
+int  hs_pose_optimize(hs_orb* h, int Q, const hs_pose_problem* problems, const int64_t* edge_offsets, const hs_pose_edge* edges, uint8_t* outlier,
+                      hs_pose_result* results);
+/* Device pointers, enqueued on `stream` (NULL = the handle's own); nothing that lives on the device is checked (the arguments themselves are: NULL
+ * problems / results, both or neither of the two count sources, d_n_edges with Q != 1, a misaligned d_edges give HS_ERR_INVALID), nothing synchronises.  Exactly one of d_edge_offsets
+ * [Q + 1] and d_n_edges [1] is non-NULL; d_n_edges needs Q == 1 and makes the problem's edges d_edges[0, min(*d_n_edges, edge_cap)) — the count
+ * hs_pose_edges_device left on the device, so the host never needs it (edge_cap is not read with d_edge_offsets).  d_work: hs_pose_work_bytes(Q,
+ * n_edges_total) bytes, which is 0 today: both kernels keep their temporaries in registers and LDS, and d_work may then be NULL.  The parameter is
+ * there so that a chain never waits for the handle's scratch, whatever a later version needs. */
+size_t hs_pose_work_bytes(int Q, int64_t n_edges_total);
+int  hs_pose_optimize_device(hs_orb* h, int Q, const hs_pose_problem* d_problems, const int64_t* d_edge_offsets, const int32_t* d_n_edges, int edge_cap,
+                             const hs_pose_edge* d_edges, uint8_t* d_outlier, hs_pose_result* d_results, void* d_work, void* stream);
+/* The loop at Optimizer.cc:94-188 on resident data: for every keypoint i of F (device pointers; kps, uR and n, size_ref are read; uR == NULL: all
+ * monocular) with 0 <= d_kp_lm[i] < L, in ASCENDING i, one edge: Xw = d_lms[d_kp_lm[i]].pos, u, v = kps[i].x, .y, ur = uR[i], inv_sigma2 =
+ * 1 / (sigma_ref * (kps[i].size / F->size_ref)^2) in float, kp = i.  The compaction is deterministic (one workgroup: a scan per chunk of 1024
+ * keypoints and a running base; no atomic counter decides a position).  d_n_edges [1] receives the full count; only the first min(count, cap)
+ * edges are written and truncation is not an error.  d_work as above. */
+int  hs_pose_edges_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const int32_t* d_kp_lm, float sigma_ref,
+                          hs_pose_edge* d_edges, int cap, int32_t* d_n_edges, void* d_work, void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the
