@@ -4,6 +4,7 @@
   - the analytic Jacobians agree with central differences of the restated error function under exp(dx) * T
   - a problem whose residuals are exactly zero keeps every inlier and returns the quaternion round trip of its input pose, bit for bit
   - round 3 (no kernel, fixed inlier set) ends where scipy's Levenberg-Marquardt ends, within a bound made of both solvers' final gradients
+  - Quat.from_matrix off its trace branch takes the branch Eigen's rule names and agrees with scipy's quaternion, at and near 180 degrees
   - every case qualifies, the directed cases take the paths they are named after, and tests/golden/poseopt_cases.npz is what the generators give
 """
 import math
@@ -25,7 +26,7 @@ def same(a, b):
 
 
 @pytest.mark.parametrize("name", ["n3", "n9", "n10", "n65", "n257", "mono_out30", "stereo_out15", "mixed_out15", "all_outliers_round", "inlier_again",
-                                  "ten_rejections"])
+                                  "ten_rejections"] + list(P.ADDED))
 def test_literal_equals_fast(name):
     c = P.case(name)
     same(R.pose_optimization_literal(c["T"], c["cam"], c["edges"]), c["ref"])
@@ -49,7 +50,17 @@ def test_jacobians_against_central_differences(stereo):
     h^2 |J| (the derivatives of a projection grow like J itself for these depths) plus the rounding of a ~1e3 px value, 1e3 * 2^-52 / h.  The stereo
     error goes through a float invz, which moves a projected coordinate by up to 2^-24 of its value (<= 1280 px): the rounding term becomes
     1280 * 2^-24 / h, and h = 1e-2 balances it against the truncation term."""
-    c = P.case("mixed_out0")
+    _jacobians_against_central_differences("mixed_out0", stereo)
+
+
+@pytest.mark.parametrize("stereo", [False, True])
+def test_jacobians_with_an_anisotropic_camera(stereo):
+    """the same with fx = 700, fy = 520: a focal length taken from the other axis is off by a quarter of the entry, far above the bound"""
+    _jacobians_against_central_differences("fxfy_stereo" if stereo else "fxfy_mono", stereo)
+
+
+def _jacobians_against_central_differences(name, stereo):
+    c = P.case(name)
     T = R.se3_from_pose(c["T"])
     cam = [float(v) for v in c["cam"]]
     h = 1e-2 if stereo else 1e-5
@@ -75,24 +86,44 @@ def test_jacobians_against_central_differences(stereo):
     assert checked >= 10
 
 
-def _exact_problem():
-    """identity pose, depths that are powers of two, coordinates with few bits: every projection is exact in float, every residual exactly zero"""
-    fx, fy, cx, cy, bf = P.CAM
-    rng = np.random.default_rng(5)
-    n = 24
-    z = 2.0 ** rng.integers(1, 5, n)
-    x, y = rng.integers(-12, 13, n) * 0.125, rng.integers(-8, 9, n) * 0.125
-    e = np.zeros(n, R.EDGE_DTYPE)
-    e["Xw"] = np.stack([x, y, z], 1)
-    e["u"], e["v"] = x / z * fx + cx, y / z * fy + cy
-    e["ur"] = np.where(np.arange(n) % 3 == 0, -1.0, x / z * fx + cx - bf / z)
-    e["inv_sigma2"], e["kp"] = 1.0, np.arange(n)
-    assert np.array_equal(e["u"].astype(np.float64), x / z * fx + cx) and (e["ur"][np.arange(n) % 3 != 0] >= 0).all()
-    return np.eye(4, dtype=np.float32), np.array(P.CAM, np.float32), e
+def _quat_sweep():
+    """rotations with trace <= 0: the exact half turns about the axes, the face diagonals and the space diagonal (their diagonal entries tie), and
+    seeded rotations of 121 .. 180 degrees about random axes"""
+    out = []
+    for k in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1), (1, 1, 1)):
+        k = np.array(k, np.float64) / math.sqrt(sum(k))
+        out.append(2.0 * np.outer(k, k) - np.eye(3))
+    rng = np.random.default_rng(77)
+    for _ in range(600):
+        k = rng.normal(0, 1, 3)
+        out.append(P._rot(k / np.linalg.norm(k) * np.deg2rad(rng.uniform(121.0, 180.0))))
+    return out
+
+
+def test_quaternion_of_a_matrix_off_the_trace_branch():
+    """Quat.from_matrix on the sweep: the branch is the one P.quat_branch (Eigen's rule: trace <= 0, then m11 > m00, then m22 > max) predicts — the
+    component the branch sets directly is 0.5 sqrt(m_ii - m_jj - m_kk + 1) bit for bit —, the quaternion is scipy's up to sign, and matrix() gives
+    the rotation back.  Measured over the sweep: 2.2e-16 against scipy, 1.0e-15 round trip; the bound is four times the larger, 4e-15.  A wrong sign or permutation misses by order 1."""
+    from scipy.spatial.transform import Rotation
+    taken, worst_q, worst_m = [0, 0, 0], 0.0, 0.0
+    for m in _quat_sweep():
+        assert np.trace(m) <= 0.0
+        i = P.quat_branch(m.tolist())
+        j, k = (i + 1) % 3, (i + 2) % 3
+        q = R.Quat.from_matrix(m.tolist())
+        v = [q.x, q.y, q.z]
+        assert v[i] == 0.5 * math.sqrt(m[i, i] - m[j, j] - m[k, k] + 1.0) and m[i, i] >= m[j, j] and m[i, i] >= m[k, k]
+        taken[i] += 1
+        mine, theirs = np.array(v + [q.w]), Rotation.from_matrix(m).as_quat()
+        worst_q = max(worst_q, min(np.abs(mine - theirs).max(), np.abs(mine + theirs).max()))
+        worst_m = max(worst_m, np.abs(np.array(q.matrix()) - m).max())
+    print("branches taken %s; worst against scipy %.3e, worst round trip %.3e" % (taken, worst_q, worst_m))
+    assert min(taken) >= 100
+    assert worst_q <= 4e-15 and worst_m <= 4e-15
 
 
 def test_zero_residuals_leave_the_round_trip_of_the_input():
-    T, cam, e = _exact_problem()
+    T, cam, e = P.exact_problem()
     for fn in (R.pose_optimization_literal, R.pose_optimization_fast):
         r = fn(T, cam, e)
         assert r["n_good"] == len(e) and not r["outlier"].any() and r["rounds"] == 4
@@ -116,7 +147,7 @@ def _local_delta(Ta, Tb):
     return np.array([(M[2, 1] - M[1, 2]) / 2, (M[0, 2] - M[2, 0]) / 2, (M[1, 0] - M[0, 1]) / 2, M[0, 3], M[1, 3], M[2, 3]])
 
 
-@pytest.mark.parametrize("name", ["mono_out15", "mixed_out15"])
+@pytest.mark.parametrize("name", ["mono_out15", "mixed_out15", "fxfy_mono", "rot_i1"])
 def test_round_three_against_scipy_lm(name):
     """Round 3 minimises sum chi2 over the inliers of round 2 from the input pose, without a kernel.  scipy's MINPACK Levenberg-Marquardt minimises the
     same residuals sqrt(w) e over x with estimate = exp(x) * input.  Two points with gradients g1, g2 of a function whose Hessian is at least
@@ -185,6 +216,87 @@ def test_directed_cases_take_their_paths():
     r = P.case("inlier_again")["ref"]
     assert ((r["round_flags"][0] == 1) & (r["outlier"] == 0)).any()
     assert P.case("ten_rejections")["ref"]["max_trials"] == 10
+    # the start pose's rotation leaves Quat.from_matrix by the branch the case is named after; the camera of these cases has fx != fy
+    for tag, lo, hi in (("rot", -1.0, -0.9), ("rot_125", -0.3, 0.0)):
+        for i in range(3):
+            c = P.case("%s_i%d" % (tag, i))
+            m = c["T"].astype(np.float64)[:3, :3]
+            assert lo <= np.trace(m) <= hi and P.quat_branch(m) == i and m[i, i] > max(m[j, j] for j in range(3) if j != i)
+            assert tuple(c["cam"]) == tuple(np.float32(P.CAM_ANISO)) and c["ref"]["rounds"] == 4
+    m = P.case("rot_tie")["T"].astype(np.float64)[:3, :3]
+    assert np.trace(m) <= 0 and abs(m[0, 0] - m[1, 1]) <= 1e-3 and m[2, 2] < -0.99 and P.quat_branch(m) in (0, 1)
+    for name in ("fxfy_mono", "fxfy_stereo", "behind_camera"):
+        assert tuple(P.case(name)["cam"]) == tuple(np.float32(P.CAM_ANISO))
+    # every factorisation fails (H = 0, lambda = 0, the first pivot 0 <= 0): the step is the last dx = 0, temp = DBL_MAX, ten rejections an iteration
+    c = P.case("zero_information")
+    r, n = c["ref"], len(c["edges"])
+    assert n == 40 and not c["edges"]["inv_sigma2"].any()
+    assert (r["rounds"], r["lm_iterations"], r["lm_trials"], r["n_good"], r["max_trials"]) == (4, 4, 40, n, 10) and not r["round_flags"].any()
+    assert r["Tcw_d"].tobytes() == R.se3_from_pose(c["T"]).matrix().tobytes()
+    c = P.case("some_zero_information")
+    r, zero = c["ref"], c["aux"]["zero"]
+    assert np.array_equal(np.nonzero(c["edges"]["inv_sigma2"] == 0)[0], zero) and len(zero) == 40
+    assert not r["outlier"][zero].any() and len(np.intersect1d(zero, c["aux"]["bad"])) > 0 and r["outlier"].any()
+    # zero residuals: chi = 0, dx = 0, rho = 0 / 1e-3 = 0 — rejected, and the iteration is the last (the other half of D14)
+    c = P.case("exact_zero")
+    r = c["ref"]
+    assert c["edges"].tobytes() == P.exact_problem()[2].tobytes()
+    assert (r["rounds"], r["lm_iterations"], r["lm_trials"], r["n_good"]) == (4, 4, 4, len(c["edges"])) and not r["round_flags"].any()
+    # points behind the camera: no depth test, so a consistent observation is an inlier with invz < 0
+    c = P.case("behind_camera")
+    r, mirrored = c["ref"], c["aux"]
+    z = c["edges"]["Xw"].astype(np.float64) @ r["Tcw_d"][2, :3] + r["Tcw_d"][2, 3]
+    assert len(mirrored) == 24 and (z[mirrored] < 0).all() and (np.delete(z, mirrored) > 0).all()
+    assert (r["outlier"][mirrored] == 0).any() and (r["outlier"][mirrored] == 1).any()
+    print("behind_camera: %d of %d mirrored edges are inliers" % (int((r["outlier"][mirrored] == 0).sum()), len(mirrored)))
+    # ur = +0.0f and -0.0f are stereo by !(ur < 0)
+    c = P.case("ur_zero")
+    ur = c["edges"]["ur"][c["aux"]]
+    assert len(ur) == 2 * P.N_SIGNED_ZERO and (ur == 0).all() and int(np.signbit(ur).sum()) == P.N_SIGNED_ZERO
+    lit = R._Literal(c["cam"], c["edges"])
+    assert all(lit.stereo[i] for i in c["aux"]) and R._Fast(c["cam"], c["edges"]).stereo[c["aux"]].all()
+    assert (c["ref"]["outlier"][c["aux"]] == 0).any()             # ... and fit as stereo edges: read as mono they would leave a pose that rejects none
+    for name in P.DIRECTED:
+        assert name in P.SPECS
+
+
+def test_chain_problem_qualifies_and_is_what_the_gather_gives():
+    """the 2049-keypoint frame of the GPU chain test: its edge list qualifies like a case (margin, flags under 8 orders, spread within SPREAD_CAP),
+    and gathering from its arrays gives that list back"""
+    c = P.chain_problem()
+    q = P.qualify(c["T"], c["cam"], c["edges"], spread_cap=P.SPREAD_CAP)
+    assert q is not None and q[0]["rounds"] == 4 and 0 < q[0]["n_good"] < P.CHAIN_N
+    got, count = R.gather_edges(c["kps"], c["uR"], c["kp_lm"], c["lm_pos"])
+    assert count == P.CHAIN_N and got.tobytes() == c["edges"].tobytes()
+    assert (c["uR"] < 0).any() and (c["uR"] >= 0).any()
+
+
+def test_reference_gather_equals_the_python_gather():
+    """ref_poseopt.gather_edges against Optimizer.pose_edges on every synthetic frame the GPU test gives hs_pose_edges_device, with another size_ref
+    and sigma_ref, a keypoint of infinite size (weight 0), no keypoint and no landmark.  Two statements of one loop: the same bytes."""
+    from hyslam_amd.features import Optimizer
+    frames = [P.edge_frame(n, v) for n in P.EDGE_FRAME_SIZES for v in P.EDGE_FRAME_VARIANTS]
+    f = P.edge_frame(2049, "sparse")
+    f["kps"]["size"][P.EDGE_CHUNK] = np.inf
+    frames.append(f)
+    frames.append({k: v[:0] if k != "lm_pos" else v for k, v in P.edge_frame(1023, "all").items()})     # F.n = 0
+    frames.append(dict(P.edge_frame(1025, "all"), lm_pos=np.zeros((0, 3), np.float32)))                   # L = 0
+    counts = []
+    for f in frames:
+        for size_ref, sigma_ref in ((31.0, 1.0), (24.5, 1.7)):
+            want, count = R.gather_edges(f["kps"], f["uR"], f["kp_lm"], f["lm_pos"], size_ref=size_ref, sigma_ref=sigma_ref)
+            got = Optimizer.pose_edges(f["kps"], f["uR"], f["kp_lm"], f["lm_pos"], size_ref=size_ref, sigma_ref=sigma_ref)
+            assert count == len(want) == len(got) and want.tobytes() == got.tobytes()
+            assert np.array_equal(want["kp"], np.nonzero((f["kp_lm"] >= 0) & (f["kp_lm"] < len(f["lm_pos"])))[0])
+        counts.append(count)
+    assert counts[-2:] == [0, 0] and 0 in counts[:-2] and 3000 in counts
+    f = frames[-3]
+    e, _ = R.gather_edges(f["kps"], f["uR"], f["kp_lm"], f["lm_pos"])
+    assert e["inv_sigma2"][e["kp"] == P.EDGE_CHUNK].tobytes() == np.float32(0.0).tobytes()
+    # sigma_ref * (s * s), not (sigma_ref * s) * s: with sigma_ref = 1.7 the two differ in the last bit on some size
+    s = f["kps"]["size"][e["kp"]] / np.float32(24.5)
+    a, b = np.float32(1.0) / (np.float32(1.7) * (s * s)), np.float32(1.0) / ((np.float32(1.7) * s) * s)
+    assert (a[np.isfinite(s)] != b[np.isfinite(s)]).any()
 
 
 def test_errors_belong_to_the_last_evaluated_estimate():
