@@ -96,6 +96,50 @@ class PoseResult(C.Structure):
                 ("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("status", C.c_int32)]
 
 
+# hs_pose_view / hs_track_* (include/hyslam_amd.h): frame tracking on resident tables
+POSE_VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), ("_pad", "<f4")])
+TRACK_RESULT_DTYPE = np.dtype([("status", "<i4"), ("used_wide", "<i4"), ("n_narrow", "<i4"), ("n_wide", "<i4"), ("n_matches_map", "<i4"), ("n_inliers", "<i4"),
+                               ("_pad", "<i4", 2)])
+HS_TRACK_MOTION, HS_TRACK_LOCAL = 0, 1
+HS_TRACK_OK, HS_TRACK_MOTION_FAILED = 0, 1
+
+
+class TrackParams(C.Structure):
+    _fields_ = [("th_motion", C.c_float), ("th_motion_wide", C.c_float), ("n_min_matches", C.c_int32), ("th_local", C.c_float), ("nnratio_motion", C.c_float),
+                ("nnratio_local", C.c_float), ("th_high", C.c_float), ("sigma_ref", C.c_float), ("n_max_local_keyframes", C.c_int32),
+                ("n_neighbor_keyframes", C.c_int32)]
+
+    def __init__(self, th_motion=15.0, th_motion_wide=30.0, n_min_matches=20, th_local=3.0, nnratio_motion=0.9, nnratio_local=0.8, th_high=100.0, sigma_ref=1.0,
+                 n_max_local_keyframes=80, n_neighbor_keyframes=10):
+        super().__init__(th_motion, th_motion_wide, n_min_matches, th_local, nnratio_motion, nnratio_local, th_high, sigma_ref, n_max_local_keyframes,
+                         n_neighbor_keyframes)
+
+
+class TrackState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("kp_lm", "kp_outl", "n_matches", "kp_lm_obs")]
+
+
+# the device outputs of the hs_track_* calls: (field, element dtype or None for a record type, count as a size name or a number)
+TRACK_OUT_HEAD = (("pose_view", "pose_view", 2), ("problem", "problem", 2), ("last_lms", "lm", "n_last"), ("narrow_idx", np.int32, "n_last"),
+                  ("narrow_dist", np.float32, "n_last"), ("narrow_n", np.int32, 1), ("wide_idx", np.int32, "n_last"), ("wide_dist", np.float32, "n_last"),
+                  ("wide_n", np.int32, 1), ("op_view", np.int32, "n_last"), ("edges_motion", "edge", "n"), ("outlier_motion", np.uint8, "n"),
+                  ("n_edges_motion", np.int32, 2), ("pose_motion", "result", 1))
+TRACK_OUT_TAIL = (("edges_local", "edge", "n"), ("outlier_local", np.uint8, "n"), ("n_edges_local", np.int32, 1), ("pose_local", "result", 1),
+                  ("result", "track_result", 1))
+LOCAL_MAP_OUT_SPEC = (("weights", np.int32, "n_kf"), ("max_slot", np.int32, 1), ("max_count", np.int32, 1), ("local", np.uint8, "n_kf"), ("n_local", np.int32, 1),
+                      ("frame_remove", np.uint8, "n"), ("sel", np.int32, "cap"), ("n_sel", np.int32, 1), ("lms", "lm", "cap"), ("match_idx", np.int32, "cap"),
+                      ("match_dist", np.float32, "cap"), ("n_matches", np.int32, 1))
+
+
+class TrackOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k, _, _ in TRACK_OUT_HEAD] + [("local", LocalMapOut)] + [(k, C.c_void_p) for k, _, _ in TRACK_OUT_TAIL])
+
+
+def track_out_dtype(kind):
+    return {"pose_view": POSE_VIEW_DTYPE, "problem": POSE_PROBLEM_DTYPE, "lm": LM_DTYPE, "edge": POSE_EDGE_DTYPE, "result": POSE_RESULT_DTYPE,
+            "track_result": TRACK_RESULT_DTYPE}[kind] if isinstance(kind, str) else np.dtype(kind)
+
+
 class FrameView(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float),
@@ -147,6 +191,8 @@ EXPORTS = [
     "hs_local_keyframes", "hs_local_keyframes_device", "hs_local_points", "hs_local_points_device", "hs_local_points_work_bytes",
     "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
+    "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
+    "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device", "hs_device_alloc", "hs_device_free", "hs_device_copy",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -290,6 +336,21 @@ def lib():
     L.hs_pose_optimize_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.hs_pose_work_bytes.argtypes, L.hs_pose_work_bytes.restype = [C.c_int, C.c_int64], C.c_size_t
     L.hs_pose_edges_device.argtypes = [vp, C.POINTER(FrameView), vp, C.c_int, vp, f32, vp, C.c_int, vp, vp, vp]
+    L.hs_pose_views_device.argtypes = [vp, vp, vp, vp]
+    L.hs_search_by_projection_posed_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, C.c_int, C.POINTER(ProjParams), vp, vp, vp, vp]
+    L.hs_local_map_search_posed_device.argtypes = [vp, C.POINTER(KfTable), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameView), vp, vp,
+                                                   C.POINTER(ProjParams), C.c_int, C.POINTER(LocalMapOut), vp, vp]
+    L.hs_track_work_bytes.argtypes, L.hs_track_work_bytes.restype = [C.c_int] * 4, C.c_size_t
+    L.hs_frame_associate_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.hs_frame_views_device.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(KfTable), C.c_int, vp, vp]
+    L.hs_track_discard_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, C.POINTER(KfTable), C.c_int, vp, vp, vp, vp, vp]
+    tail = [C.POINTER(TrackParams), C.POINTER(TrackState), C.POINTER(TrackOut), vp, vp]
+    L.hs_track_motion_model_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, vp, C.c_int, C.POINTER(KfTable), vp] + tail
+    L.hs_track_local_map_device.argtypes = [vp, C.POINTER(FrameView), vp, C.POINTER(KfTable), vp, vp, C.c_int, vp, C.c_int] + tail
+    L.hs_track_frame_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, vp, C.c_int, C.POINTER(KfTable), vp, vp, C.c_int, vp, C.c_int] + tail
+    L.hs_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
+    L.hs_device_free.argtypes = [vp, vp]
+    L.hs_device_copy.argtypes = [vp, vp, vp, sz, C.c_int, vp]
     L.hs_bow_vector.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hs_bow_vector_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.hs_place_db_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]

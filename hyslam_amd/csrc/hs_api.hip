@@ -1405,8 +1405,26 @@ int hs_frame_grid(hs_orb* h, const hs_frame_view* F, int8_t* cell_xy)
     return st.finish();
 }
 
+namespace {
+int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
+                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream);
+}
 int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
                                    int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
+{
+    return search_by_projection_device(h, F, nullptr, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, stream);
+}
+// the pose from device memory (hs_pose_views_device): F's Rcw / tcw / Ow are not read
+int hs_search_by_projection_posed_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
+                                         int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!d_pose) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    return search_by_projection_device(h, F, d_pose, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, stream);
+}
+namespace {
+int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
+                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
     if (!F || !pp || L < 1 || !d_lms || !d_match_idx || !d_match_dist || !d_n_matches || F->n < 1 || F->n > 65535 || !F->kps || !F->desc ||
@@ -1422,10 +1440,11 @@ int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_l
     if (rc != HS_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
-    hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s);
+    hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s, d_pose);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
+}  // namespace
 
 namespace {
 // one row of A*B (+c): double accumulation, alpha in double, one rounding (cv::gemm on float matrices)

@@ -268,7 +268,7 @@ void hs_launch_frame_grid(const hs_frame_view& F, const hs_keypoint* d_kps, int8
 void hs_launch_search_projection(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR,
                                  const int32_t* d_obs, const int8_t* d_cell, const hs_landmark* d_lms, int L, const hs_proj_params& pp,
                                  int32_t* d_match_idx, float* d_match_dist, int32_t* d_winner, float* d_prev_angle_scratch,
-                                 int32_t* d_n_matches, hipStream_t s);
+                                 int32_t* d_n_matches, hipStream_t s, const hs_pose_view* d_pose = nullptr /*device: read the pose from it, not from F*/);
 void hs_launch_bow(const int32_t* d_pair_a, const int32_t* d_pair_b, int n_pairs,
                    const int32_t* d_ptr1, const int32_t* d_idx1, const int32_t* d_ptr2, const int32_t* d_idx2,
                    const uint8_t* d_desc1, const uint8_t* d_desc2, const uint8_t* d_keep1, const uint8_t* d_keep2,

@@ -101,9 +101,36 @@ int hs_landmark_gather_device(hs_orb* h, const hs_landmark* d_lms, int L, const 
     return HS_OK;
 }
 
+namespace {
+int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
+                     const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream);
+}
 int hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
                                const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
                                const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
+{
+    return local_map_search(h, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, nullptr, d_lms, pp, cap, out,
+                            d_work, stream);
+}
+// the search reads the pose from device memory (hs_search_by_projection_posed_device)
+int hs_local_map_search_posed_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
+                                     const hs_pose_view* d_pose, const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out,
+                                     void* d_work, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!d_pose) return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    return local_map_search(h, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, d_pose, d_lms, pp, cap, out,
+                            d_work, stream);
+}
+
+}  // extern "C"
+
+namespace {
+int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
+                     const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
     if (!T || !out || !d_work || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
@@ -125,7 +152,7 @@ int hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d
     if (rc != HS_OK) return rc;
     rc = hs_landmark_gather_device(h, d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
     if (rc != HS_OK) return rc;
+    if (d_pose) return hs_search_by_projection_posed_device(h, F, d_pose, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
     return hs_search_by_projection_device(h, F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
 }
-
-}  // extern "C"
+}  // namespace

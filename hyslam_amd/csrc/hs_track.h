@@ -1,0 +1,20 @@
+// hs_track.h — frame tracking on resident tables (TrackMotionModel::track, TrackLocalMap::track): launchers of kernels_track.hip for the entry
+// points in hs_track.hip (include/hyslam_amd.h).  All asynchronous on `s`; every pointer is device memory unless said otherwise.
+#pragma once
+#include "hs_internal.h"
+
+#define HS_TRACK_BLOCK 256         // threads per workgroup of the per-view / per-op kernels
+
+// d_problem (may be nullptr): the optimiser's hs_pose_problem = the pose with F's camera (F: host struct, only fx .. mbf are read)
+void hs_launch_pose_view(const float* d_Tcw, hs_pose_view* d_out, hs_pose_problem* d_problem, const hs_frame_view* F, hipStream_t s);
+size_t hs_assoc_work_bytes(int n, int L);      // minw, maxw, erased [n] and jk [L], int32
+void hs_launch_frame_associate(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int n_ops, const int32_t* d_op_view, const int32_t* d_op_lm,
+                               void* d_work, hipStream_t s);
+void hs_launch_frame_views(int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const hs_kf_table& T, int drop_bad, int32_t* d_kp_lm_obs, hipStream_t s);
+void hs_launch_track_discard(int mode, const hs_pose_edge* d_edges, const int32_t* d_n_edges, int edge_cap, const uint8_t* d_outlier, const hs_pose_result* d_result,
+                             const hs_kf_table& T, int sensor, int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int32_t* d_counts, hipStream_t s);
+void hs_launch_last_gather(const hs_landmark* d_lms, int L, const int32_t* d_last_kp_lm, const hs_keypoint* d_last_kps, int n_last, hs_landmark* d_out, hipStream_t s);
+void hs_launch_track_clear(int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int32_t* d_kp_lm_obs, hipStream_t s);
+void hs_launch_track_select(int n_last, const int32_t* d_narrow_idx, const int32_t* d_narrow_n, const int32_t* d_wide_idx, const int32_t* d_wide_n, int n_min_matches,
+                            int32_t* d_op_view, hs_track_result* d_result, hipStream_t s);
+void hs_launch_track_gate(const hs_track_result* d_result, int32_t* d_n_edges /*[2]: [1] = failed ? 0 : [0]*/, hipStream_t s);

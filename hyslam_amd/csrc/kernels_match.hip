@@ -138,8 +138,9 @@ __global__ __launch_bounds__(1024) void k_first_wins(int n, int32_t* __restrict_
     if (tid == 0) *n_out = total;
 }
 
-__global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const hs_landmark* __restrict__ lms, int L, HsProjDev pp,
-                                                           int32_t* __restrict__ match_idx, float* __restrict__ match_dist)
+// the search of one landmark by one wavefront: the body of both kernels below
+__device__ __forceinline__ void search_projection_wave(const HsFrameDev F, const hs_landmark* __restrict__ lms, int L, const HsProjDev pp,
+                                                       int32_t* __restrict__ match_idx, float* __restrict__ match_dist)
 {
     const int lane = threadIdx.x & 63;
     const int li = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wave index: uniform
@@ -220,6 +221,24 @@ __global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const h
         }
     }
     if (lane == 0) { match_idx[li] = out_idx; match_dist[li] = out_dist; }
+}
+
+__global__ __launch_bounds__(256) void k_search_projection(HsFrameDev F, const hs_landmark* __restrict__ lms, int L, HsProjDev pp,
+                                                           int32_t* __restrict__ match_idx, float* __restrict__ match_dist)
+{
+    search_projection_wave(F, lms, L, pp, match_idx, match_dist);
+}
+
+// the same with the pose taken from device memory (hs_pose_view: what hs_pose_views_device derives from a pose that a kernel left in HBM); F's own
+// Rcw / tcw / Ow are ignored.  The 15 floats are wave-uniform loads, once per wave.
+__global__ __launch_bounds__(256) void k_search_projection_posed(HsFrameDev F, const hs_pose_view* __restrict__ pose, const hs_landmark* __restrict__ lms, int L,
+                                                                 HsProjDev pp, int32_t* __restrict__ match_idx, float* __restrict__ match_dist)
+{
+#pragma unroll
+    for (int i = 0; i < 9; i++) F.Rcw[i] = pose->Rcw[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { F.tcw[i] = pose->tcw[i]; F.Ow[i] = pose->Ow[i]; }
+    search_projection_wave(F, lms, L, pp, match_idx, match_dist);
 }
 
 // RotationConsistency on a match list a[i] -> b: keep only pairs whose rotation bin is one of the three most populated.
@@ -564,11 +583,12 @@ static HsFrameDev frame_dev(const hs_frame_view& F, const hs_keypoint* d_kps, co
 void hs_launch_search_projection(const hs_frame_view& F, const hs_keypoint* d_kps, const uint8_t* d_desc, const float* d_uR,
                                  const int32_t* d_obs, const int8_t* d_cell, const hs_landmark* d_lms, int L, const hs_proj_params& pp,
                                  int32_t* d_match_idx, float* d_match_dist, int32_t* d_winner, float* d_prev_angle_scratch,
-                                 int32_t* d_n_matches, hipStream_t s)
+                                 int32_t* d_n_matches, hipStream_t s, const hs_pose_view* d_pose)
 {
     const HsFrameDev D = frame_dev(F, d_kps, d_desc, d_uR, d_obs, d_cell);
     HsProjDev P; static_cast<hs_proj_params&>(P) = pp; P.cos_view_angle = cosf(pp.max_view_angle);
-    hipLaunchKernelGGL(k_search_projection, dim3((L + 3) / 4), dim3(256), 0, s, D, d_lms, L, P, d_match_idx, d_match_dist);
+    if (d_pose) hipLaunchKernelGGL(k_search_projection_posed, dim3((L + 3) / 4), dim3(256), 0, s, D, d_pose, d_lms, L, P, d_match_idx, d_match_dist);
+    else hipLaunchKernelGGL(k_search_projection, dim3((L + 3) / 4), dim3(256), 0, s, D, d_lms, L, P, d_match_idx, d_match_dist);
     if (pp.first_wins) {
         hipLaunchKernelGGL(k_first_wins, dim3(1), dim3(1024), 0, s, L, d_match_idx, d_winner, F.n, d_n_matches);
     } else if (pp.check_rotation) {

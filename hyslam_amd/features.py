@@ -857,6 +857,209 @@ class Optimizer:
         return res["Tcw"][0].reshape(4, 4).copy(), outlier, int(res["n_good"][0])
 
 
+class _DevBuf:
+    """a block of device memory on the extractor's device for FrameTracker's numpy calls (hs_device_alloc / hs_device_copy / hs_device_free)"""
+
+    def __init__(self, ex, nbytes, src=None):
+        self._ex, self.ptr, self.nbytes = ex, 0, int(max(nbytes, 16))
+        p = C.c_void_p()
+        N.check(ex._h, ex._lib.hs_device_alloc(ex._h, self.nbytes, C.byref(p)))
+        self.ptr = p.value
+        if src is not None:
+            self.write(src)
+
+    def write(self, src):
+        src = np.ascontiguousarray(src)
+        if src.nbytes > self.nbytes:
+            raise ValueError("the array is larger than the device block")
+        N.check(self._ex._h, self._ex._lib.hs_device_copy(self._ex._h, self.ptr, src.ctypes.data, src.nbytes, 1, None))
+
+    def read(self, dtype, count, offset=0):
+        out = np.empty(count, dtype)
+        N.check(self._ex._h, self._ex._lib.hs_device_copy(self._ex._h, out.ctypes.data, self.ptr + offset, out.nbytes, 2, None))
+        return out
+
+    def free(self):
+        if self.ptr:
+            ptr, self.ptr = self.ptr, 0
+            N.check(self._ex._h, self._ex._lib.hs_device_free(self._ex._h, ptr))
+
+    def __del__(self):
+        try:
+            if self._ex._h.value:                                # an extractor that was closed first took its device context along
+                self.free()
+        except Exception:                                        # interpreter shutdown: nothing left to report to
+            pass
+
+
+class FrameTracker:
+    """TrackMotionModel::track and TrackLocalMap::track (src/slam/tracking/) on resident tables: every stage — pose matrices, projection searches,
+    the association replay, the edge list, the pose optimisation, the outlier removal — is enqueued on one stream and nothing comes back to the host
+    in between (include/hyslam_amd.h, "frame tracking on resident tables").  The numpy methods upload their inputs, run the device
+    chain, synchronise once and return the frame's associations, both poses and the counts; the `*_device` methods are the raw pass-throughs.
+    Landmarks and key frames are indices in ascending address order."""
+
+    def __init__(self, extractor=None):
+        self._ex = extractor or ORBExtractor()
+
+    # ---- raw device addresses, asynchronous, nothing checked
+    def track_work_bytes(self, n, n_last, L, cap):
+        return int(self._ex._lib.hs_track_work_bytes(int(n), int(n_last), int(L), int(cap)))
+
+    def pose_views_device(self, d_Tcw, d_out, stream=0):
+        """hs_pose_views_device: d_Tcw float [16] row-major -> d_out _native.POSE_VIEW_DTYPE [1]"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_pose_views_device(ex._h, d_Tcw, d_out, stream or None))
+
+    def search_by_projection_posed_device(self, frame, d_pose, d_lms, L, proj_params, d_match_idx, d_match_dist, d_n_matches, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_search_by_projection_posed_device(ex._h, C.byref(frame), d_pose, d_lms, L, C.byref(proj_params), d_match_idx, d_match_dist,
+                                                                    d_n_matches, stream or None))
+
+    def local_map_search_posed_device(self, table, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, frame, d_pose,
+                                      d_lms, proj_params, cap, out, d_work, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_local_map_search_posed_device(ex._h, C.byref(table), d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes,
+                                                                n_neighbor_keyframes, C.byref(frame), d_pose, d_lms, C.byref(proj_params), cap, C.byref(out),
+                                                                d_work, stream or None))
+
+    def frame_associate_device(self, n, L, d_kp_lm, d_kp_outl, d_n_matches, n_ops, d_op_view, d_op_lm, d_work, stream=0):
+        """hs_frame_associate_device: the ops (d_op_view[j], d_op_lm[j]) applied in ascending landmark index to the dense state"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_frame_associate_device(ex._h, n, L, d_kp_lm, d_kp_outl, d_n_matches, n_ops, d_op_view, d_op_lm, d_work, stream or None))
+
+    def frame_views_device(self, n, d_kp_lm, d_kp_outl, d_n_matches, table, drop_bad, d_kp_lm_obs, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_frame_views_device(ex._h, n, d_kp_lm, d_kp_outl, d_n_matches, C.byref(table), int(bool(drop_bad)), d_kp_lm_obs, stream or None))
+
+    def track_discard_device(self, mode, d_edges, d_n_edges, edge_cap, d_outlier, d_result, table, sensor, d_kp_lm, d_kp_outl, d_n_matches, d_counts, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_discard_device(ex._h, mode, d_edges, d_n_edges, edge_cap, d_outlier, d_result, C.byref(table), sensor, d_kp_lm, d_kp_outl,
+                                                       d_n_matches, d_counts, stream or None))
+
+    def track_motion_model_device(self, frame, d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, table, d_lms, params, state, out, d_work, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_motion_model_device(ex._h, C.byref(frame), d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, C.byref(table), d_lms,
+                                                            C.byref(params), C.byref(state), C.byref(out), d_work, stream or None))
+
+    def track_local_map_device(self, frame, d_Tcw_in, table, d_lms, d_neigh, neigh_cap, d_parent, cap, params, state, out, d_work, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_local_map_device(ex._h, C.byref(frame), d_Tcw_in, C.byref(table), d_lms, d_neigh, neigh_cap, d_parent, cap,
+                                                         C.byref(params), C.byref(state), C.byref(out), d_work, stream or None))
+
+    def track_frame_device(self, frame, d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, table, d_lms, d_neigh, neigh_cap, d_parent, cap, params, state, out, d_work,
+                           stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_frame_device(ex._h, C.byref(frame), d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, C.byref(table), d_lms, d_neigh, neigh_cap,
+                                                     d_parent, cap, C.byref(params), C.byref(state), C.byref(out), d_work, stream or None))
+
+    # ---- numpy in, numpy out
+    def device_frame(self, frame):
+        """frame: a dict of fx, fy, cx, cy, mbf, sensor, bounds (min_x, max_x, min_y, max_y), kps (KP_DTYPE), desc (n, 32) uint8, uR float32 [n]
+        (optional size_ref, 31) -> (_native.FrameView of device pointers, the buffers).  The pose fields stay zero: the chain reads poses from HBM."""
+        kps, desc = np.ascontiguousarray(frame["kps"], N.KP_DTYPE), np.ascontiguousarray(frame["desc"], np.uint8)
+        uR = np.ascontiguousarray(frame["uR"], np.float32) if frame.get("uR") is not None else np.full(len(kps), -1, np.float32)
+        F = N.FrameView()
+        F.fx, F.fy, F.cx, F.cy, F.mbf, F.sensor = frame["fx"], frame["fy"], frame["cx"], frame["cy"], frame["mbf"], int(frame["sensor"])
+        F.min_x, F.max_x, F.min_y, F.max_y = frame["bounds"]
+        F.size_ref, F.n = frame.get("size_ref", 31.0), len(kps)
+        bufs = [_DevBuf(self._ex, a.nbytes, a) for a in (kps, desc, uR)]
+        F.kps, F.desc, F.uR = (b.ptr for b in bufs)
+        return F, bufs
+
+    def device_table(self, table):
+        """`table`: see FeatureMatcher._kf_table -> (_native.KfTable of device pointers, the buffers)"""
+        KT, keep = FeatureMatcher._kf_table(table)
+        bufs = [_DevBuf(self._ex, a.nbytes, a) for a in keep]
+        return N.KfTable(KT.L, KT.n_kf, *[b.ptr for b in bufs]), bufs
+
+    def outputs(self, sizes):
+        """device buffers for every field of _native.TrackOut; sizes: n, n_last, n_kf, cap -> (TrackOut, {field: (buffer, dtype, count)})"""
+        bufs = {}
+
+        def alloc(spec, prefix=""):
+            ptrs = []
+            for k, kind, cnt in spec:
+                dt, cnt = N.track_out_dtype(kind), sizes.get(cnt, cnt)
+                bufs[prefix + k] = (_DevBuf(self._ex, dt.itemsize * cnt), dt, cnt)
+                ptrs.append(bufs[prefix + k][0].ptr)
+            return ptrs
+        head, local, tail = alloc(N.TRACK_OUT_HEAD), alloc(N.LOCAL_MAP_OUT_SPEC, "local."), alloc(N.TRACK_OUT_TAIL)
+        return N.TrackOut(*head, N.LocalMapOut(*local), *tail), bufs
+
+    def _run(self, which, frame, Tcw, table, landmarks, last_kps=None, last_kp_lm=None, neigh=None, parent=None, cap=None, params=None, state=None):
+        ex = self._ex
+        F, fkeep = self.device_frame(frame)
+        KT, tkeep = self.device_table(table)
+        lms = np.ascontiguousarray(landmarks, N.LM_DTYPE)
+        if len(lms) != KT.L:
+            raise ValueError("one hs_landmark record per landmark of the table")
+        n, n_last = F.n, (len(last_kp_lm) if last_kp_lm is not None else 1)
+        cap = int(cap or KT.L)
+        prm = params or N.TrackParams()
+        if state is None:
+            state = (np.full(n, -1, np.int32), np.zeros(n, np.uint8), 0)
+        st_in = (np.ascontiguousarray(state[0], np.int32), np.ascontiguousarray(state[1], np.uint8), np.array([state[2]], np.int32), np.full(n, -1, np.int32))
+        if len(st_in[0]) != n or len(st_in[1]) != n:
+            raise ValueError("the state has one entry per keypoint")
+        st_bufs = [_DevBuf(ex, a.nbytes, a) for a in st_in]
+        ST = N.TrackState(*[b.ptr for b in st_bufs])
+        out, obufs = self.outputs(dict(n=n, n_last=n_last, n_kf=KT.n_kf, cap=cap))
+        d_T, d_lms = _DevBuf(ex, 64, np.ascontiguousarray(Tcw, np.float32).reshape(16)), _DevBuf(ex, lms.nbytes, lms)
+        work = _DevBuf(ex, self.track_work_bytes(n, n_last, KT.L, cap))
+        keep = [fkeep, tkeep]
+        if which != "local":
+            lk, ll = np.ascontiguousarray(last_kps, N.KP_DTYPE), np.ascontiguousarray(last_kp_lm, np.int32)
+            if len(lk) != len(ll) or len(ll) < 1:
+                raise ValueError("last_kps and last_kp_lm have one entry per keypoint of the last frame")
+            d_lk, d_ll = _DevBuf(ex, lk.nbytes, lk), _DevBuf(ex, ll.nbytes, ll)
+        if which != "motion":
+            ng, pa = np.ascontiguousarray(neigh, np.int32).reshape(KT.n_kf, -1), np.ascontiguousarray(parent, np.int32)
+            d_ng, d_pa = _DevBuf(ex, ng.nbytes, ng), _DevBuf(ex, pa.nbytes, pa)
+        if which == "motion":
+            self.track_motion_model_device(F, d_T.ptr, d_lk.ptr, d_ll.ptr, n_last, KT, d_lms.ptr, prm, ST, out, work.ptr)
+        elif which == "local":
+            self.track_local_map_device(F, d_T.ptr, KT, d_lms.ptr, d_ng.ptr, ng.shape[1], d_pa.ptr, cap, prm, ST, out, work.ptr)
+        else:
+            self.track_frame_device(F, d_T.ptr, d_lk.ptr, d_ll.ptr, n_last, KT, d_lms.ptr, d_ng.ptr, ng.shape[1], d_pa.ptr, cap, prm, ST, out, work.ptr)
+        ex.synchronize()
+        raw = {k: b.read(dt, cnt) for k, (b, dt, cnt) in obufs.items()}
+        res = dict(kp_lm=st_bufs[0].read(np.int32, n), kp_outl=st_bufs[1].read(np.uint8, n), n_matches=int(st_bufs[2].read(np.int32, 1)[0]),
+                   kp_lm_obs=st_bufs[3].read(np.int32, n), raw=raw)
+        del keep
+        return res
+
+    @staticmethod
+    def _summary(res, motion, local):
+        raw, r = res["raw"], res["raw"]["result"][0]
+        if motion:
+            res.update(pose_motion=raw["pose_motion"][0], status=int(r["status"]), used_wide=bool(r["used_wide"]), n_narrow=int(r["n_narrow"]),
+                       n_wide=int(r["n_wide"]), n_matches_map=int(r["n_matches_map"]))
+        if local:
+            res.update(pose_local=raw["pose_local"][0], n_inliers=int(r["n_inliers"]))
+        return res
+
+    def TrackMotionModel(self, frame, Tcw_pred, last_kps, last_kp_lm, table, landmarks, params=None):
+        """TrackMotionModel::track from SetPose(Tcw_pred) on.  frame: see device_frame; last_kps (KP_DTYPE; the angle is read) and last_kp_lm int32: the
+        last frame's keypoints and the landmark each holds (-1 = none); table: see FeatureMatcher._kf_table (lm_nobs is read); landmarks: LM_DTYPE
+        [L]; params: _native.TrackParams (the radii already truncated as the reference's `int th`).  Returns a dict: kp_lm, kp_outl (0 none / 1 inlier
+        / 2 outlier), n_matches, pose_motion (POSE_RESULT_DTYPE record), status (_native.HS_TRACK_*), used_wide, n_narrow, n_wide, n_matches_map, and
+        `raw`: every device output of the call by field name."""
+        return self._summary(self._run("motion", frame, Tcw_pred, table, landmarks, last_kps, last_kp_lm, params=params), True, False)
+
+    def TrackLocalMap(self, frame, Tcw_in, table, landmarks, neigh, parent, kp_lm, kp_outl, n_matches, params=None, cap=None):
+        """TrackLocalMap::track from the pose Tcw_in and the associations (kp_lm, kp_outl, n_matches).  neigh (n_kf, neigh_cap) / parent [n_kf]: as
+        FeatureMatcher.LocalKeyFrames; cap: the local map's capacity (default: every landmark).  Returns kp_lm, kp_outl, n_matches, pose_local,
+        n_inliers and `raw`."""
+        return self._summary(self._run("local", frame, Tcw_in, table, landmarks, neigh=neigh, parent=parent, cap=cap, params=params,
+                                       state=(kp_lm, kp_outl, n_matches)), False, True)
+
+    def TrackFrame(self, frame, Tcw_pred, last_kps, last_kp_lm, table, landmarks, neigh, parent, params=None, cap=None):
+        """the two, one after the other on the device (hs_track_frame_device): the local map starts from the motion model's pose whatever its status;
+        the caller reads `status` and decides what TrackingStateNormal decides.  Returns the union of the two calls' results."""
+        return self._summary(self._run("frame", frame, Tcw_pred, table, landmarks, last_kps, last_kp_lm, neigh, parent, cap, params), True, True)
+
+
 class ORBVocabulary:
     """HYSLAM::ORBVocabulary::transform (src/features/low_level/ORBVocabulary.cpp:31-42) over a flat vocabulary tree
     (_native.VocabTree; DBoW2 and ORBvoc are external to the reference).  `transform` returns the two containers Frame::ComputeBoW fills:

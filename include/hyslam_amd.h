@@ -764,6 +764,155 @@ int  hs_pose_optimize_device(hs_orb* h, int Q, const hs_pose_problem* d_problems
 int  hs_pose_edges_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const int32_t* d_kp_lm, float sigma_ref,
                           hs_pose_edge* d_edges, int cap, int32_t* d_n_edges, void* d_work, void* stream);
 
+/* ================= frame tracking on resident tables: TrackMotionModel::track + TrackLocalMap::track =================
+ * (src/slam/tracking/TrackMotionModel.cpp:14-83, TrackLocalMap.cpp:9-78, src/core/LandMarkMatches.cpp:26-64, Frame::UpdatePoseMatrices,
+ * FeatureMatcher.cc:57-176.)  The glue between the device entry points above, as kernels: a pose that a kernel left in HBM feeds the next search,
+ * a search's matches become the frame's associations, the optimiser's outlier flags come back onto them, and the two tracking strategies are one
+ * enqueue-only call each.  Every `_device` entry point of this section enqueues on `stream` (NULL = the handle's own), synchronises nothing and
+ * checks nothing that lives on the device; temporaries come from the caller's d_work (hs_track_work_bytes), except for the projection search's own
+ * grid lists, which hs_search_by_projection_posed_device takes from the handle's scratch exactly as hs_search_by_projection_device does.  The
+ * handle's one-stream-at-a-time rule applies (see hs_orb_extract_batch_device).
+ *
+ * The frame's LandMarkMatches as dense arrays by view (keypoint) index — the model of hyslam_amd/host/HipAssociationReplay.h:
+ *   kp_lm   [n] int32   views_to_landmarks: the landmark index at view i, -1 = none.  Entries lie in [-1, L).
+ *   kp_outl [n] u8      outliers: 0 = no entry, 1 = false, 2 = true
+ *   n_matches [1] int32 LandMarkMatches::n_matches (path dependent: a landmark that moves does not decrement it) */
+
+/* Frame::UpdatePoseMatrices on a pose in device memory: Rcw / tcw copied from the row-major 4x4 d_Tcw, Ow = -Rcw^T tcw as ONE cv::gemm (float
+ * inputs, double accumulation left to right, alpha = -1 applied in double, one rounding to float). */
+typedef struct hs_pose_view { float Rcw[9], tcw[3], Ow[3]; float _pad; } hs_pose_view;     /* 64 bytes */
+int  hs_pose_views_device(hs_orb* h, const float* d_Tcw, hs_pose_view* d_out, void* stream);
+/* hs_search_by_projection_device / hs_local_map_search_device in every output, with F->Rcw / tcw / Ow IGNORED and read from *d_pose by the kernels
+ * (projection, landMarkSizePixels, the distance and viewing-angle criteria). */
+int  hs_search_by_projection_posed_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L,
+                                          const hs_proj_params* pp, int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream);
+int  hs_local_map_search_posed_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                                      const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
+                                      const hs_pose_view* d_pose, const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out,
+                                      void* d_work, void* stream);
+
+/* d_work of every entry point of this section: n = keypoints of the frame, n_last = keypoints of the last frame, L = landmarks of the map, cap = the
+ * local map's capacity.  16-byte aligned, contents irrelevant before and after. */
+size_t hs_track_work_bytes(int n, int n_last, int L, int cap);
+
+/* The association loop at the end of _SearchByProjection_ (FeatureMatcher.cc:113-118) on the dense state: op j is associateLandMark(d_op_view[j],
+ * d_op_lm[j], true); an op with a negative view or landmark (or one outside [0, n) / [0, L)) is skipped.  The ops are applied in ASCENDING LANDMARK
+ * INDEX (the std::map<MapPoint*, ...> order), whatever their array order, each one literally as LandMarkMatches::associateLandMark
+ * (stale outliers entries and the path-dependent n_matches included).  PRECONDITION: a landmark occurs in at most one op.  The initial state may hold
+ * one landmark on several views.  Parallel closed form, integer atomicMin / atomicMax only: the same call gives the same bytes.
+ * d_work: hs_track_work_bytes(n, 0, L, 0). */
+int  hs_frame_associate_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int n_ops, const int32_t* d_op_view,
+                               const int32_t* d_op_lm, void* d_work, void* stream);
+/* d_kp_lm_obs[i] = -1 without a landmark, else T->lm_nobs[kp_lm[i]]: the array hs_frame_view wants.  drop_bad = 1 first removes the association of
+ * every view whose landmark is T->lm_bad (removeLandMarkAssociation, TrackLocalMap.cpp:62: kp_lm = -1, kp_outl = 0, --n_matches).  Of T only L,
+ * lm_nobs and (drop_bad) lm_bad are read.  d_kp_outl / d_n_matches may be NULL with drop_bad = 0. */
+int  hs_frame_views_device(hs_orb* h, int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const hs_kf_table* T, int drop_bad,
+                           int32_t* d_kp_lm_obs, void* stream);
+
+/* What the two track functions do after Optimizer::PoseOptimization.  For every edge k < min(*d_n_edges, edge_cap), i = d_edges[k].kp: when the
+ * problem ran (d_result->status != HS_POSE_TOO_FEW) kp_outl[i] = d_outlier[k] ? 2 : 1 (setOutlier); then, with isOutlier(i) = (kp_outl[i] == 2):
+ *   HS_TRACK_MOTION (TrackMotionModel.cpp:62-79)  an outlier loses its association (kp_lm = -1, kp_outl = 0, --n_matches); an inlier whose landmark
+ *                                                 has T->lm_nobs > 0 counts
+ *   HS_TRACK_LOCAL  (TrackLocalMap.cpp:25-38)     an inlier with lm_nobs > 0 counts; an outlier is removed only when sensor == 1, else it stays
+ *                                                 associated with its flag at 2
+ * As in the reference, setOutlier does nothing on a view without an `outliers` entry (kp_outl == 0), and the loop passes over a view that holds no
+ * landmark (kp_lm < 0): neither occurs inside the chain, where every edge is a held view with an entry.  edges[k].kp must be a valid view index.
+ * d_counts [1] = the count: nmatchesMap / mnMatchesInliers.  One workgroup; integer sums. */
+#define HS_TRACK_MOTION 0
+#define HS_TRACK_LOCAL  1
+int  hs_track_discard_device(hs_orb* h, int mode, const hs_pose_edge* d_edges, const int32_t* d_n_edges, int edge_cap, const uint8_t* d_outlier,
+                             const hs_pose_result* d_result, const hs_kf_table* T, int sensor, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches,
+                             int32_t* d_counts, void* stream);
+
+/* th_motion / th_motion_wide: the search radii of TrackMotionModel.cpp:38-50 AS THE REFERENCE'S `int th` HOLDS THEM — the caller truncates
+ * (th = (int)match_radius_threshold_x; th_wide = (int)(match_theshold_inflation_factor * th)) and picks the parameter by the reference's inverted
+ * naming (:39-42: sensor != 1 selects match_radius_threshold_stereo).  The product Vcw * Tcw_last and ScaleVelocity stay with the caller too. */
+typedef struct hs_track_params {
+    float   th_motion, th_motion_wide;
+    int32_t n_min_matches;             /* TrackMotionModelParameters::N_min_matches                      */
+    float   th_local;                  /* TrackLocalMapParameters::match_radius_threshold                */
+    float   nnratio_motion, nnratio_local;
+    float   th_high;                   /* FeatureMatcherSettings::TH_HIGH                                */
+    float   sigma_ref;
+    int32_t n_max_local_keyframes, n_neighbor_keyframes;
+} hs_track_params;
+typedef struct hs_track_state {        /* the frame's associations, device memory, in / out              */
+    int32_t* kp_lm;                    /* [n]                                                            */
+    uint8_t* kp_outl;                  /* [n]                                                            */
+    int32_t* n_matches;                /* [1]                                                            */
+    int32_t* kp_lm_obs;                /* [n]  maintained by the calls; F->kp_lm_obs is ignored          */
+} hs_track_state;
+#define HS_TRACK_OK 0
+#define HS_TRACK_MOTION_FAILED 1       /* fewer than n_min_matches matches also in the wide window: TrackMotionModel::track returned -1 */
+/* hs_track_motion_model_device writes status, used_wide, n_narrow, n_wide, n_matches_map and zeroes the rest; hs_track_local_map_device writes
+ * n_inliers ONLY (called on its own it leaves the other fields as the caller's memory had them); hs_track_frame_device therefore defines all. */
+typedef struct hs_track_result {
+    int32_t status;                    /* HS_TRACK_*                                                     */
+    int32_t used_wide;                 /* 1: the associations are the wide search's                      */
+    int32_t n_narrow, n_wide;          /* nmatches of the two searches                                   */
+    int32_t n_matches_map;             /* TrackMotionModel::track's return value (0 when it failed)      */
+    int32_t n_inliers;                 /* TrackLocalMap::track's return value                            */
+    int32_t _pad[2];
+} hs_track_result;                     /* 32 bytes */
+/* every pointer is device memory and required; n = F->n, n_last = the last frame's keypoints, cap = the local map's capacity */
+typedef struct hs_track_out {
+    hs_pose_view* pose_view;           /* [2]      the pose views of the two stages (predicted, motion-optimised)                    */
+    hs_pose_problem* problem;          /* [2]      the optimiser's problems                                                          */
+    hs_landmark* last_lms;             /* [n_last] the last frame's landmark records, 16-byte aligned                                */
+    int32_t* narrow_idx;  float* narrow_dist;  int32_t* narrow_n;      /* [n_last] [n_last] [1]  the search with th_motion           */
+    int32_t* wide_idx;    float* wide_dist;    int32_t* wide_n;        /* the search with th_motion_wide                             */
+    int32_t* op_view;                  /* [n_last] the chosen search's match_idx: the ops (op_view[j], last_kp_lm[j])                */
+    hs_pose_edge* edges_motion;        /* [n]      16-byte aligned                                                                   */
+    uint8_t* outlier_motion;           /* [n]                                                                                        */
+    int32_t* n_edges_motion;           /* [2]      [0] nInitialCorrespondences, [1] what the optimiser sees: 0 when the stage failed */
+    hs_pose_result* pose_motion;       /* [1]                                                                                        */
+    hs_local_map_out local;            /* the local map's outputs (frame_remove is all 0: stage 2 drops bad landmarks first)         */
+    hs_pose_edge* edges_local;         /* [n]                                                                                        */
+    uint8_t* outlier_local;            /* [n]                                                                                        */
+    int32_t* n_edges_local;            /* [1]                                                                                        */
+    hs_pose_result* pose_local;        /* [1]                                                                                        */
+    hs_track_result* result;           /* [1]                                                                                        */
+} hs_track_out;
+
+/* The three calls below are sequences of launches.  Arguments are checked before the first one; a HIP error from a stage in the middle (a failed
+ * launch, a scratch regrow that fails) is returned after the earlier stages were already enqueued: the outputs and the state are then undefined and
+ * the caller drains the stream (hs_orb_synchronize) before reusing the buffers.
+ * The searches use frac_smaller / frac_larger = 0.5 / 1.5 (FeatureSizeCriterion(0.5, 1.5)) and dist_is_invariance_range = 0: d_lms[].min_dist / max_dist
+ * hold mfMinDistance / mfMaxDistance, the kernel applies 0.8 / 1.2.  Records that hold the invariance range already (what an adaptor reads through
+ * GetMin / MaxDistanceInvariance) are converted once when they are made resident: min_dist / 0.8f, max_dist / 1.2f are NOT exact inverses, so such an
+ * integration keeps the raw distances in its resident records. */
+/* TrackMotionModel::track from current_frame.SetPose(Tcw_cur) on (:33).  d_Tcw_pred float[16]: the predicted pose.  Last frame: d_last_kps [n_last]
+ * (the angle is read) and d_last_kp_lm [n_last], its associations as landmark indices (a landmark at most once).  d_lms [L]: the map's records; T:
+ * lm_nobs is read.  F: the current frame with device pointers; its Rcw / tcw / Ow / kp_lm_obs are ignored.  Enqueued, in this order: pose view;
+ * gather of the last frame's landmarks (record j = last keypoint j: skip = 1 where it holds none or the index is outside [0, L), assoc_kp = -1,
+ * prev_angle = d_last_kps[j].angle); clearAssociations; BOTH searches (use_stereo, check_rotation, use_prev_matched, th_high, nnratio_motion) from
+ * the cleared frame; the select (narrow iff n_narrow >= n_min_matches, else wide; HS_TRACK_MOTION_FAILED when the chosen count is < n_min_matches);
+ * hs_frame_associate_device; hs_pose_edges_device; the gate; hs_pose_optimize_device; hs_track_discard_device.  When the stage fails the optimiser
+ * sees 0 edges, reports HS_POSE_TOO_FEW and hands back the predicted pose, nothing is discarded, and the wide search's associations stay on the
+ * frame — the state in which the reference returns -1. */
+int  hs_track_motion_model_device(hs_orb* h, const hs_frame_view* F, const float* d_Tcw_pred, const hs_keypoint* d_last_kps, const int32_t* d_last_kp_lm,
+                                  int n_last, const hs_kf_table* T, const hs_landmark* d_lms, const hs_track_params* tp, const hs_track_state* st,
+                                  const hs_track_out* out, void* d_work, void* stream);
+/* TrackLocalMap::track from the pose d_Tcw_in float[16] and the associations in *st: pose view; hs_frame_views_device with drop_bad = 1;
+ * hs_local_map_search_posed_device with d_frame_lm = kp_lm, n_assoc = n (use_distance, use_stereo, use_prev_matched, th_high, nnratio_local);
+ * hs_frame_associate_device with the ops (match_idx[j], sel[j]); hs_pose_edges_device; hs_pose_optimize_device from d_Tcw_in;
+ * hs_track_discard_device (HS_TRACK_LOCAL, F->sensor).  mnLastFrameSeen and SetReferenceMapPoints are not modelled: nothing here reads them. */
+int  hs_track_local_map_device(hs_orb* h, const hs_frame_view* F, const float* d_Tcw_in, const hs_kf_table* T, const hs_landmark* d_lms,
+                               const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent, int cap, const hs_track_params* tp, const hs_track_state* st,
+                               const hs_track_out* out, void* d_work, void* stream);
+/* the two, enqueued back to back: stage 2 starts from out->pose_motion->Tcw and runs whatever stage 1 reports (its input state is defined in every
+ * case); the caller reads *out->result once at the end and decides what TrackingStateNormal.cpp:34-41,71 decides.  It IS the two calls. */
+int  hs_track_frame_device(hs_orb* h, const hs_frame_view* F, const float* d_Tcw_pred, const hs_keypoint* d_last_kps, const int32_t* d_last_kp_lm,
+                           int n_last, const hs_kf_table* T, const hs_landmark* d_lms, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
+                           int cap, const hs_track_params* tp, const hs_track_state* st, const hs_track_out* out, void* d_work, void* stream);
+
+/* Device memory of the handle's device for callers without a HIP binding of their own (the Python FrameTracker): plain hipMalloc / hipFree /
+ * hipMemcpy after hipSetDevice(handle's device).  hs_device_copy: kind 1 = host to device, 2 = device to host; it first waits for `stream` (NULL =
+ * the handle's own), so a read after an enqueue-only call sees its results; synchronous. */
+int  hs_device_alloc(hs_orb* h, size_t bytes, void** out);
+int  hs_device_free(hs_orb* h, void* d_ptr);
+int  hs_device_copy(hs_orb* h, void* dst, const void* src, size_t bytes, int kind, void* stream);
+
 /* ---- frame records: the fixed-size unit of the cross-camera exchange (BASELINE config 5; new — the reference has no
  * multi-camera exchange).  record = { int32 count; 12 bytes pad; hs_keypoint kps[cap]; pad to a 16-byte boundary; uint8 desc[cap][32] }: the
  * extractor's three outputs laid out in one buffer, so hs_orb_extract_batch_device writes a frame straight into the all-gather message (the
