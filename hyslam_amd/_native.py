@@ -131,6 +131,11 @@ LOCAL_MAP_OUT_SPEC = (("weights", np.int32, "n_kf"), ("max_slot", np.int32, 1), 
                       ("match_dist", np.float32, "cap"), ("n_matches", np.int32, 1))
 
 
+# hs_kf_features (include/hyslam_amd.h): the key frames' features of hs_search_by_bow_kf_device
+class KfFeatures(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kf_off", C.c_void_p), ("kps", C.c_void_p), ("desc", C.c_void_p), ("node", C.c_void_p), ("kp_lm", C.c_void_p), ("weight", C.c_void_p)]
+
+
 class TrackOut(C.Structure):
     _fields_ = ([(k, C.c_void_p) for k, _, _ in TRACK_OUT_HEAD] + [("local", LocalMapOut)] + [(k, C.c_void_p) for k, _, _ in TRACK_OUT_TAIL])
 
@@ -192,7 +197,8 @@ EXPORTS = [
     "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
-    "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device", "hs_device_alloc", "hs_device_free", "hs_device_copy",
+    "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
+    "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes", "hs_device_alloc", "hs_device_free", "hs_device_copy",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -348,6 +354,9 @@ def lib():
     L.hs_track_motion_model_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, vp, C.c_int, C.POINTER(KfTable), vp] + tail
     L.hs_track_local_map_device.argtypes = [vp, C.POINTER(FrameView), vp, C.POINTER(KfTable), vp, vp, C.c_int, vp, C.c_int] + tail
     L.hs_track_frame_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, vp, C.c_int, C.POINTER(KfTable), vp, vp, C.c_int, vp, C.c_int] + tail
+    L.hs_search_by_bow_kf_device.argtypes = [vp, C.POINTER(KfFeatures), vp, C.POINTER(KfTable), vp, vp, vp, vp, C.c_int, f32, f32, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_frame_associate_views_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.hs_track_refkf_work_bytes.argtypes, L.hs_track_refkf_work_bytes.restype = [C.c_int] * 3, C.c_size_t
     L.hs_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.hs_device_free.argtypes = [vp, vp]
     L.hs_device_copy.argtypes = [vp, vp, vp, sz, C.c_int, vp]

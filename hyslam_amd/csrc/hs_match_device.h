@@ -1,4 +1,4 @@
-// hs_match_device.h — the device idioms shared by kernels_match.hip, kernels_bow.hip, kernels_place.hip, kernels_landmark.hip, hs_kfgraph.hip and kernels_localmap.hip (only these include
+// hs_match_device.h — the device idioms shared by kernels_match.hip, kernels_bow.hip, kernels_place.hip, kernels_landmark.hip, hs_kfgraph.hip, kernels_localmap.hip and kernels_track_refkf.hip (only these include
 // it).  Each helper states ONE reference rule once: first minimum wins, the (best key, second-best distance) pair, the cell range of
 // GetFeaturesInArea (D7), the no-candidate second distance (D10), the rotation histogram.  Everything is force-inlined.
 #pragma once

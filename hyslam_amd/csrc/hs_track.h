@@ -18,3 +18,11 @@ void hs_launch_track_clear(int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t*
 void hs_launch_track_select(int n_last, const int32_t* d_narrow_idx, const int32_t* d_narrow_n, const int32_t* d_wide_idx, const int32_t* d_wide_n, int n_min_matches,
                             int32_t* d_op_view, hs_track_result* d_result, hipStream_t s);
 void hs_launch_track_gate(const hs_track_result* d_result, int32_t* d_n_edges /*[2]: [1] = failed ? 0 : [0]*/, hipStream_t s);
+
+// ---- SearchByBoW(KeyFrame*, Frame&) and associateLandMarks in view order (kernels_track_refkf.hip; entry points in hs_track_refkf.hip)
+void hs_launch_search_by_bow_kf(const hs_kf_features& K, const int32_t* d_kf_slot, const hs_kf_table& T, const hs_keypoint* d_kps, const uint8_t* d_desc,
+                                const int32_t* d_node, const float* d_weight /*may be nullptr*/, int n, float th_low, float nnratio, int32_t* d_match_kf, int kf_cap,
+                                int32_t* d_op_view, int32_t* d_op_lm, int32_t* d_n_matches, hipStream_t s);
+size_t hs_vassoc_work_bytes(int n, int L);     // view_op [n], lm_view [L], idx_old [L], int32
+void hs_launch_frame_associate_views(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view, const int32_t* d_op_lm,
+                                     void* d_work, hipStream_t s);

@@ -953,7 +953,85 @@ class FrameTracker:
         N.check(ex._h, ex._lib.hs_track_frame_device(ex._h, C.byref(frame), d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, C.byref(table), d_lms, d_neigh, neigh_cap,
                                                      d_parent, cap, C.byref(params), C.byref(state), C.byref(out), d_work, stream or None))
 
+    def track_refkf_work_bytes(self, n, kf_cap, L):
+        return int(self._ex._lib.hs_track_refkf_work_bytes(int(n), int(kf_cap), int(L)))
+
+    def search_by_bow_kf_device(self, keyframes, d_kf_slot, table, d_kps, d_desc, d_node, d_weight, n, th_low, nnratio, d_match_kf, kf_cap, d_op_view, d_op_lm,
+                                d_n_matches, d_work=None, stream=0):
+        """hs_search_by_bow_kf_device: SearchByBoW(KeyFrame*, Frame&) between key frame *d_kf_slot of `keyframes` (_native.KfFeatures) and the frame;
+        d_node / d_weight: hs_bow_transform_device's outputs for the frame (d_weight 0 / None: every keypoint with a non-negative node takes part)"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_search_by_bow_kf_device(ex._h, C.byref(keyframes), d_kf_slot, C.byref(table), d_kps, d_desc, d_node, d_weight or None, n, th_low, nnratio,
+                                                          d_match_kf, kf_cap, d_op_view, d_op_lm, d_n_matches, d_work, stream or None))
+
+    def frame_associate_views_device(self, n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work, stream=0):
+        """hs_frame_associate_views_device: the ops (d_op_view[j], d_op_lm[j]), j < n, applied in ascending view index to the dense state"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_frame_associate_views_device(ex._h, n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work, stream or None))
+
     # ---- numpy in, numpy out
+    def device_keyframes(self, keyframes):
+        """keyframes: a dict of n_kf, kf_off int64 [n_kf + 1], kps (KP_DTYPE), desc (total, 32) uint8, node int32 [total] (negative: in no feature-vector
+        node), kp_lm int32 [total], optionally weight float32 [total] (the transform's word weights: not positive = in no node) -> (_native.KfFeatures of
+        device pointers, the buffers)"""
+        arrs = (np.ascontiguousarray(keyframes["kf_off"], np.int64), np.ascontiguousarray(keyframes["kps"], N.KP_DTYPE),
+                np.ascontiguousarray(keyframes["desc"], np.uint8), np.ascontiguousarray(keyframes["node"], np.int32), np.ascontiguousarray(keyframes["kp_lm"], np.int32))
+        if len(arrs[0]) != int(keyframes["n_kf"]) + 1 or any(len(a) != len(arrs[1]) for a in arrs[2:]) or (len(arrs[1]) and int(arrs[0][-1]) > len(arrs[1])):
+            raise ValueError("kf_off has n_kf + 1 entries and every keypoint array one entry per keypoint")
+        if keyframes.get("weight") is not None:
+            arrs += (np.ascontiguousarray(keyframes["weight"], np.float32),)
+            if len(arrs[-1]) != len(arrs[1]):
+                raise ValueError("one weight per keypoint")
+        bufs = [_DevBuf(self._ex, a.nbytes, a) for a in arrs]
+        return N.KfFeatures(int(keyframes["n_kf"]), *[b.ptr for b in bufs], *([None] if len(arrs) == 5 else [])), bufs
+
+    def SearchByBoWKeyFrame(self, keyframes, kf_slot, table, kps, desc, node, th_low=50.0, nnratio=0.7, kf_cap=None, weight=None):
+        """FeatureMatcher::SearchByBoW(KeyFrame*, Frame&, map&) on the device (hs_search_by_bow_kf_device).  keyframes: see device_keyframes, kf_slot
+        the key frame in it; table: see FeatureMatcher._kf_table (L and lm_bad are read); kps (KP_DTYPE), desc (n, 32) uint8 and node int32 [n]: the
+        frame as the vocabulary transform left it, with `weight` float32 [n] its word weights (a keypoint whose weight is not positive is in no node;
+        without `weight`, mark such a keypoint with a negative node).  Returns (matches {frame view: landmark}, match_kf int32 [kf_cap]: the
+        view each key-frame keypoint took or -1, nmatches = matches_internal.size())."""
+        ex = self._ex
+        KF, kkeep = self.device_keyframes(keyframes)
+        KT, tkeep = self.device_table(table)
+        arrs = np.ascontiguousarray(kps, N.KP_DTYPE), np.ascontiguousarray(desc, np.uint8), np.ascontiguousarray(node, np.int32)
+        n = len(arrs[0])
+        if len(arrs[1]) != n or len(arrs[2]) != n:
+            raise ValueError("one descriptor and one node per keypoint")
+        off = np.asarray(keyframes["kf_off"], np.int64)
+        kf_cap = int(kf_cap or max(1, int(np.diff(off).max()) if len(off) > 1 else 1))
+        ins = [_DevBuf(ex, a.nbytes, a) for a in arrs] + [_DevBuf(ex, 4, np.array([kf_slot], np.int32))]
+        d_w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, np.float32)
+            if len(w) != n:
+                raise ValueError("one weight per keypoint")
+            d_w = _DevBuf(ex, w.nbytes, w)
+        outs = _DevBuf(ex, kf_cap * 4), _DevBuf(ex, n * 4), _DevBuf(ex, n * 4), _DevBuf(ex, 4)
+        self.search_by_bow_kf_device(KF, ins[3].ptr, KT, ins[0].ptr, ins[1].ptr, ins[2].ptr, d_w.ptr if d_w else None, n, th_low, nnratio, outs[0].ptr, kf_cap, outs[1].ptr, outs[2].ptr,
+                                     outs[3].ptr)
+        ex.synchronize()
+        match_kf, op_view, op_lm = outs[0].read(np.int32, kf_cap), outs[1].read(np.int32, n), outs[2].read(np.int32, n)
+        del kkeep, tkeep
+        return {int(f): int(op_lm[f]) for f in np.nonzero(op_view >= 0)[0]}, match_kf, int(outs[3].read(np.int32, 1)[0])
+
+    def AssociateLandMarks(self, kp_lm, kp_outl, n_matches, associations, L):
+        """Frame::associateLandMarks(associations, true) on the dense state (hs_frame_associate_views_device).  associations: {view: landmark}, a
+        landmark at most once.  Returns (kp_lm, kp_outl, n_matches) afterwards."""
+        ex = self._ex
+        st = np.ascontiguousarray(kp_lm, np.int32), np.ascontiguousarray(kp_outl, np.uint8), np.array([n_matches], np.int32)
+        n = len(st[0])
+        if len(set(associations.values())) != len(associations) or len(associations) > n:
+            raise ValueError("a landmark occurs in at most one association, and there is at most one per view")
+        op_view, op_lm = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        for j, (v, m) in enumerate(sorted(associations.items())):
+            op_view[j], op_lm[j] = v, m
+        bufs = [_DevBuf(ex, a.nbytes, a) for a in st + (op_view, op_lm)]
+        work = _DevBuf(ex, self.track_refkf_work_bytes(n, 0, L))
+        self.frame_associate_views_device(n, int(L), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr, work.ptr)
+        ex.synchronize()
+        return bufs[0].read(np.int32, n), bufs[1].read(np.uint8, n), int(bufs[2].read(np.int32, 1)[0])
+
     def device_frame(self, frame):
         """frame: a dict of fx, fy, cx, cy, mbf, sensor, bounds (min_x, max_x, min_y, max_y), kps (KP_DTYPE), desc (n, 32) uint8, uR float32 [n]
         (optional size_ref, 31) -> (_native.FrameView of device pointers, the buffers).  The pose fields stay zero: the chain reads poses from HBM."""

@@ -906,6 +906,50 @@ int  hs_track_frame_device(hs_orb* h, const hs_frame_view* F, const float* d_Tcw
                            int n_last, const hs_kf_table* T, const hs_landmark* d_lms, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
                            int cap, const hs_track_params* tp, const hs_track_state* st, const hs_track_out* out, void* d_work, void* stream);
 
+/* ================= TrackReferenceKeyFrame::track on resident tables: the BoW search and the association replay =================
+ * (src/slam/tracking/TrackReferenceKeyFrame.cpp:22-30, FeatureMatcher.cc:216-278, Frame.cc:221-232)  The two steps
+ * of the tracker's fall-back that had no resident form; with hs_bow_transform_device before them and hs_pose_edges_device, hs_pose_optimize_device and
+ * hs_track_discard_device (HS_TRACK_MOTION) after them they make TrackReferenceKeyFrame::track without a host pointer.  Both are enqueue-only under
+ * the rules of the section above; temporaries come from the caller's d_work (hs_track_refkf_work_bytes), nothing takes the handle's scratch, nothing
+ * synchronises.
+ *
+ * The key frames' features, resident (every pointer device memory).  Key frame s owns keypoints [kf_off[s], kf_off[s + 1]).  node / weight: the
+ * d_node and d_weight hs_bow_transform_device wrote for the key frame's descriptors, unchanged.  A keypoint is in the feature vector when its weight is
+ * positive (DBoW2: `if (w > 0) fv.addFeature(nid, i)`) and its node is not negative; weight == NULL puts every keypoint with a non-negative node in.
+ * kp_lm: KeyFrame::hasAssociation(idx) as a landmark index, -1 = none. */
+typedef struct hs_kf_features {
+    int32_t n_kf;
+    const int64_t* kf_off;             /* [n_kf + 1]                                                     */
+    const hs_keypoint* kps;            /* [total]   the angle is read                                    */
+    const uint8_t* desc;               /* [total][32]                                                    */
+    const int32_t* node;               /* [total]                                                        */
+    const int32_t* kp_lm;              /* [total]                                                        */
+    const float* weight;               /* [total]   may be NULL                                          */
+} hs_kf_features;
+/* FeatureMatcher::SearchByBoW(KeyFrame*, Frame&, map&) between key frame *d_kf_slot (read on the device: in a chain it is the local.max_slot the
+ * previous frame's local-map stage left) and the frame: d_kps, d_desc [n] and d_node, d_weight [n] as hs_bow_transform_device left them (d_weight may be
+ * NULL: every keypoint with a non-negative node is in; otherwise as above), so the transform's outputs feed the search with no step in between.  Side 1:
+ * the key frame's keypoints with 0 <= kp_lm < T->L and !T->lm_bad[kp_lm] (PreviouslyMatchedIndexCriterion(true)); each takes the first minimum over the
+ * frame's keypoints of its node in ascending index, accepted when d < th_low && d < nnratio * d2 (d2 = FLT_MAX with one candidate);
+ * then RotationConsistencyBoW, always (rot = frame angle - key-frame angle; the reference does not read checkOri on this path).  Outputs: d_match_kf
+ * [kf_cap]: the frame view key-frame keypoint j took, -1 = none, every entry written; *d_n_matches = matches_internal.size(), counted before the
+ * collapse; d_op_view / d_op_lm [n]: `matches[idx_f] = lm` as ops for hs_frame_associate_views_device: d_op_view[f] = f and d_op_lm[f] = the landmark
+ * of the LARGEST key-frame index that took view f, both -1 for a view nobody took.  A slot outside [0, K->n_kf) or an empty key frame gives 0
+ * matches; a key frame with more than kf_cap keypoints is truncated in ascending index.  kf_cap >= 1, 1 <= n <= 65535.  Of T only L and lm_bad are
+ * read.  Integer atomics only: the same call gives the same bytes.  d_work is not used today and may be NULL. */
+int  hs_search_by_bow_kf_device(hs_orb* h, const hs_kf_features* K, const int32_t* d_kf_slot, const hs_kf_table* T, const hs_keypoint* d_kps,
+                                const uint8_t* d_desc, const int32_t* d_node, const float* d_weight, int n, float th_low, float nnratio, int32_t* d_match_kf,
+                                int kf_cap, int32_t* d_op_view, int32_t* d_op_lm, int32_t* d_n_matches, void* d_work, void* stream);
+/* Frame::associateLandMarks(matches, true) on the dense state: op j is associateLandMark(d_op_view[j], d_op_lm[j], true), j < n; an op with a view
+ * outside [0, n) or a landmark outside [0, L) is skipped.  The ops are applied in ASCENDING VIEW INDEX (the std::map<size_t, MapPoint*> order),
+ * whatever their array order, each literally as LandMarkMatches::associateLandMark.  PRECONDITIONS: a view occurs in at most one op and a landmark in
+ * at most one (hs_search_by_bow_kf_device's output satisfies both when a key frame holds a landmark on one view).  The frame is not cleared first and
+ * may hold one landmark on several views.  Parallel closed form, integer atomicMin only: the same call gives the same bytes.
+ * d_work: hs_track_refkf_work_bytes(n, 0, L), 16-byte aligned, contents irrelevant before and after. */
+size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L);
+int  hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view,
+                                     const int32_t* d_op_lm, void* d_work, void* stream);
+
 /* Device memory of the handle's device for callers without a HIP binding of their own (the Python FrameTracker): plain hipMalloc / hipFree /
  * hipMemcpy after hipSetDevice(handle's device).  hs_device_copy: kind 1 = host to device, 2 = device to host; it first waits for `stream` (NULL =
  * the handle's own), so a read after an enqueue-only call sees its results; synchronous. */
