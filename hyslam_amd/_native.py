@@ -136,13 +136,44 @@ class KfFeatures(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("kf_off", C.c_void_p), ("kps", C.c_void_p), ("desc", C.c_void_p), ("node", C.c_void_p), ("kp_lm", C.c_void_p), ("weight", C.c_void_p)]
 
 
+# hs_keyframe_* (include/hyslam_amd.h): reference key frame, key-frame decision, stereo landmark creation
+KEYFRAME_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("ref_slot", "<i4"), ("n_valid", "<i4"), ("n_ref_matches", "<i4"), ("n_tracked_close", "<i4"),
+                                  ("n_nontracked_close", "<i4"), ("insert", "<i4"), ("n_new", "<i4"), ("n_candidates", "<i4"), ("n_processed", "<i4"),
+                                  ("_pad", "<i4", 6)])
+
+
+class KeyFrameParams(C.Structure):
+    """hs_keyframe_params; the defaults are the reference's (Tracking_datastructs.h:103-113), th_depth is the camera's"""
+    _fields_ = [("frame_id", C.c_uint64), ("last_keyframe_id", C.c_uint32)] + [(k, C.c_int32) for k in (
+        "force", "mapping_stopped", "mapping_idle", "mapping_queue_length", "n_kfs_in_map", "min_N_tracked_close", "thresh_N_nontracked_close", "min_KF_interval",
+        "max_KF_interval", "N_tracked_target", "N_tracked_variance")] + [("th_depth", C.c_float)] + [(k, C.c_int32) for k in (
+            "n_min_points", "thresh_init", "thresh_refine", "force_loss", "ok_override")]
+
+    def __init__(self, frame_id=0, last_keyframe_id=0, force=0, mapping_stopped=0, mapping_idle=1, mapping_queue_length=0, n_kfs_in_map=3, min_N_tracked_close=100,
+                 thresh_N_nontracked_close=70, min_KF_interval=0, max_KF_interval=30, N_tracked_target=200, N_tracked_variance=50, th_depth=40.0, n_min_points=100,
+                 thresh_init=10, thresh_refine=30, force_loss=0, ok_override=-1):
+        super().__init__(frame_id, last_keyframe_id, force, mapping_stopped, mapping_idle, mapping_queue_length, n_kfs_in_map, min_N_tracked_close,
+                         thresh_N_nontracked_close, min_KF_interval, max_KF_interval, N_tracked_target, N_tracked_variance, th_depth, n_min_points, thresh_init,
+                         thresh_refine, force_loss, ok_override)
+
+
+# the device outputs of hs_keyframe_create_device / hs_track_keyframe_device: (field, element dtype, count as a size name or a number, columns)
+KEYFRAME_OUT_SPEC = (("result", "keyframe_result", 1), ("pose_view", "pose_view", 1), ("new_view", np.int32, "new_cap"), ("new_pos", np.float32, "new_cap3"),
+                     ("entries", "lm_entry", "new_cap"), ("obs", "lm_obs", "new_cap"), ("obs_offsets", np.int64, "new_cap1"), ("desc_offsets", np.int64, "new_cap1"),
+                     ("desc", np.uint8, "new_cap32"), ("lm_index", np.int32, "new_cap"))
+
+
+class KeyFrameOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in KEYFRAME_OUT_SPEC] + [("lms", C.c_void_p), ("lms_cap", C.c_int32)]
+
+
 class TrackOut(C.Structure):
     _fields_ = ([(k, C.c_void_p) for k, _, _ in TRACK_OUT_HEAD] + [("local", LocalMapOut)] + [(k, C.c_void_p) for k, _, _ in TRACK_OUT_TAIL])
 
 
 def track_out_dtype(kind):
     return {"pose_view": POSE_VIEW_DTYPE, "problem": POSE_PROBLEM_DTYPE, "lm": LM_DTYPE, "edge": POSE_EDGE_DTYPE, "result": POSE_RESULT_DTYPE,
-            "track_result": TRACK_RESULT_DTYPE}[kind] if isinstance(kind, str) else np.dtype(kind)
+            "track_result": TRACK_RESULT_DTYPE, "keyframe_result": KEYFRAME_RESULT_DTYPE, "lm_entry": LM_ENTRY_DTYPE, "lm_obs": LM_OBS_DTYPE}[kind] if isinstance(kind, str) else np.dtype(kind)
 
 
 class FrameView(C.Structure):
@@ -199,6 +230,8 @@ EXPORTS = [
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
     "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
     "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes", "hs_device_alloc", "hs_device_free", "hs_device_copy",
+    "hs_keyframe_work_bytes", "hs_keyframe_reference_device", "hs_keyframe_gate_device", "hs_keyframe_clean_device", "hs_keyframe_need_device",
+    "hs_keyframe_create_device", "hs_keyframe_discard_device", "hs_track_keyframe_device",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
@@ -357,6 +390,16 @@ def lib():
     L.hs_search_by_bow_kf_device.argtypes = [vp, C.POINTER(KfFeatures), vp, C.POINTER(KfTable), vp, vp, vp, vp, C.c_int, f32, f32, vp, C.c_int, vp, vp, vp, vp, vp]
     L.hs_frame_associate_views_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.hs_track_refkf_work_bytes.argtypes, L.hs_track_refkf_work_bytes.restype = [C.c_int] * 3, C.c_size_t
+    L.hs_keyframe_work_bytes.argtypes, L.hs_keyframe_work_bytes.restype = [C.c_int] * 3, C.c_size_t
+    kst, kpr = C.POINTER(TrackState), C.POINTER(KeyFrameParams)
+    L.hs_keyframe_reference_device.argtypes = [vp, C.c_int, kst, C.POINTER(KfTable), vp, vp, vp, vp]
+    L.hs_keyframe_gate_device.argtypes = [vp, vp, kpr, vp, vp]
+    L.hs_keyframe_clean_device.argtypes = [vp, C.c_int, kst, C.POINTER(KfTable), vp, vp]
+    L.hs_keyframe_need_device.argtypes = [vp, C.c_int, C.c_int, vp, kst, C.POINTER(KfTable), C.POINTER(KfFeatures), vp, vp, kpr, vp, vp]
+    L.hs_keyframe_create_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, kst, C.POINTER(KfTable), kpr, C.c_int, C.POINTER(KeyFrameOut), vp, vp]
+    L.hs_keyframe_discard_device.argtypes = [vp, C.c_int, kst, vp, vp]
+    L.hs_track_keyframe_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, C.POINTER(KfTable), C.POINTER(KfFeatures), vp, kpr, kst, vp, C.c_int,
+                                           C.POINTER(KeyFrameOut), vp, vp]
     L.hs_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.hs_device_free.argtypes = [vp, vp]
     L.hs_device_copy.argtypes = [vp, vp, vp, sz, C.c_int, vp]

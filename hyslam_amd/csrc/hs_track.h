@@ -26,3 +26,15 @@ void hs_launch_search_by_bow_kf(const hs_kf_features& K, const int32_t* d_kf_slo
 size_t hs_vassoc_work_bytes(int n, int L);     // view_op [n], lm_view [L], idx_old [L], int32
 void hs_launch_frame_associate_views(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view, const int32_t* d_op_lm,
                                      void* d_work, hipStream_t s);
+
+// ---- reference key frame, key-frame decision, stereo landmark creation (kernels_keyframe.hip; entry points in hs_keyframe.hip).  Every kernel reads
+// its gate (ok / insert / n_processed) from *d_result, where an earlier launch left it.
+void hs_launch_kfd_ref_begin(int n, int64_t* d_q_off /*[2] = {0, n}*/, hipStream_t s);
+void hs_launch_kfd_ref_update(const int32_t* d_max_slot, int32_t* d_ref_slot, hs_keyframe_result* d_result, hipStream_t s);
+void hs_launch_kfd_gate(const hs_track_result* d_track_result, const hs_keyframe_params& p, hs_keyframe_result* d_result, hipStream_t s);
+void hs_launch_kfd_clean(int n, const hs_track_state& st, const hs_kf_table& T, hs_keyframe_result* d_result, hipStream_t s);
+void hs_launch_kfd_need(int n, int sensor, const float* d_depth, const hs_track_state& st, const hs_kf_table& T, const hs_kf_features& K, const int32_t* d_ref_slot,
+                        const hs_track_result* d_track_result, const hs_keyframe_params& p, hs_keyframe_result* d_result, hipStream_t s);
+void hs_launch_kfd_create(const hs_frame_view& F, const float* d_depth, const hs_track_state& st, const hs_kf_table& T, const hs_keyframe_params& p, int new_cap,
+                          const hs_keyframe_out& out, unsigned long long* d_keys /*[n]*/, hipStream_t s);
+void hs_launch_kfd_discard(int n, const hs_track_state& st, const hs_keyframe_result* d_result, hipStream_t s);

@@ -969,6 +969,42 @@ class FrameTracker:
         ex = self._ex
         N.check(ex._h, ex._lib.hs_frame_associate_views_device(ex._h, n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work, stream or None))
 
+    def keyframe_work_bytes(self, n, kf_cap, new_cap):
+        return int(self._ex._lib.hs_keyframe_work_bytes(int(n), int(kf_cap), int(new_cap)))
+
+    def keyframe_reference_device(self, n, state, table, d_ref_slot, d_result, d_work, stream=0):
+        """hs_keyframe_reference_device (stage 1): bad landmarks dropped, the vote, *d_ref_slot updated when there is a winner"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_reference_device(ex._h, n, C.byref(state), C.byref(table), d_ref_slot, d_result, d_work, stream or None))
+
+    def keyframe_gate_device(self, d_track_result, params, d_result, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_gate_device(ex._h, d_track_result or None, C.byref(params), d_result, stream or None))
+
+    def keyframe_clean_device(self, n, state, table, d_result, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_clean_device(ex._h, n, C.byref(state), C.byref(table), d_result, stream or None))
+
+    def keyframe_need_device(self, n, sensor, d_depth, state, table, keyframes, d_ref_slot, d_track_result, params, d_result, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_need_device(ex._h, n, sensor, d_depth, C.byref(state), C.byref(table), C.byref(keyframes), d_ref_slot,
+                                                       d_track_result or None, C.byref(params), d_result, stream or None))
+
+    def keyframe_create_device(self, frame, d_depth, d_Tcw, state, table, params, new_cap, out, d_work, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_create_device(ex._h, C.byref(frame), d_depth, d_Tcw, C.byref(state), C.byref(table), C.byref(params), new_cap,
+                                                         C.byref(out), d_work, stream or None))
+
+    def keyframe_discard_device(self, n, state, d_result, stream=0):
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_keyframe_discard_device(ex._h, n, C.byref(state), d_result, stream or None))
+
+    def track_keyframe_device(self, frame, d_depth, d_Tcw, table, keyframes, d_track_result, params, state, d_ref_slot, new_cap, out, d_work, stream=0):
+        """hs_track_keyframe_device: the six stages after hs_track_frame_device, enqueued in order; out: _native.KeyFrameOut"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_keyframe_device(ex._h, C.byref(frame), d_depth, d_Tcw, C.byref(table), C.byref(keyframes), d_track_result or None,
+                                                        C.byref(params), C.byref(state), d_ref_slot, new_cap, C.byref(out), d_work, stream or None))
+
     # ---- numpy in, numpy out
     def device_keyframes(self, keyframes):
         """keyframes: a dict of n_kf, kf_off int64 [n_kf + 1], kps (KP_DTYPE), desc (total, 32) uint8, node int32 [total] (negative: in no feature-vector
@@ -1136,6 +1172,70 @@ class FrameTracker:
         """the two, one after the other on the device (hs_track_frame_device): the local map starts from the motion model's pose whatever its status;
         the caller reads `status` and decides what TrackingStateNormal decides.  Returns the union of the two calls' results."""
         return self._summary(self._run("frame", frame, Tcw_pred, table, landmarks, last_kps, last_kp_lm, neigh, parent, cap, params), True, True)
+
+    def keyframe_outputs(self, new_cap, alloc=None):
+        """device buffers for every field of _native.KeyFrameOut -> (KeyFrameOut with lms = NULL, {field: (buffer, dtype, count)})"""
+        sizes = dict(new_cap=new_cap, new_cap1=new_cap + 1, new_cap3=3 * new_cap, new_cap32=32 * new_cap)
+        alloc = alloc or (lambda nbytes: _DevBuf(self._ex, nbytes))
+        bufs = {}
+        for k, kind, cnt in N.KEYFRAME_OUT_SPEC:
+            dt, cnt = N.track_out_dtype(kind), sizes.get(cnt, cnt)
+            bufs[k] = (alloc(dt.itemsize * cnt), dt, cnt)
+        return N.KeyFrameOut(*[bufs[k][0].ptr for k, _, _ in N.KEYFRAME_OUT_SPEC], None, 0), bufs
+
+    def KeyFrameDecision(self, frame, depth, Tcw, table, keyframes, kp_lm, kp_outl, n_matches, ref_slot, track_result=None, params=None, new_cap=None):
+        """What Tracking::_Track_ does after the two track functions, on the device (hs_track_keyframe_device): the reference key-frame vote, bOK,
+        HandlePostTrackingSuccess, needNewKeyFrame, createNewKeyFrame's stereo landmarks and the final outlier removal.  frame: see device_frame; depth
+        float32 [n]; Tcw: the final pose; table: see FeatureMatcher._kf_table; keyframes: see device_keyframes (only n_kf, kf_off and kp_lm are read:
+        the other arrays may be left out); (kp_lm, kp_outl, n_matches): the frame's associations; ref_slot: the current reference key frame's slot or
+        -1; track_result: a dict of status, n_matches_map, n_inliers (TrackFrame's result has them) or None with params.ok_override set; params:
+        _native.KeyFrameParams; new_cap: room for creation records (default n).  Returns a dict: the fields of hs_keyframe_result, kp_lm, kp_outl,
+        n_matches, kp_lm_obs, pose_view, and for the min(n_new, new_cap) created points new_view, new_pos, entries, obs, desc, lm_index and the
+        offsets — the arrays FeatureMatcher.UpdateLandmarkEntries / hs_landmark_update_entries_device take."""
+        ex = self._ex
+        prm = params or N.KeyFrameParams()
+        F, fkeep = self.device_frame(frame)
+        KT, tkeep = self.device_table(table)
+        n = F.n
+        new_cap = n if new_cap is None else int(new_cap)
+        kf = dict(keyframes)
+        total = len(np.asarray(kf["kp_lm"]))
+        for k, filler in (("kps", np.zeros(total, N.KP_DTYPE)), ("desc", np.zeros((total, 32), np.uint8)), ("node", np.full(total, -1, np.int32))):
+            kf.setdefault(k, filler)
+        KF, kkeep = self.device_keyframes(kf)
+        st_in = (np.ascontiguousarray(kp_lm, np.int32), np.ascontiguousarray(kp_outl, np.uint8), np.array([n_matches], np.int32), np.full(n, -1, np.int32))
+        d_depth = np.ascontiguousarray(depth, np.float32)
+        if len(st_in[0]) != n or len(st_in[1]) != n or len(d_depth) != n:
+            raise ValueError("the state and the depths have one entry per keypoint")
+        st_bufs = [_DevBuf(ex, a.nbytes, a) for a in st_in]
+        ST = N.TrackState(*[b.ptr for b in st_bufs])
+        d_depth, d_T = _DevBuf(ex, d_depth.nbytes, d_depth), _DevBuf(ex, 64, np.ascontiguousarray(Tcw, np.float32).reshape(16))
+        d_ref = _DevBuf(ex, 4, np.array([ref_slot], np.int32))
+        d_tr = None
+        if track_result is not None:
+            tr = np.zeros(1, N.TRACK_RESULT_DTYPE)
+            for k in ("status", "n_matches_map", "n_inliers"):
+                tr[k] = int(track_result[k])
+            d_tr = _DevBuf(ex, tr.nbytes, tr)
+        elif prm.ok_override < 0:
+            raise ValueError("without a track result the gate needs params.ok_override")
+        out, obufs = self.keyframe_outputs(new_cap)
+        work = _DevBuf(ex, self.keyframe_work_bytes(n, KT.n_kf, new_cap))
+        self.track_keyframe_device(F, d_depth.ptr, d_T.ptr, KT, KF, d_tr.ptr if d_tr else None, prm, ST, d_ref.ptr, new_cap, out, work.ptr)
+        ex.synchronize()
+        r = obufs["result"][0].read(N.KEYFRAME_RESULT_DTYPE, 1)[0]
+        res = {k: int(r[k]) for k in N.KEYFRAME_RESULT_DTYPE.names if k != "_pad"}
+        m = min(res["n_new"], new_cap)
+        res.update(kp_lm=st_bufs[0].read(np.int32, n), kp_outl=st_bufs[1].read(np.uint8, n), n_matches=int(st_bufs[2].read(np.int32, 1)[0]),
+                   kp_lm_obs=st_bufs[3].read(np.int32, n), pose_view=obufs["pose_view"][0].read(N.POSE_VIEW_DTYPE, 1)[0])
+        for k in ("new_view", "entries", "obs"):
+            res[k] = obufs[k][0].read(obufs[k][1], new_cap)[:m]
+        res["new_pos"] = obufs["new_pos"][0].read(np.float32, 3 * new_cap).reshape(-1, 3)[:m]
+        res["desc"] = obufs["desc"][0].read(np.uint8, 32 * new_cap).reshape(-1, 32)[:m]
+        res["lm_index"] = obufs["lm_index"][0].read(np.int32, new_cap)
+        res["offsets"] = obufs["obs_offsets"][0].read(np.int64, new_cap + 1)
+        del fkeep, tkeep, kkeep
+        return res
 
 
 class ORBVocabulary:

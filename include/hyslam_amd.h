@@ -950,6 +950,119 @@ size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L);
 int  hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view,
                                      const int32_t* d_op_lm, void* d_work, void* stream);
 
+/* ================= after the two track functions: reference key frame, key-frame decision, stereo landmark creation =================
+ * (src/main/Tracking.cpp:179-227,273-317,375-388, src/slam/tracking/TrackingStateNormal.cpp:87-170, src/slam/tracking/TrackingState.cpp:20-93;
+ * DESIGN.md 5.14)  What Tracking::_Track_ does with the frame once hs_track_frame_device has run, on the same dense state (kp_lm,
+ * kp_outl, n_matches, kp_lm_obs) and the same tables: six stages, one enqueue-only entry point each under the rules of the tracking section
+ * (nothing synchronises, nothing on the device is checked, temporaries come from the caller's d_work = hs_keyframe_work_bytes), and one composite
+ * that IS these calls in this order.  Integer and flag work equals the reference exactly; the one float computation (UnprojectStereo) is stated
+ * at stage 5.  Every kernel is bounded by n, the reference key frame's keypoint count or new_cap; the kernel boundary is the only synchronisation.
+ *
+ * A stage that is switched off (ok == 0, insert == 0, sensor == 0) is still launched: its kernels read the flag from *d_result at entry and write
+ * zeros to their outputs — the mechanism of hs_track_motion_model_device's gate.
+ *
+ * PROVISIONAL LANDMARKS.  Stage 5 leaves the index T->L + k on the view that created point k.  Until the caller has appended the new landmarks to
+ * its tables (and calls with the larger L), every existing kernel tests `(unsigned)kp_lm < (unsigned)L` before it reads a table through the index:
+ * k_frame_views (kp_lm_obs = -1, never dropped), the replays' k_assoc_* / k_vassoc_* (the view counts as held, no jk / lm_view slot is touched),
+ * k_pose_edges (no edge), k_kf_votes and k_lp_mark (no vote, frame_remove = 0), k_last_gather (skip = 1), k_track_discard (an outlier is
+ * still removed, an inlier does not count).  So the state may be handed to the next hs_track_frame_device call before or after the append.
+ * The append must have happened before the next frame that INSERTS: stage 5 numbers from T->L again, and an index a view still holds would name two points.
+ * kp_lm_obs of a provisional view is 0 when stage 5 has just made it and -1 once a later k_frame_views (stage 1 of the next call, TrackLocalMap)
+ * has rewritten it; the searches test `> 0`, so both read "not yet matched to an observed landmark".
+ *
+ * Integer widths of the decision (read from the declarations): Frame::mnId is `long unsigned int` (Frame.h:195) = frame_id uint64;
+ * Tracking::mnLastKeyFrameId and the last_keyframe_id parameter are `unsigned int` (Tracking.h:195) = uint32; min / max_KF_interval and every
+ * other threshold are `int`.  `last_keyframe_id + max_KF_interval` is therefore evaluated in 32-bit unsigned arithmetic (wrapping) and widened to
+ * 64 bits for the comparison with mnId; getQueueLength() is `int`. */
+typedef struct hs_keyframe_params {
+    uint64_t frame_id;                 /* current_frame.mnId                                                                          */
+    uint32_t last_keyframe_id;         /* mnLastKeyFrameId                                                                            */
+    int32_t force;                     /* the `force` argument of newKeyFrame (Tracking.cpp:193: false)                               */
+    int32_t mapping_stopped;           /* thread_status->mapping.isStopped() || isStopRequested()                                     */
+    int32_t mapping_idle;              /* thread_status->mapping.isAcceptingInput()                                                   */
+    int32_t mapping_queue_length;      /* thread_status->mapping.getQueueLength()                                                     */
+    int32_t n_kfs_in_map;              /* pMap->KeyFramesInMap(): nMinObs = n_kfs_in_map <= 2 ? 2 : 3                                 */
+    int32_t min_N_tracked_close, thresh_N_nontracked_close, min_KF_interval, max_KF_interval, N_tracked_target, N_tracked_variance;
+    float   th_depth;                  /* camera.thDepth                                                                              */
+    int32_t n_min_points;              /* the literal 100 of TrackingState.cpp:85                                                     */
+    int32_t thresh_init, thresh_refine;/* StateNormalParameters (TrackingStateNormal.cpp:41,71)                                       */
+    int32_t force_loss;                /* 1: the reset_interval branch fired (:78-82); n_frames_tracked_consecutively stays a host counter */
+    int32_t ok_override;               /* -1: compute ok from *d_track_result; 0 / 1: take this (a frame that came through the fall-back) */
+} hs_keyframe_params;
+typedef struct hs_keyframe_result {
+    int32_t ok;                        /* stage 2: bOK                                                                                */
+    int32_t ref_slot;                  /* stage 1: *d_ref_slot afterwards                                                             */
+    int32_t n_valid;                   /* stage 3: numValidMatches() = held views with kp_outl != 2                                   */
+    int32_t n_ref_matches, n_tracked_close, n_nontracked_close, insert;       /* stage 4                                              */
+    int32_t n_new, n_candidates, n_processed;                                  /* stage 5: points created, vDepthIdx.size(), loop trips */
+    int32_t _pad[6];
+} hs_keyframe_result;                  /* 64 bytes */
+/* every pointer is device memory; all but lms are required.  Arrays are [new_cap] unless said otherwise. */
+typedef struct hs_keyframe_out {
+    hs_keyframe_result* result;        /* [1]                                                                                         */
+    hs_pose_view* pose_view;           /* [1]  UpdatePoseMatrices on the final pose (TrackingState.cpp:32)                            */
+    int32_t* new_view;                 /* the view that created point k                                                               */
+    float* new_pos;                    /* [new_cap][3]  its world position                                                            */
+    hs_lm_entry_in* entries;           /* the creation records, as hs_landmark_update_entries_device reads them: pos, ref_Ow = frame Ow */
+    hs_lm_obs* obs;                    /* one observation each: Ow, the frame's camera, u, v, kp_size, assoc_pos = pos, assoc = 1     */
+    int64_t* obs_offsets;              /* [new_cap + 1]  = k, every entry written                                                     */
+    int64_t* desc_offsets;             /* [new_cap + 1]  = k, every entry written                                                     */
+    uint8_t* desc;                     /* [new_cap][32]  the keypoint's descriptor, 16-byte aligned                                   */
+    int32_t* lm_index;                 /* T->L + k for k < min(n_new, new_cap), -1 behind: every entry written                        */
+    hs_landmark* lms;                  /* optional [lms_cap], 16-byte aligned: record T->L + k (when below lms_cap) receives pos, assoc_kp = -1,
+                                          prev_angle = 0 and skip = 0 — the fields the entry update's scatter never writes             */
+    int32_t lms_cap;
+} hs_keyframe_out;
+/* d_work of every entry point of this section.  n: keypoints of the frame; kf_cap: at least T->n_kf (the vote's counter row); new_cap as above.
+ * 16-byte aligned, contents irrelevant before and after. */
+size_t hs_keyframe_work_bytes(int n, int kf_cap, int new_cap);
+
+/* Stage 1, Tracking::determineReferenceKeyFrame (:273-317) and `if (mpReferenceKF) ...` (:181-183, :229-230); runs whether or not tracking
+ * succeeded.  It is hs_frame_views_device(drop_bad = 1) followed by hs_kf_votes_device with Q = 1, q_lm = kp_lm [0, n), count_bad_kf = 1, cap = 0:
+ * a landmark held on two views votes twice; the maximum is over key frames that are not bad, the lowest slot among equals.  d_ref_slot [1] in / out
+ * receives max_slot when that is >= 0 and keeps its value otherwise; d_result->ref_slot = the value afterwards.  Two one-thread kernels of its own:
+ * the query's offsets {0, n} before the vote, the update after it. */
+int  hs_keyframe_reference_device(hs_orb* h, int n, const hs_track_state* st, const hs_kf_table* T, int32_t* d_ref_slot, hs_keyframe_result* d_result,
+                                  void* d_work, void* stream);
+/* Stage 2, the gate: d_result->ok = prm->ok_override >= 0 ? prm->ok_override != 0 : (status == HS_TRACK_OK && n_matches_map > thresh_init &&
+ * n_inliers > thresh_refine && !force_loss), read from *d_track_result on the device (TrackingStateNormal.cpp:41,71,78-82).  d_track_result may be
+ * NULL with an override.  With ok == 0 stages 3-6 leave the state untouched and write zeros to their fields of *d_result. */
+int  hs_keyframe_gate_device(hs_orb* h, const hs_track_result* d_track_result, const hs_keyframe_params* prm, hs_keyframe_result* d_result, void* stream);
+/* Stage 3, HandlePostTrackingSuccess (:375-388): every held view whose landmark (an index in [0, T->L)) has T->lm_nobs < 1 loses its association
+ * (kp_lm = -1, kp_outl = 0, kp_lm_obs = -1, --n_matches; the setOutlier(false) before it is invisible after the erase); n_valid is counted after. */
+int  hs_keyframe_clean_device(hs_orb* h, int n, const hs_track_state* st, const hs_kf_table* T, hs_keyframe_result* d_result, void* stream);
+/* Stage 4, needNewKeyFrame (:87-170), literally and in the widths above.  n_ref_matches = TrackedMapPoints(nMinObs) (KeyFrame.cc:201-222) of key
+ * frame *d_ref_slot: its keypoints K->kp_lm[kf_off[s] .. kf_off[s+1]) with an index in [0, T->L), !T->lm_bad and T->lm_nobs >= nMinObs; a slot
+ * outside [0, K->n_kf) gives 0 (the reference dereferences a null mpReferenceKF there).  n_tracked_close / n_nontracked_close: over
+ * the views with d_depth > 0 && d_depth < th_depth, held && kp_outl != 2 / everything else; both 0 when sensor == 0.  mnMatchesInliers is
+ * d_track_result->n_inliers (0 when d_track_result is NULL).  The counts are written also when the decision returns early on mapping_stopped
+ * (the reference does not compute them there; nothing reads them).  thRefRatio is dead code in the reference and is not modelled. */
+int  hs_keyframe_need_device(hs_orb* h, int n, int sensor, const float* d_depth, const hs_track_state* st, const hs_kf_table* T, const hs_kf_features* K,
+                             const int32_t* d_ref_slot, const hs_track_result* d_track_result, const hs_keyframe_params* prm, hs_keyframe_result* d_result,
+                             void* stream);
+/* Stage 5, createNewKeyFrame (:20-93); does something when d_result->insert != 0 and F->sensor != 0.  hs_pose_views_device(d_Tcw) -> out->pose_view
+ * first (always).  Candidates: views with d_depth > 0 (NaN and <= 0 out, +inf in), in the order of std::sort on pair<float, int>: ascending depth,
+ * then ascending index — ranked by counting on the key (depth bits << 32 | index << 1 | creates: the low bit says whether the view would create a point, so the
+ * same count numbers the points), no atomic decides a position.  Closed form of the walk (DESIGN.md
+ * 5.14): with n_cand candidates and f = the number of them with !(depth > th_depth), the loop runs positions 0 .. j* where j* = max(n_min_points, f)
+ * when f < n_cand and that maximum is < n_cand, and the whole list otherwise (so always with a NaN th_depth).  A processed view creates a point when
+ * it is empty or when its landmark (an index in [0, T->L)) has lm_nobs < 1, whose association is removed first.  Points are numbered k = 0, 1, ...
+ * in sorted order (creation order, not address order); view i then holds T->L + k by the fresh insert of associateLandMark(i, p,
+ * false): kp_outl keeps a stale 1 or 2 on a view that was empty and becomes 1 otherwise; n_matches grows by one per view that was empty;
+ * kp_lm_obs = 0.  Position = Frame::UnprojectStereo (Frame.cc:481-494, Camera.cpp:155-159): x = (u - cx) * (z / fx), y likewise, in float as
+ * written, no contraction; then mRwc * x3Dc + mOw as one cv::gemm — float inputs, double products summed left to right from 0, + Ow in double, one
+ * rounding; mRwc = the transpose of pose_view->Rcw.  d_result->n_new holds the full count; records k >= new_cap are not written and truncation is
+ * not an error (the state is complete either way).  F: n, sensor, fx, fy, cx, cy, kps, desc are read. */
+int  hs_keyframe_create_device(hs_orb* h, const hs_frame_view* F, const float* d_depth, const float* d_Tcw, const hs_track_state* st, const hs_kf_table* T,
+                               const hs_keyframe_params* prm, int new_cap, const hs_keyframe_out* out, void* d_work, void* stream);
+/* Stage 6, the final outlier removal (:219-225): every held view with kp_outl == 2 loses its association (kp_lm_obs = -1, --n_matches). */
+int  hs_keyframe_discard_device(hs_orb* h, int n, const hs_track_state* st, hs_keyframe_result* d_result, void* stream);
+/* The six, in this order.  d_Tcw float[16]: the final pose, in a chain &track_out.pose_local->Tcw[0].  d_ref_slot [1] in / out.  The caller reads
+ * *out->result once; after an insert it appends n_new landmarks and one key frame to its tables. */
+int  hs_track_keyframe_device(hs_orb* h, const hs_frame_view* F, const float* d_depth, const float* d_Tcw, const hs_kf_table* T, const hs_kf_features* K,
+                              const hs_track_result* d_track_result, const hs_keyframe_params* prm, const hs_track_state* st, int32_t* d_ref_slot,
+                              int new_cap, const hs_keyframe_out* out, void* d_work, void* stream);
+
 /* Device memory of the handle's device for callers without a HIP binding of their own (the Python FrameTracker): plain hipMalloc / hipFree /
  * hipMemcpy after hipSetDevice(handle's device).  hs_device_copy: kind 1 = host to device, 2 = device to host; it first waits for `stream` (NULL =
  * the handle's own), so a read after an enqueue-only call sees its results; synchronous. */
