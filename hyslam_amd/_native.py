@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HYSLAM_AMD_LIB: development only — an instrumented build of the same sources (make BUILD=_build_prof OUT=../libhyslam_amd_prof.so EXTRA=-D...)
 LIB_PATH = os.environ.get("HYSLAM_AMD_LIB") or os.path.join(_HERE, "libhyslam_amd.so")
 
-HS_OK, HS_ERR_INVALID, HS_ERR_HIP, HS_ERR_CAPACITY, HS_ERR_NO_DEVICE = 0, 1, 2, 3, 4
+HS_OK, HS_ERR_INVALID, HS_ERR_HIP, HS_ERR_CAPACITY, HS_ERR_NO_DEVICE, HS_ERR_POISON = 0, 1, 2, 3, 4, 5
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
 
@@ -235,7 +235,7 @@ EXPORTS = [
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
-    "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy",
+    "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy", "hs_debug_poison", "hs_debug_poison_violations", "hs_debug_poison_selftest",
     "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected",
 ]
 
@@ -440,6 +440,10 @@ def lib():
     L.hs_comm_last_error.restype = C.c_char_p
     L.hs_comm_allgather_records.argtypes = [vp, vp, vp, sz, vp]
     L.hs_debug_stream_copy.argtypes = [vp, vp, vp, sz, C.c_int, vp]
+    L.hs_debug_poison.argtypes = [C.c_int]
+    L.hs_debug_poison_violations.restype = C.c_longlong
+    L.hs_debug_poison_violations.argtypes = []
+    L.hs_debug_poison_selftest.argtypes = [vp, vp]
     L.hs_orb_stage_launches.argtypes = [vp, C.c_int]
     L.hs_orb_profile_begin.argtypes = [vp]
     L.hs_orb_profile_pause.argtypes = [vp]

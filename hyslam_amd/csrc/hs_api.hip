@@ -31,8 +31,9 @@ template <class T, bool Pinned = false> struct HsBuf {
         if (count <= cap) return hipSuccess;
         release();
         const hipError_t e = Pinned ? hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, count * sizeof(T));
-        if (e != hipSuccess) p = nullptr; else cap = count;
-        return e;
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = count;
+        return Pinned ? hipSuccess : hs_poison_fresh(p, count * sizeof(T));      // hs_debug_poison: filled before first use
     }
     hipError_t grow(size_t count, hipStream_t drain)          // ... after everything enqueued on `drain` has finished
     {
@@ -560,6 +561,33 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
 // the digest of the plan the current configuration was made from (hs_plan_digest); 0 = nothing is configured
 uint64_t hs_debug_plan_digest(const hs_orb* h) { return h && h->geo.w > 0 ? h->geo.plan_digest : 0; }
 
+// ---- workspace poisoning (hs_internal.h; hs_debug_poison below)
+std::atomic<int> g_hs_poison{-1};
+static std::atomic<long long> g_hs_poison_violations{0};
+void hs_poison_violation() { g_hs_poison_violations.fetch_add(1, std::memory_order_relaxed); }
+// hipMemset on device memory returns before the fill has run (NULL stream); the handles' streams do not wait for that stream, so the host does
+hipError_t hs_poison_fill(void* p, size_t bytes, int byte)
+{
+    const hipError_t e = hipMemset(p, byte, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+// one workgroup per gap: the smallest arena offset in [begin, end) whose byte is not `byte` goes to first[gap] (left at all ones: none).  Reads only.
+__global__ __launch_bounds__(256) void k_poison_check(const uint8_t* __restrict__ base, const HsPoisonGaps g, int byte, unsigned long long* __restrict__ first)
+{
+    const int gap = blockIdx.x;
+    if (gap >= g.n) return;
+    const unsigned long long e = g.end[gap];
+    unsigned long long m = ~0ull;
+    for (unsigned long long i = g.begin[gap] + threadIdx.x; i < e; i += 256)
+        if (base[i] != (uint8_t)byte) { m = i; break; }
+    if (m != ~0ull) atomicMin(first + gap, m);
+}
+void hs_launch_poison_check(const uint8_t* d_base, const HsPoisonGaps& gaps, int byte, unsigned long long* d_first, hipStream_t s)
+{
+    if (gaps.n <= 0) return;
+    hipLaunchKernelGGL(k_poison_check, dim3(gaps.n), dim3(256), 0, s, d_base, gaps, byte, d_first);
+}
+
 // accessors for the other translation units of the library (declared in hs_internal.h)
 void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; }
 int hs_orb_device_of(const hs_orb* h) { return h ? h->device : 0; }
@@ -583,6 +611,7 @@ const char* hs_status_string(int s)
     case HS_ERR_HIP: return "HIP runtime error";
     case HS_ERR_CAPACITY: return "output capacity too small";
     case HS_ERR_NO_DEVICE: return "no usable device";
+    case HS_ERR_POISON: return "workspace poison check failed";
     default: return "unknown status";
     }
 }
@@ -1433,12 +1462,12 @@ int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose
     HIP_TRY(h, hipSetDevice(h->device));
     // temporaries only, and no synchronisation: the call runs on the caller's stream.  Scratch is per handle: a second call may only start
     // after the first finished (same stream ordering is enough)
-    HsStage st(h);
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    HsStage st(h, s);                                            // (under hs_debug_poison the fill is ordered in front of the launches)
     int8_t* d_cell; int32_t* d_winner; float* d_pangle;
     st.temp(&d_cell, hs_frame_grid_bytes(F->n)); st.temp(&d_winner, F->n); st.temp(&d_pangle, L);
     int rc = st.begin();
     if (rc != HS_OK) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
     hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s, d_pose);
     HIP_TRY(h, hipGetLastError());
@@ -1722,6 +1751,37 @@ int hs_debug_stream_copy(hs_orb* h, void* d_dst, const void* d_src, size_t bytes
     hs_launch_stream_copy(d_dst, d_src, bytes, width, stream ? (hipStream_t)stream : h->stream);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
+}
+
+int hs_debug_poison(int byte)
+{
+    if (byte < -1 || byte > 255) return HS_ERR_INVALID;
+    g_hs_poison.store(byte, std::memory_order_relaxed);
+    return HS_OK;
+}
+
+long long hs_debug_poison_violations(void) { return g_hs_poison_violations.load(std::memory_order_relaxed); }
+
+int hs_debug_poison_selftest(hs_orb* h, int* reported)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (reported) *reported = 0;
+    const int byte = hs_poison_byte();
+    if (!reported || byte < 0) return hs_fail(h, HS_ERR_INVALID, "hs_debug_poison_selftest: poisoning is off (hs_debug_poison)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    uint8_t src[64], back[64];
+    memset(src, ~byte & 0xFF, sizeof src);
+    HsStage st(h);
+    uint8_t *d_a, *d_b;
+    st.in(&d_a, sizeof src, src); st.out(&d_b, sizeof back, back);
+    int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    // 16 bytes of piece 0 to [64, 80) of its own 256-byte slot: padding, 176 bytes in front of piece 1 and 4 KiB + 432 bytes inside the claim
+    hs_launch_stream_copy(d_a + sizeof src, d_a, 16, 16, st.stream());
+    hs_launch_stream_copy(d_b, d_a, sizeof back, 16, st.stream());
+    rc = st.finish();
+    if (rc == HS_ERR_POISON) { *reported = 1; return HS_OK; }
+    return rc;
 }
 
 int hs_orb_stage_launches(const hs_orb* h, int stage)

@@ -3,6 +3,7 @@
 // (resize tables, fastAtan2, rBRIEF rotation) are defined by separately rounded fp32 operations.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -337,16 +338,34 @@ inline bool hs_index_range_ok(const int32_t* v, size_t n, int lo, int limit)
 }
 
 #define HS_STAGE_MAX_PIECES 17      // the largest user: bow_host (hs_api.hip)
-// bytes claimed past the last piece.  Unmeasured headroom: nobody has shown that anything needs it, nor that nothing does.
+// bytes claimed past the last piece.  No kernel needs them: under hs_debug_poison every host-pointer entry point was run with the arena filled
+// and the gaps checked (tests/test_gpu_poison.py) — no piece was written past its registered size, nothing wrote into the slack,
+// and every result was independent of the fill, so nothing reads it either.  It is kept as the guard band that check watches: a store past the
+// last piece lands here, inside the arena, and is reported instead of reaching whatever follows the allocation.
 #define HS_STAGE_SLACK 4096
+
+// ---- workspace poisoning (hs_debug_poison, include/hyslam_amd.h).  g_hs_poison is -1 (off) or the byte.  With it off the whole
+// cost is one relaxed load per HsStage::begin() and per device allocation: no launch, copy or synchronisation is added anywhere.
+extern std::atomic<int> g_hs_poison;                              // hs_api.hip
+inline int hs_poison_byte() { return g_hs_poison.load(std::memory_order_relaxed); }
+hipError_t hs_poison_fill(void* p, size_t bytes, int byte);      // hs_api.hip: hipMemset, then waits for it
+// every device allocation of the library passes through here right after its hipMalloc
+inline hipError_t hs_poison_fresh(void* p, size_t bytes) { const int b = hs_poison_byte(); return b < 0 || !p || !bytes ? hipSuccess : hs_poison_fill(p, bytes, b); }
+struct HsPoisonGaps { int32_t n, _r; unsigned long long begin[HS_STAGE_MAX_PIECES], end[HS_STAGE_MAX_PIECES]; };   // arena offsets; gap i follows piece i
+#define HS_POISON_REPORT_BYTES 256  // behind the slack while poisoning is on: one u64 per gap, the offset of its first changed byte (all ones: none)
+void hs_launch_poison_check(const uint8_t* d_base, const HsPoisonGaps& gaps, int byte, unsigned long long* d_first, hipStream_t s);   // hs_api.hip
+void hs_poison_violation();                                       // bumps what hs_debug_poison_violations() returns
 
 // The device side of one host-pointer call, laid out in the handle's scratch arena.  The caller registers every piece (element type, count and
 // what to copy; add() below is the only place a size is added up), begin() claims the arena for their sum, hands every piece its 256-byte
 // aligned address (distinct and valid also for a count of 0) and enqueues the uploads in registration order; after the launches finish() checks them, enqueues
 // the downloads in registration order and synchronises.  No heap allocation; one call at a time per handle (begin() invalidates the last layout).
+// Under hs_debug_poison begin() first fills the whole claim [0, total + HS_STAGE_SLACK) with the byte, on the call's stream, and finish() checks on
+// the device, behind the launches, that every gap between two pieces and the slack still hold it (HS_ERR_POISON; the downloads are made all the same).
 class HsStage {
 public:
     explicit HsStage(hs_orb* h) : h_(h), s_(hs_orb_stream_of(h)) {}
+    HsStage(hs_orb* h, hipStream_t s) : h_(h), s_(s) {}           // a device form that runs on the caller's stream: temporaries only
     hipStream_t stream() const { return s_; }
     template <class T> void temp(T** d, size_t count) { add(d, count * sizeof(T), nullptr, nullptr, 0); }
     // src == nullptr (an optional input that is absent): the piece is laid out, nothing is copied
@@ -357,8 +376,15 @@ public:
     int begin()
     {
         if (n_ > HS_STAGE_MAX_PIECES) return hs_fail(h_, HS_ERR_INVALID, "internal: a host call stages more than HS_STAGE_MAX_PIECES pieces");
-        uint8_t* base = hs_orb_scratch_of(h_, total_ + HS_STAGE_SLACK);
+        poison_ = hs_poison_byte();
+        const size_t claim = total_ + HS_STAGE_SLACK;
+        uint8_t* base = hs_orb_scratch_of(h_, claim + (poison_ >= 0 ? HS_POISON_REPORT_BYTES : 0));
         if (!base) return HS_ERR_HIP;
+        if (poison_ >= 0) {
+            base_ = base;
+            HIP_TRY(h_, hipMemsetAsync(base, poison_, claim, s_));
+            HIP_TRY(h_, hipMemsetAsync(base + claim, 0xFF, HS_POISON_REPORT_BYTES, s_));
+        }
         for (int i = 0; i < n_; i++) {
             const Piece& p = p_[i];
             *p.dev = base + p.off;
@@ -369,10 +395,22 @@ public:
     int finish()
     {
         HIP_TRY(h_, hipGetLastError());
+        unsigned long long first[HS_STAGE_MAX_PIECES];
+        if (poison_ >= 0) { const int rc = check_enqueue(first); if (rc != HS_OK) return rc; }
         for (int i = 0; i < n_; i++)
             if (p_[i].back) HIP_TRY(h_, hipMemcpyAsync(p_[i].dst, *p_[i].dev, p_[i].back, hipMemcpyDeviceToHost, s_));
         HIP_TRY(h_, hipStreamSynchronize(s_));
-        return HS_OK;
+        return poison_ >= 0 ? check_report(first) : HS_OK;
+    }
+    // for a call that brings its results back by itself (hs_bow_vector): the poison check alone, synchronous; HS_OK while poisoning is off
+    int verify()
+    {
+        if (poison_ < 0) return HS_OK;
+        unsigned long long first[HS_STAGE_MAX_PIECES];
+        const int rc = check_enqueue(first);
+        if (rc != HS_OK) return rc;
+        HIP_TRY(h_, hipStreamSynchronize(s_));
+        return check_report(first);
     }
 private:
     struct Piece { void** dev; size_t off, bytes, back; const void* src; void* dst; };
@@ -381,5 +419,29 @@ private:
         if (n_ < HS_STAGE_MAX_PIECES) { p_[n_] = Piece{ reinterpret_cast<void**>(d), total_, bytes, back, src, dst }; total_ += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }
         n_++;                       // past the capacity: begin() refuses
     }
+    int check_enqueue(unsigned long long* first)
+    {
+        if (n_ == 0) return HS_OK;
+        HsPoisonGaps g{};
+        g.n = n_;
+        for (int i = 0; i < n_; i++) { g.begin[i] = p_[i].off + p_[i].bytes; g.end[i] = i + 1 < n_ ? p_[i + 1].off : total_ + HS_STAGE_SLACK; }
+        unsigned long long* d_first = reinterpret_cast<unsigned long long*>(base_ + total_ + HS_STAGE_SLACK);
+        hs_launch_poison_check(base_, g, poison_, d_first, s_);
+        HIP_TRY(h_, hipGetLastError());
+        HIP_TRY(h_, hipMemcpyAsync(first, d_first, (size_t)n_ * sizeof(unsigned long long), hipMemcpyDeviceToHost, s_));
+        return HS_OK;
+    }
+    int check_report(const unsigned long long* first)
+    {
+        for (int i = 0; i < n_; i++) {
+            if (first[i] == ~0ull) continue;
+            hs_poison_violation();
+            const bool slack = i + 1 == n_ && first[i] >= total_;
+            return hs_fail(h_, HS_ERR_POISON, "workspace poison: piece " + std::to_string(i) + " (arena offset " + std::to_string(p_[i].off) + ", " + std::to_string(p_[i].bytes) +
+                           " bytes) was written past its end: first changed byte at arena offset " + std::to_string(first[i]) + (slack ? " (in the slack)" : " (in its padding)"));
+        }
+        return HS_OK;
+    }
     hs_orb* h_; hipStream_t s_; int n_ = 0; size_t total_ = 0; Piece p_[HS_STAGE_MAX_PIECES];
+    int poison_ = -1; uint8_t* base_ = nullptr;
 };

@@ -40,6 +40,7 @@ int hs_device_alloc(hs_orb* h, size_t bytes, void** out)
     *out = nullptr;
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     HIP_TRY(h, hipMalloc(out, std::max<size_t>(bytes, 16)));
+    HIP_TRY(h, hs_poison_fresh(*out, std::max<size_t>(bytes, 16)));
     return HS_OK;
 }
 

@@ -272,7 +272,7 @@ int hs_vocab_upload(hs_orb* h, const hs_vocab_tree* T, int levelsup, hs_vocab_de
     hs_vocab_dev* v = new hs_vocab_dev();
     v->device = hs_orb_device_of(h); v->n_nodes = n; v->levels = T->levels; v->levelsup = levelsup; v->groups = (int)nodes.size();
     hipError_t e = hipSetDevice(v->device);
-    auto up = [&](void** d, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMalloc(d, bytes); if (e == hipSuccess) e = hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice); };
+    auto up = [&](void** d, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMalloc(d, bytes); if (e == hipSuccess) e = hs_poison_fresh(*d, bytes); if (e == hipSuccess) e = hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice); };
     up((void**)&v->d_cb, T->child_begin, (size_t)n * 4); up((void**)&v->d_cc, T->child_count, (size_t)n * 4); up((void**)&v->d_word, T->word_id, (size_t)n * 4);
     up((void**)&v->d_weight, T->weight, (size_t)n * 4); up((void**)&v->d_desc, T->desc, (size_t)n * 32); up((void**)&v->d_group, group.data(), (size_t)n * 4);
     if (T->orig_id) up((void**)&v->d_report, T->orig_id, (size_t)n * 4);
@@ -321,6 +321,8 @@ int hs_records_bow_match_device(hs_orb* h, hs_vocab_dev* v, const uint8_t* d_rec
         hipFree(v->d_fgroup); hipFree(v->d_start); hipFree(v->d_items); v->d_fgroup = nullptr; v->d_start = nullptr; v->d_items = nullptr; v->cap_feats = v->cap_records = 0;
         if (hipMalloc(&v->d_fgroup, feats * 4) != hipSuccess || hipMalloc(&v->d_items, feats * 2) != hipSuccess ||
             hipMalloc(&v->d_start, (size_t)world * (v->groups + 1) * 4) != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, "out of device memory"); return HS_ERR_HIP; }
+        if (hs_poison_fresh(v->d_fgroup, feats * 4) != hipSuccess || hs_poison_fresh(v->d_items, feats * 2) != hipSuccess ||
+            hs_poison_fresh(v->d_start, (size_t)world * (v->groups + 1) * 4) != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, "poison fill failed"); return HS_ERR_HIP; }
         v->cap_feats = feats; v->cap_records = world;
     }
     size_t off_kps, off_desc; hs_record_offsets(cap, nullptr, &off_kps, &off_desc);
@@ -376,12 +378,13 @@ int hs_bow_vector(hs_orb* h, const int32_t* word, const float* weight, int n, in
     int32_t mm = 0;
     HIP_TRY(h, hipMemcpyAsync(&mm, d_m, 4, hipMemcpyDeviceToHost, stg.stream()));
     HIP_TRY(h, hipStreamSynchronize(stg.stream()));
+    const int poisoned = stg.verify();                         // hs_debug_poison: the outputs are brought back all the same
     if (mm > 0) {
         HIP_TRY(h, hipMemcpy(out_word, d_ow, (size_t)mm * 4, hipMemcpyDeviceToHost));
         HIP_TRY(h, hipMemcpy(out_value, d_ov, (size_t)mm * 8, hipMemcpyDeviceToHost));
     }
     *m = mm;
-    return HS_OK;
+    return poisoned;
 }
 
 } // extern "C"

@@ -204,7 +204,8 @@ template <typename T> hipError_t pl_regrow(T*& p, size_t old_n, size_t new_n, bo
 {
     T* q = nullptr;
     hipError_t e = hipMalloc(&q, std::max(new_n, (size_t)1) * sizeof(T));
-    if (e != hipSuccess) return e;
+    if (e == hipSuccess) e = hs_poison_fresh(q, std::max(new_n, (size_t)1) * sizeof(T));
+    if (e != hipSuccess) { (void)hipFree(q); return e; }
     if (keep && p && old_n) e = hipMemcpy(q, p, old_n * sizeof(T), hipMemcpyDeviceToDevice);
     if (e != hipSuccess) { hipFree(q); return e; }
     hipFree(p);
@@ -344,8 +345,10 @@ int hs_place_db_create(hs_orb* h, int n_words, int scoring, hs_place_db** out)
     db->h = h; db->device = hs_orb_device_of(h); db->n_words = n_words;
     hipError_t e = hipSetDevice(db->device);
     if (e == hipSuccess) e = hipMalloc(&db->d_dense, (size_t)n_words * 8);
+    if (e == hipSuccess) e = hs_poison_fresh(db->d_dense, (size_t)n_words * 8);
     if (e == hipSuccess) e = hipMemset(db->d_dense, 0, (size_t)n_words * 8);
     if (e == hipSuccess) e = hipMalloc(&db->d_state, 64);
+    if (e == hipSuccess) e = hs_poison_fresh(db->d_state, 64);
     if (e == hipSuccess) e = hipMemset(db->d_state, 0, 64);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { (void)hipGetLastError(); hs_set_error(h, hipGetErrorString(e)); hs_place_db_destroy(db); return HS_ERR_HIP; }

@@ -30,7 +30,8 @@ enum hs_status {
     HS_ERR_INVALID = 1,           /* bad argument / unsupported parameter combination            */
     HS_ERR_HIP = 2,               /* a HIP runtime call failed; see hs_*_last_error               */
     HS_ERR_CAPACITY = 3,          /* caller's output capacity too small (nothing partial written) */
-    HS_ERR_NO_DEVICE = 4          /* no usable gfx950 device                                       */
+    HS_ERR_NO_DEVICE = 4,         /* no usable gfx950 device                                       */
+    HS_ERR_POISON = 5             /* hs_debug_poison: a kernel wrote past a staged piece            */
 };
 
 /* The cv::KeyPoint fields the reference sets (ORBExtractor.cpp:478-487,546-552; class_id stays -1). */
@@ -1136,6 +1137,21 @@ int  hs_orb_profile_end(hs_orb* h, double* ms, int32_t* launches);
 /* Measurement utility: streams `bytes` from d_src to d_dst with `width` (4 or 16; 64 = four 16-byte vectors in flight per lane, non-temporal) bytes per lane — a kernel of KNOWN HBM traffic
  * in this library's own access widths, used to calibrate the rocprofv3 FETCH_SIZE / WRITE_SIZE counters (tools/pmc_traffic.py). */
 int  hs_debug_stream_copy(hs_orb* h, void* d_dst, const void* d_src, size_t bytes, int width, void* stream);
+
+/* Workspace poisoning, a process-wide debug switch for tests (off by default; with it off no call does anything it did not do before).
+ * byte in [0, 255] turns it on, -1 off; it may be flipped between calls.  While it is on
+ *   - every device allocation the library makes for itself (handle workspaces, the scratch arena, the place database, vocabulary and record-matcher
+ *     buffers, hs_device_alloc) is filled with the byte before its first use (synchronously); pinned host memory is not touched;
+ *   - every host-pointer entry point fills the part of the handle's scratch arena it claims with the byte before its uploads, and checks after its
+ *     kernels that the padding between its staged pieces and the slack behind the last one still hold it.  A changed byte makes the call return
+ *     HS_ERR_POISON (the message names the piece and the arena offset of the first changed byte) after its host outputs were copied back as usual,
+ *     and counts one violation.  The `_device` forms that take temporaries from the arena are filled too, but never checked: they do not wait.
+ * A result that differs between two bytes depends on memory the call never wrote. */
+int  hs_debug_poison(int byte);
+long long hs_debug_poison_violations(void);      /* violations since the process started */
+/* stages two 64-byte pieces and copies 16 bytes just past the end of the first, into its own padding inside the arena: *reported = 1 when the
+ * check caught it (one violation is counted).  HS_ERR_INVALID while poisoning is off. */
+int  hs_debug_poison_selftest(hs_orb* h, int* reported);
 
 /* ---- stage taps for parity tests (host outputs; synchronous; valid after an extract call) ---- */
 /* pyramid level `level` of image `image` of the last batch: tight w*h bytes; ORBExtractor::ComputePyramid :564-589 */
