@@ -17,6 +17,9 @@
 
 // One owned allocation — device memory, or page-locked host memory with Pinned — and its capacity in elements of T.  Grow-only; it never
 // synchronises by itself: whoever regrows a buffer that enqueued work may still use passes the stream to drain (or waits for its own event) first.
+// The rule: a regrow waits for EVERY stream that work using the old block may have been enqueued on.  grow(count, drain) waits for one; a buffer
+// used from two (the scratch arena: the handle's stream and the stream of a device-form stage) has the second drained by its owner before the
+// call (hs_orb_scratch_of).  Nothing relies on hipFree waiting for the device.  Without a regrow neither form waits, launches or copies.
 template <class T, bool Pinned = false> struct HsBuf {
     T* p = nullptr; size_t cap = 0;
     HsBuf() = default;
@@ -35,7 +38,7 @@ template <class T, bool Pinned = false> struct HsBuf {
         cap = count;
         return Pinned ? hipSuccess : hs_poison_fresh(p, count * sizeof(T));      // hs_debug_poison: filled before first use
     }
-    hipError_t grow(size_t count, hipStream_t drain)          // ... after everything enqueued on `drain` has finished
+    hipError_t grow(size_t count, hipStream_t drain)          // ... after everything enqueued on `drain` has finished (a second stream: the rule above)
     {
         if (count <= cap) return hipSuccess;
         const hipError_t e = hipStreamSynchronize(drain);
@@ -593,9 +596,15 @@ void hs_set_error(hs_orb* h, const char* msg) { if (h) h->err = msg ? msg : ""; 
 int hs_orb_device_of(const hs_orb* h) { return h ? h->device : 0; }
 hipStream_t hs_orb_stream_of(const hs_orb* h) { return h ? h->stream : nullptr; }
 // (the grow-only arena that HsStage, hs_internal.h, lays the host-pointer entry points' pieces out in)
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes)
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes, hipStream_t user)
 {
-    const auto claim = [&]() -> int { HIP_TRY(h, h->d_scratch.grow(bytes, h->stream)); return HS_OK; };
+    // a regrow frees the old block: whatever was laid out in it may still be in use by work queued on the handle's stream (the host-pointer calls)
+    // or on `user`, the stream of the stage that claims now (a device form on the caller's stream).  Both are drained first; without a regrow: no wait
+    const auto claim = [&]() -> int {
+        if (bytes > h->d_scratch.cap && user != h->stream) HIP_TRY(h, hipStreamSynchronize(user));
+        HIP_TRY(h, h->d_scratch.grow(bytes, h->stream));
+        return HS_OK;
+    };
     return claim() == HS_OK ? h->d_scratch.p : nullptr;
 }
 

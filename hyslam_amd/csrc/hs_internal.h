@@ -314,8 +314,9 @@ void hs_set_error(hs_orb* h, const char* msg);
 int hs_orb_device_of(const hs_orb* h);
 hipStream_t hs_orb_stream_of(const hs_orb* h);
 // claims `bytes` of the handle's grow-only device scratch arena and invalidates what an earlier claim handed out; a regrow synchronises the
-// handle's stream first.  nullptr on failure, the error text set (HS_ERR_HIP)
-uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes);
+// handle's stream first, and `user` (the stream the claiming stage enqueues on) where that is another one: earlier work of either may still use
+// the block a regrow frees.  No regrow: no wait.  nullptr on failure, the error text set (HS_ERR_HIP)
+uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes, hipStream_t user);
 
 inline int hs_fail(hs_orb* h, int code, const std::string& msg) { hs_set_error(h, msg.c_str()); return code; }
 // a failed HIP call leaves its code in the runtime's sticky "last error": it is cleared here so that the next successful call sequence on this
@@ -378,7 +379,7 @@ public:
         if (n_ > HS_STAGE_MAX_PIECES) return hs_fail(h_, HS_ERR_INVALID, "internal: a host call stages more than HS_STAGE_MAX_PIECES pieces");
         poison_ = hs_poison_byte();
         const size_t claim = total_ + HS_STAGE_SLACK;
-        uint8_t* base = hs_orb_scratch_of(h_, claim + (poison_ >= 0 ? HS_POISON_REPORT_BYTES : 0));
+        uint8_t* base = hs_orb_scratch_of(h_, claim + (poison_ >= 0 ? HS_POISON_REPORT_BYTES : 0), s_);
         if (!base) return HS_ERR_HIP;
         if (poison_ >= 0) {
             base_ = base;

@@ -17,6 +17,7 @@ def hip():
         L.hipFree.argtypes = [C.c_void_p]
         L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        L.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.hipDeviceSynchronize.argtypes = []
         L.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
         L.hipStreamSynchronize.argtypes = [C.c_void_p]
@@ -93,6 +94,11 @@ class Stream:
                 self.ptr = 0
         except Exception:
             pass
+
+
+def copy_async(dst, src, nbytes, stream):
+    """device to device, enqueued on `stream` (a Stream or a raw handle): the host does not wait"""
+    _ok(hip().hipMemcpyAsync(dst, src, nbytes, 3, getattr(stream, "ptr", stream)), "hipMemcpyAsync D2D")
 
 
 def sync():

@@ -15,6 +15,7 @@ import pytest
 import hipmem
 import keyframe_cases as KC
 import ref_keyframe as RKF
+from chain_compare import compare_keyframe as compare
 
 pytestmark = pytest.mark.gpu
 
@@ -126,31 +127,6 @@ class Dev:
         got["n_matches"], got["kp_lm_obs"] = int(read(self.state[2], np.int32, 1)[0]), read(self.state[3], np.int32, self.n)
         got["ref_slot_mem"] = int(read(self.d_ref, np.int32, 1)[0])
         return got
-
-
-def compare(got, want, new_cap, tag, stages=range(1, 7)):
-    r = got["result"][0]
-    fields = {1: ("ref_slot",), 2: ("ok",), 3: ("n_valid",), 4: ("n_ref_matches", "n_tracked_close", "n_nontracked_close", "insert"),
-              5: ("n_new", "n_candidates", "n_processed"), 6: ()}
-    for s in stages:
-        for k in fields[s]:
-            assert int(r[k]) == want["result"][k], (tag, k, int(r[k]), want["result"][k])
-    assert got["ref_slot_mem"] == want["result"]["ref_slot"], tag
-    for k in ("kp_lm", "kp_outl", "n_matches", "kp_lm_obs"):
-        assert np.array_equal(got[k], want[k]), (tag, k, got[k], want[k])
-    if 5 not in stages:
-        return
-    assert got["pose_view"].tobytes() == np.asarray(want["pose_view"]).tobytes(), (tag, "pose_view")
-    m = min(want["result"]["n_new"], new_cap)
-    assert np.array_equal(got["new_view"][:m], want["new_view"][:m]), (tag, "new_view")
-    assert got["new_pos"].reshape(-1, 3)[:m].tobytes() == want["new_pos"][:m].tobytes(), (tag, "new_pos")
-    assert got["entries"][:m].tobytes() == want["entries"].tobytes() and got["obs"][:m].tobytes() == want["obs"].tobytes(), (tag, "records")
-    assert got["desc"].reshape(-1, 32)[:m].tobytes() == want["desc"].tobytes(), (tag, "desc")
-    assert np.array_equal(got["lm_index"], want["lm_index"]), (tag, "lm_index")
-    assert np.array_equal(got["obs_offsets"], want["offsets"]) and np.array_equal(got["desc_offsets"], want["offsets"]), (tag, "offsets")
-    for k in ("new_view", "new_pos", "entries", "obs", "desc"):                 # nothing behind the last record
-        tail = got[k].view(np.uint8).reshape(new_cap, -1)[m:] if new_cap else np.zeros(0, np.uint8)
-        assert (tail == 0x55).all(), (tag, k, "written behind n_new")
 
 
 def stagewise(tracker, c, want, tag, ref):

@@ -18,11 +18,11 @@ import pytest
 import hipmem
 import ref_track as R
 import track_cases as TC
+from chain_compare import compare_track, same_outputs
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64
-TAU = 2.1e-9            # the bound on |Tcw_d - reference| for a qualified problem
 BLOCK = 256             # HS_TRACK_BLOCK
 
 
@@ -295,23 +295,6 @@ class Chain:
         assert assoc_bytes > 0
 
 
-# fields whose bytes a call defines completely (edge and flag arrays are written up to the count only: compared up to it)
-WHOLE = ("pose_view", "problem", "last_lms", "narrow_idx", "narrow_dist", "narrow_n", "wide_idx", "wide_dist", "wide_n", "op_view", "n_edges_motion", "pose_motion",
-         "n_edges_local", "pose_local", "result", "kp_lm", "kp_outl", "n_matches", "kp_lm_obs", "local.weights", "local.max_slot", "local.max_count", "local.local",
-         "local.n_local", "local.frame_remove", "local.sel", "local.n_sel", "local.lms", "local.match_idx", "local.match_dist", "local.n_matches")
-
-
-def same_outputs(a, b, what):
-    for k in WHOLE:
-        assert a[k].tobytes() == b[k].tobytes(), (what, k)
-    for stage in ("motion", "local"):
-        ne = int(a["n_edges_" + stage][0])
-        assert a["edges_" + stage][:ne].tobytes() == b["edges_" + stage][:ne].tobytes(), (what, stage)
-        run = int(a["n_edges_motion"][1]) if stage == "motion" else ne
-        if run >= 3:
-            assert a["outlier_" + stage][:run].tobytes() == b["outlier_" + stage][:run].tobytes(), (what, stage)
-
-
 @pytest.mark.parametrize("name", ["narrow", "wide", "both_fail", "too_few_edges"])
 def test_frame_call_is_its_parts(tracker, name):
     c, _ = TC.directed(name)
@@ -423,51 +406,11 @@ def test_frame_views_against_numpy(tracker, n, drop_bad):
 
 
 # ---------------------------------------------------------------- end to end against the reference
-def compare_stage(got, ref, stage, c, report):
-    """one stage's device outputs against the reference's: integers exactly, Tcw_d within TAU.  -> True when the float pose has the reference's bytes"""
-    pose = got["pose_" + stage][0]
-    ne = ref["n_edges"]
-    assert int(got["n_edges_" + stage][0]) == ne
-    assert got["edges_" + stage][:ne].tobytes() == np.ascontiguousarray(ref["edges"]).tobytes(), stage
-    rp = ref["pose"]
-    print("%s %s: |Tcw_d - ref| = %.3g" % (report, stage, float(np.abs(pose["Tcw_d"].reshape(4, 4) - rp["Tcw_d"]).max())))
-    assert (int(pose["status"]), int(pose["n_edges"]), int(pose["n_good"]), int(pose["rounds"])) == (rp["status"], rp["n_edges"], rp["n_good"], rp["rounds"]), stage
-    assert np.abs(pose["Tcw_d"].reshape(4, 4) - rp["Tcw_d"]).max() <= TAU, stage
-    if rp["status"] != 1:
-        assert np.array_equal(got["outlier_" + stage][:ne], rp["outlier"]), stage
-    return pose["Tcw"].tobytes() == np.ascontiguousarray(rp["Tcw"], np.float32).tobytes()
-
-
 def check_case(tracker, c, ref, report):
-    motion, local = ref
     ch = Chain(tracker, c)
     ch.frame()
     got = ch.results()
-    assert got["pose_view"][0].tobytes() == motion["pose_view"].tobytes()
-    assert got["last_lms"].tobytes() == np.ascontiguousarray(motion["last_lms"], ch.N.LM_DTYPE).tobytes()
-    for k in ("narrow_idx", "narrow_dist", "wide_idx", "wide_dist", "op_view"):
-        assert got[k].tobytes() == motion[k].tobytes(), k
-    r = got["result"][0]
-    assert (int(r["status"]), int(r["used_wide"]), int(r["n_narrow"]), int(r["n_wide"])) == (motion["status"], motion["used_wide"], motion["narrow_n"], motion["wide_n"])
-    assert (int(got["narrow_n"][0]), int(got["wide_n"][0])) == (motion["narrow_n"], motion["wide_n"])
-    assert got["n_edges_motion"].tolist() == [motion["n_edges"], motion["n_edges_run"]]
-    same_pose = compare_stage(got, motion, "motion", c, report)
-    assert int(r["n_matches_map"]) == motion["n_matches_map"]
-    if not same_pose:                                           # the float pose is a rounding of a double that may differ by 1e-10: the reference's
-        print(report + ": the device's float pose differs from the reference's; stage 2 is compared from the device's pose")      # stage 2 from the DEVICE's pose
-        local = R.track_local_map(c["frame"], got["pose_motion"][0]["Tcw"].reshape(4, 4), c["T"], c["lms"], c["neigh"], c["parent"], c["cap"], c["tp"],
-                                  R.DenseMatches.from_dense(*motion["state"]))
-    assert got["pose_view"][1].tobytes() == local["pose_view"].tobytes()
-    for k in ("weights", "local", "frame_remove", "sel", "match_idx", "match_dist"):
-        assert np.array_equal(got["local." + k], local[k]), k
-    assert (int(got["local.max_slot"][0]), int(got["local.max_count"][0]), int(got["local.n_local"][0]), int(got["local.n_sel"][0]), int(got["local.n_matches"][0])) == \
-        (local["max_slot"], local["max_count"], local["n_local"], local["n_sel"], local["n_matches"])
-    assert got["local.lms"].tobytes() == np.ascontiguousarray(local["lms"], ch.N.LM_DTYPE).tobytes()
-    compare_stage(got, local, "local", c, report)
-    assert int(r["n_inliers"]) == local["n_inliers"]
-    for g, w, what in zip((got["kp_lm"], got["kp_outl"], int(got["n_matches"][0])), local["state"], ("kp_lm", "kp_outl", "n_matches")):
-        assert np.array_equal(g, w), what
-    return got
+    return compare_track(got, c, ref, report, ch.N.LM_DTYPE)
 
 
 @pytest.mark.parametrize("name", list(TC.DIRECTED))
