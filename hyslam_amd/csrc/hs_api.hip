@@ -339,7 +339,6 @@ HsKnobs read_knobs()
     if (const char* e = getenv("HS_PYRAMID_PLAN")) { k.pyr_plan_set = true; k.pyr_plan = e; }
     return k;
 }
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The result block of a host-pointer extraction, on the device and in pinned host memory: [counts | keypoints | descriptors] of `batch` images
 // of `cap` entries and, for a stereo ticket, [uRight | depth] of `pairs` left images.  Every piece starts on a multiple of 256 bytes.
@@ -347,11 +346,11 @@ struct OutLayout { size_t off_k, off_d, off_u, off_z, bytes; };
 OutLayout out_layout(int batch, int cap, int pairs)
 {
     OutLayout o;
-    o.off_k = pad256((size_t)batch * 4);
-    o.off_d = o.off_k + pad256((size_t)batch * cap * sizeof(hs_keypoint));
+    o.off_k = hs_up256((size_t)batch * 4);
+    o.off_d = o.off_k + hs_up256((size_t)batch * cap * sizeof(hs_keypoint));
     const size_t desc = (size_t)batch * cap * HS_DESC_BYTES, ur = (size_t)pairs * cap * 4;
     o.off_u = o.off_z = o.bytes = o.off_d + desc;
-    if (pairs > 0) { o.off_u = o.off_d + pad256(desc); o.off_z = o.off_u + pad256(ur); o.bytes = o.off_z + ur; }
+    if (pairs > 0) { o.off_u = o.off_d + hs_up256(desc); o.off_z = o.off_u + hs_up256(ur); o.bytes = o.off_z + ur; }
     return o;
 }
 
@@ -780,7 +779,7 @@ int hs_orb_extract_batch_device(hs_orb* h, const uint8_t* d_imgs, int batch, int
     if (((uintptr_t)d_desc & 15) != 0 || (((uintptr_t)d_kps | (uintptr_t)d_n) & 3) != 0)
         return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores; hs_record_offsets pads for it), keypoints and counts 4");
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t s = hs_stream_or(h, stream);
     const auto body = [&](hs_orb* q, int first, int count, hipStream_t qs) -> int {
         int rc = configure(q, w, h_px, count);
         if (rc != HS_OK) return rc;
@@ -912,7 +911,7 @@ int hs_preprocess_device(hs_orb* h, const uint8_t* d_src, int w, int h_px, size_
     if (grey_row_stride < (size_t)gw) return hs_fail(h, HS_ERR_INVALID, "grey_row_stride < scaled width");
     HIP_TRY(h, hipSetDevice(h->device));
     hs_launch_preprocess(d_src, w, h_px, row_stride, image_stride, pp->channels, pp->rgb, pp->scale, d_grey, gw, gh, grey_row_stride, grey_image_stride, 0, batch,
-                         stream ? (hipStream_t)stream : h->stream);
+                         hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -951,7 +950,7 @@ int hs_stereo_match_batch_device(hs_orb* h, const hs_keypoint* d_kpsL, const uin
     HIP_TRY(h, h->st.grow((size_t)pairs * cap, h->stream));
     const int rc = ensure_stereo_strips(h, pairs, cap, sp->n_rows);
     if (rc != HS_OK) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t s = hs_stream_or(h, stream);
     run_stereo(h, false, d_kpsL, d_descL, d_nL, d_kpsR, d_descR, d_nR, pairs, cap, *sp, d_uRight, d_depth, s);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
@@ -1033,7 +1032,7 @@ int hs_stereo_frontend_batch_device(hs_orb* h, const uint8_t* d_left, const uint
     if ((((uintptr_t)d_descL | (uintptr_t)d_descR) & 15) != 0 || (((uintptr_t)d_kpsL | (uintptr_t)d_kpsR | (uintptr_t)d_nL | (uintptr_t)d_nR | (uintptr_t)d_uRight | (uintptr_t)d_depth) & 3) != 0)
         return hs_fail(h, HS_ERR_INVALID, "output alignment: descriptors 16 bytes (they are written with 16-byte vector stores), everything else 4");
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t s = hs_stream_or(h, stream);
     const auto body = [&](hs_orb* q, int first, int count, hipStream_t qs) -> int {
         int rc = configure(q, w, h_px, 2 * count);
         if (rc != HS_OK) return rc;
@@ -1211,35 +1210,6 @@ int hs_ticket_frames_copied(hs_orb* h, int32_t ticket)
     return -1;
 }
 
-int hs_search_by_projection(hs_orb* h, const hs_frame_view* F, const hs_landmark* lms, int L, const hs_proj_params* pp,
-                            int32_t* match_idx, float* match_dist, int32_t* n_matches)
-{
-    if (!h) return HS_ERR_INVALID;
-    if (!F || !pp || L < 0 || !n_matches || (L > 0 && (!lms || !match_idx || !match_dist)) || F->n < 0 || F->n > 65535 ||
-        (F->n > 0 && (!F->kps || !F->desc)) || (pp->use_stereo && F->sensor != 0 && F->n > 0 && !F->uR))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    *n_matches = 0;
-    if (L == 0) return HS_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int n = F->n;
-    HsStage st(h);
-    DevFrame D; float *d_uR, *d_mdist, *d_pangle; int32_t *d_obs, *d_winner, *d_midx, *d_nm; hs_landmark* d_lms;
-    stage_frame(st, F, &D);
-    st.in(&d_uR, n, F->uR); st.in(&d_obs, n, F->kp_lm_obs); st.temp(&d_winner, n);
-    st.in(&d_lms, L, lms);
-    st.out(&d_midx, L, match_idx); st.out(&d_mdist, L, match_dist); st.temp(&d_pangle, L); st.out(&d_nm, 1, n_matches);
-    int rc = st.begin();
-    if (rc != HS_OK) return rc;
-    hipStream_t s = st.stream();
-    hs_launch_frame_grid(*F, D.kps, D.cell, true, s);
-    hs_launch_search_projection(*F, D.kps, D.desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, D.cell, d_lms, L, *pp,
-                                d_midx, d_mdist, d_winner, d_pangle, d_nm, s);
-    rc = st.finish();
-    if (rc != HS_OK) return rc;
-    for (int i = 0; i < L; i++) if (match_idx[i] < 0) match_dist[i] = -1.f;      // entries dropped by the rotation check
-    return HS_OK;
-}
-
 // ================= device-resident frames (FeatureViews stay in HBM between ImageProcessing and Tracking) =================
 // hySLAM copies a frame's keypoints and descriptors out of the extractor into FeatureViews (host objects), and every matcher call gathers them
 // again and uploads them (Frame.cc:45-72, FeatureViews.h:20-81).  The features were produced on this device a moment earlier: hs_frame_publish
@@ -1379,6 +1349,45 @@ int hs_frame_info(int device, hs_frame_token token, int32_t* n)
     return HS_ERR_INVALID;
 }
 
+// what hs_search_by_projection and hs_search_by_projection_frame do once their arguments are checked and L > 0.  ref: the published frame that
+// supplies keypoints and descriptors (the launches wait for it), nullptr: they are staged from F
+static int search_by_projection_host(hs_orb* h, const FrameRef* ref, const hs_frame_view* F, const hs_landmark* lms, int L, const hs_proj_params* pp,
+                                     int32_t* match_idx, float* match_dist, int32_t* n_matches)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int n = F->n;
+    HsStage st(h);
+    DevFrame D{}; float *d_uR, *d_mdist, *d_pangle; int32_t *d_obs, *d_winner, *d_midx, *d_nm; hs_landmark* d_lms;
+    if (ref) st.temp(&D.cell, hs_frame_grid_bytes(n)); else stage_frame(st, F, &D);
+    st.in(&d_uR, n, F->uR); st.in(&d_obs, n, F->kp_lm_obs); st.temp(&d_winner, n);
+    st.in(&d_lms, L, lms);
+    st.out(&d_midx, L, match_idx); st.out(&d_mdist, L, match_dist); st.temp(&d_pangle, L); st.out(&d_nm, 1, n_matches);
+    int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    hipStream_t s = st.stream();
+    if (ref) HIP_TRY(h, hipStreamWaitEvent(s, ref->ready, 0));
+    const hs_keypoint* d_kps = ref ? ref->d_kps : D.kps;
+    hs_launch_frame_grid(*F, d_kps, D.cell, true, s);
+    hs_launch_search_projection(*F, d_kps, ref ? ref->d_desc : D.desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, D.cell, d_lms, L, *pp,
+                                d_midx, d_mdist, d_winner, d_pangle, d_nm, s);
+    rc = st.finish();
+    if (rc != HS_OK) return rc;
+    for (int i = 0; i < L; i++) if (match_idx[i] < 0) match_dist[i] = -1.f;      // entries dropped by the rotation check
+    return HS_OK;
+}
+
+int hs_search_by_projection(hs_orb* h, const hs_frame_view* F, const hs_landmark* lms, int L, const hs_proj_params* pp,
+                            int32_t* match_idx, float* match_dist, int32_t* n_matches)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!F || !pp || L < 0 || !n_matches || (L > 0 && (!lms || !match_idx || !match_dist)) || F->n < 0 || F->n > 65535 ||
+        (F->n > 0 && (!F->kps || !F->desc)) || (pp->use_stereo && F->sensor != 0 && F->n > 0 && !F->uR))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    *n_matches = 0;
+    if (L == 0) return HS_OK;
+    return search_by_projection_host(h, nullptr, F, lms, L, pp, match_idx, match_dist, n_matches);
+}
+
 int hs_search_by_projection_frame(hs_orb* h, hs_frame_token frame, const hs_frame_view* F, const hs_landmark* lms, int L, const hs_proj_params* pp,
                                   int32_t* match_idx, float* match_dist, int32_t* n_matches)
 {
@@ -1392,24 +1401,7 @@ int hs_search_by_projection_frame(hs_orb* h, hs_frame_token frame, const hs_fram
     FrameGuard guard{ &ref, nullptr };
     if (ref.n != F->n) return hs_fail(h, HS_ERR_INVALID, "hs_search_by_projection_frame: F->n differs from the published frame");
     if (L == 0) return HS_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int n = F->n;
-    HsStage st(h);
-    float *d_uR, *d_mdist, *d_pangle; int32_t *d_obs, *d_winner, *d_midx, *d_nm; int8_t* d_cell; hs_landmark* d_lms;
-    st.in(&d_uR, n, F->uR); st.in(&d_obs, n, F->kp_lm_obs); st.temp(&d_cell, hs_frame_grid_bytes(n)); st.temp(&d_winner, n);
-    st.in(&d_lms, L, lms);
-    st.out(&d_midx, L, match_idx); st.out(&d_mdist, L, match_dist); st.temp(&d_pangle, L); st.out(&d_nm, 1, n_matches);
-    int rc = st.begin();
-    if (rc != HS_OK) return rc;
-    hipStream_t s = st.stream();
-    HIP_TRY(h, hipStreamWaitEvent(s, ref.ready, 0));
-    hs_launch_frame_grid(*F, ref.d_kps, d_cell, true, s);
-    hs_launch_search_projection(*F, ref.d_kps, ref.d_desc, F->uR ? d_uR : nullptr, F->kp_lm_obs ? d_obs : nullptr, d_cell, d_lms, L, *pp,
-                                d_midx, d_mdist, d_winner, d_pangle, d_nm, s);
-    rc = st.finish();
-    if (rc != HS_OK) return rc;
-    for (int i = 0; i < L; i++) if (match_idx[i] < 0) match_dist[i] = -1.f;      // entries dropped by the rotation check
-    return HS_OK;
+    return search_by_projection_host(h, &ref, F, lms, L, pp, match_idx, match_dist, n_matches);
 }
 
 int hs_stereo_match_frames(hs_orb* h, hs_frame_token left, hs_frame_token right, const hs_stereo_params* sp, float* uRight, float* depth)
@@ -1445,8 +1437,27 @@ int hs_frame_grid(hs_orb* h, const hs_frame_view* F, int8_t* cell_xy)
 
 namespace {
 int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
-                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream);
+                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!F || !pp || L < 1 || !d_lms || !d_match_idx || !d_match_dist || !d_n_matches || F->n < 1 || F->n > 65535 || !F->kps || !F->desc ||
+        (pp->use_stereo && F->sensor != 0 && !F->uR))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // temporaries only, and no synchronisation: the call runs on the caller's stream.  Scratch is per handle: a second call may only start
+    // after the first finished (same stream ordering is enough)
+    hipStream_t s = hs_stream_or(h, stream);
+    HsStage st(h, s);                                            // (under hs_debug_poison the fill is ordered in front of the launches)
+    int8_t* d_cell; int32_t* d_winner; float* d_pangle;
+    st.temp(&d_cell, hs_frame_grid_bytes(F->n)); st.temp(&d_winner, F->n); st.temp(&d_pangle, L);
+    int rc = st.begin();
+    if (rc != HS_OK) return rc;
+    hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
+    hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s, d_pose);
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
 }
+}  // namespace
 int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
                                    int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
 {
@@ -1460,29 +1471,6 @@ int hs_search_by_projection_posed_device(hs_orb* h, const hs_frame_view* F, cons
     if (!d_pose) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     return search_by_projection_device(h, F, d_pose, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, stream);
 }
-namespace {
-int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
-                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
-{
-    if (!h) return HS_ERR_INVALID;
-    if (!F || !pp || L < 1 || !d_lms || !d_match_idx || !d_match_dist || !d_n_matches || F->n < 1 || F->n > 65535 || !F->kps || !F->desc ||
-        (pp->use_stereo && F->sensor != 0 && !F->uR))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    // temporaries only, and no synchronisation: the call runs on the caller's stream.  Scratch is per handle: a second call may only start
-    // after the first finished (same stream ordering is enough)
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    HsStage st(h, s);                                            // (under hs_debug_poison the fill is ordered in front of the launches)
-    int8_t* d_cell; int32_t* d_winner; float* d_pangle;
-    st.temp(&d_cell, hs_frame_grid_bytes(F->n)); st.temp(&d_winner, F->n); st.temp(&d_pangle, L);
-    int rc = st.begin();
-    if (rc != HS_OK) return rc;
-    hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
-    hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s, d_pose);
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
-}
-}  // namespace
 
 namespace {
 // one row of A*B (+c): double accumulation, alpha in double, one rounding (cv::gemm on float matrices)
@@ -1705,7 +1693,7 @@ int hs_hamming_knn2_device(hs_orb* h, const uint8_t* d_q, int nq, const uint8_t*
     if (!h) return HS_ERR_INVALID;
     if (nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_best_idx || !d_best_dist || !d_second_dist)) || (nt > 0 && !d_t)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    hs_launch_knn2(d_q, nq, d_t, nt, d_best_idx, d_best_dist, d_second_dist, stream ? (hipStream_t)stream : h->stream);
+    hs_launch_knn2(d_q, nq, d_t, nt, d_best_idx, d_best_dist, d_second_dist, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -1747,7 +1735,7 @@ int hs_records_knn2_device(hs_orb* h, const uint8_t* d_records, size_t record_st
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     size_t od; hs_record_offsets(cap, nullptr, nullptr, &od);
-    hs_launch_knn2_records(d_records, record_stride, world, rank, cap, od, d_best_idx, d_best_dist, d_second_dist, stream ? (hipStream_t)stream : h->stream);
+    hs_launch_knn2_records(d_records, record_stride, world, rank, cap, od, d_best_idx, d_best_dist, d_second_dist, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -1757,7 +1745,7 @@ int hs_debug_stream_copy(hs_orb* h, void* d_dst, const void* d_src, size_t bytes
     if (!h) return HS_ERR_INVALID;
     if (!d_dst || !d_src || (width != 4 && width != 16 && width != 64) || bytes % 16) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    hs_launch_stream_copy(d_dst, d_src, bytes, width, stream ? (hipStream_t)stream : h->stream);
+    hs_launch_stream_copy(d_dst, d_src, bytes, width, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -1876,7 +1864,7 @@ int hs_orb_synchronize(hs_orb* h, void* stream)
 {
     if (!h) return HS_ERR_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(stream ? (hipStream_t)stream : h->stream));
+    HIP_TRY(h, hipStreamSynchronize(hs_stream_or(h, stream)));
     return HS_OK;
 }
 

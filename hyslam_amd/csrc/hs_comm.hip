@@ -171,7 +171,7 @@ int hs_comm_allgather_records(hs_comm* c, const void* d_record, void* d_gathered
     if (!d_record || !d_gathered || record_bytes == 0) { c->err = "bad argument"; return HS_ERR_INVALID; }
     Rccl& r = rccl();
     if (hipSetDevice(hs_orb_device_of(c->h)) != hipSuccess) { (void)hipGetLastError(); c->err = "hipSetDevice failed"; return HS_ERR_HIP; }
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(c->h);
+    hipStream_t s = hs_stream_or(c->h, stream);
     // ncclChar = 0; in place when d_record == d_gathered + rank * record_bytes (NCCL's in-place all-gather convention)
     const hs_nccl_result rc = r.AllGather(d_record, d_gathered, record_bytes, 0, c->comm, s);
     if (rc != 0) { c->err = nccl_text(r, "ncclAllGather", rc); return HS_ERR_HIP; }

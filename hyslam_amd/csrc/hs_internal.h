@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/hyslam_amd.h"
+#include "hs_work.h"                // the caller-owned work areas (d_work) and hs_up256
 
 #define HS_MAX_LEVELS 16
 #define HS_EDGE 19                 // EDGE_THRESHOLD, ORBExtractor.cpp:74
@@ -298,13 +299,11 @@ void hs_launch_search_init(const hs_frame_view& F2, const hs_keypoint* d_kps2, c
                            const hs_keypoint* d_kps1, const uint8_t* d_desc1, int n1, const float* d_prev_xy, float window, float th_low, float nnratio,
                            int32_t* d_owner, int32_t* d_odist, float* d_angle_scratch, int32_t* d_self_scratch, int32_t* d_n_matches, hipStream_t s);
 
-// ---- the local map (kernels_localmap.hip; entry points in hs_localmap.hip).  d_work of hs_launch_local_points: hs_local_points_flag_bytes(L) flag bytes,
-// then one int32 per block of HS_LOCAL_POINTS_BLOCK landmarks
+// ---- the local map (kernels_localmap.hip; entry points in hs_localmap.hip)
 void hs_launch_local_keyframes(int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
                                int n_max, int n_neighbor, uint8_t* d_local, int32_t* d_n_local, hipStream_t s);
-size_t hs_local_points_flag_bytes(int L);
 void hs_launch_local_points(const hs_kf_table& T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
-                            int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, hipStream_t s);
+                            int32_t* d_sel, int cap, int32_t* d_n_sel, const HsLocalPointsWork& w, hipStream_t s);
 void hs_launch_landmark_gather(const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out, hipStream_t s);
 void hs_launch_local_map_query(int n_assoc, int64_t* d_q_off, hipStream_t s);
 
@@ -317,6 +316,8 @@ hipStream_t hs_orb_stream_of(const hs_orb* h);
 // handle's stream first, and `user` (the stream the claiming stage enqueues on) where that is another one: earlier work of either may still use
 // the block a regrow frees.  No regrow: no wait.  nullptr on failure, the error text set (HS_ERR_HIP)
 uint8_t* hs_orb_scratch_of(hs_orb* h, size_t bytes, hipStream_t user);
+// the stream a device entry point enqueues on: the caller's, or the handle's where the caller passes NULL
+inline hipStream_t hs_stream_or(const hs_orb* h, void* stream) { return stream ? (hipStream_t)stream : hs_orb_stream_of(h); }
 
 inline int hs_fail(hs_orb* h, int code, const std::string& msg) { hs_set_error(h, msg.c_str()); return code; }
 // a failed HIP call leaves its code in the runtime's sticky "last error": it is cleared here so that the next successful call sequence on this
@@ -417,7 +418,7 @@ private:
     struct Piece { void** dev; size_t off, bytes, back; const void* src; void* dst; };
     template <class T> void add(T** d, size_t bytes, const void* src, void* dst, size_t back)
     {
-        if (n_ < HS_STAGE_MAX_PIECES) { p_[n_] = Piece{ reinterpret_cast<void**>(d), total_, bytes, back, src, dst }; total_ += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }
+        if (n_ < HS_STAGE_MAX_PIECES) { p_[n_] = Piece{ reinterpret_cast<void**>(d), total_, bytes, back, src, dst }; total_ += hs_up256(std::max<size_t>(bytes, 1)); }
         n_++;                       // past the capacity: begin() refuses
     }
     int check_enqueue(unsigned long long* first)

@@ -5,8 +5,6 @@
 #include <cstddef>
 
 namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool state_ok(const hs_track_state* s) { return s && s->kp_lm && s->kp_outl && s->n_matches && s->kp_lm_obs; }
 bool n_ok(int n) { return n >= 1 && n <= 65535; }
 bool table_ok(const hs_kf_table* T) { return T && T->L >= 0 && (T->L == 0 || (T->lm_nobs && T->lm_bad)); }
 // what stage 1's vote reads beyond that: hs_kf_votes_device would refuse it only after the launches before it
@@ -16,22 +14,11 @@ bool out_ok(const hs_keyframe_out* o, int new_cap)
     return o && new_cap >= 0 && o->result && o->pose_view && o->obs_offsets && o->desc_offsets && (!o->lms || (o->lms_cap >= 0 && !((uintptr_t)o->lms & 15))) &&
            (new_cap == 0 || (o->new_view && o->new_pos && o->entries && o->obs && o->desc && o->lm_index));
 }
-// d_work: the vote's query offsets and scalars, the depth keys [n], the vote's counter row [kf_cap]
-struct Work {
-    int64_t* q_off; int32_t* vote; unsigned long long* keys; int32_t* weights;
-    Work(void* d_work, int n) : q_off(static_cast<int64_t*>(d_work)), vote(reinterpret_cast<int32_t*>(q_off + 2)),
-                                keys(reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(d_work) + 256)),
-                                weights(reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_work) + 256 + up256((size_t)std::max(n, 0) * 8))) {}
-};
 }  // namespace
 
 extern "C" {
 
-size_t hs_keyframe_work_bytes(int n, int kf_cap, int new_cap)
-{
-    (void)new_cap;
-    return 256 + up256((size_t)std::max(n, 0) * 8) + up256((size_t)std::max(kf_cap, 0) * sizeof(int32_t)) + 256;
-}
+size_t hs_keyframe_work_bytes(int n, int kf_cap, int new_cap) { (void)new_cap; return HsKeyframeWork::bytes(n, kf_cap); }
 
 int hs_keyframe_reference_device(hs_orb* h, int n, const hs_track_state* st, const hs_kf_table* T, int32_t* d_ref_slot, hs_keyframe_result* d_result, void* d_work,
                                  void* stream)
@@ -39,8 +26,9 @@ int hs_keyframe_reference_device(hs_orb* h, int n, const hs_track_state* st, con
     if (!h) return HS_ERR_INVALID;
     if (!n_ok(n) || !state_ok(st) || !vote_table_ok(T) || !d_ref_slot || !d_result || !d_work) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
-    const Work w(d_work, n);
+    hipStream_t s = hs_stream_or(h, stream);
+    HsWorkCursor c(d_work);
+    const HsKeyframeWork w(c, n, T->n_kf);                       // the caller's kf_cap is at least T->n_kf (HsKeyframeWork)
     hs_launch_kfd_ref_begin(n, w.q_off, s);
     int rc = hs_frame_views_device(h, n, st->kp_lm, st->kp_outl, st->n_matches, T, 1, st->kp_lm_obs, s);                // removeLandMarkAssociation of bad landmarks (:290)
     if (rc != HS_OK) return rc;
@@ -56,7 +44,7 @@ int hs_keyframe_gate_device(hs_orb* h, const hs_track_result* d_track_result, co
     if (!h) return HS_ERR_INVALID;
     if (!prm || !d_result || (prm->ok_override < 0 && !d_track_result)) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_kfd_gate(d_track_result, *prm, d_result, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_kfd_gate(d_track_result, *prm, d_result, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -66,7 +54,7 @@ int hs_keyframe_clean_device(hs_orb* h, int n, const hs_track_state* st, const h
     if (!h) return HS_ERR_INVALID;
     if (!n_ok(n) || !state_ok(st) || !table_ok(T) || !d_result) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_kfd_clean(n, *st, *T, d_result, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_kfd_clean(n, *st, *T, d_result, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -79,7 +67,7 @@ int hs_keyframe_need_device(hs_orb* h, int n, int sensor, const float* d_depth, 
         !d_result)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_kfd_need(n, sensor, d_depth, *st, *T, *K, d_ref_slot, d_track_result, *prm, d_result, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_kfd_need(n, sensor, d_depth, *st, *T, *K, d_ref_slot, d_track_result, *prm, d_result, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -91,10 +79,11 @@ int hs_keyframe_create_device(hs_orb* h, const hs_frame_view* F, const float* d_
     if (!F || !n_ok(F->n) || !F->kps || !F->desc || !d_depth || !d_Tcw || !state_ok(st) || !table_ok(T) || !prm || !out_ok(out, new_cap) || !d_work)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    hipStream_t s = hs_stream_or(h, stream);
     const int rc = hs_pose_views_device(h, d_Tcw, out->pose_view, s);                                                  // current_frame.UpdatePoseMatrices() (:32)
     if (rc != HS_OK) return rc;
-    hs_launch_kfd_create(*F, d_depth, *st, *T, *prm, new_cap, *out, Work(d_work, F->n).keys, s);
+    HsWorkCursor c(d_work);
+    hs_launch_kfd_create(*F, d_depth, *st, *T, *prm, new_cap, *out, HsKeyframeWork(c, F->n, T->n_kf).keys, s);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -104,7 +93,7 @@ int hs_keyframe_discard_device(hs_orb* h, int n, const hs_track_state* st, hs_ke
     if (!h) return HS_ERR_INVALID;
     if (!n_ok(n) || !state_ok(st) || !d_result) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_kfd_discard(n, *st, d_result, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_kfd_discard(n, *st, d_result, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }

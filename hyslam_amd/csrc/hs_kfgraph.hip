@@ -210,7 +210,7 @@ int hs_kf_votes_device(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* d_
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     const KfVoteArgs a{T->L, T->n_kf, count_bad_kf ? 1 : 0, th, cap, 0, T->lm_obs_offsets, T->lm_obs_kf, T->lm_bad, T->kf_bad, T->kf_id,
                        d_q_offsets, d_q_lm, d_q_self_id, d_weights, d_weights, d_max_slot, d_max_count, d_ordered_slot, d_ordered_weight, d_n_ordered};
-    launch_votes(a, Q, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    launch_votes(a, Q, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -267,7 +267,7 @@ int hs_kf_redundancy_device(hs_orb* h, const hs_kf_table* T, int C, const int32_
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     const KfRedArgs a{T->L, is_mono ? 1 : 0, th_obs, frac_redundant, T->lm_obs_offsets, T->lm_obs_kf, T->lm_obs_octave, T->lm_bad, T->lm_nobs,
                       d_cand_slot, d_cand_th_depth, d_cand_offsets, d_item_lm, d_item_octave, d_item_depth, d_n_mps, d_n_redundant, d_cull};
-    hipLaunchKernelGGL(k_kf_redundancy, dim3(C), dim3(KF_RED_THREADS), 0, stream ? (hipStream_t)stream : hs_orb_stream_of(h), a);
+    hipLaunchKernelGGL(k_kf_redundancy, dim3(C), dim3(KF_RED_THREADS), 0, hs_stream_or(h, stream), a);
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }

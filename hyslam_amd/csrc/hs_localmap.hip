@@ -5,14 +5,39 @@
 #include "hs_internal.h"
 
 namespace {
-size_t lp_blocks(int L) { return ((size_t)std::max(L, 0) + HS_LOCAL_POINTS_BLOCK - 1) / HS_LOCAL_POINTS_BLOCK; }
-const size_t LM_WORK_HEAD = 256;       // hs_local_map_search_device: q_offsets [2] int64, then n_ordered int32, in front of the local-points work
+// the vote, the local key frames, the local points, the gather and the search on one stream; d_pose (may be nullptr): the search reads the pose from it
+int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
+                     const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (!T || !out || !d_work || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
+        !out->frame_remove || !out->sel || !out->n_sel || !out->lms || !out->match_idx || !out->match_dist || !out->n_matches)
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    hipStream_t s = hs_stream_or(h, stream);
+    HsWorkCursor c(d_work);
+    const HsLocalMapWork w(c, T->L);
+    hs_launch_local_map_query(n_assoc, w.q_off, s);
+    // keyframeCounter with the bad key frames in it, pKFmax among those that are not bad; no ordered list (TrackLocalMap.cpp:80-123)
+    int rc = hs_kf_votes_device(h, T, 1, w.q_off, d_frame_lm, nullptr, 1, 1, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, w.n_ordered, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_local_keyframes_device(h, T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes,
+                                   out->local, out->n_local, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_local_points_device(h, T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, w.points.base, s);
+    if (rc != HS_OK) return rc;
+    rc = hs_landmark_gather_device(h, d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
+    if (rc != HS_OK) return rc;
+    if (d_pose) return hs_search_by_projection_posed_device(h, F, d_pose, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
+    return hs_search_by_projection_device(h, F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
+}
 }  // namespace
 
 extern "C" {
 
-size_t hs_local_points_work_bytes(int L) { return hs_local_points_flag_bytes(L) + ((lp_blocks(L) * sizeof(int32_t) + 255) & ~(size_t)255) + 256; }
-size_t hs_local_map_work_bytes(int L) { return LM_WORK_HEAD + hs_local_points_work_bytes(L); }
+size_t hs_local_points_work_bytes(int L) { return HsLocalPointsWork::bytes(L); }
+size_t hs_local_map_work_bytes(int L) { return HsLocalMapWork::bytes(L); }
 
 int hs_local_keyframes_device(hs_orb* h, int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap,
                               const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* d_local, int32_t* d_n_local, void* stream)
@@ -22,7 +47,7 @@ int hs_local_keyframes_device(hs_orb* h, int n_kf, const int32_t* d_weights, con
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     hs_launch_local_keyframes(n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local, d_n_local,
-                              stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+                              hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -56,7 +81,8 @@ int hs_local_points_device(hs_orb* h, const hs_kf_table* T, const uint8_t* d_loc
         (T->L > 0 && (!T->lm_obs_offsets || !T->lm_bad)) || (T->n_kf > 0 && !d_local))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_local_points(*T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, d_work, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HsWorkCursor c(d_work);
+    hs_launch_local_points(*T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, HsLocalPointsWork(c, T->L), hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -86,7 +112,8 @@ int hs_local_points(hs_orb* h, const hs_kf_table* T, const uint8_t* local, const
     if (rc != HS_OK) return rc;
     D.lm_obs_offsets = d_off; D.lm_obs_kf = d_kf; D.lm_bad = d_bad;
     D.lm_obs_octave = nullptr; D.lm_nobs = nullptr; D.kf_bad = nullptr; D.kf_id = nullptr;
-    hs_launch_local_points(D, d_local, d_flm, n_assoc, d_rem, d_sel, cap, d_n, d_work, st.stream());
+    HsWorkCursor c(d_work);
+    hs_launch_local_points(D, d_local, d_flm, n_assoc, d_rem, d_sel, cap, d_n, HsLocalPointsWork(c, L), st.stream());
     return st.finish();
 }
 
@@ -96,16 +123,11 @@ int hs_landmark_gather_device(hs_orb* h, const hs_landmark* d_lms, int L, const 
     if (L < 0 || cap < 0 || !d_n_sel || (cap > 0 && (!d_sel || !d_out)) || (L > 0 && !d_lms) || ((uintptr_t)d_lms & 15) || ((uintptr_t)d_out & 15))
         return hs_fail(h, HS_ERR_INVALID, "bad argument (d_lms and d_out are 16-byte aligned)");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_landmark_gather(d_lms, L, d_sel, d_n_sel, cap, d_out, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_landmark_gather(d_lms, L, d_sel, d_n_sel, cap, d_out, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
 
-namespace {
-int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
-                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
-                     const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream);
-}
 int hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
                                const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
                                const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
@@ -126,33 +148,3 @@ int hs_local_map_search_posed_device(hs_orb* h, const hs_kf_table* T, const int3
 }
 
 }  // extern "C"
-
-namespace {
-int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
-                     const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
-                     const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
-{
-    if (!h) return HS_ERR_INVALID;
-    if (!T || !out || !d_work || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
-        !out->frame_remove || !out->sel || !out->n_sel || !out->lms || !out->match_idx || !out->match_dist || !out->n_matches)
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    void* s = stream ? stream : (void*)hs_orb_stream_of(h);
-    int64_t* d_q_off = static_cast<int64_t*>(d_work);
-    int32_t* d_n_ordered = reinterpret_cast<int32_t*>(d_q_off + 2);
-    void* d_lp_work = static_cast<uint8_t*>(d_work) + LM_WORK_HEAD;
-    hs_launch_local_map_query(n_assoc, d_q_off, (hipStream_t)s);
-    // keyframeCounter with the bad key frames in it, pKFmax among those that are not bad; no ordered list (TrackLocalMap.cpp:80-123)
-    int rc = hs_kf_votes_device(h, T, 1, d_q_off, d_frame_lm, nullptr, 1, 1, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, d_n_ordered, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_local_keyframes_device(h, T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes,
-                                   out->local, out->n_local, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_local_points_device(h, T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, d_lp_work, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_landmark_gather_device(h, d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
-    if (rc != HS_OK) return rc;
-    if (d_pose) return hs_search_by_projection_posed_device(h, F, d_pose, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
-    return hs_search_by_projection_device(h, F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
-}
-}  // namespace

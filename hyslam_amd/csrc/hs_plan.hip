@@ -64,7 +64,7 @@ Refusal plan_levels(const HsPlanInput& in, HsPlan& P)
         V.scale = in.scale[l];
         V.kp_size = (float)(int)(31 * in.scale[l]);              // ORBExtractor.cpp:478
     }
-    P.pyr_per_img = (pyr_per_img + 255) & ~(size_t)255;
+    P.pyr_per_img = hs_up256(pyr_per_img);
     for (int l = 0; l < L; l++) {
         P.lv[l].img_stride = P.pyr_per_img;
         P.max_wcell = std::max(P.max_wcell, P.lv[l].wcell); P.max_hcell = std::max(P.max_hcell, P.lv[l].hcell);

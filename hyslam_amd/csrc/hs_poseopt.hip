@@ -17,7 +17,7 @@ int hs_pose_optimize_device(hs_orb* h, int Q, const hs_pose_problem* d_problems,
         ((uintptr_t)d_edges & 15))
         return hs_fail(h, HS_ERR_INVALID, "bad argument (exactly one of d_edge_offsets and d_n_edges; d_n_edges needs Q == 1; d_edges is 16-byte aligned)");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_pose_optimize(Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_outlier, d_results, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_pose_optimize(Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_outlier, d_results, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -51,7 +51,7 @@ int hs_pose_edges_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d
     if (!F || F->n < 0 || L < 0 || cap < 0 || !d_n_edges || (cap > 0 && !d_edges) || (F->n > 0 && (!F->kps || !d_kp_lm)) || (L > 0 && !d_lms))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_pose_edges(*F, d_lms, L, d_kp_lm, sigma_ref, d_edges, cap, d_n_edges, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_pose_edges(*F, d_lms, L, d_kp_lm, sigma_ref, d_edges, cap, d_n_edges, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }

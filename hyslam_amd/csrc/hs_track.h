@@ -5,11 +5,12 @@
 
 #define HS_TRACK_BLOCK 256         // threads per workgroup of the per-view / per-op kernels
 
+inline bool state_ok(const hs_track_state* s) { return s && s->kp_lm && s->kp_outl && s->n_matches && s->kp_lm_obs; }
+
 // d_problem (may be nullptr): the optimiser's hs_pose_problem = the pose with F's camera (F: host struct, only fx .. mbf are read)
 void hs_launch_pose_view(const float* d_Tcw, hs_pose_view* d_out, hs_pose_problem* d_problem, const hs_frame_view* F, hipStream_t s);
-size_t hs_assoc_work_bytes(int n, int L);      // minw, maxw, erased [n] and jk [L], int32
 void hs_launch_frame_associate(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int n_ops, const int32_t* d_op_view, const int32_t* d_op_lm,
-                               void* d_work, hipStream_t s);
+                               const HsAssocWork& w, hipStream_t s);
 void hs_launch_frame_views(int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const hs_kf_table& T, int drop_bad, int32_t* d_kp_lm_obs, hipStream_t s);
 void hs_launch_track_discard(int mode, const hs_pose_edge* d_edges, const int32_t* d_n_edges, int edge_cap, const uint8_t* d_outlier, const hs_pose_result* d_result,
                              const hs_kf_table& T, int sensor, int n, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int32_t* d_counts, hipStream_t s);
@@ -23,9 +24,8 @@ void hs_launch_track_gate(const hs_track_result* d_result, int32_t* d_n_edges /*
 void hs_launch_search_by_bow_kf(const hs_kf_features& K, const int32_t* d_kf_slot, const hs_kf_table& T, const hs_keypoint* d_kps, const uint8_t* d_desc,
                                 const int32_t* d_node, const float* d_weight /*may be nullptr*/, int n, float th_low, float nnratio, int32_t* d_match_kf, int kf_cap,
                                 int32_t* d_op_view, int32_t* d_op_lm, int32_t* d_n_matches, hipStream_t s);
-size_t hs_vassoc_work_bytes(int n, int L);     // view_op [n], lm_view [L], idx_old [L], int32
 void hs_launch_frame_associate_views(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view, const int32_t* d_op_lm,
-                                     void* d_work, hipStream_t s);
+                                     const HsVassocWork& w, hipStream_t s);
 
 // ---- reference key frame, key-frame decision, stereo landmark creation (kernels_keyframe.hip; entry points in hs_keyframe.hip).  Every kernel reads
 // its gate (ok / insert / n_processed) from *d_result, where an earlier launch left it.

@@ -6,14 +6,12 @@
 #include <cstddef>
 
 namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool out_ok(const hs_track_out* o)
 {
     return o && o->pose_view && o->problem && o->last_lms && o->narrow_idx && o->narrow_dist && o->narrow_n && o->wide_idx && o->wide_dist && o->wide_n && o->op_view &&
            o->edges_motion && o->outlier_motion && o->n_edges_motion && o->pose_motion && o->edges_local && o->outlier_local && o->n_edges_local && o->pose_local &&
            o->result && !((uintptr_t)o->last_lms & 15) && !((uintptr_t)o->edges_motion & 15) && !((uintptr_t)o->edges_local & 15);
 }
-bool state_ok(const hs_track_state* s) { return s && s->kp_lm && s->kp_outl && s->n_matches && s->kp_lm_obs; }
 hs_proj_params proj_params(float th, float ratio, const hs_track_params& tp, bool last_frame)
 {
     hs_proj_params pp{};
@@ -26,12 +24,7 @@ hs_proj_params proj_params(float th, float ratio, const hs_track_params& tp, boo
 
 extern "C" {
 
-// the replay's arrays and the local map's work area follow each other: a chain uses them one after the other, but never has to think about it
-size_t hs_track_work_bytes(int n, int n_last, int L, int cap)
-{
-    (void)n_last; (void)cap;
-    return up256(hs_assoc_work_bytes(n, L)) + up256(hs_local_map_work_bytes(L)) + 256;
-}
+size_t hs_track_work_bytes(int n, int n_last, int L, int cap) { (void)n_last; (void)cap; return HsTrackWork::bytes(n, L); }
 
 int hs_device_alloc(hs_orb* h, size_t bytes, void** out)
 {
@@ -58,7 +51,7 @@ int hs_device_copy(hs_orb* h, void* dst, const void* src, size_t bytes, int kind
     if (!h) return HS_ERR_INVALID;
     if ((kind != 1 && kind != 2) || (bytes > 0 && (!dst || !src))) return hs_fail(h, HS_ERR_INVALID, "bad argument (kind: 1 host to device, 2 device to host)");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    HIP_TRY(h, hipStreamSynchronize(stream ? (hipStream_t)stream : hs_orb_stream_of(h)));
+    HIP_TRY(h, hipStreamSynchronize(hs_stream_or(h, stream)));
     if (bytes > 0) HIP_TRY(h, hipMemcpy(dst, src, bytes, kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return HS_OK;
 }
@@ -68,7 +61,7 @@ int hs_pose_views_device(hs_orb* h, const float* d_Tcw, hs_pose_view* d_out, voi
     if (!h) return HS_ERR_INVALID;
     if (!d_Tcw || !d_out) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_pose_view(d_Tcw, d_out, nullptr, nullptr, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_pose_view(d_Tcw, d_out, nullptr, nullptr, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -80,7 +73,8 @@ int hs_frame_associate_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t
     if (n < 0 || L < 0 || n_ops < 0 || !d_n_matches || !d_work || (n > 0 && (!d_kp_lm || !d_kp_outl)) || (n_ops > 0 && (!d_op_view || !d_op_lm)))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_frame_associate(n, L, d_kp_lm, d_kp_outl, d_n_matches, n_ops, d_op_view, d_op_lm, d_work, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HsWorkCursor c(d_work);
+    hs_launch_frame_associate(n, L, d_kp_lm, d_kp_outl, d_n_matches, n_ops, d_op_view, d_op_lm, HsAssocWork(c, n, L), hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -93,7 +87,7 @@ int hs_frame_views_device(hs_orb* h, int n, int32_t* d_kp_lm, uint8_t* d_kp_outl
         (drop_bad && (!d_kp_outl || !d_n_matches || (T->L > 0 && !T->lm_bad))))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_frame_views(n, d_kp_lm, d_kp_outl, d_n_matches, *T, drop_bad ? 1 : 0, d_kp_lm_obs, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    hs_launch_frame_views(n, d_kp_lm, d_kp_outl, d_n_matches, *T, drop_bad ? 1 : 0, d_kp_lm_obs, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -109,7 +103,7 @@ int hs_track_discard_device(hs_orb* h, int mode, const hs_pose_edge* d_edges, co
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     hs_launch_track_discard(mode, d_edges, d_n_edges, edge_cap, d_outlier, d_result, *T, sensor, 65536, d_kp_lm, d_kp_outl, d_n_matches, d_counts,
-                            stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+                            hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -123,8 +117,10 @@ int hs_track_motion_model_device(hs_orb* h, const hs_frame_view* F, const float*
         ((uintptr_t)d_lms & 15) || !tp || !state_ok(st) || !out_ok(out) || !d_work)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    hipStream_t s = hs_stream_or(h, stream);
     const int n = F->n, L = T->L;
+    HsWorkCursor c(d_work);
+    const HsTrackWork w(c, n, L);
     hs_frame_view Fs = *F;
     Fs.kp_lm_obs = st->kp_lm_obs;
     hs_launch_pose_view(d_Tcw_pred, &out->pose_view[0], &out->problem[0], F, s);                                  // current_frame.SetPose(Tcw_cur)
@@ -136,7 +132,7 @@ int hs_track_motion_model_device(hs_orb* h, const hs_frame_view* F, const float*
     rc = hs_search_by_projection_posed_device(h, &Fs, &out->pose_view[0], out->last_lms, n_last, &wide, out->wide_idx, out->wide_dist, out->wide_n, s);
     if (rc != HS_OK) return rc;
     hs_launch_track_select(n_last, out->narrow_idx, out->narrow_n, out->wide_idx, out->wide_n, tp->n_min_matches, out->op_view, out->result, s);
-    hs_launch_frame_associate(n, L, st->kp_lm, st->kp_outl, st->n_matches, n_last, out->op_view, d_last_kp_lm, d_work, s);
+    hs_launch_frame_associate(n, L, st->kp_lm, st->kp_outl, st->n_matches, n_last, out->op_view, d_last_kp_lm, w.assoc, s);
     rc = hs_pose_edges_device(h, &Fs, d_lms, L, st->kp_lm, tp->sigma_ref, out->edges_motion, n, &out->n_edges_motion[0], nullptr, s);
     if (rc != HS_OK) return rc;
     hs_launch_track_gate(out->result, out->n_edges_motion, s);                                                     // `return -1` ahead of PoseOptimization
@@ -157,18 +153,19 @@ int hs_track_local_map_device(hs_orb* h, const hs_frame_view* F, const float* d_
         !tp || !state_ok(st) || !out_ok(out) || !d_work)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    hipStream_t s = hs_stream_or(h, stream);
     const int n = F->n, L = T->L;
+    HsWorkCursor c(d_work);
+    const HsTrackWork w(c, n, L);
     hs_frame_view Fs = *F;
     Fs.kp_lm_obs = st->kp_lm_obs;
-    void* d_lm_work = static_cast<uint8_t*>(d_work) + up256(hs_assoc_work_bytes(n, L));
     hs_launch_pose_view(d_Tcw_in, &out->pose_view[1], &out->problem[1], F, s);
     hs_launch_frame_views(n, st->kp_lm, st->kp_outl, st->n_matches, *T, 1, st->kp_lm_obs, s);                     // SearchLocalPoints :56-67
     const hs_proj_params pp = proj_params(tp->th_local, tp->nnratio_local, *tp, false);
     int rc = hs_local_map_search_posed_device(h, T, st->kp_lm, n, d_neigh, neigh_cap, d_parent, tp->n_max_local_keyframes, tp->n_neighbor_keyframes, &Fs,
-                                              &out->pose_view[1], d_lms, &pp, cap, &out->local, d_lm_work, s);
+                                              &out->pose_view[1], d_lms, &pp, cap, &out->local, w.local_map.base, s);
     if (rc != HS_OK) return rc;
-    hs_launch_frame_associate(n, L, st->kp_lm, st->kp_outl, st->n_matches, cap, out->local.match_idx, out->local.sel, d_work, s);
+    hs_launch_frame_associate(n, L, st->kp_lm, st->kp_outl, st->n_matches, cap, out->local.match_idx, out->local.sel, w.assoc, s);
     rc = hs_pose_edges_device(h, &Fs, d_lms, L, st->kp_lm, tp->sigma_ref, out->edges_local, n, out->n_edges_local, nullptr, s);
     if (rc != HS_OK) return rc;
     rc = hs_pose_optimize_device(h, 1, &out->problem[1], nullptr, out->n_edges_local, n, out->edges_local, out->outlier_local, out->pose_local, nullptr, s);

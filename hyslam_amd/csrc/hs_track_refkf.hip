@@ -5,17 +5,12 @@
 #include <cstddef>
 
 namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool feats_ok(const hs_kf_features* K) { return K && K->n_kf >= 0 && K->kf_off && K->kps && K->desc && K->node && K->kp_lm; }
 }  // namespace
 
 extern "C" {
 
-size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L)
-{
-    (void)kf_cap;
-    return up256(hs_vassoc_work_bytes(n, L));
-}
+size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L) { (void)kf_cap; return HsVassocWork::bytes(n, L); }
 
 int hs_search_by_bow_kf_device(hs_orb* h, const hs_kf_features* K, const int32_t* d_kf_slot, const hs_kf_table* T, const hs_keypoint* d_kps, const uint8_t* d_desc,
                                const int32_t* d_node, const float* d_weight, int n, float th_low, float nnratio, int32_t* d_match_kf, int kf_cap, int32_t* d_op_view,
@@ -28,7 +23,7 @@ int hs_search_by_bow_kf_device(hs_orb* h, const hs_kf_features* K, const int32_t
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     hs_launch_search_by_bow_kf(*K, d_kf_slot, *T, d_kps, d_desc, d_node, d_weight, n, th_low, nnratio, d_match_kf, kf_cap, d_op_view, d_op_lm, d_n_matches,
-                               stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+                               hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -39,7 +34,8 @@ int hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, u
     if (!h) return HS_ERR_INVALID;
     if (n < 0 || L < 0 || !d_n_matches || !d_work || (n > 0 && (!d_kp_lm || !d_kp_outl || !d_op_view || !d_op_lm))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_frame_associate_views(n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    HsWorkCursor c(d_work);
+    hs_launch_frame_associate_views(n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, HsVassocWork(c, n, L), hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }

@@ -299,7 +299,7 @@ int hs_bow_transform_device(hs_orb* h, const hs_vocab_dev* v, const uint8_t* d_d
     if (n_max < 0 || (n_max > 0 && (!d_desc || !d_word || !d_weight || !d_node)) || v->device != hs_orb_device_of(h)) { hs_set_error(h, "bad argument"); return HS_ERR_INVALID; }
     if (n_max == 0) return HS_OK;
     if (hipSetDevice(v->device) != hipSuccess) return HS_ERR_HIP;
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    hipStream_t s = hs_stream_or(h, stream);
     hipLaunchKernelGGL(k_bow_transform_dev, dim3((n_max + 255) / 256), dim3(256), 0, s, tree_of(v), d_desc, d_n, n_max, d_word, d_weight, d_node);
     if (hipGetLastError() != hipSuccess) { hs_set_error(h, "k_bow_transform_dev launch failed"); return HS_ERR_HIP; }
     return HS_OK;
@@ -313,7 +313,7 @@ int hs_records_bow_match_device(hs_orb* h, hs_vocab_dev* v, const uint8_t* d_rec
     if (!d_records || world < 1 || world > 65535 || rank < 0 || rank >= world || cap < 1 || cap > 65535 || record_stride < hs_record_bytes(cap) ||
         (record_stride & 3) || ((uintptr_t)d_records & 15) || !d_match12 || !d_n_matches || v->device != hs_orb_device_of(h)) { hs_set_error(h, "bad argument"); return HS_ERR_INVALID; }
     if (hipSetDevice(v->device) != hipSuccess) return HS_ERR_HIP;
-    hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    hipStream_t s = hs_stream_or(h, stream);
     const size_t feats = (size_t)world * cap;
     if (feats > v->cap_feats || (size_t)world > v->cap_records) {             // scratch grows; steady state allocates nothing
         // the scratch belongs to the vocabulary object, which callers may have used on another stream before: drain the whole device (rare path)
@@ -358,7 +358,7 @@ int hs_bow_vector_device(hs_orb* h, const int32_t* d_word, const float* d_weight
         hs_set_error(h, "bad argument (n_max <= 16384)"); return HS_ERR_INVALID;
     }
     if (hipSetDevice(hs_orb_device_of(h)) != hipSuccess) return HS_ERR_HIP;
-    return bowv_launch(h, d_word, d_weight, d_n, n_max, d_out_word, d_out_value, d_m, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    return bowv_launch(h, d_word, d_weight, d_n, n_max, d_out_word, d_out_value, d_m, hs_stream_or(h, stream));
 }
 
 int hs_bow_vector(hs_orb* h, const int32_t* word, const float* weight, int n, int32_t* out_word, double* out_value, int32_t* m)

@@ -239,7 +239,7 @@ int hs_landmark_best_descriptors_device(hs_orb* h, const int64_t* d_offsets, con
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     if (L == 0) return HS_OK;
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    launch_landmark_best(d_offsets, d_desc, L, d_best, d_median, true, stream ? (hipStream_t)stream : hs_orb_stream_of(h));
+    launch_landmark_best(d_offsets, d_desc, L, d_best, d_median, true, hs_stream_or(h, stream));
     HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
@@ -288,7 +288,7 @@ int hs_landmark_update_entries_device(hs_orb* h, const hs_lm_entry_params* param
         ((uintptr_t)d_entries & 3) || ((uintptr_t)d_obs & 3) || ((uintptr_t)d_lms & 3) || ((uintptr_t)d_lm_index & 3))
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    const hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(h);
+    const hipStream_t s = hs_stream_or(h, stream);
     const LmEntryArgs a{*params, L, d_entries, d_obs_offsets, d_obs, d_desc_offsets, d_desc, d_best,
                         d_normal, d_min_dist, d_max_dist, d_mean_dist, d_size, d_flags, d_lms, d_lm_index, n_lms};
     launch_landmark_best(d_desc_offsets, d_desc, L, d_best, d_median, true, s);

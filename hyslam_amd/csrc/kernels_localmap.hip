@@ -166,19 +166,17 @@ void hs_launch_local_keyframes(int n_kf, const int32_t* d_weights, const uint8_t
     hipLaunchKernelGGL(k_local_keyframes, dim3(1), dim3(LK_THREADS), 0, s, n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max, n_neighbor, d_local, d_n_local);
 }
 
-size_t hs_local_points_flag_bytes(int L) { return ((size_t)std::max(L, 0) + 255) & ~(size_t)255; }
-
 void hs_launch_local_points(const hs_kf_table& T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
-                            int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, hipStream_t s)
+                            int32_t* d_sel, int cap, int32_t* d_n_sel, const HsLocalPointsWork& w, hipStream_t s)
 {
-    const int L = T.L, n_blocks = (int)(((int64_t)L + LP_THREADS - 1) / LP_THREADS);
-    uint8_t* flag = static_cast<uint8_t*>(d_work);
-    int32_t* block_cnt = reinterpret_cast<int32_t*>(flag + hs_local_points_flag_bytes(L));
+    const int L = T.L, n_blocks = w.n_blocks;
+    uint8_t* flag = w.flag;
+    int32_t* block_cnt = w.block_cnt;
     if (L > 0) (void)hipMemsetAsync(flag, 0, (size_t)L, s);
     if (n_assoc > 0) hipLaunchKernelGGL(k_lp_mark, dim3((n_assoc + 255) / 256), dim3(256), 0, s, L, T.lm_bad, d_frame_lm, n_assoc, d_frame_remove, flag);
-    if (n_blocks > 0) hipLaunchKernelGGL(k_lp_count, dim3(n_blocks), dim3(LP_THREADS), 0, s, L, T.n_kf, T.lm_obs_offsets, T.lm_obs_kf, T.lm_bad, d_local, flag, block_cnt);
-    hipLaunchKernelGGL(k_lp_scan, dim3(1), dim3(LP_THREADS), 0, s, n_blocks, block_cnt, d_n_sel);
-    hipLaunchKernelGGL(k_lp_scatter, dim3(std::max(n_blocks, 1)), dim3(LP_THREADS), 0, s, L, n_blocks, flag, block_cnt, d_n_sel, d_sel, cap);
+    if (n_blocks > 0) hipLaunchKernelGGL(k_lp_count, dim3(n_blocks), dim3(HS_LOCAL_POINTS_BLOCK), 0, s, L, T.n_kf, T.lm_obs_offsets, T.lm_obs_kf, T.lm_bad, d_local, flag, block_cnt);
+    hipLaunchKernelGGL(k_lp_scan, dim3(1), dim3(HS_LOCAL_POINTS_BLOCK), 0, s, n_blocks, block_cnt, d_n_sel);
+    hipLaunchKernelGGL(k_lp_scatter, dim3(std::max(n_blocks, 1)), dim3(HS_LOCAL_POINTS_BLOCK), 0, s, L, n_blocks, flag, block_cnt, d_n_sel, d_sel, cap);
 }
 
 void hs_launch_landmark_gather(const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out, hipStream_t s)

@@ -392,7 +392,7 @@ int hs_place_db_add_device(hs_place_db* db, uint64_t key, const int32_t* d_word,
     PL_TRY(db, hipSetDevice(db->device));
     const int st = pl_reserve(db, m_max);
     if (st != HS_OK) return st;
-    const hipStream_t s = stream ? (hipStream_t)stream : hs_orb_stream_of(db->h);
+    const hipStream_t s = hs_stream_or(db->h, stream);
     const int64_t at = db->pool_used;
     if (m_max) {
         PL_TRY(db, hipMemcpyAsync(db->d_pw + at, d_word, (size_t)m_max * 4, hipMemcpyDeviceToDevice, s));
@@ -455,7 +455,7 @@ static int pl_query_device_checked(hs_place_db* db, int loop, const int32_t* d_q
         return pl_fail(db, HS_ERR_INVALID, "bad argument");
     PL_TRY(db, hipSetDevice(db->device));
     return pl_query(db, loop, d_qword, d_qvalue, d_qm, qm_max, d_exclude, min_score, d_neigh, d_cand_slot, cap, d_n_cand, d_words, d_score, d_acc, d_best,
-                    stream ? (hipStream_t)stream : hs_orb_stream_of(db->h));
+                    hs_stream_or(db->h, stream));
 }
 
 int hs_place_query_reloc_device(hs_place_db* db, const int32_t* d_qword, const double* d_qvalue, const int32_t* d_qm, int qm_max, const int32_t* d_neigh,

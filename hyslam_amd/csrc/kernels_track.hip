@@ -204,14 +204,11 @@ void hs_launch_pose_view(const float* d_Tcw, hs_pose_view* d_out, hs_pose_proble
     hipLaunchKernelGGL(k_pose_view, dim3(1), dim3(64), 0, s, d_Tcw, d_out, d_problem, F ? F->fx : 0.f, F ? F->fy : 0.f, F ? F->cx : 0.f, F ? F->cy : 0.f, F ? F->mbf : 0.f, -1.0);
 }
 
-size_t hs_assoc_work_bytes(int n, int L) { return ((size_t)std::max(n, 0) * 3 + (size_t)std::max(L, 0)) * sizeof(int32_t) + 256; }
-
 void hs_launch_frame_associate(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, int n_ops, const int32_t* d_op_view, const int32_t* d_op_lm,
-                               void* d_work, hipStream_t s)
+                               const HsAssocWork& w, hipStream_t s)
 {
     if (n <= 0 || n_ops <= 0) return;
-    int32_t* minw = static_cast<int32_t*>(d_work);
-    int32_t *maxw = minw + n, *erased = maxw + n, *jk = erased + n;
+    int32_t *minw = w.minw, *maxw = w.maxw, *erased = w.erased, *jk = w.jk;
     hipLaunchKernelGGL(k_assoc_init, trk_grid(std::max(n, n_ops)), dim3(HS_TRACK_BLOCK), 0, s, n, L, d_kp_lm, n_ops, d_op_lm, minw, maxw, erased, jk);
     hipLaunchKernelGGL(k_assoc_writers, trk_grid(n_ops), dim3(HS_TRACK_BLOCK), 0, s, n, L, n_ops, d_op_view, d_op_lm, minw, maxw);
     hipLaunchKernelGGL(k_assoc_holders, trk_grid(n), dim3(HS_TRACK_BLOCK), 0, s, n, L, d_kp_lm, minw, jk);

@@ -171,14 +171,11 @@ void hs_launch_search_by_bow_kf(const hs_kf_features& K, const int32_t* d_kf_slo
     hipLaunchKernelGGL(k_refkf_finish, dim3(1), dim3(1024), 0, s, K, d_kf_slot, kf_cap, d_kps, n, d_match_kf, d_op_view, d_op_lm, d_n_matches);
 }
 
-size_t hs_vassoc_work_bytes(int n, int L) { return ((size_t)std::max(n, 0) + 2 * (size_t)std::max(L, 0)) * sizeof(int32_t) + 256; }
-
 void hs_launch_frame_associate_views(int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view, const int32_t* d_op_lm,
-                                     void* d_work, hipStream_t s)
+                                     const HsVassocWork& w, hipStream_t s)
 {
     if (n <= 0) return;
-    int32_t* view_op = static_cast<int32_t*>(d_work);
-    int32_t *lm_view = view_op + n, *idx_old = lm_view + L;
+    int32_t *view_op = w.view_op, *lm_view = w.lm_view, *idx_old = w.idx_old;
     hipLaunchKernelGGL(k_vassoc_init, rk_grid(n), dim3(HS_TRACK_BLOCK), 0, s, n, L, d_kp_lm, d_op_lm, view_op, lm_view, idx_old);
     hipLaunchKernelGGL(k_vassoc_ops, rk_grid(n), dim3(HS_TRACK_BLOCK), 0, s, n, L, d_op_view, d_op_lm, view_op, lm_view);
     hipLaunchKernelGGL(k_vassoc_holders, rk_grid(n), dim3(HS_TRACK_BLOCK), 0, s, n, L, d_kp_lm, view_op, lm_view, idx_old);
