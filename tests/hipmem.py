@@ -20,8 +20,15 @@ def hip():
         L.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.hipDeviceSynchronize.argtypes = []
         L.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+        L.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
         L.hipStreamSynchronize.argtypes = [C.c_void_p]
         L.hipStreamDestroy.argtypes = [C.c_void_p]
+        L.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+        L.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+        L.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        L.hipEventQuery.argtypes = [C.c_void_p]
+        L.hipEventDestroy.argtypes = [C.c_void_p]
+        L.hipGetLastError.argtypes = []
         _hip = L
     return _hip
 
@@ -62,6 +69,17 @@ class DevBuf:
             _ok(hip().hipMemcpy(out.ctypes.data, self.ptr + offset, out.nbytes, 2), "hipMemcpy D2H")
         return out
 
+    def read_after(self, stream, dtype=np.uint8, count=None, offset=0):
+        """the bytes after waiting for `stream` (a Stream or a raw handle) ALONE: no device-wide wait, a plain blocking hipMemcpy.  What another stream
+        still has to write is not waited for"""
+        dt = np.dtype(dtype)
+        n = (self.nbytes - offset) // dt.itemsize if count is None else count
+        out = np.empty(n, dt)
+        _ok(hip().hipStreamSynchronize(getattr(stream, "ptr", stream)), "hipStreamSynchronize")
+        if out.nbytes:
+            _ok(hip().hipMemcpy(out.ctypes.data, self.ptr + offset, out.nbytes, 2), "hipMemcpy D2H")
+        return out
+
     def fill(self, byte):
         _ok(hip().hipMemset(self.ptr, byte, self.nbytes), "hipMemset")
         _ok(hip().hipStreamSynchronize(None), "hipStreamSynchronize")
@@ -79,9 +97,13 @@ class DevBuf:
 
 
 class Stream:
-    def __init__(self):
+    def __init__(self, non_blocking=False):
+        """non_blocking: hipStreamNonBlocking — not ordered with the NULL stream either, so work that lands there by mistake is not ordered with this one"""
         p = C.c_void_p()
-        _ok(hip().hipStreamCreate(C.byref(p)), "hipStreamCreate")
+        if non_blocking:
+            _ok(hip().hipStreamCreateWithFlags(C.byref(p), 1), "hipStreamCreateWithFlags")
+        else:
+            _ok(hip().hipStreamCreate(C.byref(p)), "hipStreamCreate")
         self.ptr = p.value
 
     def synchronize(self):
@@ -94,6 +116,42 @@ class Stream:
                 self.ptr = 0
         except Exception:
             pass
+
+
+class Event:
+    def __init__(self):
+        p = C.c_void_p()
+        _ok(hip().hipEventCreate(C.byref(p)), "hipEventCreate")
+        self.ptr = p.value
+
+    def record(self, stream):
+        _ok(hip().hipEventRecord(self.ptr, getattr(stream, "ptr", stream)), "hipEventRecord")
+
+    def ready(self):
+        """hipEventQuery: True once everything enqueued in front of the record has completed.  "Not ready" is a status the runtime also keeps as its
+        last error: it is cleared here, or the library's next hipGetLastError() check would report it as a failure of its own launch"""
+        rc = hip().hipEventQuery(self.ptr)
+        hip().hipGetLastError()
+        if rc not in (0, HIP_ERROR_NOT_READY):
+            raise RuntimeError("hipEventQuery failed with hipError %d" % rc)
+        return rc == 0
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                hip().hipEventDestroy(self.ptr)
+                self.ptr = 0
+        except Exception:
+            pass
+
+
+HIP_ERROR_NOT_READY = 600
+
+
+def memset_async(dst, byte, nbytes, stream):
+    """enqueued on `stream`: the host does not wait"""
+    if nbytes:
+        _ok(hip().hipMemsetAsync(dst, byte, nbytes, getattr(stream, "ptr", stream)), "hipMemsetAsync")
 
 
 def copy_async(dst, src, nbytes, stream):
