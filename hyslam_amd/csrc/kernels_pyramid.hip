@@ -275,10 +275,15 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
     pyr_stage_source<NW>(hs_uniform_ptr(sbase + (size_t)Y.sy_first * spitch + X.col0), spitch, s_src, (uint32_t)lds_pitch, nvec, nSr, tx, wave);
     // per-lane column data of one horizontal pass: window position, byte-pair selectors, coefficient pairs
     struct ColData { int wbase, wshift; uint32_t sel[4], coef[4]; };
-    auto col_data = [&](const HsXTab* xt, int dx0, int wmax, int origin) {
+    // (two steps: the four x-table records of a lane are REQUESTED where their addresses are known and turned into column data where they are needed)
+    auto col_fetch = [&](const HsXTab* xt, int dx0, int wmax, uint64_t (&traw)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) traw[i] = hs_gload<uint64_t>(&xt[min(dx0 + i, wmax)]);
+    };
+    auto col_data = [&](const uint64_t (&traw)[4], int origin) {
         HsXTab t[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) t[i] = __builtin_bit_cast(HsXTab, hs_gload<uint64_t>(&xt[min(dx0 + i, wmax)]));
+        for (int i = 0; i < 4; i++) t[i] = __builtin_bit_cast(HsXTab, traw[i]);
         ColData c;
         const int o0 = t[0].sx - origin;
         c.wbase = o0 & ~3; c.wshift = o0 & 3;
@@ -305,10 +310,19 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
         const uint2 H1 = *reinterpret_cast<const uint2*>(h_lane + rec.off1);
         return pyr_vquad(H0, H1, rec.b0, rec.b1);
     };
-    const ColData cA = col_data(F.xtA, ax0 + 4 * tx, F.aw - 1, X.col0);
+    // The level-B records are requested here, next to the level-A ones, and not after the level-A region is made: requested there, every workgroup
+    // waited a full memory round trip for them between its two levels with nothing else to do (two workgroups per CU: nobody to cover it).  They
+    // become column data right after the first horizontal pass — by then they have arrived, and the wait for them there does not have to drain the
+    // level-A stores the way a wait after the row loop would (one counter, in order, for vector loads and stores).
+    uint64_t tA[4], tB[4];
+    col_fetch(F.xtA, ax0 + 4 * tx, F.aw - 1, tA);
+    col_fetch(F.xtB, bx0 + 4 * tx, F.bw - 1, tB);
+    const ColData cA = col_data(tA, X.col0);
     __syncthreads();
     // ---- 2: horizontal sums of the source rows for the level-A columns
     h_pass(s_src, lds_pitch, nSr, cA);
+    const ColData cB = col_data(tB, ax0);
+    asm volatile("" :: "v"(cB.wbase), "v"(cB.wshift), "v"(cB.sel[0]), "v"(cB.sel[1]), "v"(cB.sel[2]), "v"(cB.sel[3]), "v"(cB.coef[0]), "v"(cB.coef[1]), "v"(cB.coef[2]), "v"(cB.coef[3]));      // made HERE, not where first used
     __syncthreads();
     // ---- 3: level-A region -> LDS (it overlays the source rectangle, which is dead now) and, for the owned part, HBM
     {
@@ -333,7 +347,6 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
             arow += NW * (FZ_APITCH / 4); rowp += rstep;
         }
     }
-    const ColData cB = col_data(F.xtB, bx0 + 4 * tx, F.bw - 1, ax0);
     __syncthreads();
     // ---- 4: horizontal sums of the level-A rows for the tile's level-B columns (the sums overlay the level-A sums)
     if (4 * tx < TBX) h_pass(s_a, FZ_APITCH, nAr, cB);

@@ -4,6 +4,23 @@
 TAG=${1:-x}
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT      # a tag used before must not leave its files behind (summarize_profiles.py takes the first match)
+# `collect_profiles.sh TAG counters`: after a change of some kernels' sources, only the passes behind the per-kernel tables and the counters bench.py
+# replays (kernel stats, FETCH / WRITE traffic, SQ counters; each pass a run of its own) — `tools/summarize_profiles.py TAG rNN --kernels k_a,k_b`
+# then replaces those kernels' entries in profiles/rNN_* and leaves every other file and entry alone.  Every step has its own time limit and the
+# first one that fails ends the script: nothing more is started on a GPU that a step has faulted.
+if [ "$2" = counters ]; then
+  set -e -o pipefail
+  export TMPDIR=/tmp
+  Q="--cpu-seconds 0 --pcie-seconds 0 --call-site 0 --latency-calls 0 --copy-gib 0 --min-timed-ms 0"
+  python3 -c "import json; from hyslam_amd._native import source_digests; json.dump(source_digests(), open('$OUT/source_digests.json', 'w'))"
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 20 --warmup 3 $Q > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+  timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 tools/pmc_traffic.py run > /dev/null 2> $OUT/pmc_fetch.err
+  timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 tools/pmc_traffic.py run > /dev/null 2> $OUT/pmc_write.err
+  python3 tools/pmc_traffic.py report $OUT/pmc_fetch $OUT/pmc_write > $OUT/traffic.csv
+  timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CU_CYCLES SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/sq -- python3 bench.py --steps 4 --warmup 1 $Q > /dev/null 2> $OUT/sq.err
+  tail -1 $OUT/bench_under_rocprof.json | cut -c1-400
+  exit 0
+fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python3 -c "import json; from hyslam_amd._native import source_digests; json.dump(source_digests(), open('$OUT/source_digests.json', 'w'))"
 timeout 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err

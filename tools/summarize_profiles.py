@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Turns gpurun_out/prof_TAG (made by tools/collect_profiles.sh on the GPU box) into the committed files under profiles/.
-usage: python tools/summarize_profiles.py TAG PREFIX          e.g.  a r02"""
+usage: python tools/summarize_profiles.py TAG PREFIX          e.g.  a r02
+       python tools/summarize_profiles.py TAG PREFIX --kernels k_resize,k_describe
+           after `collect_profiles.sh TAG counters`: replaces the rows / entries of the kernels whose names start with one of the prefixes in
+           PREFIX_kernel_stats.csv, _pyramid_launches.csv (with k_resize), _hbm_traffic_pmc.csv, _hbm_traffic.json, _sq_counters.csv and
+           _sq_counters.json, and leaves every other kernel's entry (with its source digest) and every other file as committed"""
 import collections
 import csv
 import glob
@@ -26,6 +30,16 @@ def stamp(kernel):
 
 src = "gpurun_out/prof_" + tag
 os.makedirs("profiles", exist_ok=True)
+ONLY = tuple(sys.argv[sys.argv.index("--kernels") + 1].split(",")) if "--kernels" in sys.argv else None
+
+
+def merge_rows(path, new_lines, key, note):
+    """the committed CSV at `path` with the selected kernels' rows replaced by `new_lines` (comment lines and the other kernels' rows stay, one note is added)"""
+    old = open(path).read().splitlines()
+    head = [l for l in old if l.startswith("#") and not l.startswith("# re-collected")]
+    body = [l for l in old if not l.startswith("#")]
+    keep = [body[0]] + [l for l in body[1:] if not key(l).startswith(ONLY)]
+    open(path, "w").write("\n".join(head + ["# re-collected for %s (tag %s) after their sources changed: %s" % (", ".join(ONLY), tag, note)] + keep + new_lines) + "\n")
 import re as _re
 _m = _re.search(r'^DEFAULT_PAIRS = (\d+)', open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py')).read(), _re.M)
 PAIRS, HANDLES = int(os.environ.get('HS_PROFILE_PAIRS', _m.group(1) if _m else 16)), 1          # bench.py's defaults: PAIRS pairs per step on one handle -> every launch sequence covers 2 * PAIRS frames
@@ -40,6 +54,62 @@ def short(name):
     return name.split("(")[0].replace("void ", "").strip()
 
 
+def partial():
+    import io
+    name_of = lambda line: next(csv.reader([line]))[0]
+    # kernel stats: the selected kernels' rows of this run (their percentages are those of this run)
+    rows = [r for r in csv.reader(open(first("stats/**/*kernel_stats.csv")))][1:]
+    out = []
+    for r in rows:
+        r[0] = short(r[0])[:60]
+        if r[0].startswith(ONLY):
+            b = io.StringIO(); csv.writer(b, lineterminator="").writerow(r); out.append(b.getvalue())
+    merge_rows("profiles/%s_kernel_stats.csv" % rnd, out, name_of, "rows of the same command line, percentages of their own run")
+    kt = first("stats/**/*kernel_trace.csv")
+    if kt and any(p.startswith("k_resize") or "k_resize".startswith(p) for p in ONLY):
+        d = collections.defaultdict(list)
+        for r in csv.DictReader(open(kt)):
+            k = short(r["Kernel_Name"])
+            if k.startswith("k_resize"):
+                d[(k, int(r["Grid_Size_X"]) // 256, int(r["Grid_Size_Y"]), int(r["Grid_Size_Z"]))].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+        with open("profiles/%s_pyramid_launches.csv" % rnd, "w") as o:
+            o.write("# per-launch duration of the pyramid kernels by grid (workgroups x, y, frames), rocprofv3 --kernel-trace of the same run (tag %s)\nkernel,grid_x,grid_y,frames,launches,avg_us\n" % tag)
+            for k, v in sorted(d.items(), key=lambda kv: -sum(kv[1])):
+                o.write("%s,%d,%d,%d,%d,%.2f\n" % (k[0], k[1], k[2], k[3], len(v), sum(v) / len(v) / 1e3))
+    # FETCH / WRITE traffic
+    tlines = [l for l in open(os.path.join(src, "traffic.csv")).read().splitlines() if not l.startswith("#") and not l.startswith("kernel,")]
+    merge_rows("profiles/%s_hbm_traffic_pmc.csv" % rnd, [l for l in tlines if l.startswith(ONLY)], lambda l: l, "same passes, same calibration factors")
+    tj = json.load(open("profiles/%s_hbm_traffic.json" % rnd))
+    for r in csv.reader(tlines):
+        if r[0].startswith(ONLY):
+            tj["kernels"][r[0].split("<")[0]] = {"read_MB": float(r[4]), "written_MB": float(r[5]), "frames_per_launch": int(r[6]), "launches": int(r[1]),
+                                                 "launches_per_sequence": int(r[1]) / 3.0, "source_sha16": stamp(r[0])}
+    json.dump(tj, open("profiles/%s_hbm_traffic.json" % rnd, "w"), indent=1)
+    # SQ counters
+    agg = collections.defaultdict(lambda: collections.defaultdict(list))
+    for r in csv.DictReader(open(first("sq/**/*counter_collection.csv"))):
+        k = short(r["Kernel_Name"])
+        if k.startswith("k_"):
+            agg[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
+    n_seq = max([len(next(iter(d.values()))) for k, d in agg.items() if k.startswith("k_fast_rows")] or [5 * HANDLES])
+    sj = json.load(open("profiles/%s_sq_counters.json" % rnd))
+    header = [l for l in open("profiles/%s_sq_counters.csv" % rnd).read().splitlines() if l.startswith("kernel,")][0].split(",")[2:]
+    out = []
+    for k, d in agg.items():
+        if not k.startswith(ONLY):
+            continue
+        n = len(next(iter(d.values())))
+        out.append(k.replace(",", ";") + "," + str(n) + "," + ",".join(str(round(sum(d[c]) / len(d[c]))) for c in header))
+        sj["kernels"][k.split("<")[0]] = dict({c: round(sum(d[c]) / len(d[c])) for c in header}, frames_per_launch=2 * PAIRS // HANDLES, launches=n,
+                                              launches_per_sequence=n / float(n_seq), source_sha16=stamp(k))
+    merge_rows("profiles/%s_sq_counters.csv" % rnd, out, lambda l: l, "same counters, same command line")
+    json.dump(sj, open("profiles/%s_sq_counters.json" % rnd, "w"), indent=1)
+    print("replaced", ", ".join(ONLY), "in profiles/%s_{kernel_stats,pyramid_launches,hbm_traffic_pmc,sq_counters}.csv and _{hbm_traffic,sq_counters}.json" % rnd)
+
+
+if ONLY:
+    partial()
+    sys.exit(0)
 f = first("stats/**/*kernel_stats.csv")
 rows = list(csv.reader(open(f)))
 with open("profiles/%s_kernel_stats.csv" % rnd, "w") as o:
