@@ -8,7 +8,22 @@
  *
  * Threading: a handle is thread-compatible (one thread at a time); distinct handles are fully
  * concurrent — this matches the reference, which runs two separate extractor instances for the
- * left and right image (src/main/ImageProcessing.cpp:31-32,82-84).  No global mutable state.
+ * left and right image (src/main/ImageProcessing.cpp:31-32,82-84).  What a handle reaches that is NOT its own (DESIGN.md 5.17 names the test that
+ * holds each line under concurrent handles):
+ *   - the frame cache (hs_frame_*): one per device and process, 16 slots, guarded by one mutex.  Any thread may publish, find, read by token,
+ *     release and clear at the same time.  A reader of a token gets that frame's exact data, or HS_ERR_INVALID when the slot was pushed out,
+ *     released or cleared meanwhile (the caller then passes host pointers); a slot is never refilled or freed under a reader (publish skips it,
+ *     hs_frame_cache_clear answers HS_ERR_INVALID);
+ *   - the poison mode (hs_debug_poison) and its violation counter: two process-wide atomics.  Setting the mode while other threads are inside
+ *     calls is allowed and takes effect per call; which calls see it is not defined, so a test sets it while nothing else runs;
+ *   - per-device kernel attributes (the raised dynamic-LDS limits of k_resize_chain, once per device, and of k_bow_vector, on every long call):
+ *     idempotent; several threads may race through the first use;
+ *   - the tuning variables (HS_*): read from the environment when a handle is created, a few once per process at their first use.  Creating
+ *     handles on several threads is fine; changing the environment while another thread creates one is the caller's race (getenv);
+ *   - hs_vocab_last_error: per calling thread.  hs_comm_available: loads the collective library once, under std::call_once.
+ * An object made from a handle follows its own rule, stated where it is declared: an hs_vocab_dev may serve hs_bow_transform_device calls of several
+ * handles at once but hs_records_bow_match_device of one caller at a time; an hs_place_db takes one caller at a time (add and erase also wait for
+ * the whole device: other handles' work is waited for, never disturbed).
  *
  * Device pointers: every `*_device` entry point takes pointers into HBM of the handle's device
  * and enqueues work on `stream` (a hipStream_t passed as void*; NULL = the handle's own stream)

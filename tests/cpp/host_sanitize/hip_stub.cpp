@@ -42,17 +42,24 @@ hipError_t hipGetLastError() { return 0; }
 const char* hipGetErrorString(hipError_t) { return "hip_stub"; }
 // live "device" allocations, so that a test can put them back into the state a kernel-less run starts from (hip_stub_zero_device)
 static std::mutex g_dev_mu;
-static std::map<void*, size_t> g_dev;
+// a block's owner is a number handed to each thread once and never again (a std::thread::id is reused after a join: a block that outlives its
+// thread, a published frame for instance, would then pass for a later thread's)
+static std::atomic<unsigned long long> g_next_owner{1};
+static unsigned long long my_owner() { static thread_local const unsigned long long id = g_next_owner++; return id; }
+struct DevBlock { size_t n; unsigned long long owner; };
+static std::map<void*, DevBlock> g_dev;
 hipError_t hipMalloc(void** p, size_t n)
 {
     *p = calloc(n ? n : 1, 1);
-    if (*p) { std::lock_guard<std::mutex> g(g_dev_mu); g_dev[*p] = n; g_c[HS_C_LIVE_DEV]++; g_c[HS_C_MALLOC_CALLS]++; g_c[HS_C_MALLOC_BYTES] += n; }
+    if (*p) { std::lock_guard<std::mutex> g(g_dev_mu); g_dev[*p] = DevBlock{ n, my_owner() }; g_c[HS_C_LIVE_DEV]++; g_c[HS_C_MALLOC_CALLS]++; g_c[HS_C_MALLOC_BYTES] += n; }
     return *p ? 0 : 2;
 }
 hipError_t hipFree(void* p) { { std::lock_guard<std::mutex> g(g_dev_mu); if (g_dev.erase(p)) g_c[HS_C_LIVE_DEV]--; } free(p); return 0; }
 // no kernel writes the outputs here: a reused allocation would hand the host code the last call's uploads as "results" (indices, counts).  Zero
-// everything instead, as a fresh allocation is
-void hip_stub_zero_device() { std::lock_guard<std::mutex> g(g_dev_mu); for (auto& a : g_dev) memset(a.first, 0, a.second); }
+// everything instead, as a fresh allocation is — everything the CALLING THREAD allocated: another thread's handle may be in the middle of a call.
+// (What other threads allocated and left behind, the frames the cache section's publisher threads published for instance, is therefore no longer
+// zeroed by the main thread's later calls: the driver clears the cache at the end of that section.)
+void hip_stub_zero_device() { std::lock_guard<std::mutex> g(g_dev_mu); const auto me = my_owner(); for (auto& a : g_dev) if (a.second.owner == me) memset(a.first, 0, a.second.n); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); if (*p) { g_c[HS_C_LIVE_PIN]++; g_c[HS_C_PIN_CALLS]++; g_c[HS_C_PIN_BYTES] += n; } return *p ? 0 : 2; }
 hipError_t hipHostFree(void* p) { if (p) g_c[HS_C_LIVE_PIN]--; free(p); return 0; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, int k) { count_copy(k, n); memcpy(d, s, n); return 0; }

@@ -5,8 +5,15 @@
 // FAST work items (wide and narrow), quadtree key tables, workspace sizing and uploads; the host-pointer entry points' staging (extract, batch,
 // stereo, the matchers' CSR / scratch handling, and a sweep of all thirteen entry points that stage through HsStage on ONE handle, so that its scratch
 // arena grows and is reused: staged_sweep), the ingest ticket state machine (submit / wait, errors, both slots busy), and the vocabulary
-// loaders on valid, truncated and randomly corrupted text / binary files (hs_vocab_last_error instead of stderr).
+// loaders on valid, truncated and randomly corrupted text / binary files (hs_vocab_last_error instead of stderr); the host-pointer forms of the key-frame
+// graph, the local map and the pose optimiser, the *_work_bytes functions and the `_device` forms of the tracking, reference-key-frame and key-frame
+// stages on work areas of exactly the stated size (map_sweep); the place database's slot mirror, tombstones, both regrow paths and the key-order
+// upload (place_section).  The same file builds under ThreadSanitizer (make SAN=thread): `threads <seed>` runs the sections that share something
+// between threads — handle destruction against the last borrower, the frame cache, the sweeps on four threads with handles of their own, handle
+// churn beside extraction and matching, place databases with and without a mutex, the vocabulary loaders and hs_comm_available's first call.
 // usage: host_sanitize [seed] [geometries] [vocab_cases]      prints "HOST SANITIZE OK ..." (any sanitizer report aborts with a non-zero status)
+//        host_sanitize threads [seed]                         prints "HOST SANITIZE THREADS OK ..."
+//        host_sanitize plan W H [nfeat scale levels [cell]]   the host-side plan of a geometry
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +22,9 @@
 #include <vector>
 #include <thread>
 #include <atomic>
+#include <mutex>
+#include <cmath>
+#include <limits>
 #include <unistd.h>
 #include "../../../include/hyslam_amd.h"
 void hs_orb_borrow(hs_orb* h, int delta);      // hs_api.hip (internal: what hs_comm_create / hs_comm_destroy call)
@@ -27,7 +37,7 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/);        // hs_
 
 #define CHECK(c) do { if (!(c)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
 
-static std::mt19937_64 rng;
+static thread_local std::mt19937_64 rng;      // one per thread: the main thread's is what the seed made it, whatever the other threads draw
 static int rnd(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }
 
 // what the host code asked of the runtime so far, as one line: two commits that claim the same behaviour print the same figures
@@ -163,7 +173,8 @@ static void rand_featvec(int n, int nn, std::vector<int32_t>& id, std::vector<in
 // CSR offsets of L lists with 0..3 entries each
 static std::vector<int64_t> rand_csr(int L) { std::vector<int64_t> o((size_t)L + 1, 0); for (int i = 0; i < L; i++) o[i + 1] = o[i] + rnd(0, 3); return o; }
 
-static int staged_sweep(int rounds)
+// alone: nothing else runs (the live-allocation count and the cache are this call's own to check)
+static int staged_sweep(int rounds, bool alone = true)
 {
     hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300;
     hs_orb *ex = nullptr, *h = nullptr;                          // ex extracts and publishes frames, h is the ONE handle of the sweep
@@ -267,57 +278,405 @@ static int staged_sweep(int rounds)
         }
     }
     hs_orb_destroy(ex); hs_orb_destroy(h);
-    CHECK(hs_frame_cache_clear(0) == HS_OK);                     // (the published frames belong to the cache, not to a handle)
-    CHECK(same_live(before));
+    if (alone) {
+        CHECK(hs_frame_cache_clear(0) == HS_OK);                 // (the published frames belong to the cache, not to a handle)
+        CHECK(same_live(before));
+    }
     return calls > 0 ? 0 : 1;
 }
 
-int main(int argc, char** argv)
+// ---- the key-frame graph, the local map and the pose optimiser by host pointers, the *_work_bytes functions, and the `_device` forms of the
+// tracking, reference-key-frame and key-frame stages ("device" pointers are host memory under the stub; every work area is a vector of exactly
+// *_work_bytes), on ONE handle in a random order, in the style of staged_sweep: counts from [0, 300] with 0 and 1 forced in the first two rounds,
+// every host buffer a std::vector of exactly the documented size, optional arguments toggled, the refusals on the way.
+struct Table {
+    std::vector<int64_t> off, kf_id; std::vector<int32_t> kf, oct, nobs; std::vector<uint8_t> lm_bad, kf_bad;
+    hs_kf_table T;
+};
+static void rand_table(Table& t, int L, int n_kf)
 {
-    if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels [cell]]: the host-side plan of a geometry, or its refusal
-        hs_orb_params p; hs_orb_default_params(&p);
-        p.nfeatures = argc > 4 ? atoi(argv[4]) : 2000; if (argc > 5) p.scale_factor = (float)atof(argv[5]); if (argc > 6) p.nlevels = atoi(argv[6]);
-        if (argc > 7) p.cell_px = atoi(argv[7]);
-        hs_orb* ex = nullptr;
-        CHECK(hs_orb_create(&p, 0, &ex) == HS_OK);
-        const int rc = hs_orb_reserve(ex, atoi(argv[2]), atoi(argv[3]), 2);
-        if (rc != HS_OK) { printf("refused: status %d: %s\n", rc, hs_orb_last_error(ex)); hs_orb_destroy(ex); return 0; }
-        int32_t s[8]; hs_debug_plan_summary(ex, s);
-        printf("pyramid launches: standard plan %d, small-batch plan %d (longest chain %d levels, %d B of LDS, %d workgroups per frame); FAST items per frame: %d wide, %d narrow; levels with quadtree keys: %d\n",
-               s[0], s[1], s[5], s[6], s[7], s[2], s[3], s[4]);
-        printf("plan digest: %016llx\n", (unsigned long long)hs_debug_plan_digest(ex));
-        hs_orb_destroy(ex);
-        return 0;
+    t.off.assign((size_t)L + 1, 0); t.kf.clear(); t.oct.clear();
+    for (int l = 0; l < L; l++) {                               // ascending slots within a landmark
+        const int m = n_kf > 0 ? rnd(0, std::min(3, n_kf)) : 0;
+        for (int j = 0, s = rnd(0, std::max(n_kf - m, 0)); j < m; j++, s++) { t.kf.push_back(s); t.oct.push_back(rnd(0, 7)); }
+        t.off[l + 1] = (int64_t)t.kf.size();
     }
-    const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
-    const int n_geo = argc > 2 ? atoi(argv[2]) : 120, n_voc = argc > 3 ? atoi(argv[3]) : 400;
-    rng.seed(seed);
-    int ndev = 0;
-    CHECK(hs_device_count(&ndev) == HS_OK && ndev == 1);
+    t.nobs.resize(L); t.lm_bad.resize(L); t.kf_bad.resize(n_kf); t.kf_id.resize(n_kf);
+    for (int l = 0; l < L; l++) { t.nobs[l] = (int32_t)(t.off[l + 1] - t.off[l]) + rnd(0, 1); t.lm_bad[l] = rnd(0, 9) == 0; }
+    for (int k = 0; k < n_kf; k++) { t.kf_bad[k] = rnd(0, 9) == 0; t.kf_id[k] = 100 + k; }
+    t.T = hs_kf_table{ L, n_kf, t.off.data(), t.kf.data(), t.oct.data(), t.lm_bad.data(), t.nobs.data(), t.kf_bad.data(), t.kf_id.data() };
+}
+// Q lists of 0..max_len indices below `bound` (none when bound is 0)
+static void rand_lists(int Q, int bound, int max_len, std::vector<int64_t>& off, std::vector<int32_t>& idx)
+{
+    off.assign((size_t)Q + 1, 0); idx.clear();
+    for (int q = 0; q < Q; q++) { const int m = bound > 0 ? rnd(0, max_len) : 0; for (int j = 0; j < m; j++) idx.push_back(rnd(0, bound - 1)); off[q + 1] = (int64_t)idx.size(); }
+}
 
-    // ---- geometry: the fixed shapes of the GPU suites, then the random sweep
-    int accepted = 0, tried = 0;
-    const int fixed[][7] = { {640, 480, 1000, 120, 8, 30, 2}, {1920, 1080, 2000, 120, 8, 30, 2}, {1920, 1080, 2000, 120, 8, 30, 32}, {4000, 3000, 3000, 140, 8, 30, 1},
-                             {643, 481, 700, 120, 8, 30, 1}, {3840, 2160, 2000, 120, 8, 30, 1}, {2560, 40, 500, 120, 3, 30, 1}, {64, 64, 100, 120, 8, 30, 1}, {33, 33, 50, 200, 12, 12, 4},
-                             {1200, 300, 1500, 120, 6, 30, 1}, {1900, 200, 1200, 120, 3, 30, 1}, {16384, 64, 100, 110, 2, 62, 1}, {1920, 1080, 9000, 120, 8, 30, 1}, {800, 600, 1500, 140, 8, 62, 2} };
-    for (const auto& f : fixed) {
-        const int r = geometry_case(f[0], f[1], f[2], f[3] / 100.f, f[4], f[5], f[6], (size_t)f[0] * f[1] * f[6] < 6000000);
-        CHECK(r >= 0); accepted += r; tried++;
+static int map_sweep(int rounds, bool alone = true)
+{
+    hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300;
+    hs_orb* h = nullptr;
+    const Live before = live_now();
+    CHECK(hs_orb_create(&p, 0, &h) == HS_OK);
+    hs_track_params tp; memset(&tp, 0, sizeof(tp));
+    tp.th_motion = 15.f; tp.th_motion_wide = 30.f; tp.n_min_matches = 20; tp.th_local = 3.f; tp.nnratio_motion = 0.9f; tp.nnratio_local = 0.8f; tp.th_high = 100.f; tp.sigma_ref = 1.f;
+    tp.n_max_local_keyframes = 80; tp.n_neighbor_keyframes = 10;
+    hs_keyframe_params kp; memset(&kp, 0, sizeof(kp)); kp.frame_id = 100; kp.last_keyframe_id = 10; kp.max_KF_interval = 30; kp.th_depth = 40.f; kp.n_min_points = 100; kp.ok_override = -1;
+    const hs_lm_entry_params ep{ 2.0f, 0.5f };
+    // the work-size functions alone: monotone in every argument over the sweep's range, and 0 never crashes
+    for (int i = 0; i < 50; i++) {
+        const int n = rnd(0, 300), m = rnd(0, 300), L = rnd(0, 300), c = rnd(0, 300);
+        CHECK(hs_local_points_work_bytes(L) <= hs_local_points_work_bytes(L + 1024) && hs_local_map_work_bytes(L) >= hs_local_points_work_bytes(L));
+        CHECK(hs_track_work_bytes(n, m, L, c) <= hs_track_work_bytes(n + 64, m, L + 64, c) && hs_track_refkf_work_bytes(n, c, L) <= hs_track_refkf_work_bytes(n + 64, c, L + 64));
+        CHECK(hs_keyframe_work_bytes(n, m, c) <= hs_keyframe_work_bytes(n + 64, m + 64, c + 64) && hs_pose_work_bytes(n, (int64_t)n * m) == 0);
     }
-    for (int i = 0; i < n_geo; i++) {
-        // the tuning knobs that are PARSED (read once per handle): explicit pyramid plans incl. malformed ones, chain / deep-plan switches
-        static const char* const plans[] = { "3,4", "2,5", "1,2,3,1", "7", "9,9", "1,1,1,1,1,1,1", "", "a,b", "2,,3", "0,0,0", "2,2,2,2,2,2,2,2,2,2", "-3,4" };
-        if (i % 4 == 1) setenv("HS_PYRAMID_PLAN", plans[rnd(0, (int)(sizeof(plans) / sizeof(plans[0])) - 1)], 1); else unsetenv("HS_PYRAMID_PLAN");
-        if (i % 7 == 2) setenv("HS_PYRAMID_CHAIN", rnd(0, 1) ? "2" : "0", 1); else unsetenv("HS_PYRAMID_CHAIN");
-        if (i % 5 == 3) setenv("HS_PYRAMID_DEEP_MAX", rnd(0, 1) ? "0" : "100000", 1); else unsetenv("HS_PYRAMID_DEEP_MAX");
-        const int w = rnd(1, 10) == 1 ? rnd(20, 120) : rnd(64, 2600), h = rnd(1, 10) == 1 ? rnd(20, 120) : rnd(64, 1600);
-        const int r = geometry_case(w, h, rnd(20, 4000), 1.1f + 0.01f * (float)rnd(0, 90), rnd(1, 12), rnd(1, 8) == 1 ? rnd(8, 70) : 30, rnd(1, 5), (size_t)w * h < 1500000);
-        CHECK(r >= 0); accepted += r; tried++;
+    int calls = 0, refused = 0;
+    for (int r = 0; r < rounds; r++) {
+        int order[8]; for (int i = 0; i < 8; i++) order[i] = i;
+        for (int i = 7; i > 0; i--) std::swap(order[i], order[rnd(0, i)]);
+        for (int oi = 0; oi < 8; oi++) {
+            const int forced = r == 0 ? 0 : (r == 1 ? 1 : -1);
+            const int L = cnt(forced), n_kf = cnt(forced), Q = cnt(forced) % 8, n = cnt(forced);
+            const bool opt_a = rnd(0, 1), opt_b = rnd(0, 1);
+            Table t; rand_table(t, L, n_kf);
+            hip_stub_zero_device();
+            int st = HS_OK;
+            switch (order[oi]) {
+            case 0: {                                            // hs_kf_votes: weights and the self ids optional, cap 0 = no list
+                std::vector<int64_t> qo; std::vector<int32_t> ql; rand_lists(Q, L, 40, qo, ql);
+                const std::vector<int64_t> self(Q, -1); const int cap = opt_b ? 0 : rnd(1, 12);
+                std::vector<int32_t> w((size_t)Q * n_kf), ms(Q), mc(Q), os((size_t)Q * cap), ow((size_t)Q * cap), no(Q);
+                st = hs_kf_votes(h, &t.T, Q, qo.data(), ql.data(), opt_a ? self.data() : nullptr, rnd(0, 1), 2, opt_a ? w.data() : nullptr, ms.data(), mc.data(), os.data(), ow.data(), cap, no.data());
+                if (st == HS_OK && Q > 0) {                      // the refusals: offsets that decrease, a landmark outside the table; no output touched
+                    std::vector<int64_t> bad = qo; bad[Q] = -1;
+                    ms.assign(Q, 77);
+                    CHECK(hs_kf_votes(h, &t.T, Q, bad.data(), ql.data(), nullptr, 0, 2, nullptr, ms.data(), mc.data(), os.data(), ow.data(), cap, no.data()) == HS_ERR_INVALID && ms[0] == 77);
+                    if (!ql.empty()) { std::vector<int32_t> out_of = ql; out_of[0] = L; CHECK(hs_kf_votes(h, &t.T, Q, qo.data(), out_of.data(), nullptr, 0, 2, nullptr, ms.data(), mc.data(), os.data(), ow.data(), cap, no.data()) == HS_ERR_INVALID); refused++; }
+                    if (L > 0) { Table u = t; u.off[L] = u.off[L - 1] - 1; u.T.lm_obs_offsets = u.off.data(); CHECK(hs_kf_votes(h, &u.T, Q, qo.data(), ql.data(), nullptr, 0, 2, nullptr, ms.data(), mc.data(), os.data(), ow.data(), cap, no.data()) == HS_ERR_INVALID); }
+                    refused += 2;
+                }
+                break; }
+            case 1: {                                            // hs_kf_redundancy: mono (no depths) or not
+                const int Cn = Q; std::vector<int64_t> co; std::vector<int32_t> il; rand_lists(Cn, L, 60, co, il);
+                std::vector<int32_t> slot(Cn), io(il.size()), nm(Cn), nr(Cn); std::vector<float> thd(Cn, 40.f), dep(il.size(), 10.f); std::vector<uint8_t> cull(Cn);
+                for (auto& v : slot) v = n_kf > 0 ? rnd(0, n_kf - 1) : 0;
+                st = hs_kf_redundancy(h, &t.T, Cn, slot.data(), thd.data(), co.data(), il.data(), io.data(), opt_a ? nullptr : dep.data(), opt_a, 3, 0.9f, nm.data(), nr.data(), cull.data());
+                if (st == HS_OK && Cn > 0) {
+                    std::vector<int64_t> bad = co; bad[0] = 1; if (Cn > 1) bad[1] = 0; else bad[1] = 0;      // decreasing (or starting above its end)
+                    nm.assign(Cn, 77);
+                    CHECK(hs_kf_redundancy(h, &t.T, Cn, slot.data(), thd.data(), bad.data(), il.data(), io.data(), dep.data(), 0, 3, 0.9f, nm.data(), nr.data(), cull.data()) == HS_ERR_INVALID && nm[0] == 77);
+                    bad = co; bad[Cn] = -5;
+                    CHECK(hs_kf_redundancy(h, &t.T, Cn, slot.data(), thd.data(), bad.data(), il.data(), io.data(), dep.data(), 0, 3, 0.9f, nm.data(), nr.data(), cull.data()) == HS_ERR_INVALID);
+                    if (!il.empty()) { std::vector<int32_t> out_of = il; out_of.back() = -1; CHECK(hs_kf_redundancy(h, &t.T, Cn, slot.data(), thd.data(), co.data(), out_of.data(), io.data(), dep.data(), 0, 3, 0.9f, nm.data(), nr.data(), cull.data()) == HS_ERR_INVALID); }
+                    refused += 2;
+                }
+                break; }
+            case 2: {                                            // hs_local_keyframes
+                const int nc = opt_a ? 10 : rnd(0, 12);
+                std::vector<int32_t> w(n_kf), neigh((size_t)n_kf * nc, -1), parent(n_kf, -1); int32_t nl = -1; std::vector<uint8_t> local(n_kf);
+                for (auto& v : w) v = rnd(0, 3);
+                for (auto& v : neigh) v = rnd(-1, n_kf - 1);
+                for (auto& v : parent) v = rnd(-1, n_kf - 1);
+                st = hs_local_keyframes(h, n_kf, w.data(), t.kf_bad.data(), neigh.data(), nc, parent.data(), opt_b ? -1 : 80, std::min(nc, 10), local.data(), &nl);
+                if (st == HS_OK) {
+                    CHECK(hs_local_keyframes(h, n_kf, w.data(), t.kf_bad.data(), neigh.data(), nc, parent.data(), 80, nc + 1, local.data(), &nl) == HS_ERR_INVALID);
+                    if (n_kf > 0) { parent[n_kf - 1] = n_kf; CHECK(hs_local_keyframes(h, n_kf, w.data(), t.kf_bad.data(), neigh.data(), nc, parent.data(), 80, 0, local.data(), &nl) == HS_ERR_INVALID); }
+                    refused++;
+                }
+                break; }
+            case 3: {                                            // hs_local_points
+                const int cap = opt_a ? 0 : cnt(forced);
+                std::vector<uint8_t> local(n_kf, 1), rem(n); std::vector<int32_t> flm(n), sel(cap); int32_t ns = -1;
+                for (auto& v : flm) v = rnd(-1, L - 1);
+                st = hs_local_points(h, &t.T, local.data(), flm.data(), n, rem.data(), sel.data(), cap, &ns);
+                if (st == HS_OK && n > 0) { flm[0] = L; CHECK(hs_local_points(h, &t.T, local.data(), flm.data(), n, rem.data(), sel.data(), cap, &ns) == HS_ERR_INVALID); refused++; }
+                break; }
+            case 4: {                                            // hs_pose_optimize: Q of 0, 1 and several; problems with fewer than 3 edges among them
+                std::vector<int64_t> eo((size_t)Q + 1, 0);
+                for (int q = 0; q < Q; q++) eo[q + 1] = eo[q] + (forced >= 0 ? forced : rnd(0, 40));
+                std::vector<hs_pose_problem> pr(Q); std::vector<hs_pose_edge> ed((size_t)eo[Q]); std::vector<uint8_t> outl((size_t)eo[Q], 0); std::vector<hs_pose_result> res(Q);
+                for (auto& q : pr) { memset(&q, 0, sizeof(q)); q.Tcw[0] = q.Tcw[5] = q.Tcw[10] = q.Tcw[15] = 1.f; q.fx = q.fy = 300.f; q.cx = 160.f; q.cy = 120.f; q.bf = 40.f; }
+                for (auto& e : ed) e = hs_pose_edge{ { (float)rnd(-3, 3), (float)rnd(-3, 3), 5.f }, (float)rnd(0, 320), (float)rnd(0, 240), opt_a ? -1.f : 100.f, 1.f, 0 };
+                st = hs_pose_optimize(h, Q, pr.data(), eo.data(), ed.data(), outl.data(), res.data());
+                if (st == HS_OK && Q > 0) { eo[Q] = -1; CHECK(hs_pose_optimize(h, Q, pr.data(), eo.data(), ed.data(), outl.data(), res.data()) == HS_ERR_INVALID); refused++; }
+                break; }
+            case 5: case 6: {                                    // the tracking chain: the two stages, or the fused call (n, n_last, L, cap >= 1 by contract)
+                const int nf = std::max(n, 1), nlast = std::max(cnt(forced), 1), Lf = std::max(L, 1), kf = std::max(n_kf, 1), cap = std::max(cnt(forced), 1);
+                Table u; rand_table(u, Lf, kf);
+                const std::vector<hs_keypoint> k1 = rand_kps(nf, 320, 240), kl = rand_kps(nlast, 320, 240); const std::vector<uint8_t> d1 = rand_bytes((size_t)nf * 32);
+                const std::vector<float> uR(nf, -1.f), Tp(16, 0.f); const std::vector<hs_landmark> lms = rand_lms(Lf);
+                std::vector<int32_t> last_lm(nlast, -1), neigh((size_t)kf * 10, -1), parent(kf, -1);
+                hs_frame_view F; memset(&F, 0, sizeof(F));
+                F.fx = F.fy = 300.f; F.cx = 160.f; F.cy = 120.f; F.max_x = 320.f; F.max_y = 240.f; F.size_ref = 31.f; F.mbf = 40.f; F.sensor = opt_a; F.n = nf; F.kps = k1.data(); F.desc = d1.data();
+                F.uR = opt_a ? uR.data() : nullptr;
+                std::vector<int32_t> s_lm(nf, -1), s_nm(1, 0), s_obs(nf, -1); std::vector<uint8_t> s_outl(nf, 0);
+                const hs_track_state S{ s_lm.data(), s_outl.data(), s_nm.data(), s_obs.data() };
+                std::vector<hs_pose_view> pv(2); std::vector<hs_pose_problem> prob(2); std::vector<hs_landmark> last_rec(nlast), loc_lms(cap);
+                std::vector<int32_t> ni(nlast), wi(nlast), nn(1), wn(1), opv(nlast), ne_m(2), ne_l(1), lw(kf), lms_slot(1), lmc(1), lnl(1), lsel(cap), lns(1), lmi(cap), lnm(1);
+                std::vector<float> nd(nlast), wd(nlast), lmd(cap); std::vector<hs_pose_edge> em(nf), el(nf); std::vector<uint8_t> om(nf), ol(nf), lloc(kf), lrem(nf);
+                std::vector<hs_pose_result> pm(1), pl(1); std::vector<hs_track_result> tr(1);
+                const hs_local_map_out lo{ lw.data(), lms_slot.data(), lmc.data(), lloc.data(), lnl.data(), lrem.data(), lsel.data(), lns.data(), loc_lms.data(), lmi.data(), lmd.data(), lnm.data() };
+                const hs_track_out O{ pv.data(), prob.data(), last_rec.data(), ni.data(), nd.data(), nn.data(), wi.data(), wd.data(), wn.data(), opv.data(), em.data(), om.data(), ne_m.data(), pm.data(), lo,
+                                      el.data(), ol.data(), ne_l.data(), pl.data(), tr.data() };
+                std::vector<uint8_t> work(hs_track_work_bytes(nf, nlast, Lf, cap));
+                CHECK(!work.empty());
+                if (order[oi] == 5) {
+                    st = hs_track_motion_model_device(h, &F, Tp.data(), kl.data(), last_lm.data(), nlast, &u.T, lms.data(), &tp, &S, &O, work.data(), nullptr);
+                    if (st == HS_OK) st = hs_track_local_map_device(h, &F, pm[0].Tcw, &u.T, lms.data(), neigh.data(), 10, parent.data(), cap, &tp, &S, &O, work.data(), nullptr);
+                } else
+                    st = hs_track_frame_device(h, &F, Tp.data(), kl.data(), last_lm.data(), nlast, &u.T, lms.data(), neigh.data(), 10, parent.data(), cap, &tp, &S, &O, work.data(), nullptr);
+                if (st == HS_OK) {                               // refused before the first launch: no work area, a frame without keypoints, a state with a hole
+                    CHECK(hs_track_frame_device(h, &F, Tp.data(), kl.data(), last_lm.data(), nlast, &u.T, lms.data(), neigh.data(), 10, parent.data(), cap, &tp, &S, &O, nullptr, nullptr) == HS_ERR_INVALID);
+                    hs_frame_view F0 = F; F0.n = 0;
+                    CHECK(hs_track_motion_model_device(h, &F0, Tp.data(), kl.data(), last_lm.data(), nlast, &u.T, lms.data(), &tp, &S, &O, work.data(), nullptr) == HS_ERR_INVALID);
+                    hs_track_state S0 = S; S0.kp_outl = nullptr;
+                    CHECK(hs_track_local_map_device(h, &F, pm[0].Tcw, &u.T, lms.data(), neigh.data(), 10, parent.data(), cap, &tp, &S0, &O, work.data(), nullptr) == HS_ERR_INVALID);
+                    CHECK(hs_track_local_map_device(h, &F, pm[0].Tcw, &u.T, lms.data(), neigh.data(), 10, parent.data(), 0, &tp, &S, &O, work.data(), nullptr) == HS_ERR_INVALID);
+                    refused += 4;
+                    // the replay, the frame views and the discard on their own
+                    std::vector<uint8_t> aw(hs_track_work_bytes(nf, 0, Lf, 0));
+                    st = hs_frame_associate_device(h, nf, Lf, s_lm.data(), s_outl.data(), s_nm.data(), nlast, opv.data(), last_lm.data(), aw.data(), nullptr);
+                    if (st == HS_OK) st = hs_frame_views_device(h, nf, s_lm.data(), s_outl.data(), s_nm.data(), &u.T, opt_b, s_obs.data(), nullptr);
+                    if (st == HS_OK) st = hs_track_discard_device(h, opt_b ? HS_TRACK_LOCAL : HS_TRACK_MOTION, em.data(), ne_l.data(), nf, om.data(), pm.data(), &u.T, F.sensor, s_lm.data(), s_outl.data(), s_nm.data(), lnm.data(), nullptr);
+                    if (st == HS_OK) st = hs_pose_views_device(h, Tp.data(), pv.data(), nullptr);
+                    CHECK(hs_track_discard_device(h, 2, em.data(), ne_l.data(), nf, om.data(), pm.data(), &u.T, F.sensor, s_lm.data(), s_outl.data(), s_nm.data(), lnm.data(), nullptr) == HS_ERR_INVALID);
+                }
+                break; }
+            case 7: {                                            // the reference-key-frame pair, then the key-frame stages one by one and fused, then the entry update they feed
+                const int nf = std::max(n, 1), Lf = std::max(L, 1), kf = std::max(n_kf, 1), kf_cap = std::max(cnt(forced), 1), new_cap = opt_a ? 0 : std::max(cnt(forced), 1);
+                Table u; rand_table(u, Lf, kf);
+                std::vector<int64_t> ko((size_t)kf + 1, 0);
+                for (int k = 0; k < kf; k++) ko[k + 1] = ko[k] + rnd(0, 5);
+                const int total = (int)ko[kf];
+                const std::vector<hs_keypoint> kk = rand_kps(std::max(total, 1), 320, 240), k1 = rand_kps(nf, 320, 240);
+                const std::vector<uint8_t> kd = rand_bytes((size_t)std::max(total, 1) * 32), d1 = rand_bytes((size_t)nf * 32);
+                const std::vector<int32_t> knode(std::max(total, 1), 3), klm(std::max(total, 1), -1), fnode(nf, 3); const std::vector<float> kw(std::max(total, 1), 1.f), fw(nf, 1.f);
+                const hs_kf_features K{ kf, ko.data(), kk.data(), kd.data(), knode.data(), klm.data(), opt_b ? kw.data() : nullptr };
+                std::vector<int32_t> slot(1, rnd(-1, kf)), mkf(kf_cap), opv(nf), opl(nf), nm(1);
+                st = hs_search_by_bow_kf_device(h, &K, slot.data(), &u.T, k1.data(), d1.data(), fnode.data(), opt_b ? fw.data() : nullptr, nf, 50.f, 0.7f, mkf.data(), kf_cap, opv.data(), opl.data(), nm.data(), nullptr, nullptr);
+                if (st != HS_OK) break;
+                CHECK(hs_search_by_bow_kf_device(h, &K, slot.data(), &u.T, k1.data(), d1.data(), fnode.data(), nullptr, nf, 50.f, 0.7f, mkf.data(), 0, opv.data(), opl.data(), nm.data(), nullptr, nullptr) == HS_ERR_INVALID);
+                CHECK(hs_search_by_bow_kf_device(h, nullptr, slot.data(), &u.T, k1.data(), d1.data(), fnode.data(), nullptr, nf, 50.f, 0.7f, mkf.data(), kf_cap, opv.data(), opl.data(), nm.data(), nullptr, nullptr) == HS_ERR_INVALID);
+                std::vector<int32_t> s_lm(nf, -1), s_nm(1, 0), s_obs(nf, -1); std::vector<uint8_t> s_outl(nf, 0);
+                const hs_track_state S{ s_lm.data(), s_outl.data(), s_nm.data(), s_obs.data() };
+                std::vector<uint8_t> vw(hs_track_refkf_work_bytes(nf, kf_cap, Lf));
+                st = hs_frame_associate_views_device(h, nf, Lf, s_lm.data(), s_outl.data(), s_nm.data(), opv.data(), opl.data(), vw.data(), nullptr);
+                if (st != HS_OK) break;
+                CHECK(hs_frame_associate_views_device(h, nf, Lf, s_lm.data(), s_outl.data(), s_nm.data(), opv.data(), opl.data(), nullptr, nullptr) == HS_ERR_INVALID);
+                hs_frame_view F; memset(&F, 0, sizeof(F));
+                F.fx = F.fy = 300.f; F.cx = 160.f; F.cy = 120.f; F.max_x = 320.f; F.max_y = 240.f; F.size_ref = 31.f; F.mbf = 40.f; F.sensor = 1; F.n = nf; F.kps = k1.data(); F.desc = d1.data();
+                const std::vector<float> depth(nf, 10.f), Tcw(16, 0.f);
+                std::vector<hs_keyframe_result> res(1); std::vector<hs_pose_view> pv(1); std::vector<int32_t> nv(new_cap), lmi(new_cap); std::vector<float> np((size_t)new_cap * 3);
+                std::vector<hs_lm_entry_in> ent(new_cap); std::vector<hs_lm_obs> obs(new_cap); std::vector<int64_t> oo((size_t)new_cap + 1), od((size_t)new_cap + 1); std::vector<uint8_t> nd((size_t)new_cap * 32);
+                std::vector<hs_landmark> lms((size_t)Lf + new_cap);
+                const hs_keyframe_out KO{ res.data(), pv.data(), nv.data(), np.data(), ent.data(), obs.data(), oo.data(), od.data(), nd.data(), lmi.data(), opt_b ? lms.data() : nullptr, opt_b ? Lf + new_cap : 0 };
+                std::vector<hs_track_result> tr(1); std::vector<int32_t> ref(1, -1);
+                std::vector<uint8_t> kwork(hs_keyframe_work_bytes(nf, kf, new_cap));
+                CHECK(!kwork.empty());
+                st = hs_keyframe_reference_device(h, nf, &S, &u.T, ref.data(), res.data(), kwork.data(), nullptr);
+                if (st == HS_OK) st = hs_keyframe_gate_device(h, tr.data(), &kp, res.data(), nullptr);
+                if (st == HS_OK) st = hs_keyframe_clean_device(h, nf, &S, &u.T, res.data(), nullptr);
+                if (st == HS_OK) st = hs_keyframe_need_device(h, nf, 1, depth.data(), &S, &u.T, &K, ref.data(), tr.data(), &kp, res.data(), nullptr);
+                if (st == HS_OK) st = hs_keyframe_create_device(h, &F, depth.data(), Tcw.data(), &S, &u.T, &kp, new_cap, &KO, kwork.data(), nullptr);
+                if (st == HS_OK) st = hs_keyframe_discard_device(h, nf, &S, res.data(), nullptr);
+                if (st == HS_OK) st = hs_track_keyframe_device(h, &F, depth.data(), Tcw.data(), &u.T, &K, tr.data(), &kp, &S, ref.data(), new_cap, &KO, kwork.data(), nullptr);
+                if (st != HS_OK) break;
+                CHECK(hs_keyframe_gate_device(h, nullptr, &kp, res.data(), nullptr) == HS_ERR_INVALID);              // no track result and no override
+                CHECK(hs_track_keyframe_device(h, &F, depth.data(), Tcw.data(), &u.T, &K, tr.data(), &kp, &S, ref.data(), new_cap, &KO, nullptr, nullptr) == HS_ERR_INVALID);
+                CHECK(hs_track_keyframe_device(h, &F, depth.data(), Tcw.data(), &u.T, &K, tr.data(), &kp, &S, ref.data(), -1, &KO, kwork.data(), nullptr) == HS_ERR_INVALID);
+                refused += 6;
+                if (new_cap > 0) {
+                    std::vector<float> nrm((size_t)new_cap * 3), a1(new_cap), a2(new_cap), a3(new_cap), a4(new_cap); std::vector<int32_t> b1(new_cap), b2(new_cap), b3(new_cap);
+                    st = hs_landmark_update_entries_device(h, &ep, new_cap, ent.data(), oo.data(), obs.data(), od.data(), nd.data(), nrm.data(), a1.data(), a2.data(), a3.data(), a4.data(), b1.data(), b2.data(), b3.data(),
+                                                           opt_b ? lms.data() : nullptr, opt_b ? lmi.data() : nullptr, opt_b ? Lf + new_cap : 0, nullptr);
+                }
+                break; }
+            }
+            if (st != HS_OK) { printf("map sweep: entry point %d, L %d n_kf %d Q %d n %d: status %d (%s)\n", order[oi], L, n_kf, Q, n, st, hs_orb_last_error(h)); return 1; }
+            calls++;
+        }
     }
-    unsetenv("HS_PYRAMID_PLAN"); unsetenv("HS_PYRAMID_CHAIN"); unsetenv("HS_PYRAMID_DEEP_MAX");
-    CHECK(accepted > tried / 2);
-    print_counters("HOST SANITIZE COUNTERS after the geometry sweep");       // (everything up to here is single-threaded: the same for every run of a commit)
+    hs_orb_destroy(h);
+    if (alone) CHECK(same_live(before));
+    return calls > 0 && refused > 0 ? 0 : 1;
+}
 
+// ---- the place database's host code: the slot mirror, tombstones, the two regrow paths (slots from 1024, the entry pool from 65 536), the key-order
+// upload of the first query after a change, clear and reuse, two databases alive at once, the refused vectors
+static int place_add(hs_place_db* db, uint64_t key, int m, int n_words, int32_t* slot)
+{
+    std::vector<int32_t> w(m); std::vector<double> v(m);
+    for (int i = 0, at = rnd(0, std::max(n_words - m, 0) / std::max(m, 1)); i < m; i++, at += 1 + rnd(0, std::max(n_words / std::max(m, 1) - 2, 0))) { w[i] = std::min(at, n_words - m + i); v[i] = 1.0 / m; }
+    for (int i = 1; i < m; i++) if (w[i] <= w[i - 1]) w[i] = w[i - 1] + 1;
+    return hs_place_db_add(db, key, w.data(), v.data(), m, slot);
+}
+static int place_queries(hs_place_db* db, int n_words, int want_slots)
+{
+    int32_t live = -1, slots = -1;
+    CHECK(hs_place_db_size(db, &live, &slots) == HS_OK && slots == want_slots && live <= slots);
+    const int qm = 30;
+    std::vector<int32_t> qw(qm); std::vector<double> qv(qm, 1.0 / qm);
+    for (int i = 0; i < qm; i++) qw[i] = i * (n_words / qm);
+    std::vector<int32_t> neigh((size_t)slots * 10, -1), cand(std::max(slots, 1)), words(slots), best(slots); std::vector<float> score(slots), acc(slots); std::vector<uint8_t> excl(slots, 0);
+    for (auto& v : neigh) v = rnd(-1, slots);                    // (out-of-range and tombstoned slots are ignored by contract)
+    int32_t nc = -1;
+    CHECK(hs_place_query_reloc(db, qw.data(), qv.data(), qm, neigh.data(), cand.data(), (int)cand.size(), &nc, words.data(), score.data(), acc.data(), best.data()) == HS_OK && nc >= 0);
+    CHECK(hs_place_query_loop(db, qw.data(), qv.data(), qm, excl.data(), 0.f, nullptr, cand.data(), (int)cand.size(), &nc, nullptr, nullptr, nullptr, nullptr) == HS_OK && nc >= 0);
+    CHECK(hs_place_query_reloc(db, qw.data(), qv.data(), 0, nullptr, cand.data(), (int)cand.size(), &nc, nullptr, nullptr, nullptr, nullptr) == HS_OK && nc == 0);
+    return 0;
+}
+static int place_section(bool alone = true)
+{
+    hs_orb_params p; hs_orb_default_params(&p);
+    hs_orb* h = nullptr;
+    const Live before = live_now();
+    CHECK(hs_orb_create(&p, 0, &h) == HS_OK);
+    const int n_words = 5000;
+    hs_place_db *db = nullptr, *db2 = nullptr;
+    CHECK(hs_place_db_create(h, n_words, 1, &db) != HS_OK && db == nullptr);                    // only L1 scoring
+    CHECK(hs_place_db_create(h, n_words, 0, &db) == HS_OK && hs_place_db_create(h, 100, 0, &db2) == HS_OK);
+    CHECK(place_queries(db, n_words, 0) == 0);                                                   // an empty database answers
+    int32_t slot = -1;
+    // refused vectors: not ascending, a word >= n_words, a value <= 0 or not finite; nothing is stored
+    { const int32_t w[3] = { 5, 4, 9 }; const double v[3] = { .3, .3, .4 }; CHECK(hs_place_db_add(db, 1, w, v, 3, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[3] = { 5, 5, 9 }; const double v[3] = { .3, .3, .4 }; CHECK(hs_place_db_add(db, 1, w, v, 3, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[2] = { 5, n_words }; const double v[2] = { .5, .5 }; CHECK(hs_place_db_add(db, 1, w, v, 2, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[2] = { 5, 6 }; const double v[2] = { .5, 0.0 }; CHECK(hs_place_db_add(db, 1, w, v, 2, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[2] = { 5, 6 }; const double v[2] = { -.5, .5 }; CHECK(hs_place_db_add(db, 1, w, v, 2, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[2] = { 5, 6 }; const double v[2] = { .5, std::numeric_limits<double>::infinity() }; CHECK(hs_place_db_add(db, 1, w, v, 2, &slot) == HS_ERR_INVALID); }
+    { const int32_t w[2] = { 5, 6 }; const double v[2] = { std::nan(""), .5 }; CHECK(hs_place_db_add(db, 1, w, v, 2, &slot) == HS_ERR_INVALID); }
+    int32_t live = -1, slots = -1;
+    CHECK(hs_place_db_size(db, &live, &slots) == HS_OK && live == 0 && slots == 0);
+    // past the first slot capacity (1024) and the first pool capacity (65 536 entries): 1100 vectors of 64 entries = 70 400
+    const int N = 1100, M = 64;
+    for (int i = 0; i < N; i++) {
+        CHECK(place_add(db, 1000 + 7919ull * (uint64_t)((i * 37) % N), M, n_words, &slot) == HS_OK && slot == i);
+        if (i == 5 || i == 1023 || i == 1024 || i == 1030) CHECK(place_queries(db, n_words, i + 1) == 0);           // before and after each regrow: the order is rebuilt
+        if (i < 20) CHECK(place_add(db2, (uint64_t)i, 1 + i % 7, 100, &slot) == HS_OK && slot == i);                 // the second database grows beside it
+    }
+    CHECK(hs_place_db_size(db, &live, &slots) == HS_OK && live == N && slots == N);
+    // tombstones: erase every third, twice is refused, out of range is refused; query after it
+    for (int i = 0; i < N; i += 3) CHECK(hs_place_db_erase(db, i) == HS_OK);
+    CHECK(hs_place_db_erase(db, 0) != HS_OK && hs_place_db_erase(db, N) != HS_OK && hs_place_db_erase(db, -1) != HS_OK);
+    CHECK(hs_place_db_size(db, &live, &slots) == HS_OK && live == N - (N + 2) / 3 && slots == N);
+    CHECK(place_queries(db, n_words, N) == 0);
+    CHECK(place_add(db, 99, M, n_words, &slot) == HS_OK && slot == N);                          // a tombstone's slot is not reused
+    CHECK(place_queries(db, n_words, N + 1) == 0 && place_queries(db2, 100, 20) == 0);
+    // clear keeps the allocations; reuse from slot 0
+    CHECK(hs_place_db_clear(db) == HS_OK && hs_place_db_size(db, &live, &slots) == HS_OK && live == 0 && slots == 0);
+    CHECK(place_queries(db, n_words, 0) == 0);
+    for (int i = 0; i < 40; i++) CHECK(place_add(db, 5000 - (uint64_t)i, rnd(1, 200), n_words, &slot) == HS_OK && slot == i);
+    CHECK(place_queries(db, n_words, 40) == 0);
+    hs_place_db_destroy(db); hs_place_db_destroy(db2); hs_place_db_destroy(nullptr);
+    hs_orb_destroy(h);
+    if (alone) CHECK(same_live(before));
+    return 0;
+}
+
+// ---- `threads <seed>`: everything that is shared between threads, for ThreadSanitizer (it runs under ASan + UBSan as well).  Every section starts its
+// threads behind a barrier of its own and gives each a bounded amount of work.
+struct Gate {
+    std::atomic<int> waiting{0}; const int n;
+    explicit Gate(int n_) : n(n_) {}
+    void arrive() { waiting++; while (waiting.load() < n) std::this_thread::yield(); }
+};
+static int threads_mode(uint64_t seed)
+{
+    const Live before = live_now();
+    std::atomic<int> bad{0};
+    {   // hs_comm_available: its first call, from four threads at once (the dlopen of librccl happens once)
+        Gate g(4); std::vector<std::thread> th; std::atomic<int> sum{0};
+        for (int t = 0; t < 4; t++) th.emplace_back([&] { g.arrive(); sum += hs_comm_available(); (void)hs_comm_unavailable_reason(); });
+        for (auto& t : th) t.join();
+        CHECK(sum.load() == 0 || sum.load() == 4);
+    }
+    {   // the four sweeps at once: a handle (or two) per thread, a generator per thread
+        Gate g(4); std::vector<std::thread> th;
+        for (int t = 0; t < 4; t++) th.emplace_back([&, t] { rng.seed(seed * 100 + t); g.arrive(); if ((t & 1 ? map_sweep(4, false) : staged_sweep(4, false)) != 0) bad++; if ((t & 1 ? staged_sweep(3, false) : map_sweep(3, false)) != 0) bad++; });
+        for (auto& t : th) t.join();
+        CHECK(bad.load() == 0);
+    }
+    {   // handle churn on two threads while two others extract and match
+        Gate g(4); std::vector<std::thread> th;
+        for (int t = 0; t < 2; t++) th.emplace_back([&, t] {
+            rng.seed(seed * 100 + 10 + t); g.arrive();
+            for (int i = 0; i < 150; i++) { hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 100 + 50 * (i % 5); hs_orb* x = nullptr; if (hs_orb_create(&p, 0, &x) != HS_OK) { bad++; break; } if (i % 3 == 0 && hs_orb_reserve(x, 160 + i, 120, 1) != HS_OK) bad++; hs_orb_destroy(x); }
+        });
+        for (int t = 0; t < 2; t++) th.emplace_back([&, t] {
+            rng.seed(seed * 100 + 20 + t); g.arrive();
+            hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300; hs_orb* x = nullptr;
+            if (hs_orb_create(&p, 0, &x) != HS_OK || hs_orb_reserve(x, 320, 240, 1) != HS_OK) { bad++; return; }
+            const int cap = hs_orb_max_keypoints(x); const std::vector<uint8_t> img = rand_bytes(320 * 240);
+            std::vector<hs_keypoint> k(cap); std::vector<uint8_t> d((size_t)cap * 32); int32_t n = 0;
+            for (int i = 0; i < 40; i++) {
+                if (hs_orb_extract(x, img.data(), 320, 240, 320, k.data(), d.data(), cap, &n) != HS_OK) bad++;
+                const int nq = rnd(1, 200), nt = rnd(1, 200); const std::vector<uint8_t> q = rand_bytes((size_t)nq * 32), tt = rand_bytes((size_t)nt * 32); std::vector<int32_t> bi(nq), bd(nq), sd(nq);
+                if (hs_hamming_knn2(x, q.data(), nq, tt.data(), nt, bi.data(), bd.data(), sd.data()) != HS_OK) bad++;
+            }
+            hs_orb_destroy(x);
+        });
+        for (auto& t : th) t.join();
+        CHECK(bad.load() == 0);
+    }
+    {   // place databases: one used from two threads under a mutex (the adaptor's discipline, HipPlaceRecognizer::mutex), one freely on a third
+        hs_orb_params p; hs_orb_default_params(&p); hs_orb *h1 = nullptr, *h2 = nullptr;
+        CHECK(hs_orb_create(&p, 0, &h1) == HS_OK && hs_orb_create(&p, 0, &h2) == HS_OK);
+        hs_place_db* shared = nullptr;
+        CHECK(hs_place_db_create(h1, 2000, 0, &shared) == HS_OK);
+        std::mutex mu; int added = 0;
+        Gate g(3); std::vector<std::thread> th;
+        th.emplace_back([&] { rng.seed(seed * 100 + 30); g.arrive(); for (int i = 0; i < 300; i++) { std::lock_guard<std::mutex> l(mu); int32_t s = -1; if (place_add(shared, 10 + (uint64_t)i, rnd(1, 60), 2000, &s) != HS_OK || s != added) bad++; added++; if (i % 50 == 49 && hs_place_db_erase(shared, s) != HS_OK) bad++; } });
+        th.emplace_back([&] { rng.seed(seed * 100 + 31); g.arrive(); for (int i = 0; i < 120; i++) { std::lock_guard<std::mutex> l(mu); if (place_queries(shared, 2000, added) != 0) bad++; } });
+        th.emplace_back([&] {
+            rng.seed(seed * 100 + 32); g.arrive();
+            hs_place_db* own = nullptr;
+            if (hs_place_db_create(h2, 500, 0, &own) != HS_OK) { bad++; return; }
+            for (int i = 0; i < 200; i++) { int32_t s = -1; if (place_add(own, (uint64_t)i, rnd(1, 40), 500, &s) != HS_OK) bad++; if (i % 20 == 19 && place_queries(own, 500, i + 1) != 0) bad++; }
+            hs_place_db_destroy(own);
+        });
+        for (auto& t : th) t.join();
+        hs_place_db_destroy(shared); hs_orb_destroy(h1); hs_orb_destroy(h2);
+        CHECK(bad.load() == 0);
+    }
+    {   // the vocabulary loaders on good and corrupted files, four threads; hs_vocab_last_error is the calling thread's own
+        char dir[] = "/tmp/hs_host_sanitize_XXXXXX";
+        CHECK(mkdtemp(dir) != nullptr);
+        const std::string good = std::string(dir) + "/v.bin", gtxt = std::string(dir) + "/v.txt";
+        std::vector<int32_t> cb, cc, word; std::vector<uint8_t> desc; std::vector<float> weight;
+        hs_vocab* v = make_vocab(4, 3, cb, cc, desc, word, weight);
+        CHECK(v != nullptr && hs_vocab_save(v, good.c_str()) == HS_OK && hs_vocab_save(v, gtxt.c_str()) == HS_OK);
+        hs_vocab_destroy(v);
+        const std::vector<uint8_t> bytes = slurp(good);
+        Gate g(4); std::vector<std::thread> th;
+        for (int t = 0; t < 4; t++) th.emplace_back([&, t] {
+            rng.seed(seed * 100 + 40 + t); g.arrive();
+            const std::string mine = std::string(dir) + "/bad" + std::to_string(t) + ".bin";
+            for (int i = 0; i < 40; i++) {
+                hs_vocab* a = nullptr;
+                if (t & 1) {                                         // the odd threads only ever load good files: their error text must stay empty
+                    if (hs_vocab_load(i & 1 ? good.c_str() : gtxt.c_str(), &a) != HS_OK || !a || hs_vocab_last_error()[0] != 0) bad++;
+                } else {
+                    std::vector<uint8_t> b = bytes; b.resize((size_t)rnd(0, (int)b.size() - 1));
+                    spit(mine, b);
+                    if (hs_vocab_load(mine.c_str(), &a) == HS_OK ? a == nullptr : (a != nullptr || hs_vocab_last_error()[0] == 0)) bad++;
+                }
+                if (a) hs_vocab_destroy(a);
+            }
+            unlink(mine.c_str());
+        });
+        for (auto& t : th) t.join();
+        unlink(good.c_str()); unlink(gtxt.c_str()); rmdir(dir);
+        CHECK(bad.load() == 0);
+    }
+    CHECK(hs_frame_cache_clear(0) == HS_OK);
+    CHECK(same_live(before));
+    return 0;
+}
+
+// exactly one of hs_orb_destroy and the last borrower's release frees the handle
+static int borrow_race()
+{
     // ---- a handle outliving its communicators: hs_orb_destroy and the last borrower's release race on two threads; exactly one of them frees
     // the handle (ASan: a double free or a leak fails the run), in either order and with several borrowers
     for (int i = 0; i < 200; i++) {
@@ -334,6 +693,11 @@ int main(int argc, char** argv)
         td.join(); tb.join();
     }
 
+    return 0;
+}
+
+static int frame_cache_section(uint64_t seed)
+{
     // ---- the frame cache (hs_frame_*): publish after an extraction, find by keypoints, the *_frame(s) entry points, release, slot reuse after 16
     //      publishes, refusals (no extraction to publish, unknown tokens, a count that disagrees); then publishers, finders and consumers on four threads
     {
@@ -412,6 +776,68 @@ int main(int argc, char** argv)
         CHECK(hs_frame_info(0, latest.load(), &ninfo) != HS_OK);
     }
 
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels [cell]]: the host-side plan of a geometry, or its refusal
+        hs_orb_params p; hs_orb_default_params(&p);
+        p.nfeatures = argc > 4 ? atoi(argv[4]) : 2000; if (argc > 5) p.scale_factor = (float)atof(argv[5]); if (argc > 6) p.nlevels = atoi(argv[6]);
+        if (argc > 7) p.cell_px = atoi(argv[7]);
+        hs_orb* ex = nullptr;
+        CHECK(hs_orb_create(&p, 0, &ex) == HS_OK);
+        const int rc = hs_orb_reserve(ex, atoi(argv[2]), atoi(argv[3]), 2);
+        if (rc != HS_OK) { printf("refused: status %d: %s\n", rc, hs_orb_last_error(ex)); hs_orb_destroy(ex); return 0; }
+        int32_t s[8]; hs_debug_plan_summary(ex, s);
+        printf("pyramid launches: standard plan %d, small-batch plan %d (longest chain %d levels, %d B of LDS, %d workgroups per frame); FAST items per frame: %d wide, %d narrow; levels with quadtree keys: %d\n",
+               s[0], s[1], s[5], s[6], s[7], s[2], s[3], s[4]);
+        printf("plan digest: %016llx\n", (unsigned long long)hs_debug_plan_digest(ex));
+        hs_orb_destroy(ex);
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "threads")) {
+        const uint64_t seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 1;
+        rng.seed(seed);
+        CHECK(borrow_race() == 0);
+        CHECK(frame_cache_section(seed) == 0);
+        CHECK(threads_mode(seed) == 0);
+        printf("HOST SANITIZE THREADS OK seed %llu; ", (unsigned long long)seed);
+        print_counters("totals");
+        return 0;
+    }
+    const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
+    const int n_geo = argc > 2 ? atoi(argv[2]) : 120, n_voc = argc > 3 ? atoi(argv[3]) : 400;
+    rng.seed(seed);
+    int ndev = 0;
+    CHECK(hs_device_count(&ndev) == HS_OK && ndev == 1);
+
+    // ---- geometry: the fixed shapes of the GPU suites, then the random sweep
+    int accepted = 0, tried = 0;
+    const int fixed[][7] = { {640, 480, 1000, 120, 8, 30, 2}, {1920, 1080, 2000, 120, 8, 30, 2}, {1920, 1080, 2000, 120, 8, 30, 32}, {4000, 3000, 3000, 140, 8, 30, 1},
+                             {643, 481, 700, 120, 8, 30, 1}, {3840, 2160, 2000, 120, 8, 30, 1}, {2560, 40, 500, 120, 3, 30, 1}, {64, 64, 100, 120, 8, 30, 1}, {33, 33, 50, 200, 12, 12, 4},
+                             {1200, 300, 1500, 120, 6, 30, 1}, {1900, 200, 1200, 120, 3, 30, 1}, {16384, 64, 100, 110, 2, 62, 1}, {1920, 1080, 9000, 120, 8, 30, 1}, {800, 600, 1500, 140, 8, 62, 2} };
+    for (const auto& f : fixed) {
+        const int r = geometry_case(f[0], f[1], f[2], f[3] / 100.f, f[4], f[5], f[6], (size_t)f[0] * f[1] * f[6] < 6000000);
+        CHECK(r >= 0); accepted += r; tried++;
+    }
+    for (int i = 0; i < n_geo; i++) {
+        // the tuning knobs that are PARSED (read once per handle): explicit pyramid plans incl. malformed ones, chain / deep-plan switches
+        static const char* const plans[] = { "3,4", "2,5", "1,2,3,1", "7", "9,9", "1,1,1,1,1,1,1", "", "a,b", "2,,3", "0,0,0", "2,2,2,2,2,2,2,2,2,2", "-3,4" };
+        if (i % 4 == 1) setenv("HS_PYRAMID_PLAN", plans[rnd(0, (int)(sizeof(plans) / sizeof(plans[0])) - 1)], 1); else unsetenv("HS_PYRAMID_PLAN");
+        if (i % 7 == 2) setenv("HS_PYRAMID_CHAIN", rnd(0, 1) ? "2" : "0", 1); else unsetenv("HS_PYRAMID_CHAIN");
+        if (i % 5 == 3) setenv("HS_PYRAMID_DEEP_MAX", rnd(0, 1) ? "0" : "100000", 1); else unsetenv("HS_PYRAMID_DEEP_MAX");
+        const int w = rnd(1, 10) == 1 ? rnd(20, 120) : rnd(64, 2600), h = rnd(1, 10) == 1 ? rnd(20, 120) : rnd(64, 1600);
+        const int r = geometry_case(w, h, rnd(20, 4000), 1.1f + 0.01f * (float)rnd(0, 90), rnd(1, 12), rnd(1, 8) == 1 ? rnd(8, 70) : 30, rnd(1, 5), (size_t)w * h < 1500000);
+        CHECK(r >= 0); accepted += r; tried++;
+    }
+    unsetenv("HS_PYRAMID_PLAN"); unsetenv("HS_PYRAMID_CHAIN"); unsetenv("HS_PYRAMID_DEEP_MAX");
+    CHECK(accepted > tried / 2);
+    print_counters("HOST SANITIZE COUNTERS after the geometry sweep");       // (everything up to here is single-threaded: the same for every run of a commit)
+
+    CHECK(borrow_race() == 0);
+    CHECK(frame_cache_section(seed) == 0);
+
     print_counters("HOST SANITIZE COUNTERS after the threaded frame-cache section (varies from run to run)");
     CHECK(staged_sweep(12) == 0);
 
@@ -456,6 +882,11 @@ int main(int argc, char** argv)
     unlink(ptxt.c_str()); unlink(pbin.c_str()); unlink(pbad_t.c_str()); unlink(pbad_b.c_str()); rmdir(dir);
     printf("HOST SANITIZE OK seed %llu: %d of %d geometries configured, %ld kernel launches issued into the stub, %d corrupted vocabularies refused, %d still well-formed; ",
            (unsigned long long)seed, accepted, tried, hip_stub_launches(), refused, loaded);
+    print_counters("totals");
+    // (behind the line above, which earlier versions of this driver print too: what follows draws from the generator and issues launches)
+    CHECK(map_sweep(12) == 0);
+    CHECK(place_section() == 0);
+    printf("HOST SANITIZE MAP OK seed %llu: key-frame graph, local map, pose optimiser, tracking / reference-key-frame / key-frame stages, place database; ", (unsigned long long)seed);
     print_counters("totals");
     return 0;
 }

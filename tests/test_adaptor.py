@@ -46,11 +46,16 @@ def run():
     return subprocess.run([EXE, "640", "480"], input=L.tobytes() + R.tobytes(), capture_output=True, timeout=300)
 
 
-def write_scene(path):
-    """a tracking scene (tests/scenes.py) in the flat layout tests/cpp/test_matcher_adaptor.cpp reads"""
+GATHER_SPLIT = 4096      # HipFeatureMatcher's gather splits the landmarks by field over helper threads from this many landmarks on
+
+
+def write_scene(path, copies=3):
+    """a tracking scene (tests/scenes.py) in the flat layout tests/cpp/test_matcher_adaptor.cpp reads: copies=3 gives 3000 landmarks (gathered on the
+    calling thread), copies=5 gives 5000 (above GATHER_SPLIT: the helper-thread gather of TrackLocalMap's large local maps)"""
     import scenes
-    sc = scenes.projection_scene(71, 640, 480, nfeat=1000, copies=3)
+    sc = scenes.projection_scene(71, 640, 480, nfeat=1000, copies=copies)
     fa, lms = sc["frame_args"], sc["lms"]
+    assert (len(lms) >= GATHER_SPLIT) == (copies >= 5), len(lms)
     with open(path, "wb") as f:
         np.array([len(fa["kps"]), len(lms), fa["sensor"], 640, 480, 0, 0, 0], np.int32).tofile(f)
         np.concatenate([np.asarray(fa["Rcw"], np.float32).reshape(-1), np.asarray(fa["tcw"], np.float32),
@@ -62,10 +67,14 @@ def write_scene(path):
         np.ascontiguousarray(lms).tofile(f)
 
 
-def run_matcher(exe=EXE_M):
-    scene = os.path.join(BUILD, "scene.bin")
-    write_scene(scene)
-    return subprocess.run([exe, scene], capture_output=True, timeout=600)
+def run_matcher(exe=EXE_M, copies=3, gather_threads=None):
+    """gather_threads: HYSLAM_AMD_GATHER_THREADS of the child process (the adaptor reads it once per process)"""
+    scene = os.path.join(BUILD, "scene.bin" if copies == 3 else "scene_x%d.bin" % copies)
+    write_scene(scene, copies)
+    env = {k: v for k, v in os.environ.items() if k != "HYSLAM_AMD_GATHER_THREADS"}
+    if gather_threads is not None:
+        env["HYSLAM_AMD_GATHER_THREADS"] = str(gather_threads)
+    return subprocess.run([exe, scene], capture_output=True, timeout=600, env=env)
 
 
 def run_bench(w=640, h=480, reps=6, n_lm=5000):
@@ -161,4 +170,26 @@ def test_matcher_replacement_unit_on_gpu(gpu):
     base class's non-virtual FeatureFactory::getFeatureMatcher()), whose member functions hyslam_amd/host/replace/FeatureMatcher.cc defines over the C ABI"""
     build_replacement()
     r = run_matcher(EXE_R)
+    assert r.returncode == 0 and b"MATCHER ADAPTOR OK" in r.stdout, r.stdout + r.stderr
+
+
+_BUILT = set()
+
+
+def built_once(which):
+    if which not in _BUILT:
+        build_replacement() if which == "replacement" else build("test_matcher_adaptor.cpp", EXE_M)
+        _BUILT.add(which)
+    return EXE_R if which == "replacement" else EXE_M
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("helpers", [0, 1, 2])
+@pytest.mark.parametrize("which", ["adaptor", "replacement"])
+def test_matcher_adaptors_gather_with_helper_threads_on_gpu(gpu, which, helpers):
+    """the same ten searches on a scene of 5000 landmarks: from 4096 on HipFeatureMatcher's gather hands the geometry fields to helper threads
+    (hip_detail::Worker) while the calling thread copies the descriptors — the path TrackLocalMap takes with its 50 000-point local maps.  0, 1 and 2
+    helpers (HYSLAM_AMD_GATHER_THREADS, read once per process: a child process each) must all give the oracle's matches and the reference-order
+    replay, through the adaptor and through the replacement translation unit"""
+    r = run_matcher(built_once(which), copies=5, gather_threads=helpers)
     assert r.returncode == 0 and b"MATCHER ADAPTOR OK" in r.stdout, r.stdout + r.stderr

@@ -2,10 +2,15 @@
 hyslam_amd/csrc compiled host-only (`hipcc --cuda-host-only`: no device code) and linked against a stand-in for the HIP runtime on host memory
 (hip_stub.cpp: device calls stubbed at the hipMalloc seam, the logic runs for real).  The driver sweeps random geometries through hs_orb_create /
 hs_orb_reserve / the host-pointer entry points (planners, table builders, workspace sizing, staging, the ingest tickets) and feeds the vocabulary
-loaders truncated and corrupted files.  Any sanitizer report aborts the driver.  (GPU AddressSanitizer is not available on this pool; the oracle has
-its own sanitizer test, tests/test_oracle_sanitizers.py.)"""
+loaders truncated and corrupted files, then the host-pointer forms of the key-frame graph, the local map and the pose optimiser, the `_device` forms of
+the tracking, reference-key-frame and key-frame stages on work areas of exactly their stated size, and the place database through both of its regrow
+paths.  Any sanitizer report aborts the driver.  The same sources build under ThreadSanitizer (`make SAN=thread`, a build directory of its own; never
+both sanitizers in one binary): the driver's `threads` mode runs every section that shares something between threads, adaptor_threads the thread
+code of the header-only adaptors on the same stub objects.  Stand-alone programs throughout: nothing is loaded into python under a sanitizer.  (GPU
+AddressSanitizer is not available on this pool; the oracle has its own sanitizer test, tests/test_oracle_sanitizers.py.)"""
 import json
 import os
+import re
 import shutil
 import subprocess
 
@@ -14,6 +19,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "cpp", "host_sanitize")
 EXE = os.path.join(DIR, "_build", "host_sanitize")
+EXE_T = os.path.join(DIR, "_build_thread", "host_sanitize")
+REPORTS = ("ERROR: AddressSanitizer", "runtime error", "WARNING: ThreadSanitizer", "ERROR: LeakSanitizer")
 
 # a CPU-only build: its hipcc lines pass -fno-gpu-sanitize beside -fsanitize= (no device code is sanitized or even compiled), and it never runs on a GPU
 pytestmark = pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or not os.path.exists(os.path.join(DIR, "Makefile")),
@@ -24,12 +31,61 @@ def build():
     subprocess.check_call(["make", "-s", "-j4", "-C", DIR], timeout=1500)
 
 
+def build_thread():
+    subprocess.check_call(["make", "-s", "-j4", "-C", DIR, "SAN=thread"], timeout=1500)
+
+
+def clean_run(cmd, marker, env=None, timeout=900):
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+    assert r.returncode == 0 and marker in r.stdout, (cmd, (r.stdout + r.stderr)[-4000:])
+    assert not any(x in r.stdout + r.stderr for x in REPORTS), (cmd, (r.stdout + r.stderr)[-4000:])
+    return r
+
+
+def test_every_translation_unit_of_the_library_is_built():
+    """the sanitizer build takes its list from hyslam_amd/csrc/Makefile's SRCS: the two are equal, and every .hip file of the directory is on it"""
+    with open(os.path.join(ROOT, "hyslam_amd", "csrc", "Makefile")) as f:
+        srcs = re.search(r"^SRCS\s*:=\s*(.+)$", f.read(), re.M).group(1).split()
+    assert all(x.endswith(".hip") for x in srcs) and len(set(srcs)) == len(srcs) >= 25
+    for flavour in ([], ["SAN=thread"]):
+        listed = subprocess.run(["make", "-s", "-C", DIR, "list"] + flavour, capture_output=True, text=True, timeout=60, check=True).stdout.split()
+        assert listed == [x[:-4] for x in srcs], (flavour, listed)
+    on_disk = sorted(x for x in os.listdir(os.path.join(ROOT, "hyslam_amd", "csrc")) if x.endswith(".hip"))
+    assert sorted(srcs) == on_disk
+
+
 def test_product_host_code_is_sanitizer_clean():
     build()
     for seed, geo, voc in ((1, 150, 500), (2, 150, 500), (7, 100, 300)):
         r = subprocess.run([EXE, str(seed), str(geo), str(voc)], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0 and "HOST SANITIZE OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
+        assert "HOST SANITIZE MAP OK" in r.stdout, (r.stdout + r.stderr)[-4000:]          # map_sweep and the place database, behind the earlier sections
         assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
+def test_threaded_sections_are_thread_sanitizer_clean():
+    """`host_sanitize threads <seed>` under ThreadSanitizer: destroy against the last borrower, the frame cache's publishers / finders / consumers, the
+    two sweeps on four threads with handles of their own, handle churn beside extraction and matching, one place database under a mutex beside one
+    without, the vocabulary loaders with their thread-local error text, hs_comm_available's first call from four threads.  No suppression file.  The
+    same mode under AddressSanitizer + UndefinedBehaviorSanitizer: what one thread frees under another is a report there"""
+    build_thread()
+    build()
+    for exe, seeds in ((EXE_T, (1, 2, 7)), (EXE, (1,))):
+        for seed in seeds:
+            clean_run([exe, "threads", str(seed)], "HOST SANITIZE THREADS OK")
+
+
+def test_adaptor_thread_code_is_sanitizer_clean():
+    """hip_detail::Worker (run / wait, a job that throws, destruction with a job outstanding), hip_detail::thread_handle (one per thread, destroyed
+    at thread exit beside working threads) and HipFeatureMatcher's projection search over 5000 landmarks with 0, 1 and 2 gather helpers from two
+    calling threads, built against the stub objects; ThreadSanitizer, then AddressSanitizer + UndefinedBehaviorSanitizer"""
+    build_thread()
+    build()
+    clean = {k: v for k, v in os.environ.items() if k != "HYSLAM_AMD_GATHER_THREADS"}
+    for flavour in ("_build_thread", "_build"):
+        for helpers in (0, 1, 2):
+            r = clean_run([os.path.join(DIR, flavour, "adaptor_threads")], "ADAPTOR THREADS OK", env=dict(clean, HYSLAM_AMD_GATHER_THREADS=str(helpers)))
+            assert "%d gather helper threads seen per caller" % min(helpers, len(os.sched_getaffinity(0)) - 1) in r.stdout      # 4096 landmarks took the split path
 
 
 def test_small_batch_pyramid_plan_is_one_launch_at_1080p():
