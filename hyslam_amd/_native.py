@@ -136,6 +136,31 @@ class KfFeatures(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("kf_off", C.c_void_p), ("kps", C.c_void_p), ("desc", C.c_void_p), ("node", C.c_void_p), ("kp_lm", C.c_void_p), ("weight", C.c_void_p)]
 
 
+# hs_track_initial_* (include/hyslam_amd.h): initial pose estimation as one resident call
+HS_REFKF_OK, HS_REFKF_BOW_FAILED, HS_REFKF_SKIPPED = 0, 1, 2
+TRACK_INITIAL_RESULT_DTYPE = np.dtype([("refkf_status", "<i4"), ("n_bow", "<i4"), ("n_matches_map_refkf", "<i4"), ("n_init", "<i4"), ("success", "<i4"),
+                                       ("_pad", "<i4", 3)])
+
+
+class TrackRefkfParams(C.Structure):
+    """hs_track_refkf_params; the defaults are the reference's (TrackReferenceKeyFrameParameters, StateNormalParameters)"""
+    _fields_ = [("th_low", C.c_float), ("nnratio", C.c_float), ("n_min_matches_bow", C.c_int32), ("thresh_init", C.c_int32)]
+
+    def __init__(self, th_low=50.0, nnratio=0.7, n_min_matches_bow=15, thresh_init=10):
+        super().__init__(th_low, nnratio, n_min_matches_bow, thresh_init)
+
+
+# the device outputs of the hs_track_initial_* calls: (field, element dtype, count as a size name or a number)
+TRACK_INITIAL_OUT_SPEC = (("bow_word", np.int32, "n"), ("bow_weight", np.float32, "n"), ("bow_node", np.int32, "n"), ("match_kf", np.int32, "kf_cap"),
+                          ("op_view", np.int32, "n"), ("op_lm", np.int32, "n"), ("pose_view", "pose_view", 1), ("problem", "problem", 1), ("edges", "edge", "n"),
+                          ("outlier", np.uint8, "n"), ("n_edges", np.int32, 2), ("pose", "result", 1), ("Tcw_init", np.float32, 16),
+                          ("result", "track_initial_result", 1), ("frame_result", "track_result", 1))
+
+
+class TrackInitialOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in TRACK_INITIAL_OUT_SPEC]
+
+
 # hs_keyframe_* (include/hyslam_amd.h): reference key frame, key-frame decision, stereo landmark creation
 KEYFRAME_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("ref_slot", "<i4"), ("n_valid", "<i4"), ("n_ref_matches", "<i4"), ("n_tracked_close", "<i4"),
                                   ("n_nontracked_close", "<i4"), ("insert", "<i4"), ("n_new", "<i4"), ("n_candidates", "<i4"), ("n_processed", "<i4"),
@@ -173,7 +198,7 @@ class TrackOut(C.Structure):
 
 def track_out_dtype(kind):
     return {"pose_view": POSE_VIEW_DTYPE, "problem": POSE_PROBLEM_DTYPE, "lm": LM_DTYPE, "edge": POSE_EDGE_DTYPE, "result": POSE_RESULT_DTYPE,
-            "track_result": TRACK_RESULT_DTYPE, "keyframe_result": KEYFRAME_RESULT_DTYPE, "lm_entry": LM_ENTRY_DTYPE, "lm_obs": LM_OBS_DTYPE}[kind] if isinstance(kind, str) else np.dtype(kind)
+            "track_result": TRACK_RESULT_DTYPE, "track_initial_result": TRACK_INITIAL_RESULT_DTYPE, "keyframe_result": KEYFRAME_RESULT_DTYPE, "lm_entry": LM_ENTRY_DTYPE, "lm_obs": LM_OBS_DTYPE}[kind] if isinstance(kind, str) else np.dtype(kind)
 
 
 class FrameView(C.Structure):
@@ -229,7 +254,8 @@ EXPORTS = [
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
     "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
-    "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes", "hs_device_alloc", "hs_device_free", "hs_device_copy",
+    "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes",
+    "hs_track_initial_work_bytes", "hs_track_reference_keyframe_device", "hs_track_initial_device", "hs_track_normal_device", "hs_device_alloc", "hs_device_free", "hs_device_copy",
     "hs_keyframe_work_bytes", "hs_keyframe_reference_device", "hs_keyframe_gate_device", "hs_keyframe_clean_device", "hs_keyframe_need_device",
     "hs_keyframe_create_device", "hs_keyframe_discard_device", "hs_track_keyframe_device",
     "hs_bow_vector", "hs_bow_vector_device", "hs_place_db_create", "hs_place_db_destroy", "hs_place_db_add", "hs_place_db_add_device", "hs_place_db_erase",
@@ -390,6 +416,14 @@ def lib():
     L.hs_search_by_bow_kf_device.argtypes = [vp, C.POINTER(KfFeatures), vp, C.POINTER(KfTable), vp, vp, vp, vp, C.c_int, f32, f32, vp, C.c_int, vp, vp, vp, vp, vp]
     L.hs_frame_associate_views_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.hs_track_refkf_work_bytes.argtypes, L.hs_track_refkf_work_bytes.restype = [C.c_int] * 3, C.c_size_t
+    L.hs_track_initial_work_bytes.argtypes, L.hs_track_initial_work_bytes.restype = [C.c_int] * 5, C.c_size_t
+    refkf = [vp, C.POINTER(KfFeatures), vp, C.c_int, vp, vp]                # vocab, K, d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry
+    itail = [C.POINTER(TrackParams), C.POINTER(TrackRefkfParams), C.POINTER(TrackState)]
+    L.hs_track_reference_keyframe_device.argtypes = [vp, C.POINTER(FrameView)] + refkf + [vp, C.POINTER(KfTable), vp] + itail + [C.POINTER(TrackInitialOut), vp, vp]
+    motion = [vp, C.POINTER(FrameView), C.c_int, vp, vp, vp, C.c_int]       # h, F, velocity_valid, d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last
+    L.hs_track_initial_device.argtypes = motion + refkf + [C.POINTER(KfTable), vp] + itail + [C.POINTER(TrackOut), C.POINTER(TrackInitialOut), vp, vp]
+    L.hs_track_normal_device.argtypes = (motion + refkf + [C.POINTER(KfTable), vp, vp, C.c_int, vp, C.c_int] + itail +
+                                         [C.POINTER(TrackOut), C.POINTER(TrackInitialOut), vp, vp])
     L.hs_keyframe_work_bytes.argtypes, L.hs_keyframe_work_bytes.restype = [C.c_int] * 3, C.c_size_t
     kst, kpr = C.POINTER(TrackState), C.POINTER(KeyFrameParams)
     L.hs_keyframe_reference_device.argtypes = [vp, C.c_int, kst, C.POINTER(KfTable), vp, vp, vp, vp]

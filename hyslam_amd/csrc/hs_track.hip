@@ -6,12 +6,6 @@
 #include <cstddef>
 
 namespace {
-bool out_ok(const hs_track_out* o)
-{
-    return o && o->pose_view && o->problem && o->last_lms && o->narrow_idx && o->narrow_dist && o->narrow_n && o->wide_idx && o->wide_dist && o->wide_n && o->op_view &&
-           o->edges_motion && o->outlier_motion && o->n_edges_motion && o->pose_motion && o->edges_local && o->outlier_local && o->n_edges_local && o->pose_local &&
-           o->result && !((uintptr_t)o->last_lms & 15) && !((uintptr_t)o->edges_motion & 15) && !((uintptr_t)o->edges_local & 15);
-}
 hs_proj_params proj_params(float th, float ratio, const hs_track_params& tp, bool last_frame)
 {
     hs_proj_params pp{};
@@ -114,7 +108,7 @@ int hs_track_motion_model_device(hs_orb* h, const hs_frame_view* F, const float*
 {
     if (!h) return HS_ERR_INVALID;
     if (!F || F->n < 1 || F->n > 65535 || !F->kps || !F->desc || !d_Tcw_pred || n_last < 1 || !d_last_kps || !d_last_kp_lm || !T || T->L < 1 || !T->lm_nobs || !d_lms ||
-        ((uintptr_t)d_lms & 15) || !tp || !state_ok(st) || !out_ok(out) || !d_work)
+        ((uintptr_t)d_lms & 15) || !tp || !state_ok(st) || !track_out_ok(out) || !d_work)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     hipStream_t s = hs_stream_or(h, stream);
@@ -150,7 +144,7 @@ int hs_track_local_map_device(hs_orb* h, const hs_frame_view* F, const float* d_
 {
     if (!h) return HS_ERR_INVALID;
     if (!F || F->n < 1 || F->n > 65535 || !F->kps || !F->desc || !d_Tcw_in || !T || T->L < 1 || !T->lm_nobs || !T->lm_bad || !d_lms || ((uintptr_t)d_lms & 15) || cap < 1 ||
-        !tp || !state_ok(st) || !out_ok(out) || !d_work)
+        !tp || !state_ok(st) || !track_out_ok(out) || !d_work)
         return hs_fail(h, HS_ERR_INVALID, "bad argument");
     HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
     hipStream_t s = hs_stream_or(h, stream);

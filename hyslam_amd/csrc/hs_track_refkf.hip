@@ -4,10 +4,6 @@
 #include "hs_track.h"
 #include <cstddef>
 
-namespace {
-bool feats_ok(const hs_kf_features* K) { return K && K->n_kf >= 0 && K->kf_off && K->kps && K->desc && K->node && K->kp_lm; }
-}  // namespace
-
 extern "C" {
 
 size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L) { (void)kf_cap; return HsVassocWork::bytes(n, L); }

@@ -75,6 +75,18 @@ struct HsTrackWork {
     static size_t bytes(int n, int L) { HsWorkCursor c; HsTrackWork(c, n, L); return c.offset(); }
 };
 
+// initial pose estimation (hs_track_reference_keyframe_device, hs_track_initial_device, hs_track_normal_device): the tracking area first, so that the
+// motion and local-map stages carve theirs from the same base; then the replay in view order and the search's ops as the gate masked them
+struct HsInitialWork {
+    void* base; HsTrackWork track; HsVassocWork vassoc; int32_t *op_view_run, *op_lm_run /*[n]*/;
+    HsInitialWork(HsWorkCursor& c, int n, int L) : base(c.here()), track(c, n, L), vassoc(c.align256(), n, L)
+    {
+        op_view_run = c.take<int32_t>(hs_dim(n)); op_lm_run = c.take<int32_t>(hs_dim(n)); c.align256();
+        c.skip(256);
+    }
+    static size_t bytes(int n, int L) { HsWorkCursor c; HsInitialWork(c, n, L); return c.offset(); }
+};
+
 // key frame (hs_keyframe_reference_device, hs_keyframe_create_device): the vote's query and its three scalars in a 256-byte head, the depth keys,
 // the vote's counter row.  The caller sizes the row with kf_cap; hs_keyframe_reference_device votes over T->n_kf counters and has no way to check
 // kf_cap >= T->n_kf: that is the caller's contract (include/hyslam_amd.h), and the entry points carve with T->n_kf, which moves no pointer.

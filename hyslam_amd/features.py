@@ -969,6 +969,36 @@ class FrameTracker:
         ex = self._ex
         N.check(ex._h, ex._lib.hs_frame_associate_views_device(ex._h, n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work, stream or None))
 
+    def track_initial_work_bytes(self, n, n_last, L, cap, kf_cap):
+        return int(self._ex._lib.hs_track_initial_work_bytes(int(n), int(n_last), int(L), int(cap), int(kf_cap)))
+
+    def track_reference_keyframe_device(self, frame, vocab, keyframes, d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry, d_motion_result, table, d_lms, params, refkf_params,
+                                        state, iout, d_work, stream=0):
+        """hs_track_reference_keyframe_device: the fall-back of initialPoseEstimation with both gates on the device.  vocab: the hs_vocab_dev handle
+        (distributed.DeviceVocabulary._v); d_motion_result 0 / None: the stage always runs; iout: _native.TrackInitialOut"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_reference_keyframe_device(ex._h, C.byref(frame), vocab, C.byref(keyframes), d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry,
+                                                                  d_motion_result or None, C.byref(table), d_lms, C.byref(params), C.byref(refkf_params),
+                                                                  C.byref(state), C.byref(iout), d_work, stream or None))
+
+    def track_initial_device(self, frame, velocity_valid, d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, vocab, keyframes, d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry,
+                             table, d_lms, params, refkf_params, state, out, iout, d_work, stream=0):
+        """hs_track_initial_device: TrackingStateNormal::initialPoseEstimation; out (_native.TrackOut) may be None when the velocity is not valid"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_initial_device(ex._h, C.byref(frame), int(bool(velocity_valid)), d_Tcw_pred or None, d_last_kps or None, d_last_kp_lm or None,
+                                                       n_last, vocab, C.byref(keyframes), d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry or None, C.byref(table), d_lms,
+                                                       C.byref(params), C.byref(refkf_params), C.byref(state), C.byref(out) if out is not None else None,
+                                                       C.byref(iout), d_work, stream or None))
+
+    def track_normal_device(self, frame, velocity_valid, d_Tcw_pred, d_last_kps, d_last_kp_lm, n_last, vocab, keyframes, d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry,
+                            table, d_lms, d_neigh, neigh_cap, d_parent, cap, params, refkf_params, state, out, iout, d_work, stream=0):
+        """hs_track_normal_device: hs_track_initial_device, the local-map stage from iout.Tcw_init, and iout.frame_result for the key-frame stage"""
+        ex = self._ex
+        N.check(ex._h, ex._lib.hs_track_normal_device(ex._h, C.byref(frame), int(bool(velocity_valid)), d_Tcw_pred or None, d_last_kps or None, d_last_kp_lm or None,
+                                                      n_last, vocab, C.byref(keyframes), d_kf_slot, kf_cap, d_Tcw_last, d_Tcw_entry or None, C.byref(table), d_lms,
+                                                      d_neigh, neigh_cap, d_parent, cap, C.byref(params), C.byref(refkf_params), C.byref(state), C.byref(out),
+                                                      C.byref(iout), d_work, stream or None))
+
     def keyframe_work_bytes(self, n, kf_cap, new_cap):
         return int(self._ex._lib.hs_keyframe_work_bytes(int(n), int(kf_cap), int(new_cap)))
 
@@ -1172,6 +1202,93 @@ class FrameTracker:
         """the two, one after the other on the device (hs_track_frame_device): the local map starts from the motion model's pose whatever its status;
         the caller reads `status` and decides what TrackingStateNormal decides.  Returns the union of the two calls' results."""
         return self._summary(self._run("frame", frame, Tcw_pred, table, landmarks, last_kps, last_kp_lm, neigh, parent, cap, params), True, True)
+
+    def initial_outputs(self, n, kf_cap, alloc=None):
+        """device buffers for every field of _native.TrackInitialOut -> (TrackInitialOut, {field: (buffer, dtype, count)})"""
+        sizes, bufs = dict(n=n, kf_cap=kf_cap), {}
+        alloc = alloc or (lambda nbytes: _DevBuf(self._ex, nbytes))
+        for k, kind, cnt in N.TRACK_INITIAL_OUT_SPEC:
+            dt, cnt = N.track_out_dtype(kind), sizes.get(cnt, cnt)
+            bufs[k] = (alloc(dt.itemsize * cnt), dt, cnt)
+        return N.TrackInitialOut(*[bufs[k][0].ptr for k, _, _ in N.TRACK_INITIAL_OUT_SPEC]), bufs
+
+    def _run_initial(self, local, frame, vocab, keyframes, kf_slot, Tcw_last, table, landmarks, velocity_valid, Tcw_pred, last_kps, last_kp_lm, Tcw_entry, state,
+                     neigh, parent, cap, params, refkf_params, kf_cap):
+        ex = self._ex
+        F, fkeep = self.device_frame(frame)
+        KT, tkeep = self.device_table(table)
+        KF, kkeep = self.device_keyframes(keyframes)
+        lms = np.ascontiguousarray(landmarks, N.LM_DTYPE)
+        if len(lms) != KT.L:
+            raise ValueError("one hs_landmark record per landmark of the table")
+        n = F.n
+        off = np.asarray(keyframes["kf_off"], np.int64)
+        kf_cap = int(kf_cap or max(1, int(np.diff(off).max()) if len(off) > 1 else 1))
+        cap = int(cap or KT.L)
+        prm, rprm = params or N.TrackParams(), refkf_params or N.TrackRefkfParams()
+        if state is None:
+            state = (np.full(n, -1, np.int32), np.zeros(n, np.uint8), 0)
+        st_in = (np.ascontiguousarray(state[0], np.int32), np.ascontiguousarray(state[1], np.uint8), np.array([state[2]], np.int32), np.full(n, -1, np.int32))
+        if len(st_in[0]) != n or len(st_in[1]) != n:
+            raise ValueError("the state has one entry per keypoint")
+        st_bufs = [_DevBuf(ex, a.nbytes, a) for a in st_in]
+        ST = N.TrackState(*[b.ptr for b in st_bufs])
+        pose = lambda T: _DevBuf(ex, 64, np.ascontiguousarray(T, np.float32).reshape(16))
+        d_last, d_lms, d_slot = pose(Tcw_last), _DevBuf(ex, lms.nbytes, lms), _DevBuf(ex, 4, np.array([kf_slot], np.int32))
+        d_pred = d_entry = d_lk = d_ll = None
+        n_last = 1
+        if velocity_valid:
+            lk, ll = np.ascontiguousarray(last_kps, N.KP_DTYPE), np.ascontiguousarray(last_kp_lm, np.int32)
+            if len(lk) != len(ll) or len(ll) < 1:
+                raise ValueError("last_kps and last_kp_lm have one entry per keypoint of the last frame")
+            d_pred, d_lk, d_ll, n_last = pose(Tcw_pred), _DevBuf(ex, lk.nbytes, lk), _DevBuf(ex, ll.nbytes, ll), len(ll)
+        else:
+            d_entry = pose(Tcw_entry)
+        out, obufs = self.outputs(dict(n=n, n_last=n_last, n_kf=KT.n_kf, cap=cap))
+        iout, ibufs = self.initial_outputs(n, kf_cap)
+        work = _DevBuf(ex, self.track_initial_work_bytes(n, n_last, KT.L, cap, kf_cap))
+        ptr = lambda b: b.ptr if b is not None else None
+        head = (F, velocity_valid, ptr(d_pred), ptr(d_lk), ptr(d_ll), n_last, vocab._v, KF, d_slot.ptr, kf_cap, d_last.ptr, ptr(d_entry), KT, d_lms.ptr)
+        if local:
+            ng, pa = np.ascontiguousarray(neigh, np.int32).reshape(KT.n_kf, -1), np.ascontiguousarray(parent, np.int32)
+            d_ng, d_pa = _DevBuf(ex, ng.nbytes, ng), _DevBuf(ex, pa.nbytes, pa)
+            self.track_normal_device(*head, d_ng.ptr, ng.shape[1], d_pa.ptr, cap, prm, rprm, ST, out, iout, work.ptr)
+        else:
+            self.track_initial_device(*head, prm, rprm, ST, out, iout, work.ptr)
+        ex.synchronize()
+        raw = {k: b.read(dt, cnt) for k, (b, dt, cnt) in obufs.items()}
+        raw.update({"initial." + k: b.read(dt, cnt) for k, (b, dt, cnt) in ibufs.items()})
+        r = raw["initial.result"][0]
+        res = dict(kp_lm=st_bufs[0].read(np.int32, n), kp_outl=st_bufs[1].read(np.uint8, n), n_matches=int(st_bufs[2].read(np.int32, 1)[0]),
+                   kp_lm_obs=st_bufs[3].read(np.int32, n), raw=raw, Tcw_init=raw["initial.Tcw_init"].reshape(4, 4).copy(), pose_refkf=raw["initial.pose"][0])
+        res.update({k: int(r[k]) for k in N.TRACK_INITIAL_RESULT_DTYPE.names if k != "_pad"})
+        if velocity_valid:
+            m = raw["result"][0]
+            res.update(pose_motion=raw["pose_motion"][0], status=int(m["status"]), used_wide=bool(m["used_wide"]), n_narrow=int(m["n_narrow"]), n_wide=int(m["n_wide"]),
+                       n_matches_map=int(m["n_matches_map"]))
+        if local:
+            res.update(pose_local=raw["pose_local"][0], n_inliers=int(raw["result"][0]["n_inliers"]), frame_result=raw["initial.frame_result"][0])
+        del fkeep, tkeep, kkeep
+        return res
+
+    def InitialPoseEstimation(self, frame, vocab, keyframes, kf_slot, Tcw_last, table, landmarks, velocity_valid, Tcw_pred=None, last_kps=None, last_kp_lm=None,
+                              Tcw_entry=None, state=None, params=None, refkf_params=None, kf_cap=None):
+        """TrackingStateNormal::initialPoseEstimation on the device (hs_track_initial_device): the motion model when `velocity_valid` (Tcw_pred, last_kps,
+        last_kp_lm as TrackMotionModel), then TrackReferenceKeyFrame::track when the motion model found fewer than thresh_init matches, both decisions
+        taken on the device.  vocab: a distributed.DeviceVocabulary; keyframes: see device_keyframes, kf_slot the reference key frame in it; Tcw_last: the
+        last frame's pose; without a valid velocity the fall-back always runs, on `state` (kp_lm, kp_outl, n_matches; default: empty) and with Tcw_entry
+        the pose the frame holds.  params: _native.TrackParams, refkf_params: _native.TrackRefkfParams.  Returns a dict: kp_lm, kp_outl, n_matches, the
+        fields of hs_track_initial_result (refkf_status, n_bow, n_matches_map_refkf, n_init, success), Tcw_init (4, 4), pose_refkf, with a valid velocity
+        the motion model's fields as TrackMotionModel returns them, and `raw`: every device output by field name (the initial stage's as "initial.<field>")."""
+        return self._run_initial(False, frame, vocab, keyframes, kf_slot, Tcw_last, table, landmarks, velocity_valid, Tcw_pred, last_kps, last_kp_lm, Tcw_entry, state,
+                                 None, None, None, params, refkf_params, kf_cap)
+
+    def TrackNormal(self, frame, vocab, keyframes, kf_slot, Tcw_last, table, landmarks, neigh, parent, velocity_valid, Tcw_pred=None, last_kps=None, last_kp_lm=None,
+                    Tcw_entry=None, state=None, params=None, refkf_params=None, kf_cap=None, cap=None):
+        """InitialPoseEstimation, then TrackLocalMap::track from Tcw_init (hs_track_normal_device); the local map runs whatever `success` says, and the
+        caller decides.  Adds pose_local, n_inliers and frame_result: the hs_track_result record KeyFrameDecision takes as track_result."""
+        return self._run_initial(True, frame, vocab, keyframes, kf_slot, Tcw_last, table, landmarks, velocity_valid, Tcw_pred, last_kps, last_kp_lm, Tcw_entry, state,
+                                 neigh, parent, cap, params, refkf_params, kf_cap)
 
     def keyframe_outputs(self, new_cap, alloc=None):
         """device buffers for every field of _native.KeyFrameOut -> (KeyFrameOut with lms = NULL, {field: (buffer, dtype, count)})"""

@@ -966,6 +966,87 @@ size_t hs_track_refkf_work_bytes(int n, int kf_cap, int L);
 int  hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view,
                                      const int32_t* d_op_lm, void* d_work, void* stream);
 
+/* ================= initial pose estimation as one resident call: both gates on the device =================
+ * (src/slam/tracking/TrackingStateNormal.cpp:21-58, TrackReferenceKeyFrame.cpp:10-58; DESIGN.md 5.13 "the chain")
+ * TrackingStateNormal::initialPoseEstimation decides twice on a count: the motion model's return value decides whether the fall-back runs (:34), and
+ * the BoW search's count decides whether the fall-back optimises (TrackReferenceKeyFrame.cpp:27).  The three calls below take both decisions on the
+ * device: every step is enqueued whatever the counts are, and a step that is switched off reads its gate from device memory and changes nothing.
+ * They are enqueue-only under the rules of the tracking section: the arguments are checked on the host before the first launch (a vocabulary that
+ * lives on another device than h excepted: hs_bow_transform_device refuses it where it is reached), nothing synchronises, nothing reads device memory
+ * on the host, and nothing takes the handle's scratch beyond what the reused calls take (the projection searches' grid lists).
+ *
+ * The gate, evaluated by every thread of k_init_gate from the same two words:
+ *   motion_return = motion status == HS_TRACK_MOTION_FAILED ? -1 : n_matches_map      (0 for a stage that is not predicated)
+ *   run           = not predicated || motion_return < thresh_init
+ *   refkf_status  = !run ? HS_REFKF_SKIPPED : n_bow < n_min_matches_bow ? HS_REFKF_BOW_FAILED : HS_REFKF_OK
+ * A stage that is not HS_REFKF_OK leaves the state (kp_lm, kp_outl, n_matches) byte for byte as it found it, hands the optimiser 0 edges
+ * (n_edges[1] = 0, pose->status = HS_POSE_TOO_FEW, pose->Tcw = d_Tcw_last) and copies d_Tcw_entry to Tcw_init bit for bit.  The transform and the
+ * search run in every case: bow_*, match_kf, op_view / op_lm, n_bow and n_edges[0] are what they are for a stage that runs. */
+typedef struct hs_track_refkf_params {
+    float   th_low, nnratio;           /* FeatureMatcherSettings::TH_LOW; TrackReferenceKeyFrame's matcher ratio                       */
+    int32_t n_min_matches_bow;         /* TrackReferenceKeyFrameParameters::N_min_matches_BoW                                          */
+    int32_t thresh_init;               /* StateNormalParameters::thresh_init                                                           */
+} hs_track_refkf_params;
+#define HS_REFKF_OK 0
+#define HS_REFKF_BOW_FAILED 1          /* fewer than n_min_matches_bow matches: TrackReferenceKeyFrame::track returned -1               */
+#define HS_REFKF_SKIPPED 2             /* the motion model's return value was at least thresh_init: the fall-back did not run           */
+typedef struct hs_track_initial_result {
+    int32_t refkf_status;              /* HS_REFKF_*                                                                                   */
+    int32_t n_bow;                     /* the search's nmatches, also for a skipped stage                                              */
+    int32_t n_matches_map_refkf;       /* TrackReferenceKeyFrame::track's nmatchesMap; 0 unless HS_REFKF_OK                            */
+    int32_t n_init;                    /* initialPoseEstimation's nmatches: OK: the line above; BOW_FAILED: -1; SKIPPED: motion_return */
+    int32_t success;                   /* n_init > thresh_init (:41)                                                                   */
+    int32_t _pad[3];                   /* written as 0                                                                                 */
+} hs_track_initial_result;             /* 32 bytes */
+typedef struct hs_track_initial_out {  /* all device memory, all required; n = F->n                                                    */
+    int32_t* bow_word; float* bow_weight; int32_t* bow_node;      /* [n]  hs_bow_transform_device's outputs for the frame              */
+    int32_t* match_kf;                 /* [kf_cap] hs_search_by_bow_kf_device's                                                        */
+    int32_t* op_view; int32_t* op_lm;  /* [n]  as the search leaves them: never masked                                                 */
+    hs_pose_view* pose_view; hs_pose_problem* problem;            /* [1]  from d_Tcw_last                                              */
+    hs_pose_edge* edges;               /* [n]  16-byte aligned                                                                         */
+    uint8_t* outlier;                  /* [n]                                                                                          */
+    int32_t* n_edges;                  /* [2]  [0] nInitialCorrespondences, [1] what the optimiser sees: 0 unless HS_REFKF_OK          */
+    hs_pose_result* pose;              /* [1]                                                                                          */
+    float* Tcw_init;                   /* [16] the pose the frame holds after the stage: pose->Tcw when OK, else d_Tcw_entry           */
+    hs_track_initial_result* result;   /* [1]                                                                                          */
+    hs_track_result* frame_result;     /* [1]  written by hs_track_normal_device only; not the record hs_track_out.result points to    */
+} hs_track_initial_out;
+/* d_work of the three calls: hs_track_work_bytes's area, hs_track_refkf_work_bytes's, the masked ops.  16-byte aligned, contents irrelevant before
+ * and after. */
+size_t hs_track_initial_work_bytes(int n, int n_last, int L, int cap, int kf_cap);
+/* TrackReferenceKeyFrame::track as the fall-back of initialPoseEstimation.  F: the frame with device pointers (n, sensor, the camera, kps, desc, uR,
+ * size_ref are read).  vocab: the resident vocabulary; K, d_kf_slot, kf_cap: as hs_search_by_bow_kf_device.  d_Tcw_last float[16]: the last frame's
+ * pose, from which the optimiser starts (SetPose(last_frame.mTcw), :32).  d_Tcw_entry float[16]: the pose the frame holds on entry.
+ * d_motion_result: the motion stage's record, on which the stage is predicated, or NULL for a stage that always runs.  tp: sigma_ref is read.
+ * Enqueued, in this order: hs_bow_transform_device on F->desc; hs_search_by_bow_kf_device (always: n_bow is reported for a skipped stage too); the
+ * gate; hs_frame_associate_views_device on the masked ops; pose view and problem from d_Tcw_last; hs_pose_edges_device; the edge gate;
+ * hs_pose_optimize_device; hs_track_discard_device (HS_TRACK_MOTION) on &n_edges[1]; the finish (n_init, success, Tcw_init).
+ * iout->frame_result is not touched.  1 <= F->n <= 65535, kf_cap >= 1, T->L >= 1. */
+int  hs_track_reference_keyframe_device(hs_orb* h, const hs_frame_view* F, const hs_vocab_dev* vocab, const hs_kf_features* K, const int32_t* d_kf_slot, int kf_cap,
+                                        const float* d_Tcw_last, const float* d_Tcw_entry, const hs_track_result* d_motion_result, const hs_kf_table* T,
+                                        const hs_landmark* d_lms, const hs_track_params* tp, const hs_track_refkf_params* rp, const hs_track_state* st,
+                                        const hs_track_initial_out* iout, void* d_work, void* stream);
+/* TrackingStateNormal::initialPoseEstimation.  The validity of the trajectory's velocity stays a host fact.  velocity_valid != 0:
+ * hs_track_motion_model_device (its arguments as there), then the call above predicated on out->result with d_Tcw_entry = out->pose_motion->Tcw (the
+ * caller's d_Tcw_entry is not read).  velocity_valid == 0: the call above alone, not predicated, on the caller's d_Tcw_entry and on the state as it
+ * is; d_Tcw_pred, the last frame and `out` are not read and may be NULL.  It IS these calls. */
+int  hs_track_initial_device(hs_orb* h, const hs_frame_view* F, int velocity_valid, const float* d_Tcw_pred, const hs_keypoint* d_last_kps,
+                             const int32_t* d_last_kp_lm, int n_last, const hs_vocab_dev* vocab, const hs_kf_features* K, const int32_t* d_kf_slot, int kf_cap,
+                             const float* d_Tcw_last, const float* d_Tcw_entry, const hs_kf_table* T, const hs_landmark* d_lms, const hs_track_params* tp,
+                             const hs_track_refkf_params* rp, const hs_track_state* st, const hs_track_out* out, const hs_track_initial_out* iout, void* d_work,
+                             void* stream);
+/* TrackingStateNormal's two stages: hs_track_initial_device, then hs_track_local_map_device from iout->Tcw_init, then one record for the key-frame
+ * stage: iout->frame_result = { status = HS_TRACK_OK, used_wide / n_narrow / n_wide of the motion stage (0 when it did not run), n_matches_map =
+ * n_init, n_inliers of the local stage }.  With that record and ok_override = -1, hs_keyframe_gate_device computes n_init > thresh_init && n_inliers
+ * > thresh_refine && !force_loss: TrackingStateNormal.cpp:41,71 for every path, the fall-back included.  `out` is required in both modes (the local
+ * stage writes into it).  It is these calls and nothing else: the local-map stage runs whatever the initial stage reports, exactly as in
+ * hs_track_frame_device; gating it on `success` is NOT done here and stays with the caller, who reads iout->result / iout->frame_result once. */
+int  hs_track_normal_device(hs_orb* h, const hs_frame_view* F, int velocity_valid, const float* d_Tcw_pred, const hs_keypoint* d_last_kps,
+                            const int32_t* d_last_kp_lm, int n_last, const hs_vocab_dev* vocab, const hs_kf_features* K, const int32_t* d_kf_slot, int kf_cap,
+                            const float* d_Tcw_last, const float* d_Tcw_entry, const hs_kf_table* T, const hs_landmark* d_lms, const int32_t* d_neigh,
+                            int neigh_cap, const int32_t* d_parent, int cap, const hs_track_params* tp, const hs_track_refkf_params* rp,
+                            const hs_track_state* st, const hs_track_out* out, const hs_track_initial_out* iout, void* d_work, void* stream);
+
 /* ================= after the two track functions: reference key frame, key-frame decision, stereo landmark creation =================
  * (src/main/Tracking.cpp:179-227,273-317,375-388, src/slam/tracking/TrackingStateNormal.cpp:87-170, src/slam/tracking/TrackingState.cpp:20-93;
  * DESIGN.md 5.14)  What Tracking::_Track_ does with the frame once hs_track_frame_device has run, on the same dense state (kp_lm,
@@ -1003,7 +1084,7 @@ typedef struct hs_keyframe_params {
     int32_t n_min_points;              /* the literal 100 of TrackingState.cpp:85                                                     */
     int32_t thresh_init, thresh_refine;/* StateNormalParameters (TrackingStateNormal.cpp:41,71)                                       */
     int32_t force_loss;                /* 1: the reset_interval branch fired (:78-82); n_frames_tracked_consecutively stays a host counter */
-    int32_t ok_override;               /* -1: compute ok from *d_track_result; 0 / 1: take this (a frame that came through the fall-back) */
+    int32_t ok_override;               /* -1: compute ok from *d_track_result; 0 / 1: take this (a fall-back driven step by step; hs_track_normal_device's frame_result needs none) */
 } hs_keyframe_params;
 typedef struct hs_keyframe_result {
     int32_t ok;                        /* stage 2: bOK                                                                                */
