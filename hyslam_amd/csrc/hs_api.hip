@@ -4,6 +4,7 @@
 // sequence.  The whole extraction of a batch is GPU-resident: pyramid -> FAST/NMS cells -> quadtree
 // distribution -> blur+orientation+rBRIEF, 10 kernel launches for an 8-level pyramid regardless of batch size.
 #include "hs_plan.h"
+#include "hs_track.h"               // hs_search_by_projection_why / _enqueue: the search is a stage of the track chains
 #include <atomic>
 #include <climits>
 #include <cmath>
@@ -1435,41 +1436,34 @@ int hs_frame_grid(hs_orb* h, const hs_frame_view* F, int8_t* cell_xy)
     return st.finish();
 }
 
-namespace {
-int search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
-                                int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
+} // extern "C"
+int hs_search_by_projection_enqueue(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
+                                    int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, hipStream_t s)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!F || !pp || L < 1 || !d_lms || !d_match_idx || !d_match_dist || !d_n_matches || F->n < 1 || F->n > 65535 || !F->kps || !F->desc ||
-        (pp->use_stereo && F->sensor != 0 && !F->uR))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(h->device));
     // temporaries only, and no synchronisation: the call runs on the caller's stream.  Scratch is per handle: a second call may only start
     // after the first finished (same stream ordering is enough)
-    hipStream_t s = hs_stream_or(h, stream);
     HsStage st(h, s);                                            // (under hs_debug_poison the fill is ordered in front of the launches)
     int8_t* d_cell; int32_t* d_winner; float* d_pangle;
     st.temp(&d_cell, hs_frame_grid_bytes(F->n)); st.temp(&d_winner, F->n); st.temp(&d_pangle, L);
-    int rc = st.begin();
+    const int rc = st.begin();
     if (rc != HS_OK) return rc;
     hs_launch_frame_grid(*F, F->kps, d_cell, true, s);
     hs_launch_search_projection(*F, F->kps, F->desc, F->uR, F->kp_lm_obs, d_cell, d_lms, L, *pp, d_match_idx, d_match_dist, d_winner, d_pangle, d_n_matches, s, d_pose);
-    HIP_TRY(h, hipGetLastError());
     return HS_OK;
 }
-}  // namespace
+extern "C" {
 int hs_search_by_projection_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
                                    int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
 {
-    return search_by_projection_device(h, F, nullptr, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, stream);
+    return hs_device_call(h, hs_search_by_projection_why(F, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches), stream,
+                          [&](hipStream_t s) { return hs_search_by_projection_enqueue(h, F, nullptr, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, s); });
 }
 // the pose from device memory (hs_pose_views_device): F's Rcw / tcw / Ow are not read
 int hs_search_by_projection_posed_device(hs_orb* h, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms, int L, const hs_proj_params* pp,
                                          int32_t* d_match_idx, float* d_match_dist, int32_t* d_n_matches, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!d_pose) return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    return search_by_projection_device(h, F, d_pose, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, stream);
+    return hs_device_call(h, d_pose ? hs_search_by_projection_why(F, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches) : "bad argument", stream,
+                          [&](hipStream_t s) { return hs_search_by_projection_enqueue(h, F, d_pose, d_lms, L, pp, d_match_idx, d_match_dist, d_n_matches, s); });
 }
 
 namespace {

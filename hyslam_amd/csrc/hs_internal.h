@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -324,6 +325,22 @@ inline int hs_fail(hs_orb* h, int code, const std::string& msg) { hs_set_error(h
 // thread does not report it again through hipGetLastError()
 #define HIP_TRY(h, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); \
     return hs_fail(h, HS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
+
+// The public form of every enqueue-only `_device` entry point of the resident chain.  `why` is the entry point's predicate over its
+// arguments — pure host code, the refusal's text or nullptr — and `enqueue(stream)` its launches with no check in them: a composite's predicate is
+// its stages' predicates and its enqueue their enqueues, so this is the one place a chain sets the device and asks for the last error, once each,
+// and a refused call enqueues, copies and allocates nothing.  enqueue returns void, or an HS_ status where it makes a HIP call that is no launch.
+inline const char* hs_bad(bool refused) { return refused ? "bad argument" : nullptr; }
+template <class Enqueue> int hs_device_call(hs_orb* h, const char* why, void* stream, Enqueue enqueue)
+{
+    if (!h) return HS_ERR_INVALID;
+    if (why) return hs_fail(h, HS_ERR_INVALID, why);
+    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
+    if constexpr (std::is_void<decltype(enqueue(hipStream_t()))>::value) enqueue(hs_stream_or(h, stream));
+    else { const int rc = enqueue(hs_stream_or(h, stream)); if (rc != HS_OK) return rc; }
+    HIP_TRY(h, hipGetLastError());
+    return HS_OK;
+}
 
 // argument checks of the host forms over an observation table (hs_kfgraph.hip, hs_localmap.hip): a CSR of `n` rows has offsets[0] >= 0 and is
 // non-decreasing; every index lies in [lo, limit)

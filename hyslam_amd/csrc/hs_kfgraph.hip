@@ -11,6 +11,7 @@
 // Where the reference's result depends on the walk order of a std::map<KeyFrame*, ...> the rule is spelled out on the slot: the maximum
 // is reduced over the key (count, ~slot), the ordered list is ranked on the key (count, slot).
 #include "hs_match_device.h"
+#include "hs_track.h"               // hs_kf_votes_why / _enqueue: the vote is a stage of the local map and of the reference key frame
 #include <climits>
 
 #define KF_VOTE_THREADS 1024       // block_scan_excl (hs_match_device.h) is written for 1024 threads
@@ -194,25 +195,27 @@ static void launch_votes(const KfVoteArgs& a, int Q, hipStream_t s)
     else hipLaunchKernelGGL(k_kf_votes<false>, dim3(Q), dim3(KF_VOTE_THREADS), 0, s, a);
 }
 
+void hs_kf_votes_enqueue(const hs_kf_table* T, int Q, const int64_t* d_q_offsets, const int32_t* d_q_lm, const int64_t* d_q_self_id, int count_bad_kf, int th,
+                         int32_t* d_weights, int32_t* d_max_slot, int32_t* d_max_count, int32_t* d_ordered_slot, int32_t* d_ordered_weight, int cap, int32_t* d_n_ordered,
+                         hipStream_t s)
+{
+    if (Q == 0) return;
+    const KfVoteArgs a{T->L, T->n_kf, count_bad_kf ? 1 : 0, th, cap, 0, T->lm_obs_offsets, T->lm_obs_kf, T->lm_bad, T->kf_bad, T->kf_id,
+                       d_q_offsets, d_q_lm, d_q_self_id, d_weights, d_weights, d_max_slot, d_max_count, d_ordered_slot, d_ordered_weight, d_n_ordered};
+    launch_votes(a, Q, s);
+}
+
 extern "C" {
 
 int hs_kf_votes_device(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* d_q_offsets, const int32_t* d_q_lm, const int64_t* d_q_self_id,
                        int count_bad_kf, int th, int32_t* d_weights, int32_t* d_max_slot, int32_t* d_max_count,
                        int32_t* d_ordered_slot, int32_t* d_ordered_weight, int cap, int32_t* d_n_ordered, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!T || Q < 0 || cap < 0 || T->L < 0 || T->n_kf < 0) return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (Q == 0) return HS_OK;
-    if (!T->lm_obs_offsets || !d_q_offsets || !d_max_slot || !d_max_count || !d_n_ordered || (cap > 0 && (!d_ordered_slot || !d_ordered_weight)) ||
-        (T->n_kf > 0 && (!T->kf_bad || !T->kf_id)) || (T->L > 0 && !T->lm_bad))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    if (T->n_kf > HS_KF_LDS_SLOTS && !d_weights) return hs_fail(h, HS_ERR_INVALID, "beyond HS_KF_LDS_SLOTS key frames the weights rows are the counters: d_weights is required");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    const KfVoteArgs a{T->L, T->n_kf, count_bad_kf ? 1 : 0, th, cap, 0, T->lm_obs_offsets, T->lm_obs_kf, T->lm_bad, T->kf_bad, T->kf_id,
-                       d_q_offsets, d_q_lm, d_q_self_id, d_weights, d_weights, d_max_slot, d_max_count, d_ordered_slot, d_ordered_weight, d_n_ordered};
-    launch_votes(a, Q, hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_kf_votes_why(T, Q, d_q_offsets, d_weights, d_max_slot, d_max_count, d_ordered_slot, d_ordered_weight, cap, d_n_ordered), stream,
+                          [&](hipStream_t s) {
+        hs_kf_votes_enqueue(T, Q, d_q_offsets, d_q_lm, d_q_self_id, count_bad_kf, th, d_weights, d_max_slot, d_max_count, d_ordered_slot, d_ordered_weight, cap,
+                            d_n_ordered, s);
+    });
 }
 
 int hs_kf_votes(hs_orb* h, const hs_kf_table* T, int Q, const int64_t* q_offsets, const int32_t* q_lm, const int64_t* q_self_id,

@@ -2,35 +2,48 @@
 // hs_landmark_gather_device and hs_local_map_search_device, which is the vote of hs_kfgraph.hip, these three and the projection search enqueued on one
 // stream.  The kernels and their launchers are in kernels_localmap.hip.  The host forms check their arguments and stage through HsStage; the device
 // forms take their temporaries from the caller, so nothing here claims the handle's scratch between two launches of a chain.
-#include "hs_internal.h"
+#include "hs_track.h"
+
+// the vote (keyframeCounter with the bad key frames in it, pKFmax among those that are not bad; no ordered list: TrackLocalMap.cpp:80-123), the local
+// key frames, the local points, the gather and the search on one stream
+const char* hs_local_map_search_why(const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
+                                    const hs_frame_view* F, const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out,
+                                    const HsLocalMapWork& w)
+{
+    if (!T || !out || !w.base || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
+        !out->frame_remove || !out->sel || !out->n_sel || !out->lms || !out->match_idx || !out->match_dist || !out->n_matches)
+        return "bad argument";
+    return hs_first({ hs_kf_votes_why(T, 1, w.q_off, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, w.n_ordered),
+                      hs_local_keyframes_why(T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, out->local, out->n_local),
+                      hs_local_points_why(T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, w.points.base),
+                      hs_landmark_gather_why(d_lms, T->L, out->sel, out->n_sel, cap, out->lms),
+                      hs_search_by_projection_why(F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches) });
+}
+int hs_local_map_search_enqueue(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap, const int32_t* d_parent,
+                                int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose, const hs_landmark* d_lms,
+                                const hs_proj_params* pp, int cap, const hs_local_map_out* out, const HsLocalMapWork& w, hipStream_t s)
+{
+    hs_launch_local_map_query(n_assoc, w.q_off, s);
+    hs_kf_votes_enqueue(T, 1, w.q_off, d_frame_lm, nullptr, 1, 1, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, w.n_ordered, s);
+    hs_launch_local_keyframes(T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, out->local, out->n_local, s);
+    hs_launch_local_points(*T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, w.points, s);
+    hs_launch_landmark_gather(d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
+    return hs_search_by_projection_enqueue(h, F, d_pose, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
+}
 
 namespace {
-// the vote, the local key frames, the local points, the gather and the search on one stream; d_pose (may be nullptr): the search reads the pose from it
-int local_map_search(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
+// both public forms; refuse: the posed form without a pose
+int local_map_search(hs_orb* h, bool refuse, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
                      const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F, const hs_pose_view* d_pose,
                      const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!T || !out || !d_work || cap < 1 || n_assoc < 0 || !out->weights || !out->max_slot || !out->max_count || !out->local || !out->n_local ||
-        !out->frame_remove || !out->sel || !out->n_sel || !out->lms || !out->match_idx || !out->match_dist || !out->n_matches)
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hipStream_t s = hs_stream_or(h, stream);
     HsWorkCursor c(d_work);
-    const HsLocalMapWork w(c, T->L);
-    hs_launch_local_map_query(n_assoc, w.q_off, s);
-    // keyframeCounter with the bad key frames in it, pKFmax among those that are not bad; no ordered list (TrackLocalMap.cpp:80-123)
-    int rc = hs_kf_votes_device(h, T, 1, w.q_off, d_frame_lm, nullptr, 1, 1, out->weights, out->max_slot, out->max_count, nullptr, nullptr, 0, w.n_ordered, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_local_keyframes_device(h, T->n_kf, out->weights, T->kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes,
-                                   out->local, out->n_local, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_local_points_device(h, T, out->local, d_frame_lm, n_assoc, out->frame_remove, out->sel, cap, out->n_sel, w.points.base, s);
-    if (rc != HS_OK) return rc;
-    rc = hs_landmark_gather_device(h, d_lms, T->L, out->sel, out->n_sel, cap, out->lms, s);
-    if (rc != HS_OK) return rc;
-    if (d_pose) return hs_search_by_projection_posed_device(h, F, d_pose, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
-    return hs_search_by_projection_device(h, F, out->lms, cap, pp, out->match_idx, out->match_dist, out->n_matches, s);
+    const HsLocalMapWork w(c, T ? T->L : 0);
+    return hs_device_call(h, refuse ? "bad argument" : hs_local_map_search_why(T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, F, d_lms, pp, cap, out, w), stream,
+                          [&](hipStream_t s) {
+        return hs_local_map_search_enqueue(h, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, d_pose, d_lms, pp, cap,
+                                           out, w, s);
+    });
 }
 }  // namespace
 
@@ -42,14 +55,9 @@ size_t hs_local_map_work_bytes(int L) { return HsLocalMapWork::bytes(L); }
 int hs_local_keyframes_device(hs_orb* h, int n_kf, const int32_t* d_weights, const uint8_t* d_kf_bad, const int32_t* d_neigh, int neigh_cap,
                               const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, uint8_t* d_local, int32_t* d_n_local, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (n_kf < 0 || neigh_cap < 0 || !d_n_local || (n_kf > 0 && (!d_weights || !d_kf_bad || !d_parent || !d_local || (neigh_cap > 0 && !d_neigh))))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_local_keyframes(n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local, d_n_local,
-                              hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_local_keyframes_why(n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, d_local, d_n_local), stream, [&](hipStream_t s) {
+        hs_launch_local_keyframes(n_kf, d_weights, d_kf_bad, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, d_local, d_n_local, s);
+    });
 }
 
 int hs_local_keyframes(hs_orb* h, int n_kf, const int32_t* weights, const uint8_t* kf_bad, const int32_t* neigh, int neigh_cap, const int32_t* parent,
@@ -76,15 +84,10 @@ int hs_local_keyframes(hs_orb* h, int n_kf, const int32_t* weights, const uint8_
 int hs_local_points_device(hs_orb* h, const hs_kf_table* T, const uint8_t* d_local, const int32_t* d_frame_lm, int n_assoc, uint8_t* d_frame_remove,
                            int32_t* d_sel, int cap, int32_t* d_n_sel, void* d_work, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!T || T->L < 0 || T->n_kf < 0 || n_assoc < 0 || cap < 0 || !d_n_sel || !d_work || (cap > 0 && !d_sel) || (n_assoc > 0 && (!d_frame_lm || !d_frame_remove)) ||
-        (T->L > 0 && (!T->lm_obs_offsets || !T->lm_bad)) || (T->n_kf > 0 && !d_local))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    HsWorkCursor c(d_work);
-    hs_launch_local_points(*T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, HsLocalPointsWork(c, T->L), hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_local_points_why(T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, d_work), stream, [&](hipStream_t s) {
+        HsWorkCursor c(d_work);
+        hs_launch_local_points(*T, d_local, d_frame_lm, n_assoc, d_frame_remove, d_sel, cap, d_n_sel, HsLocalPointsWork(c, T->L), s);
+    });
 }
 
 int hs_local_points(hs_orb* h, const hs_kf_table* T, const uint8_t* local, const int32_t* frame_lm, int n_assoc, uint8_t* frame_remove,
@@ -119,20 +122,15 @@ int hs_local_points(hs_orb* h, const hs_kf_table* T, const uint8_t* local, const
 
 int hs_landmark_gather_device(hs_orb* h, const hs_landmark* d_lms, int L, const int32_t* d_sel, const int32_t* d_n_sel, int cap, hs_landmark* d_out, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (L < 0 || cap < 0 || !d_n_sel || (cap > 0 && (!d_sel || !d_out)) || (L > 0 && !d_lms) || ((uintptr_t)d_lms & 15) || ((uintptr_t)d_out & 15))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument (d_lms and d_out are 16-byte aligned)");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_landmark_gather(d_lms, L, d_sel, d_n_sel, cap, d_out, hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_landmark_gather_why(d_lms, L, d_sel, d_n_sel, cap, d_out), stream,
+                          [&](hipStream_t s) { hs_launch_landmark_gather(d_lms, L, d_sel, d_n_sel, cap, d_out, s); });
 }
 
 int hs_local_map_search_device(hs_orb* h, const hs_kf_table* T, const int32_t* d_frame_lm, int n_assoc, const int32_t* d_neigh, int neigh_cap,
                                const int32_t* d_parent, int n_max_local_keyframes, int n_neighbor_keyframes, const hs_frame_view* F,
                                const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out, void* d_work, void* stream)
 {
-    return local_map_search(h, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, nullptr, d_lms, pp, cap, out,
+    return local_map_search(h, false, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, nullptr, d_lms, pp, cap, out,
                             d_work, stream);
 }
 // the search reads the pose from device memory (hs_search_by_projection_posed_device)
@@ -141,9 +139,7 @@ int hs_local_map_search_posed_device(hs_orb* h, const hs_kf_table* T, const int3
                                      const hs_pose_view* d_pose, const hs_landmark* d_lms, const hs_proj_params* pp, int cap, const hs_local_map_out* out,
                                      void* d_work, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (!d_pose) return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    return local_map_search(h, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, d_pose, d_lms, pp, cap, out,
+    return local_map_search(h, !d_pose, T, d_frame_lm, n_assoc, d_neigh, neigh_cap, d_parent, n_max_local_keyframes, n_neighbor_keyframes, F, d_pose, d_lms, pp, cap, out,
                             d_work, stream);
 }
 

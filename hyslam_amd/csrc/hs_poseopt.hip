@@ -1,7 +1,7 @@
 // hs_poseopt.hip — entry points of the pose-only optimisation (include/hyslam_amd.h): hs_pose_optimize(_device), hs_pose_work_bytes and
 // hs_pose_edges_device.  The kernels and their launchers are in kernels_poseopt.hip.  The host form checks its arguments and stages through HsStage;
 // the device forms check nothing that lives on the device and claim nothing of the handle's scratch, so a chain of launches never waits for it.
-#include "hs_poseopt.h"
+#include "hs_track.h"               // the predicates of the two device forms, which the track stages call too
 
 extern "C" {
 
@@ -12,14 +12,8 @@ int hs_pose_optimize_device(hs_orb* h, int Q, const hs_pose_problem* d_problems,
                             const hs_pose_edge* d_edges, uint8_t* d_outlier, hs_pose_result* d_results, void* d_work, void* stream)
 {
     (void)d_work;
-    if (!h) return HS_ERR_INVALID;
-    if (Q < 0 || (Q > 0 && (!d_problems || !d_results)) || (d_edge_offsets != nullptr) == (d_n_edges != nullptr) || (d_n_edges && (Q != 1 || edge_cap < 0)) ||
-        ((uintptr_t)d_edges & 15))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument (exactly one of d_edge_offsets and d_n_edges; d_n_edges needs Q == 1; d_edges is 16-byte aligned)");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_pose_optimize(Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_outlier, d_results, hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_pose_optimize_why(Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_results), stream,
+                          [&](hipStream_t s) { hs_launch_pose_optimize(Q, d_problems, d_edge_offsets, d_n_edges, edge_cap, d_edges, d_outlier, d_results, s); });
 }
 
 int hs_pose_optimize(hs_orb* h, int Q, const hs_pose_problem* problems, const int64_t* edge_offsets, const hs_pose_edge* edges, uint8_t* outlier,
@@ -47,13 +41,8 @@ int hs_pose_edges_device(hs_orb* h, const hs_frame_view* F, const hs_landmark* d
                          hs_pose_edge* d_edges, int cap, int32_t* d_n_edges, void* d_work, void* stream)
 {
     (void)d_work;
-    if (!h) return HS_ERR_INVALID;
-    if (!F || F->n < 0 || L < 0 || cap < 0 || !d_n_edges || (cap > 0 && !d_edges) || (F->n > 0 && (!F->kps || !d_kp_lm)) || (L > 0 && !d_lms))
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_pose_edges(*F, d_lms, L, d_kp_lm, sigma_ref, d_edges, cap, d_n_edges, hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_pose_edges_why(F, d_lms, L, d_kp_lm, d_edges, cap, d_n_edges), stream,
+                          [&](hipStream_t s) { hs_launch_pose_edges(*F, d_lms, L, d_kp_lm, sigma_ref, d_edges, cap, d_n_edges, s); });
 }
 
 }  // extern "C"

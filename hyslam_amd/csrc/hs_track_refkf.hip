@@ -13,27 +13,19 @@ int hs_search_by_bow_kf_device(hs_orb* h, const hs_kf_features* K, const int32_t
                                int32_t* d_op_lm, int32_t* d_n_matches, void* d_work, void* stream)
 {
     (void)d_work;
-    if (!h) return HS_ERR_INVALID;
-    if (!feats_ok(K) || !d_kf_slot || !T || T->L < 0 || (T->L > 0 && !T->lm_bad) || n < 1 || n > 65535 || !d_kps || !d_desc || !d_node || kf_cap < 1 || !d_match_kf ||
-        !d_op_view || !d_op_lm || !d_n_matches)
-        return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    hs_launch_search_by_bow_kf(*K, d_kf_slot, *T, d_kps, d_desc, d_node, d_weight, n, th_low, nnratio, d_match_kf, kf_cap, d_op_view, d_op_lm, d_n_matches,
-                               hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_search_by_bow_kf_why(K, d_kf_slot, T, d_kps, d_desc, d_node, n, d_match_kf, kf_cap, d_op_view, d_op_lm, d_n_matches), stream,
+                          [&](hipStream_t s) {
+        hs_launch_search_by_bow_kf(*K, d_kf_slot, *T, d_kps, d_desc, d_node, d_weight, n, th_low, nnratio, d_match_kf, kf_cap, d_op_view, d_op_lm, d_n_matches, s);
+    });
 }
 
 int hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, uint8_t* d_kp_outl, int32_t* d_n_matches, const int32_t* d_op_view,
                                     const int32_t* d_op_lm, void* d_work, void* stream)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (n < 0 || L < 0 || !d_n_matches || !d_work || (n > 0 && (!d_kp_lm || !d_kp_outl || !d_op_view || !d_op_lm))) return hs_fail(h, HS_ERR_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    HsWorkCursor c(d_work);
-    hs_launch_frame_associate_views(n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, HsVassocWork(c, n, L), hs_stream_or(h, stream));
-    HIP_TRY(h, hipGetLastError());
-    return HS_OK;
+    return hs_device_call(h, hs_frame_associate_views_why(n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, d_work), stream, [&](hipStream_t s) {
+        HsWorkCursor c(d_work);
+        hs_launch_frame_associate_views(n, L, d_kp_lm, d_kp_outl, d_n_matches, d_op_view, d_op_lm, HsVassocWork(c, n, L), s);
+    });
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 // dist<<32 | side-2 index, which makes the bucket's internal order irrelevant.  Features whose word weight is not positive are left out of the
 // feature vector, as in DBoW2 (`if (w > 0) fv.addFeature(nid, i)`).
 #include "hs_match_device.h"
+#include "hs_track.h"               // hs_bow_transform_why / _enqueue: the transform is a stage of the reference-key-frame chain
 #include <algorithm>
 #include <vector>
 
@@ -292,17 +293,24 @@ void hs_vocab_dev_destroy(hs_vocab_dev* v)
 
 int hs_vocab_dev_groups(const hs_vocab_dev* v) { return v ? v->groups : 0; }
 
+} // extern "C"
+const char* hs_bow_transform_why(const hs_vocab_dev* v, int device, const uint8_t* d_desc, int n_max, const int32_t* d_word, const float* d_weight, const int32_t* d_node)
+{
+    if (!v || n_max < 0 || v->device != device) return "bad argument";
+    return hs_bad(n_max > 0 && (!d_desc || !d_word || !d_weight || !d_node));      // nothing to transform: the pointers are not looked at
+}
+void hs_bow_transform_enqueue(const hs_vocab_dev* v, const uint8_t* d_desc, const int32_t* d_n, int n_max, int32_t* d_word, float* d_weight, int32_t* d_node, hipStream_t s)
+{
+    if (n_max > 0) hipLaunchKernelGGL(k_bow_transform_dev, dim3((n_max + 255) / 256), dim3(256), 0, s, tree_of(v), d_desc, d_n, n_max, d_word, d_weight, d_node);
+}
+extern "C" {
+
 int hs_bow_transform_device(hs_orb* h, const hs_vocab_dev* v, const uint8_t* d_desc, const int32_t* d_n, int n_max,
                             int32_t* d_word, float* d_weight, int32_t* d_node, void* stream)
 {
-    if (!h || !v) return HS_ERR_INVALID;
-    if (n_max < 0 || (n_max > 0 && (!d_desc || !d_word || !d_weight || !d_node)) || v->device != hs_orb_device_of(h)) { hs_set_error(h, "bad argument"); return HS_ERR_INVALID; }
-    if (n_max == 0) return HS_OK;
-    if (hipSetDevice(v->device) != hipSuccess) return HS_ERR_HIP;
-    hipStream_t s = hs_stream_or(h, stream);
-    hipLaunchKernelGGL(k_bow_transform_dev, dim3((n_max + 255) / 256), dim3(256), 0, s, tree_of(v), d_desc, d_n, n_max, d_word, d_weight, d_node);
-    if (hipGetLastError() != hipSuccess) { hs_set_error(h, "k_bow_transform_dev launch failed"); return HS_ERR_HIP; }
-    return HS_OK;
+    if (!v) return HS_ERR_INVALID;                               // as a null handle: no text
+    return hs_device_call(h, hs_bow_transform_why(v, hs_orb_device_of(h), d_desc, n_max, d_word, d_weight, d_node), stream,
+                          [&](hipStream_t s) { hs_bow_transform_enqueue(v, d_desc, d_n, n_max, d_word, d_weight, d_node, s); });
 }
 
 int hs_records_bow_match_device(hs_orb* h, hs_vocab_dev* v, const uint8_t* d_records, size_t record_stride, int world, int rank, int cap,

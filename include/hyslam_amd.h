@@ -972,7 +972,7 @@ int  hs_frame_associate_views_device(hs_orb* h, int n, int L, int32_t* d_kp_lm, 
  * the BoW search's count decides whether the fall-back optimises (TrackReferenceKeyFrame.cpp:27).  The three calls below take both decisions on the
  * device: every step is enqueued whatever the counts are, and a step that is switched off reads its gate from device memory and changes nothing.
  * They are enqueue-only under the rules of the tracking section: the arguments are checked on the host before the first launch (a vocabulary that
- * lives on another device than h excepted: hs_bow_transform_device refuses it where it is reached), nothing synchronises, nothing reads device memory
+ * lives on another device than h among them: what hs_bow_transform_device refuses, these refuse), nothing synchronises, nothing reads device memory
  * on the host, and nothing takes the handle's scratch beyond what the reused calls take (the projection searches' grid lists).
  *
  * The gate, evaluated by every thread of k_init_gate from the same two words:

@@ -14,9 +14,13 @@
 // usage: host_sanitize [seed] [geometries] [vocab_cases]      prints "HOST SANITIZE OK ..." (any sanitizer report aborts with a non-zero status)
 //        host_sanitize threads [seed]                         prints "HOST SANITIZE THREADS OK ..."
 //        host_sanitize plan W H [nfeat scale levels [cell]]   the host-side plan of a geometry
+//        host_sanitize refusals [list]                        prints "HOST SANITIZE REFUSALS OK ..." (list: every call's status first)
+#include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <random>
 #include <string>
 #include <vector>
@@ -779,8 +783,213 @@ static int frame_cache_section(uint64_t seed)
     return 0;
 }
 
+// ---- `host_sanitize refusals`: a refused call enqueues nothing.  Every enqueue-only `_device` entry point that is a stage of a resident chain, and
+// every chain, gets one valid argument set at small sizes (no kernel runs under the stub) and then one knock-out at a time: every pointer argument and
+// every pointer field of every struct argument NULL (found by scanning the argument set for words that point into the arena every buffer comes from),
+// every struct argument NULL, every integer at its first refused value, the 16-byte aligned arrays off their alignment, sensor != 0 without uR, the
+// frame_result alias.  Each call returns HS_OK or HS_ERR_INVALID; across a refused call no counter of the stub moves (launches, their digest, copies,
+// memsets, allocations); an accepted call launches what the valid call launches (an integer knock-out may leave it less); the knock-outs a chain's LATER stages refuse (MUST below) are refused by the chain.
+namespace refusals {
+struct Arena {
+    std::vector<uint8_t> mem = std::vector<uint8_t>(4u << 20, 0); size_t used = 0;
+    template <class T> T* take(size_t n) { used = (used + 255) & ~(size_t)255; T* p = reinterpret_cast<T*>(mem.data() + used); used += std::max<size_t>(n * sizeof(T), 16); return p; }
+    bool holds(const void* p) const { return (const uint8_t*)p >= mem.data() && (const uint8_t*)p < mem.data() + mem.size(); }
+};
+struct Args {                                                     // plain data: a knock-out edits a copy
+    hs_frame_view F; hs_kf_table T; hs_kf_features K; hs_track_state S; hs_track_out O; hs_track_initial_out IO; hs_keyframe_out KO;
+    hs_track_params tp; hs_track_refkf_params rp; hs_keyframe_params kp; hs_proj_params pp;
+    int has_F, has_T, has_K, has_S, has_O, has_IO, has_KO, has_tp, has_rp, has_kp, has_pp;      // 0: the call gets NULL for the struct
+    const hs_vocab_dev* vocab;
+    float *Tpred, *Tlast, *Tentry, *Tcw, *depth; hs_keypoint* last_kps; int32_t *last_lm, *neigh, *parent, *kf_slot, *ref_slot, *counts; int64_t* q_off;
+    hs_landmark* lms; hs_track_result* track_result; void* work;
+    int n_last, neigh_cap, cap, kf_cap, new_cap;
+};
+struct Knock { std::string name; std::function<void(Args&)> apply; bool size = false; /* an integer: an accepted call may find nothing to launch */ };
+struct Entry { const char* name; std::function<int(hs_orb*, const Args&)> call; std::vector<std::string> must; };
+#define P(x) (a.has_##x ? &a.x : nullptr)
+
+static int run(bool list /*print every call's status: two commits that refuse the same calls print the same lines*/)
+{
+    hs_orb_params p; hs_orb_default_params(&p); p.nfeatures = 300;
+    hs_orb* h = nullptr;
+    CHECK(hs_orb_create(&p, 0, &h) == HS_OK);
+    const int n = 100, n_last = 80, L = 120, n_kf = 5, cap = 60, kf_cap = 8, new_cap = 16, neigh_cap = 10, n_kps_kf = 12;
+    Arena ar;
+    Args v; memset(&v, 0, sizeof(v));
+    v.has_F = v.has_T = v.has_K = v.has_S = v.has_O = v.has_IO = v.has_KO = v.has_tp = v.has_rp = v.has_kp = v.has_pp = 1;
+    v.n_last = n_last; v.neigh_cap = neigh_cap; v.cap = cap; v.kf_cap = kf_cap; v.new_cap = new_cap;
+    v.F.fx = v.F.fy = 300.f; v.F.cx = 160.f; v.F.cy = 120.f; v.F.max_x = 320.f; v.F.max_y = 240.f; v.F.size_ref = 31.f; v.F.mbf = 40.f; v.F.sensor = 1; v.F.n = n;
+    v.F.kps = ar.take<hs_keypoint>(n); v.F.desc = ar.take<uint8_t>((size_t)n * 32); v.F.uR = ar.take<float>(n); v.F.kp_lm_obs = ar.take<int32_t>(n);
+    v.T = hs_kf_table{ L, n_kf, ar.take<int64_t>(L + 1), ar.take<int32_t>(16), ar.take<int32_t>(16), ar.take<uint8_t>(L), ar.take<int32_t>(L), ar.take<uint8_t>(n_kf), ar.take<int64_t>(n_kf) };
+    v.K = hs_kf_features{ n_kf, ar.take<int64_t>(n_kf + 1), ar.take<hs_keypoint>(n_kps_kf), ar.take<uint8_t>(n_kps_kf * 32), ar.take<int32_t>(n_kps_kf), ar.take<int32_t>(n_kps_kf), ar.take<float>(n_kps_kf) };
+    v.S = hs_track_state{ ar.take<int32_t>(n), ar.take<uint8_t>(n), ar.take<int32_t>(1), ar.take<int32_t>(n) };
+    const hs_local_map_out lo{ ar.take<int32_t>(n_kf), ar.take<int32_t>(1), ar.take<int32_t>(1), ar.take<uint8_t>(n_kf), ar.take<int32_t>(1), ar.take<uint8_t>(n), ar.take<int32_t>(cap), ar.take<int32_t>(1),
+                               ar.take<hs_landmark>(cap), ar.take<int32_t>(cap), ar.take<float>(cap), ar.take<int32_t>(1) };
+    v.O = hs_track_out{ ar.take<hs_pose_view>(2), ar.take<hs_pose_problem>(2), ar.take<hs_landmark>(n_last), ar.take<int32_t>(n_last), ar.take<float>(n_last), ar.take<int32_t>(1), ar.take<int32_t>(n_last),
+                        ar.take<float>(n_last), ar.take<int32_t>(1), ar.take<int32_t>(n_last), ar.take<hs_pose_edge>(n), ar.take<uint8_t>(n), ar.take<int32_t>(2), ar.take<hs_pose_result>(1), lo,
+                        ar.take<hs_pose_edge>(n), ar.take<uint8_t>(n), ar.take<int32_t>(1), ar.take<hs_pose_result>(1), ar.take<hs_track_result>(1) };
+    v.IO = hs_track_initial_out{ ar.take<int32_t>(n), ar.take<float>(n), ar.take<int32_t>(n), ar.take<int32_t>(kf_cap), ar.take<int32_t>(n), ar.take<int32_t>(n), ar.take<hs_pose_view>(1),
+                                 ar.take<hs_pose_problem>(1), ar.take<hs_pose_edge>(n), ar.take<uint8_t>(n), ar.take<int32_t>(2), ar.take<hs_pose_result>(1), ar.take<float>(16),
+                                 ar.take<hs_track_initial_result>(1), ar.take<hs_track_result>(1) };
+    v.KO = hs_keyframe_out{ ar.take<hs_keyframe_result>(1), ar.take<hs_pose_view>(1), ar.take<int32_t>(new_cap), ar.take<float>(new_cap * 3), ar.take<hs_lm_entry_in>(new_cap), ar.take<hs_lm_obs>(new_cap),
+                            ar.take<int64_t>(new_cap + 1), ar.take<int64_t>(new_cap + 1), ar.take<uint8_t>(new_cap * 32), ar.take<int32_t>(new_cap), ar.take<hs_landmark>(L + new_cap), L + new_cap };
+    v.tp.th_motion = 7.f; v.tp.th_motion_wide = 14.f; v.tp.n_min_matches = 20; v.tp.th_local = 3.f; v.tp.nnratio_motion = 0.9f; v.tp.nnratio_local = 0.8f; v.tp.th_high = 100.f; v.tp.sigma_ref = 1.f;
+    v.tp.n_max_local_keyframes = 80; v.tp.n_neighbor_keyframes = 10;
+    v.rp = hs_track_refkf_params{ 50.f, 0.7f, 15, 10 };
+    v.kp.frame_id = 100; v.kp.last_keyframe_id = 10; v.kp.max_KF_interval = 30; v.kp.th_depth = 40.f; v.kp.n_min_points = 100; v.kp.ok_override = -1;
+    v.pp.th = 3.f; v.pp.score_threshold = 100.f; v.pp.second_best_ratio = 0.8f; v.pp.frac_smaller = 0.5f; v.pp.frac_larger = 1.5f; v.pp.use_stereo = 1;
+    v.Tpred = ar.take<float>(16); v.Tlast = ar.take<float>(16); v.Tentry = ar.take<float>(16); v.Tcw = ar.take<float>(16); v.depth = ar.take<float>(n);
+    v.last_kps = ar.take<hs_keypoint>(n_last); v.last_lm = ar.take<int32_t>(n_last); v.neigh = ar.take<int32_t>(n_kf * neigh_cap); v.parent = ar.take<int32_t>(n_kf);
+    v.kf_slot = ar.take<int32_t>(1); v.ref_slot = ar.take<int32_t>(1); v.counts = ar.take<int32_t>(1); v.q_off = ar.take<int64_t>(2); v.lms = ar.take<hs_landmark>(L);
+    v.track_result = ar.take<hs_track_result>(1);
+    v.work = ar.take<uint8_t>(std::max(hs_track_initial_work_bytes(n, n_last, L, cap, kf_cap), hs_keyframe_work_bytes(n, kf_cap, new_cap)));
+    std::vector<int32_t> cb, cc, word; std::vector<uint8_t> vdesc; std::vector<float> weight;
+    { hs_vocab* voc = make_vocab(3, 3, cb, cc, vdesc, word, weight); CHECK(voc != nullptr); hs_vocab_destroy(voc); }
+    const hs_vocab_tree tree{ (int32_t)cb.size(), 3, cb.data(), cc.data(), vdesc.data(), word.data(), weight.data(), nullptr };
+    hs_vocab_dev* vocab = nullptr;
+    CHECK(hs_vocab_upload(h, &tree, 1, &vocab) == HS_OK && vocab);
+    v.vocab = vocab;
+    CHECK(ar.used < ar.mem.size());
+
+    // ---- the knock-outs
+    std::vector<Knock> kos;
+    static const struct { size_t off; const char* name; } parts[] = {
+        { offsetof(Args, F), "F" }, { offsetof(Args, T), "T" }, { offsetof(Args, K), "K" }, { offsetof(Args, S), "st" }, { offsetof(Args, O), "out" }, { offsetof(Args, IO), "iout" },
+        { offsetof(Args, KO), "kout" }, { offsetof(Args, tp), "params" }, { offsetof(Args, vocab), "argument" } };
+    for (size_t off = 0; off + sizeof(void*) <= sizeof(Args); off += sizeof(void*)) {
+        void* word_at; memcpy(&word_at, (const char*)&v + off, sizeof(void*));
+        if (!ar.holds(word_at)) continue;
+        size_t k = 0;
+        while (k + 1 < sizeof(parts) / sizeof(parts[0]) && parts[k + 1].off <= off) k++;
+        kos.push_back({ std::string(parts[k].name) + " + " + std::to_string(off - parts[k].off) + " = NULL", [off](Args& a) { memset((char*)&a + off, 0, sizeof(void*)); } });
+    }
+    const size_t n_scanned = kos.size();
+    CHECK(n_scanned == 4 + 7 + 6 + 4 + (19 + 12) + 15 + 11 + 16);      // every pointer field of the seven structs and the sixteen pointer arguments were found
+    kos.push_back({ "F->uR = NULL, sensor 1", [](Args& a) { a.F.uR = nullptr; } });
+    kos.push_back({ "out->local.weights = NULL", [](Args& a) { a.O.local.weights = nullptr; } });
+    kos.push_back({ "out->local.match_idx = NULL", [](Args& a) { a.O.local.match_idx = nullptr; } });
+    kos.push_back({ "d_parent = NULL", [](Args& a) { a.parent = nullptr; } });
+    kos.push_back({ "d_neigh = NULL", [](Args& a) { a.neigh = nullptr; } });
+    kos.push_back({ "T->lm_obs_offsets = NULL", [](Args& a) { a.T.lm_obs_offsets = nullptr; } });
+    kos.push_back({ "T->kf_bad = NULL", [](Args& a) { a.T.kf_bad = nullptr; } });
+    kos.push_back({ "cap = 0", [](Args& a) { a.cap = 0; }, true });
+    kos.push_back({ "vocab = NULL", [](Args& a) { a.vocab = nullptr; } });
+    kos.push_back({ "F = NULL", [](Args& a) { a.has_F = 0; } }); kos.push_back({ "T = NULL", [](Args& a) { a.has_T = 0; } }); kos.push_back({ "K = NULL", [](Args& a) { a.has_K = 0; } });
+    kos.push_back({ "st = NULL", [](Args& a) { a.has_S = 0; } }); kos.push_back({ "out = NULL", [](Args& a) { a.has_O = 0; } }); kos.push_back({ "iout = NULL", [](Args& a) { a.has_IO = 0; } });
+    kos.push_back({ "kout = NULL", [](Args& a) { a.has_KO = 0; } }); kos.push_back({ "tp = NULL", [](Args& a) { a.has_tp = 0; } }); kos.push_back({ "rp = NULL", [](Args& a) { a.has_rp = 0; } });
+    kos.push_back({ "prm = NULL", [](Args& a) { a.has_kp = 0; } }); kos.push_back({ "pp = NULL", [](Args& a) { a.has_pp = 0; } });
+    kos.push_back({ "n = 0", [](Args& a) { a.F.n = 0; }, true }); kos.push_back({ "n = 65536", [](Args& a) { a.F.n = 65536; }, true }); kos.push_back({ "L = 0", [](Args& a) { a.T.L = 0; }, true });
+    kos.push_back({ "kf_cap = 0", [](Args& a) { a.kf_cap = 0; }, true }); kos.push_back({ "n_last = 0", [](Args& a) { a.n_last = 0; }, true }); kos.push_back({ "new_cap = -1", [](Args& a) { a.new_cap = -1; }, true });
+    kos.push_back({ "neigh_cap = -1", [](Args& a) { a.neigh_cap = -1; }, true });
+    kos.push_back({ "d_lms + 4", [](Args& a) { a.lms = (hs_landmark*)((char*)a.lms + 4); } });
+    kos.push_back({ "out->last_lms + 4", [](Args& a) { a.O.last_lms = (hs_landmark*)((char*)a.O.last_lms + 4); } });
+    kos.push_back({ "out->local.lms + 4", [](Args& a) { a.O.local.lms = (hs_landmark*)((char*)a.O.local.lms + 4); } });
+    kos.push_back({ "out->edges_motion + 8", [](Args& a) { a.O.edges_motion = (hs_pose_edge*)((char*)a.O.edges_motion + 8); } });
+    kos.push_back({ "out->edges_local + 8", [](Args& a) { a.O.edges_local = (hs_pose_edge*)((char*)a.O.edges_local + 8); } });
+    kos.push_back({ "iout->edges + 8", [](Args& a) { a.IO.edges = (hs_pose_edge*)((char*)a.IO.edges + 8); } });
+    kos.push_back({ "iout->frame_result = out->result", [](Args& a) { a.IO.frame_result = a.O.result; } });
+
+    // ---- the entry points.  MUST: what only a later stage of the chain reads, so that the chain has to ask that stage's predicate before its first launch
+    const std::vector<std::string> uR{ "F->uR = NULL, sensor 1" };
+    std::vector<std::string> local{ "out->local.weights = NULL", "out->local.match_idx = NULL", "d_parent = NULL", "d_neigh = NULL", "T->lm_obs_offsets = NULL", "T->kf_bad = NULL", "cap = 0" };
+    local.push_back(uR[0]);
+    auto motion_model = [](hs_orb* h, const Args& a) { return hs_track_motion_model_device(h, P(F), a.Tpred, a.last_kps, a.last_lm, a.n_last, P(T), a.lms, P(tp), P(S), P(O), a.work, nullptr); };
+    auto local_map = [](hs_orb* h, const Args& a) { return hs_track_local_map_device(h, P(F), a.Tcw, P(T), a.lms, a.neigh, a.neigh_cap, a.parent, a.cap, P(tp), P(S), P(O), a.work, nullptr); };
+    auto initial = [](int vv) { return [vv](hs_orb* h, const Args& a) {
+        return hs_track_initial_device(h, P(F), vv, a.Tpred, a.last_kps, a.last_lm, a.n_last, a.vocab, P(K), a.kf_slot, a.kf_cap, a.Tlast, a.Tentry, P(T), a.lms, P(tp), P(rp), P(S), P(O), P(IO), a.work, nullptr); }; };
+    auto normal = [](int vv) { return [vv](hs_orb* h, const Args& a) {
+        return hs_track_normal_device(h, P(F), vv, a.Tpred, a.last_kps, a.last_lm, a.n_last, a.vocab, P(K), a.kf_slot, a.kf_cap, a.Tlast, a.Tentry, P(T), a.lms, a.neigh, a.neigh_cap, a.parent, a.cap, P(tp),
+                                      P(rp), P(S), P(O), P(IO), a.work, nullptr); }; };
+    auto map_search = [](bool posed) { return [posed](hs_orb* h, const Args& a) {
+        const hs_local_map_out* o = a.has_O ? &a.O.local : nullptr;
+        return posed ? hs_local_map_search_posed_device(h, P(T), a.S.kp_lm, a.F.n, a.neigh, a.neigh_cap, a.parent, 80, 10, P(F), a.O.pose_view, a.lms, P(pp), a.cap, o, a.work, nullptr)
+                     : hs_local_map_search_device(h, P(T), a.S.kp_lm, a.F.n, a.neigh, a.neigh_cap, a.parent, 80, 10, P(F), a.lms, P(pp), a.cap, o, a.work, nullptr); }; };
+    auto projection = [](bool posed) { return [posed](hs_orb* h, const Args& a) {
+        const hs_local_map_out& o = a.O.local;
+        return posed ? hs_search_by_projection_posed_device(h, P(F), a.O.pose_view, o.lms, a.cap, P(pp), o.match_idx, o.match_dist, o.n_matches, nullptr)
+                     : hs_search_by_projection_device(h, P(F), o.lms, a.cap, P(pp), o.match_idx, o.match_dist, o.n_matches, nullptr); }; };
+    const std::vector<Entry> entries = {
+        { "hs_pose_views_device", [](hs_orb* h, const Args& a) { return hs_pose_views_device(h, a.Tpred, a.O.pose_view, nullptr); }, {} },
+        { "hs_frame_associate_device", [](hs_orb* h, const Args& a) { return hs_frame_associate_device(h, a.F.n, a.T.L, a.S.kp_lm, a.S.kp_outl, a.S.n_matches, a.n_last, a.O.op_view, a.last_lm, a.work, nullptr); }, {} },
+        { "hs_frame_views_device", [](hs_orb* h, const Args& a) { return hs_frame_views_device(h, a.F.n, a.S.kp_lm, a.S.kp_outl, a.S.n_matches, P(T), 1, a.S.kp_lm_obs, nullptr); }, {} },
+        { "hs_track_discard_device", [](hs_orb* h, const Args& a) { return hs_track_discard_device(h, HS_TRACK_MOTION, a.O.edges_motion, a.O.n_edges_motion, a.F.n, a.O.outlier_motion, a.O.pose_motion, P(T), a.F.sensor,
+                                                                                                   a.S.kp_lm, a.S.kp_outl, a.S.n_matches, a.counts, nullptr); }, {} },
+        { "hs_track_motion_model_device", motion_model, uR },
+        { "hs_track_local_map_device", local_map, local },
+        { "hs_track_frame_device", [](hs_orb* h, const Args& a) { return hs_track_frame_device(h, P(F), a.Tpred, a.last_kps, a.last_lm, a.n_last, P(T), a.lms, a.neigh, a.neigh_cap, a.parent, a.cap, P(tp), P(S), P(O),
+                                                                                               a.work, nullptr); }, local },
+        { "hs_search_by_bow_kf_device", [](hs_orb* h, const Args& a) { return hs_search_by_bow_kf_device(h, P(K), a.kf_slot, P(T), a.F.kps, a.F.desc, a.IO.bow_node, a.IO.bow_weight, a.F.n, 50.f, 0.7f, a.IO.match_kf,
+                                                                                                         a.kf_cap, a.IO.op_view, a.IO.op_lm, a.counts, nullptr, nullptr); }, {} },
+        { "hs_frame_associate_views_device", [](hs_orb* h, const Args& a) { return hs_frame_associate_views_device(h, a.F.n, a.T.L, a.S.kp_lm, a.S.kp_outl, a.S.n_matches, a.IO.op_view, a.IO.op_lm, a.work, nullptr); }, {} },
+        { "hs_track_reference_keyframe_device", [](hs_orb* h, const Args& a) { return hs_track_reference_keyframe_device(h, P(F), a.vocab, P(K), a.kf_slot, a.kf_cap, a.Tlast, a.Tentry, a.track_result, P(T), a.lms, P(tp),
+                                                                                                                         P(rp), P(S), P(IO), a.work, nullptr); }, {} },
+        { "hs_track_initial_device (valid velocity)", initial(1), uR },
+        { "hs_track_initial_device (no velocity)", initial(0), {} },
+        { "hs_track_normal_device (valid velocity)", normal(1), local },
+        { "hs_track_normal_device (no velocity)", normal(0), local },
+        { "hs_keyframe_reference_device", [](hs_orb* h, const Args& a) { return hs_keyframe_reference_device(h, a.F.n, P(S), P(T), a.ref_slot, a.KO.result, a.work, nullptr); }, {} },
+        { "hs_keyframe_gate_device", [](hs_orb* h, const Args& a) { return hs_keyframe_gate_device(h, a.track_result, P(kp), a.KO.result, nullptr); }, {} },
+        { "hs_keyframe_clean_device", [](hs_orb* h, const Args& a) { return hs_keyframe_clean_device(h, a.F.n, P(S), P(T), a.KO.result, nullptr); }, {} },
+        { "hs_keyframe_need_device", [](hs_orb* h, const Args& a) { return hs_keyframe_need_device(h, a.F.n, a.F.sensor, a.depth, P(S), P(T), P(K), a.ref_slot, a.track_result, P(kp), a.KO.result, nullptr); }, {} },
+        { "hs_keyframe_create_device", [](hs_orb* h, const Args& a) { return hs_keyframe_create_device(h, P(F), a.depth, a.Tcw, P(S), P(T), P(kp), a.new_cap, P(KO), a.work, nullptr); }, {} },
+        { "hs_keyframe_discard_device", [](hs_orb* h, const Args& a) { return hs_keyframe_discard_device(h, a.F.n, P(S), a.KO.result, nullptr); }, {} },
+        { "hs_track_keyframe_device", [](hs_orb* h, const Args& a) { return hs_track_keyframe_device(h, P(F), a.depth, a.Tcw, P(T), P(K), a.track_result, P(kp), P(S), a.ref_slot, a.new_cap, P(KO), a.work, nullptr); }, {} },
+        { "hs_local_keyframes_device", [](hs_orb* h, const Args& a) { return hs_local_keyframes_device(h, a.T.n_kf, a.O.local.weights, a.T.kf_bad, a.neigh, a.neigh_cap, a.parent, 80, 10, a.O.local.local,
+                                                                                                       a.O.local.n_local, nullptr); }, {} },
+        { "hs_local_points_device", [](hs_orb* h, const Args& a) { return hs_local_points_device(h, P(T), a.O.local.local, a.S.kp_lm, a.F.n, a.O.local.frame_remove, a.O.local.sel, a.cap, a.O.local.n_sel, a.work, nullptr); }, {} },
+        { "hs_landmark_gather_device", [](hs_orb* h, const Args& a) { return hs_landmark_gather_device(h, a.lms, a.T.L, a.O.local.sel, a.O.local.n_sel, a.cap, a.O.local.lms, nullptr); }, {} },
+        { "hs_local_map_search_device", map_search(false), {} },
+        { "hs_local_map_search_posed_device", map_search(true), {} },
+        { "hs_pose_optimize_device", [](hs_orb* h, const Args& a) { return hs_pose_optimize_device(h, 1, a.O.problem, nullptr, a.O.n_edges_local, a.F.n, a.O.edges_local, a.O.outlier_local, a.O.pose_local, nullptr, nullptr); }, {} },
+        { "hs_pose_edges_device", [](hs_orb* h, const Args& a) { return hs_pose_edges_device(h, P(F), a.lms, a.T.L, a.S.kp_lm, 1.f, a.O.edges_local, a.F.n, a.O.n_edges_local, nullptr, nullptr); }, {} },
+        { "hs_kf_votes_device", [](hs_orb* h, const Args& a) { return hs_kf_votes_device(h, P(T), 1, a.q_off, a.S.kp_lm, nullptr, 1, 1, a.O.local.weights, a.O.local.max_slot, a.O.local.max_count, nullptr, nullptr, 0,
+                                                                                         a.counts, nullptr); }, {} },
+        { "hs_search_by_projection_device", projection(false), {} },
+        { "hs_search_by_projection_posed_device", projection(true), {} },
+        { "hs_bow_transform_device", [](hs_orb* h, const Args& a) { return hs_bow_transform_device(h, a.vocab, a.F.desc, nullptr, a.F.n, a.IO.bow_word, a.IO.bow_weight, a.IO.bow_node, nullptr); }, {} },
+    };
+
+    int failures = 0, total_refused = 0;
+    auto counters_moved = [](const unsigned long long* c0) { unsigned long long c1[14]; hip_stub_counters(c1); return memcmp(c0, c1, sizeof(c1)) != 0; };
+    for (const Entry& e : entries) {
+        unsigned long long c0[14];
+        hip_stub_counters(c0);
+        const long l0 = hip_stub_launches();
+        const int rc0 = e.call(h, v);
+        const long valid_launches = hip_stub_launches() - l0;
+        if (rc0 != HS_OK || valid_launches < 1) { printf("REFUSALS FAILED %s: the valid call returned %d (%s) after %ld launches\n", e.name, rc0, hs_orb_last_error(h), valid_launches); failures++; continue; }
+        int refused = 0;
+        for (const Knock& k : kos) {
+            Args a = v;
+            k.apply(a);
+            hip_stub_counters(c0);
+            const long l1 = hip_stub_launches();
+            const int rc = e.call(h, a);
+            const long launched = hip_stub_launches() - l1;
+            const bool moved = counters_moved(c0), must = std::find(e.must.begin(), e.must.end(), k.name) != e.must.end();
+            refused += rc == HS_ERR_INVALID;
+            if (list) printf("status %d: %s, %s\n", rc, e.name, k.name.c_str());
+            const char* what = rc != HS_OK && rc != HS_ERR_INVALID ? "a status that is neither HS_OK nor HS_ERR_INVALID" : rc == HS_ERR_INVALID && moved ? "refused after the stub's counters moved"
+                             : rc == HS_OK && !k.size && launched != valid_launches ? "accepted, but not with the valid call's launches" : rc == HS_OK && must ? "accepted what a later stage refuses" : nullptr;
+            if (what) { printf("REFUSALS FAILED %s, %s: %s (status %d, %ld launches enqueued)\n", e.name, k.name.c_str(), what, rc, launched); failures++; }
+        }
+        if (refused < 1) { printf("REFUSALS FAILED %s: no knock-out was refused\n", e.name); failures++; }
+        printf("%-44s valid call: %3ld launches; %3d of %zu knock-outs refused\n", e.name, valid_launches, refused, kos.size());
+        total_refused += refused;
+    }
+    hs_vocab_dev_destroy(vocab);
+    hs_orb_destroy(h);
+    if (failures) { printf("HOST SANITIZE REFUSALS FAILED: %d findings\n", failures); return 1; }
+    printf("HOST SANITIZE REFUSALS OK: %zu entry points, %zu knock-outs each (%zu pointers found by the scan), %d calls refused, none of them moved a counter\n", entries.size(), kos.size(), n_scanned,
+           total_refused);
+    return 0;
+}
+#undef P
+}  // namespace refusals
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "refusals")) { const int rc = refusals::run(argc > 2 && !strcmp(argv[2], "list")); fflush(stdout); return rc; }      // (a failed run leaves its handle behind: its lines come before the leak report)
     if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels [cell]]: the host-side plan of a geometry, or its refusal
         hs_orb_params p; hs_orb_default_params(&p);
         p.nfeatures = argc > 4 ? atoi(argv[4]) : 2000; if (argc > 5) p.scale_factor = (float)atof(argv[5]); if (argc > 6) p.nlevels = atoi(argv[6]);

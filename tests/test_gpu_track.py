@@ -426,6 +426,67 @@ def test_end_to_end_random(tracker):
         check_case(tracker, c, ref, "seed %d" % c["seed"])
 
 
+def test_refusals(tracker):
+    """what only a LATER stage of a chain reads — the frame's uR under a stereo sensor, the local map's outputs, neigh, parent, two of its tables, cap —
+    is refused by hs_track_motion_model_device / _local_map_ / _frame_ on the host, before the first launch: each gives HS_ERR_INVALID and every output
+    byte, the work area and the state keep their bytes (n = 300, stereo); the valid call then reproduces the reference"""
+    from hyslam_amd import _native as N
+    c, ref = TC.directed("narrow")
+    assert c["frame"]["sensor"] != 0 and len(c["frame"]["kps"]) == 300
+    ch = Chain(tracker, c)
+    lib, h = tracker._ex._lib, tracker._ex._h
+    state_bytes = [b.to_numpy(np.uint8, nb + GUARD).copy() for b, nb in zip(ch.state, (4 * ch.n, ch.n, 4, 4 * ch.n))]
+    d_Tin = ch.ptr("pose_motion") + N.POSE_RESULT_DTYPE.fields["Tcw"][1]
+
+    def args(**kw):
+        a = dict(F=ch.F, T=ch.KT, out=ch.out, neigh=ch.d_neigh.ptr, neigh_cap=10, parent=ch.d_parent.ptr, cap=ch.cap)
+        a.update(kw)
+        return a
+
+    def motion(**kw):
+        a = args(**kw)
+        return lib.hs_track_motion_model_device(h, C.byref(a["F"]), ch.d_Tpred.ptr, ch.d_last_kps.ptr, ch.d_last_kp_lm.ptr, ch.n_last, C.byref(a["T"]), ch.d_lms.ptr,
+                                                C.byref(ch.tp), C.byref(ch.ST), C.byref(a["out"]), ch.work.ptr, ch.stream.ptr)
+
+    def local(**kw):
+        a = args(**kw)
+        return lib.hs_track_local_map_device(h, C.byref(a["F"]), d_Tin, C.byref(a["T"]), ch.d_lms.ptr, a["neigh"], a["neigh_cap"], a["parent"], a["cap"], C.byref(ch.tp),
+                                             C.byref(ch.ST), C.byref(a["out"]), ch.work.ptr, ch.stream.ptr)
+
+    def frame(**kw):
+        a = args(**kw)
+        return lib.hs_track_frame_device(h, C.byref(a["F"]), ch.d_Tpred.ptr, ch.d_last_kps.ptr, ch.d_last_kp_lm.ptr, ch.n_last, C.byref(a["T"]), ch.d_lms.ptr, a["neigh"],
+                                         a["neigh_cap"], a["parent"], a["cap"], C.byref(ch.tp), C.byref(ch.ST), C.byref(a["out"]), ch.work.ptr, ch.stream.ptr)
+
+    def without(struct, field, value=None):
+        s = type(struct).from_buffer_copy(struct)
+        setattr(s, field, value)
+        return s
+
+    def out_without(field):
+        o = type(ch.out).from_buffer_copy(ch.out)
+        setattr(o.local, field, None)
+        return o
+    no_uR = dict(F=without(ch.F, "uR"))
+    later = [no_uR, dict(out=out_without("weights")), dict(out=out_without("match_idx")), dict(parent=None), dict(neigh=None),
+             dict(T=without(ch.KT, "lm_obs_offsets")), dict(T=without(ch.KT, "kf_bad"))]
+    assert motion(**no_uR) == N.HS_ERR_INVALID
+    for kw in later:
+        for f in (local, frame):
+            assert f(**kw) == N.HS_ERR_INVALID, (f.__name__, list(kw))
+    assert frame(cap=0) == N.HS_ERR_INVALID and local(cap=0) == N.HS_ERR_INVALID and frame(neigh_cap=-1) == N.HS_ERR_INVALID
+    tracker._ex.synchronize()
+    ch.stream.synchronize()
+    for k, (b, dt, cnt) in ch.spec.items():
+        assert (b.to_numpy(np.uint8, dt.itemsize * cnt + GUARD) == 0x55).all(), (k, "an output of a refused call was written")
+    assert (ch.work.to_numpy(np.uint8, ch.work_bytes + GUARD) == 0x55).all(), "the work area of a refused call was written"
+    for b, was, k in zip(ch.state, state_bytes, ("kp_lm", "kp_outl", "n_matches", "kp_lm_obs")):
+        assert np.array_equal(b.to_numpy(np.uint8, len(was)), was), (k, "the state was touched by a refused call")
+    # the handle is as good as before
+    ch.frame()
+    compare_track(ch.results(), c, ref, "after the refusals", ch.N.LM_DTYPE)
+
+
 def test_frame_tracker_returns_what_the_device_calls_compute(tracker):
     from hyslam_amd import _native as N
     c, ref = TC.directed("outlier_removed")

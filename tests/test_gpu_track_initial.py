@@ -718,6 +718,19 @@ def test_refusals(world, tracker):
     assert normal(iout=without(run.iout, "frame_result", run.ptr("result"))) == N.HS_ERR_INVALID
     assert initial(Tpred=None) == N.HS_ERR_INVALID and initial(out=None) == N.HS_ERR_INVALID and initial(n_last=0) == N.HS_ERR_INVALID
     assert initial(vv=0, Tentry=None) == N.HS_ERR_INVALID and normal(vv=0, Tentry=None) == N.HS_ERR_INVALID and refkf(Tentry=None) == N.HS_ERR_INVALID
+    # what only the local stage reads, with and without a valid velocity: its outputs, neigh, parent; and what the projection searches of the motion and
+    # local stages read: uR under a stereo sensor
+
+    def out_without(field):
+        o = type(run.out).from_buffer_copy(run.out)
+        setattr(o.local, field, None)
+        return o
+    no_uR = without(sc.F, "uR")
+    no_uR.sensor = no_uR.sensor or 1
+    for vv in (1, 0):
+        for kw in [dict(out=out_without(k)) for k, _, _ in N.LOCAL_MAP_OUT_SPEC] + [dict(neigh=None), dict(parent=None), dict(F=no_uR)]:
+            assert normal(vv=vv, **kw) == N.HS_ERR_INVALID, ("normal", vv, list(kw))
+    assert initial(F=no_uR) == N.HS_ERR_INVALID
     tracker._ex.synchronize()
     run.stream.synchronize()
     for k, (b, dt, cnt) in run.spec.items():

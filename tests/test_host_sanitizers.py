@@ -4,7 +4,8 @@ hyslam_amd/csrc compiled host-only (`hipcc --cuda-host-only`: no device code) an
 hs_orb_reserve / the host-pointer entry points (planners, table builders, workspace sizing, staging, the ingest tickets) and feeds the vocabulary
 loaders truncated and corrupted files, then the host-pointer forms of the key-frame graph, the local map and the pose optimiser, the `_device` forms of
 the tracking, reference-key-frame and key-frame stages on work areas of exactly their stated size, and the place database through both of its regrow
-paths.  Any sanitizer report aborts the driver.  The same sources build under ThreadSanitizer (`make SAN=thread`, a build directory of its own; never
+paths; its `refusals` mode holds every enqueue-only `_device` entry point of the resident chain to "a refused call enqueues nothing".  Any sanitizer
+report aborts the driver.  The same sources build under ThreadSanitizer (`make SAN=thread`, a build directory of its own; never
 both sanitizers in one binary): the driver's `threads` mode runs every section that shares something between threads, adaptor_threads the thread
 code of the header-only adaptors on the same stub objects.  Stand-alone programs throughout: nothing is loaded into python under a sanitizer.  (GPU
 AddressSanitizer is not available on this pool; the oracle has its own sanitizer test, tests/test_oracle_sanitizers.py.)"""
@@ -61,6 +62,18 @@ def test_product_host_code_is_sanitizer_clean():
         assert r.returncode == 0 and "HOST SANITIZE OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
         assert "HOST SANITIZE MAP OK" in r.stdout, (r.stdout + r.stderr)[-4000:]          # map_sweep and the place database, behind the earlier sections
         assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
+def test_no_refused_call_enqueues_anything():
+    """`host_sanitize refusals` from the address / UB build: every enqueue-only `_device` entry point of the resident chain and every chain, one valid
+    argument set each and one knock-out at a time (every pointer and pointer field NULL, every integer at its first refused value, alignment, sensor
+    without uR, the frame_result alias).  A call returns HS_OK or HS_ERR_INVALID; across a refused one the stub counts no launch, copy, memset or
+    allocation; what only a later stage of a chain reads is refused by the chain"""
+    build()
+    r = clean_run([EXE, "refusals"], "HOST SANITIZE REFUSALS OK: 32 entry points")
+    assert "REFUSALS FAILED" not in r.stdout, r.stdout[-4000:]
+    for chain, launches in (("hs_track_motion_model_device", 21), ("hs_track_local_map_device", 22), ("hs_track_frame_device", 43)):
+        assert re.search(r"^%s +valid call: +%d launches; +\d+ of \d+ knock-outs refused$" % (chain, launches), r.stdout, re.M), r.stdout[-4000:]
 
 
 def test_threaded_sections_are_thread_sanitizer_clean():
