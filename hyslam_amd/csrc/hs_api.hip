@@ -112,6 +112,9 @@ struct hs_orb {
         bool keys_dirty = false;           // a keyed call was enqueued and did not reach its end (any error return of run_extract): d_qhist / d_qbest may hold stale keys -> zeroed before the next call
         HsBuf<uint8_t> d_pyr_tabs;         // tile / row records of the two-level pyramid kernel (hs_pyramid_build_tables)
         std::vector<HsPyrFuse> pyr_fuse;   // [level]: kernel argument of the pair (level, level + 1) when it is fused
+        HsBuf<uint8_t> d_pyr_cols;         // column records of the LDS-staged pyramid kernels (HsPlan::pyr_cols)
+        std::vector<HsPyrFuseCols> pyr_fuse_cols; std::vector<HsPyrChainCols> pyr_chain_cols, pyr_deep_cols;   // [level]: the records of pyr_fuse / pyr_chain / pyr_deep (in d_pyr_cols)
+        std::vector<const uint8_t*> pyr_level_cols;   // [level]: column records of a level made on its own (in d_pyr_cols)
         std::vector<HsPyrChain> pyr_deep;  // [level]: the small-batch plan — chains as long as the LDS allows (8 levels: all seven in ONE launch); valid = 0 where none starts
         std::vector<HsPyrChain> pyr_chain; // [level]: kernel argument of the chain launch that starts at this level (HsLevel::chain_n levels)
         HsBuf<uint2> d_cand; HsBuf<uint32_t> d_pts_xy, d_pts_sk; HsBuf<uint16_t> d_pt_node;
@@ -207,6 +210,11 @@ void relocate_pyramid(hs_orb::Geometry& g)
         relocate(F.abase, g.d_pyr.p); relocate(F.bbase, g.d_pyr.p); relocate(F.xtA, g.d_tables.p); relocate(F.xtB, g.d_tables.p);
         relocate(F.rowA, g.d_pyr_tabs.p); relocate(F.rowB, g.d_pyr_tabs.p); relocate(F.xt, g.d_pyr_tabs.p); relocate(F.yt, g.d_pyr_tabs.p);
     }
+    // the column records: every place that was given one (a null offset cannot occur: word 0 of the blob is padding)
+    for (HsPyrFuseCols& K : g.pyr_fuse_cols) { if (K.a) relocate(K.a, g.d_pyr_cols.p); if (K.b) relocate(K.b, g.d_pyr_cols.p); }
+    for (std::vector<HsPyrChainCols>* plan : { &g.pyr_chain_cols, &g.pyr_deep_cols })
+        for (HsPyrChainCols& K : *plan) for (const uint8_t*& c : K.st) if (c) relocate(c, g.d_pyr_cols.p);
+    for (size_t l = 1; l < g.pyr_level_cols.size(); l++) relocate(g.pyr_level_cols[l], g.d_pyr_cols.p);
 }
 template <class T, class V> hipError_t upload(const HsBuf<T>& d, const std::vector<V>& v)
 {
@@ -240,6 +248,8 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     g.qhist_stride = P.qhist_stride; g.qbest_stride = P.qbest_stride; g.plan_digest = P.digest;
     g.lv = std::move(P.lv); g.lv_n = std::move(P.lv_n);
     g.pyr_fuse = std::move(P.pyr_fuse); g.pyr_chain = std::move(P.pyr_chain); g.pyr_deep = std::move(P.pyr_deep);
+    g.pyr_fuse_cols = std::move(P.pyr_fuse_cols); g.pyr_chain_cols = std::move(P.pyr_chain_cols); g.pyr_deep_cols = std::move(P.pyr_deep_cols);
+    g.pyr_level_cols = std::move(P.pyr_level_cols);
 
     // ---- allocate: every size is the plan's per-image figure times `batch`, with a floor that keeps an empty buffer addressable
     HIP_TRY(h, g.d_pyr.grow(std::max<size_t>(P.pyr_per_img * batch, 256)));
@@ -261,6 +271,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     HIP_TRY(h, g.d_qhist.grow(std::max<size_t>((size_t)g.qhist_stride * batch, 256 / 4)));
     HIP_TRY(h, g.d_qbest.grow(std::max<size_t>((size_t)g.qbest_stride * batch, 256 / 8)));
     HIP_TRY(h, g.d_pyr_tabs.grow(std::max<size_t>(P.pyr_tabs.size() * 8, 256)));
+    HIP_TRY(h, g.d_pyr_cols.grow(std::max<size_t>(P.pyr_cols.size() * 8, 256)));
     HIP_TRY(h, g.d_fast_items.grow(P.items.size()));
     HIP_TRY(h, g.d_fast_items_n.grow(P.items_n.size()));
     HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(g.max_hcell, std::max(g.fast_items, g.fast_items_n) * batch, h->fast_knobs), 256) / 4));      // (a multiple of 4 bytes)
@@ -279,6 +290,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     HIP_TRY(h, upload(g.d_qkeys, P.qkeys));
     HIP_TRY(h, upload(g.d_fast_qt, P.fast_qt));
     HIP_TRY(h, upload(g.d_pyr_tabs, P.pyr_tabs));
+    HIP_TRY(h, upload(g.d_pyr_cols, P.pyr_cols));
     HIP_TRY(h, hipMemcpy(h->d_lv, g.lv.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_lv + L, g.lv_n.data(), sizeof(HsLevel) * L, hipMemcpyHostToDevice));
     HIP_TRY(h, upload(g.d_fast_items, P.items));
@@ -455,14 +467,14 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         if (rc != HS_OK) return rc;
         quadtree(0, 1, h->s_aux);
         HIP_TRY(h, hipEventRecord(h->ev_sjoin, h->s_aux));
-        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
+        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, HsPyrCols{ g.pyr_fuse_cols.data(), g.pyr_chain_cols.data(), g.pyr_deep_cols.data(), g.pyr_level_cols.data() }, deep);
         rc = fast(0, n_items - items0, 0, s);
         if (rc != HS_OK) return rc;
         quadtree(1, L - 1, s);
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_sjoin, 0));
     } else {
         mark(h, 0, s);
-        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, deep);
+        h->geo.last_pyr_launches = hs_launch_pyramid(h->d_lv, h->geo.lv.data(), g.pyr_fuse.data(), g.pyr_chain.data(), L, img0, batch, s, HsPyrCols{ g.pyr_fuse_cols.data(), g.pyr_chain_cols.data(), g.pyr_deep_cols.data(), g.pyr_level_cols.data() }, deep);
         mark(h, 1, s);
         const int rc = fast(0, n_items, 0, s);
         if (rc != HS_OK) return rc;
@@ -560,6 +572,16 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
     for (int l = 0; l < L; l++) out[4] += h->geo.lv[l].qt_hist_off != 0xFFFFFFFFu;
     out[5] = longest; out[6] = lds;
     if (L > 1 && !h->geo.pyr_deep.empty() && h->geo.pyr_deep[1].valid) out[7] = h->geo.pyr_deep[1].grid_x * h->geo.pyr_deep[1].grid_y;
+}
+// the pyramid plans of the current configuration as the launches get them: relocated, their tables uploaded (tests/cpp/test_pyramid_columns.cpp reads
+// them through the stand-in runtime, where device memory is host memory)
+void hs_debug_pyramid_plan(const hs_orb* h, HsDebugPyramidPlan* out)
+{
+    *out = HsDebugPyramidPlan{};
+    if (!h || h->geo.w <= 0) return;
+    out->nlevels = h->p.nlevels; out->lv = h->geo.lv.data();
+    out->fuse = h->geo.pyr_fuse.data(); out->chain = h->geo.pyr_chain.data(); out->deep = h->geo.pyr_deep.data();
+    out->cols = HsPyrCols{ h->geo.pyr_fuse_cols.data(), h->geo.pyr_chain_cols.data(), h->geo.pyr_deep_cols.data(), h->geo.pyr_level_cols.data() };
 }
 // the digest of the plan the current configuration was made from (hs_plan_digest); 0 = nothing is configured
 uint64_t hs_debug_plan_digest(const hs_orb* h) { return h && h->geo.w > 0 ? h->geo.plan_digest : 0; }

@@ -27,7 +27,8 @@ struct HsPlanInput {
 // buffer the field will point into, until hs_api.hip relocates it:
 //   HsLevel::base, HsFastItem::base, HsPyrFuse::{s,a,b}base, HsPyrChain::sbase, HsPyrStage::base   -> one image's pyramid (d_pyr)
 //   HsLevel::{xofs,ialpha,yofs,ibeta}, HsPyrFuse::xtA/xtB, HsPyrStage::xt                          -> tables (d_tables)
-//   HsLevel::qt_xtab/qt_ytab -> qt_tabs;   HsFastQt::xkey/ykey -> qkeys;   HsPyrFuse::row*/xt/yt, HsPyrStage::rows/tx/ty -> pyr_tabs
+//   HsLevel::qt_xtab/qt_ytab -> qt_tabs;   HsFastQt::xkey/ykey -> qkeys;
+//   HsPyrFuse::row*/xt/yt, HsPyrStage::rows/tx/ty -> pyr_tabs;   HsPyrFuseCols, HsPyrChainCols, pyr_level_cols -> pyr_cols
 // Offset 0 is a valid place (level 1 starts one image's pyramid), so "none" is never told from the field's value: level 0 has no pyramid buffer
 // and no resize tables, a fused pair / chain that starts at level 1 reads the caller's frames (sbase stays nullptr), a level has quadtree
 // tables iff qt_ytab != 0 (the y table follows the x table), a HsFastQt record iff enabled, a pyramid record iff valid.
@@ -43,11 +44,17 @@ struct HsPlan {
     std::vector<uint16_t> qkeys;               // the FAST kernel's u16 key tables
     std::vector<HsFastQt> fast_qt;             // [nlevels]
     std::vector<uint64_t> pyr_tabs;            // tile / row records of the fused and chain pyramid kernels
+    std::vector<uint64_t> pyr_cols;            // column records (HsPyrCol) of the LDS-staged pyramid kernels: HS_PYR_COL_TILE_BYTES (3 KiB) per tile column, one set per fused pair
+                                               // and level, per chain stage and per level on its own (1080p, 8 levels: 132 tile columns, 396 KiB).  Derived from `tables` and
+                                               // the tile records, hence not part of the digest (hs_plan_digest)
+    std::vector<HsPyrFuseCols> pyr_fuse_cols;  // [level]: where the records of pyr_fuse[level] are
+    std::vector<HsPyrChainCols> pyr_chain_cols, pyr_deep_cols;   // [level]: the same for pyr_chain / pyr_deep, per stage
     std::vector<HsPyrFuse> pyr_fuse;           // [level]: the pair (level, level + 1) when it is fused
     std::vector<HsPyrChain> pyr_chain;         // [level]: the chain launch that starts at this level (HsLevel::chain_n levels)
     std::vector<HsPyrChain> pyr_deep;          // [level]: the small-batch plan; valid = 0 where no chain starts
+    std::vector<const uint8_t*> pyr_level_cols;// [level]: column records of the level made on its own (k_resize_level_lds); level 0 has none
     std::vector<HsFastItem> items, items_n;    // one image's FAST work items, wide / narrow (items_n: fast_items_n > 0); at least one record each
-    uint64_t digest = 0;                       // hs_plan_digest of all of the above
+    uint64_t digest = 0;                       // hs_plan_digest of all of the above but the column records
 };
 
 // HS_OK and the plan, or the status and the text of a refusal (the plan is then unspecified)

@@ -181,16 +181,17 @@ void plan_pyramid(const HsKnobs& k, HsPlan& P)
     hs_pyramid_plan_fusion(lv.data(), L, xt.data(), yo.data(), k.pyr_tbx_max);
     if (k.no_fuse) for (int l = 0; l < L; l++) lv[l].fuse_tbx = 0;
     std::vector<uint64_t>& blob = P.pyr_tabs;
-    hs_pyramid_build_tables(lv.data(), L, xt.data(), yo.data(), ib.data(), blob, P.pyr_fuse);
+    std::vector<uint64_t>& cblob = P.pyr_cols;                 // the column records (HsPyrCol): a blob of their own, see hs_plan.h
+    hs_pyramid_build_tables(lv.data(), L, xt.data(), yo.data(), ib.data(), blob, P.pyr_fuse, cblob, P.pyr_fuse_cols);
     // chains: the last three levels in one launch when the number of levels to make is odd (8 levels: (1,2) (3,4) (5,6,7))
-    P.pyr_chain.assign(L, HsPyrChain{});
+    P.pyr_chain.assign(L, HsPyrChain{}); P.pyr_chain_cols.assign(L, HsPyrChainCols{});
     for (int l = 0; l < L; l++) lv[l].chain_n = 0;
     if (!k.no_fuse && k.chain_mode != 0) {
         if (k.chain_mode == 2) {
             for (int l = 1; l + 1 < L; l += 2) {
                 int n = (l + 3 == L) ? 3 : 2;
-                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
-                if (!P.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
+                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
+                if (!P.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
                 if (P.pyr_chain[l].valid) { lv[l].chain_n = P.pyr_chain[l].nstage; if (P.pyr_chain[l].nstage == 3) l++; }
             }
         } else if (k.pyr_plan_set) {      // tuning knob HS_PYRAMID_PLAN: explicit chain lengths from level 1, e.g. "2,3,2" (1 = a single level, 2 = the two-level kernel unless HS_PYRAMID_CHAIN2=1)
@@ -199,7 +200,7 @@ void plan_pyramid(const HsKnobs& k, HsPlan& P)
             for (const char* q = k.pyr_plan.c_str(); *q && l < L; ) {
                 const int n = std::min(atoi(q), L - l);
                 if (n >= 3 || (n == 2 && (chain2 || !(l & 1)))) {       // (the two-level kernel is planned for pairs that start on an odd level)
-                    hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], HS_PYR_DEEP_LDS, 0);
+                    hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l], HS_PYR_DEEP_LDS, 0);
                     if (P.pyr_chain[l].valid) lv[l].chain_n = n;
                 }
                 if (n == 1) lv[l].fuse_tbx = 0;
@@ -209,18 +210,21 @@ void plan_pyramid(const HsKnobs& k, HsPlan& P)
             }
         } else if (L >= 4 && ((L - 1) & 1)) {
             const int l = L - 3;
-            hs_pyramid_plan_chain(lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l]);
+            hs_pyramid_plan_chain(lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
             if (P.pyr_chain[l].valid) lv[l].chain_n = 3;
         }
     }
     // the small-batch plan: a launch of few frames lasts as long as one workgroup lives and costs ~5 us whatever it does, so the dependent
     // launches are what counts — greedy: from level 1, the longest chain that fits HS_PYR_DEEP_LDS, then the next (1080p: ONE launch for levels 1-7)
-    P.pyr_deep.assign(L, HsPyrChain{});
+    // a level made on its own (a pair that is not fused, the level after a pair that fell back for the caller's frame alignment): its column records
+    P.pyr_level_cols.assign(L, nullptr);
+    for (int l = 1; l < L; l++) P.pyr_level_cols[l] = at_offset<uint8_t>(hs_pyramid_level_cols(xt[l], lv[l].w, cblob));
+    P.pyr_deep.assign(L, HsPyrChain{}); P.pyr_deep_cols.assign(L, HsPyrChainCols{});
     if (!k.no_fuse && k.deep_max_batch > 0) {
         for (int l = 1; l + 1 < L;) {
             int took = 0;
             for (int n = std::min(HS_PYR_CHAIN_MAX, L - l); n >= 2 && !took; n--) {
-                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_deep[l], HS_PYR_DEEP_LDS, k.deep_rows);
+                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_deep[l], cblob, P.pyr_deep_cols[l], HS_PYR_DEEP_LDS, k.deep_rows);
                 if (P.pyr_deep[l].valid) took = n;
             }
             l += took ? took : 1;
@@ -321,7 +325,9 @@ int hs_plan_geometry(const HsPlanInput& in, HsPlan& P, std::string& err)
 
 // Order: the scalars (w, h, total_cells, max_wcell, max_hcell, fast_items, fast_items_n, cand_img_stride, sel_img_stride, max_kp, qhist_stride,
 // qbest_stride, pyr_per_img), the wide levels, the narrow levels, the resize tables, the quadtree blob, the key table, the HsFastQt records,
-// the pyramid blob, pyr_fuse, pyr_chain, pyr_deep, the wide items, the narrow items.  Arrays are preceded by their length.
+// the pyramid blob, pyr_fuse, pyr_chain, pyr_deep, the wide items, the narrow items.  The column records (pyr_cols and the offsets into it) are NOT
+// hashed: they are derived from what is — the x tables and the tile records — by hs_pyramid_col_records, and tests/test_pyramid_columns.py holds every
+// one of them to those, so the digest still decides what the kernels get and keeps the values recorded for it.  Arrays are preceded by their length.
 uint64_t hs_plan_digest(const HsPlan& P)
 {
     Fnv H;

@@ -121,6 +121,29 @@ __device__ __forceinline__ uint32_t pyr_vquad(uint2 H0, uint2 H1, uint32_t b0, u
     return __builtin_amdgcn_perm(c2, a2, 0x06040200u);                                                  // bytes 0 and 2 of both
 }
 
+// Per-lane column data of a horizontal pass (HsPyrCol): made by the plan, one record per (tile column, lane).  The kernels used to derive it from
+// four 8-byte x-table entries per lane — 64-bit address arithmetic and clamps for the loads, then ~5 vector instructions per column — in every
+// workgroup, although it is the same for every tile row, image and call.  Two steps, as before: the record is REQUESTED where the tile column is
+// known (three loads at constant offsets from one lane offset, each a contiguous KiB per wave) and taken where it is needed, with no arithmetic.
+typedef uint32_t hs_u32x2 __attribute__((ext_vector_type(2)));
+struct PyrColRaw { hs_u32x4 p0, p1; hs_u32x2 p2; };
+__device__ __forceinline__ PyrColRaw pyr_col_request(const uint8_t* cols /*wave-uniform: the level's records*/, uint32_t tile_col, int tx)
+{
+    const uint8_t* const tile = cols + (size_t)tile_col * HS_PYR_COL_TILE_BYTES;
+    const uint32_t off = 16u * (uint32_t)tx;
+    PyrColRaw r;
+    r.p0 = hs_gload_off<hs_u32x4>(tile, off); r.p1 = hs_gload_off<hs_u32x4>(tile, off + 1024u); r.p2 = hs_gload_off<hs_u32x2>(tile, off + 2048u);
+    return r;
+}
+__device__ __forceinline__ HsPyrCol pyr_col_data(const PyrColRaw& r)
+{
+    HsPyrCol c;
+    c.wbase = (int)r.p0.x; c.wshift = (int)r.p0.y;
+    c.sel[0] = r.p0.z; c.sel[1] = r.p0.w; c.sel[2] = r.p1.x; c.sel[3] = r.p1.y;
+    c.coef[0] = r.p1.z; c.coef[1] = r.p1.w; c.coef[2] = r.p2.x; c.coef[3] = r.p2.y;
+    return c;
+}
+
 // Source rectangle -> LDS with 16-byte vectors: a wave takes whole source rows, floor(64 / nvec) at a time (no per-lane division by the runtime nvec).
 // FOUR rows per lane are in flight before the first LDS write (round 4): written as `load; store` per row the loop waited for every load on the spot —
 // three dependent HBM round trips at the head of every workgroup (7 k of the 22 k cycles a workgroup of the levels 5-7 launch lives).  Rows past the
@@ -160,7 +183,7 @@ __device__ __forceinline__ void pyr_stage_source(const uint8_t* src0 /*wave-unif
 // prefetched the next tile's vectors into registers was measured slower: 0.164 vs 0.146 ms for the 7 levels of 32 frames.)
 // Needs 16-byte aligned source rows and a scale <= 2 (the 4 columns of a lane then span <= 8 source bytes).
 #define LT_ROWS 16
-__global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restrict__ lv, int level, HsImg0 img0, int lds_pitch, int lds_rows)
+__global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restrict__ lv, int level, HsImg0 img0, int lds_pitch, int lds_rows, const uint8_t* cols /*hs_pyramid_level_cols*/)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_src[];
     uint16_t* const s_h = reinterpret_cast<uint16_t*>(s_src + (size_t)lds_pitch * lds_rows);      // [lds_rows][256] (H >> 4)
@@ -184,27 +207,16 @@ __global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restr
     const int nvec = ((col_last - col0) >> 4) + 1, nrow = sy_last - sy_first + 1;      // host guarantees nvec*16 <= lds_pitch - 16, nrow <= lds_rows
     // ---- A: a wave takes whole source rows, floor(64 / nvec) at a time (no per-lane division by the runtime nvec)
     pyr_stage_source<4>(hs_uniform_ptr(sbase + (size_t)sy_first * spitch + col0), (uint32_t)spitch, s_src, (uint32_t)lds_pitch, nvec, nrow, threadIdx.x & 63, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-    // per-lane column data (independent of the row): 8-byte window position, byte-pair selectors, coefficient pairs
+    // per-lane column data (independent of the row): 8-byte window position in a staged row, byte-pair selectors, coefficient pairs
     const int dx0 = dx_tile + 4 * tx;
-    HsXTab t[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) t[i] = __builtin_bit_cast(HsXTab, hs_gload<uint64_t>(&xt[min(dx0 + i, D.w - 1)]));
-    const int o0 = t[0].sx - col0;                              // byte offset of the window in a staged row
-    const int wbase = o0 & ~3, wshift = o0 & 3;
-    uint32_t sel[4], coef[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t q = (uint32_t)(t[i].sx - t[0].sx);       // 0..6: bytes q, q+1 of the window (a1 == 0 wherever sx+1 is past the row)
-        sel[i] = q | 0x0c00u | ((q + 1) << 16) | 0x0c000000u;
-        coef[i] = ((uint32_t)(uint16_t)t[i].a0 << 4) | ((uint32_t)(uint16_t)t[i].a1 << 20);      // 16 a0 | 16 a1 << 16
-    }
+    const HsPyrCol c = pyr_col_data(pyr_col_request(cols, blockIdx.x, tx));
     __syncthreads();
     // ---- B
     for (int r = __builtin_amdgcn_readfirstlane(ty); r < nrow; r += 4) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(&s_src[r * lds_pitch + wbase]);
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(&s_src[r * lds_pitch + c.wbase]);
         const uint32_t d0 = w[0], d1 = w[1], d2 = w[2];
-        const uint32_t wlo = __builtin_amdgcn_alignbyte(d1, d0, wshift), whi = __builtin_amdgcn_alignbyte(d2, d1, wshift);
-        *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = make_uint2(pyr_hpair(whi, wlo, sel[0], sel[1], coef[0], coef[1]), pyr_hpair(whi, wlo, sel[2], sel[3], coef[2], coef[3]));
+        const uint32_t wlo = __builtin_amdgcn_alignbyte(d1, d0, c.wshift), whi = __builtin_amdgcn_alignbyte(d2, d1, c.wshift);
+        *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = make_uint2(pyr_hpair(whi, wlo, c.sel[0], c.sel[1], c.coef[0], c.coef[1]), pyr_hpair(whi, wlo, c.sel[2], c.sel[3], c.coef[2], c.coef[3]));
     }
     __syncthreads();
     // ---- C: the destination row of a wave is uniform, so its source rows and weights come from scalar loads
@@ -241,7 +253,6 @@ __global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restr
 // descriptions are a kernel argument, the tile geometry is two 32-byte records (HsPyrXTile / HsPyrYTile), a destination row is one 8-byte
 // record (HsPyrRow: clamped source rows + weights, fetched one row ahead) and stores use a scalar row base + a 32-bit lane offset.
 typedef uint32_t hs_u32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t hs_u32x2 __attribute__((ext_vector_type(2)));
 #ifndef FZ_ROWS
 #define FZ_ROWS 16
 #endif
@@ -253,7 +264,7 @@ template <typename T> __device__ __forceinline__ void hs_gstore_off(uint8_t* uni
 // NW = wavefronts per workgroup: 4, or 8 when the launch has few workgroups per CU (small batches) — the same tile, half the rows per wave, so a
 // workgroup's life (the launch's critical path when every workgroup is resident at once) is shorter.
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsImg0 img0)
+__global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsImg0 img0, HsPyrFuseCols K)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int TBX = F.tbx, lds_pitch = F.lds_pitch;
@@ -273,29 +284,8 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
 
     // ---- 1: the source rectangle (a wave takes whole source rows, floor(64 / nvec) at a time)
     pyr_stage_source<NW>(hs_uniform_ptr(sbase + (size_t)Y.sy_first * spitch + X.col0), spitch, s_src, (uint32_t)lds_pitch, nvec, nSr, tx, wave);
-    // per-lane column data of one horizontal pass: window position, byte-pair selectors, coefficient pairs
-    struct ColData { int wbase, wshift; uint32_t sel[4], coef[4]; };
-    // (two steps: the four x-table records of a lane are REQUESTED where their addresses are known and turned into column data where they are needed)
-    auto col_fetch = [&](const HsXTab* xt, int dx0, int wmax, uint64_t (&traw)[4]) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) traw[i] = hs_gload<uint64_t>(&xt[min(dx0 + i, wmax)]);
-    };
-    auto col_data = [&](const uint64_t (&traw)[4], int origin) {
-        HsXTab t[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) t[i] = __builtin_bit_cast(HsXTab, traw[i]);
-        ColData c;
-        const int o0 = t[0].sx - origin;
-        c.wbase = o0 & ~3; c.wshift = o0 & 3;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t q = (uint32_t)(t[i].sx - t[0].sx);
-            c.sel[i] = q | 0x0c00u | ((q + 1) << 16) | 0x0c000000u;
-            c.coef[i] = ((uint32_t)(uint16_t)t[i].a0 << 4) | ((uint32_t)(uint16_t)t[i].a1 << 20);  // 16 a0 | 16 a1 << 16
-        }
-        return c;
-    };
-    auto h_pass = [&](const uint8_t* src, int pitch, int nrow, const ColData& c) {
+    // (the per-lane column data of a horizontal pass — window position, byte-pair selectors, coefficient pairs — is a ready-made record: pyr_col_request / pyr_col_data)
+    auto h_pass = [&](const uint8_t* src, int pitch, int nrow, const HsPyrCol& c) {
         for (int r = wave; r < nrow; r += NW) {
             const uint32_t* w = reinterpret_cast<const uint32_t*>(&src[r * pitch + c.wbase]);
             const uint32_t d0 = w[0], d1 = w[1], d2 = w[2];
@@ -314,14 +304,12 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
     // waited a full memory round trip for them between its two levels with nothing else to do (two workgroups per CU: nobody to cover it).  They
     // become column data right after the first horizontal pass — by then they have arrived, and the wait for them there does not have to drain the
     // level-A stores the way a wait after the row loop would (one counter, in order, for vector loads and stores).
-    uint64_t tA[4], tB[4];
-    col_fetch(F.xtA, ax0 + 4 * tx, F.aw - 1, tA);
-    col_fetch(F.xtB, bx0 + 4 * tx, F.bw - 1, tB);
-    const ColData cA = col_data(tA, X.col0);
+    const PyrColRaw rA = pyr_col_request(K.a, blockIdx.x, tx), rB = pyr_col_request(K.b, blockIdx.x, tx);
+    const HsPyrCol cA = pyr_col_data(rA);
     __syncthreads();
     // ---- 2: horizontal sums of the source rows for the level-A columns
     h_pass(s_src, lds_pitch, nSr, cA);
-    const ColData cB = col_data(tB, ax0);
+    const HsPyrCol cB = pyr_col_data(rB);
     asm volatile("" :: "v"(cB.wbase), "v"(cB.wshift), "v"(cB.sel[0]), "v"(cB.sel[1]), "v"(cB.sel[2]), "v"(cB.sel[3]), "v"(cB.coef[0]), "v"(cB.coef[1]), "v"(cB.coef[2]), "v"(cB.coef[3]));      // made HERE, not where first used
     __syncthreads();
     // ---- 3: level-A region -> LDS (it overlays the source rectangle, which is dead now) and, for the owned part, HBM
@@ -386,7 +374,7 @@ extern "C" void hs_debug_pyr_workgroups(unsigned long long* out8192) { (void)hip
 #define PYR_MARK()
 #endif
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 img0)
+__global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 img0, HsPyrChainCols K)
 {
 #ifdef HS_PYR_PROFILE
     int pk = 0;
@@ -405,37 +393,22 @@ __global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 i
     else { sbase = F.sbase + (size_t)img * F.s_img_stride; spitch = (uint32_t)F.spitch; }
     int src_pitch = F.lds_pitch;
     // The stages are a dependent sequence inside the workgroup, and every stage starts with two dependent fetches: its tile records (scalar loads) and,
-    // addressed by them, the four x-table entries of every lane.  At one workgroup per CU (small batches: the deep chains) nothing hides them, so
-    // they are software-pipelined: the records of stage st + 1 are requested at the top of stage st, its x-table entries between the two passes.
+    // addressed by them, the column record of every lane.  At one workgroup per CU (small batches: the deep chains) nothing hides them, so
+    // they are software-pipelined: the records of stage st + 1 are requested at the top of stage st, its column records between the two passes.
     auto ld_x = [&](int st) { return __builtin_bit_cast(HsPyrStageX, hs_cload<hs_u32x8>(&F.st[st].tx[blockIdx.x])); };
     auto ld_y = [&](int st) { return __builtin_bit_cast(HsPyrStageY, hs_cload<hs_u32x8>(&F.st[st].ty[blockIdx.y])); };
-    auto ld_t = [&](int st, const HsPyrStageX& X, uint64_t (&t)[4]) {
-        const HsPyrStage& S = F.st[st];
-#pragma unroll
-        for (int i = 0; i < 4; i++) t[i] = hs_gload<uint64_t>(&S.xt[min(X.x0 + 4 * tx + i, S.w - 1)]);
-    };
+    auto ld_c = [&](int st) { return pyr_col_request(K.st[st], blockIdx.x, tx); };
     HsPyrStageX X = ld_x(0); HsPyrStageY Y = ld_y(0);
-    uint64_t traw[4]; ld_t(0, X, traw);
+    PyrColRaw craw = ld_c(0);
     for (int st = 0; st < F.nstage; st++) {
         const HsPyrStage& S = F.st[st];
         const int stn = min(st + 1, F.nstage - 1);                   // (the last stage re-requests its own records: harmless, keeps the loads unconditional)
         const HsPyrStageX Xn = ld_x(stn); const HsPyrStageY Yn = ld_y(stn);
         if (st == 0) pyr_stage_source<NW>(hs_uniform_ptr(sbase + (size_t)Y.src_y0 * spitch + X.src_x0), spitch, s_x, (uint32_t)src_pitch, X.nvec, Y.n_src, tx, wave);
         // per-lane column data of the stage's horizontal pass: window position, byte-pair selectors, coefficient pairs
-        int wbase, wshift; uint32_t sel[4], coef[4];
-        {
-            HsXTab t[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) t[i] = __builtin_bit_cast(HsXTab, traw[i]);
-            const int o0 = t[0].sx - X.src_x0;
-            wbase = o0 & ~3; wshift = o0 & 3;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t q = (uint32_t)(t[i].sx - t[0].sx);
-                sel[i] = q | 0x0c00u | ((q + 1) << 16) | 0x0c000000u;
-                coef[i] = ((uint32_t)(uint16_t)t[i].a0 << 4) | ((uint32_t)(uint16_t)t[i].a1 << 20);
-            }
-        }
+        const HsPyrCol c = pyr_col_data(craw);
+        const int wbase = c.wbase, wshift = c.wshift;
+        const uint32_t (&sel)[4] = c.sel, (&coef)[4] = c.coef;
         __syncthreads();                                             // the source is in LDS (staged, or written by the previous stage)
         PYR_MARK();
         if (4 * tx < X.ncols) {
@@ -452,7 +425,7 @@ __global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 i
                 if (two) *reinterpret_cast<uint2*>(&s_h[(r + NW) * 256 + 4 * tx]) = make_uint2(pyr_hpair(bhi, blo, sel[0], sel[1], coef[0], coef[1]), pyr_hpair(bhi, blo, sel[2], sel[3], coef[2], coef[3]));
             }
         }
-        ld_t(stn, Xn, traw);                                         // in flight during the vertical pass
+        craw = ld_c(stn);                                            // in flight during the vertical pass
         __syncthreads();                                             // the sums are complete, the source is dead: the region overlays it
         PYR_MARK();
         {
@@ -495,12 +468,51 @@ __global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 i
 #endif
 }
 
+// Host side of pyr_col_request / pyr_col_data: the 64 column records of one tile column in the plane layout (HsPyrCol, hs_internal.h).  Lane t makes
+// the columns x0 + 4 t + i, i = 0..3; a column past the level's last one repeats it (its pixels land in the row padding or are never stored).
+//   wbase | wshift   byte offset of the lane's 8-byte window in a staged row (origin = first source column the row holds), split into dword and byte part
+//   sel[i]           v_perm selector: bytes q, q + 1 of the window as two 16-bit fields, q = sx[i] - sx[0] (a1 == 0 wherever sx + 1 is past the row)
+//   coef[i]          16 a0 | 16 a1 << 16
+size_t hs_pyramid_col_records(const int16_t* xt, int w, int x0, int origin, std::vector<uint64_t>& blob)
+{
+    if (blob.empty()) blob.push_back(0);
+    if (blob.size() & 1) blob.push_back(0);                     // the planes are read as 16-byte vectors
+    const size_t o = blob.size(); blob.resize(o + HS_PYR_COL_TILE_BYTES / 8, 0);
+    uint32_t* const out = reinterpret_cast<uint32_t*>(&blob[o]);
+    for (int t = 0; t < 64; t++) {
+        const int16_t* e[4];
+        for (int i = 0; i < 4; i++) e[i] = xt + 4 * (size_t)std::min(x0 + 4 * t + i, w - 1);
+        HsPyrCol c;
+        const int o0 = e[0][0] - origin;
+        c.wbase = o0 & ~3; c.wshift = o0 & 3;
+        for (int i = 0; i < 4; i++) {
+            const uint32_t q = (uint32_t)(e[i][0] - e[0][0]);
+            c.sel[i] = q | 0x0c00u | ((q + 1) << 16) | 0x0c000000u;
+            c.coef[i] = ((uint32_t)(uint16_t)e[i][1] << 4) | ((uint32_t)(uint16_t)e[i][2] << 20);
+        }
+        uint32_t* const p0 = out + 4 * t, * const p1 = out + 256 + 4 * t, * const p2 = out + 512 + 4 * t;
+        p0[0] = (uint32_t)c.wbase; p0[1] = (uint32_t)c.wshift; p0[2] = c.sel[0]; p0[3] = c.sel[1];
+        p1[0] = c.sel[2]; p1[1] = c.sel[3]; p1[2] = c.coef[0]; p1[3] = c.coef[1];
+        p2[0] = c.coef[2]; p2[1] = c.coef[3];
+    }
+    return o * 8;
+}
+size_t hs_pyramid_level_cols(const int16_t* xt, int w, std::vector<uint64_t>& blob)
+{
+    size_t first = 0;
+    for (int x0 = 0; x0 < w; x0 += 256) {
+        const size_t o = hs_pyramid_col_records(xt, w, x0, xt[4 * (size_t)x0] & ~15, blob);
+        if (x0 == 0) first = o;
+    }
+    return first;
+}
+
 // Host side of k_resize_chain for the levels [first, first + n): walks the tiles of the LAST level from the largest tile width downwards until every
 // stage's region fits 256 columns and the LDS buffers, with the expressions of hs_pyramid_build_tables / the two-level kernel.
 void hs_pyramid_plan_chain(const HsLevel* h_lv, int first, int n, const int16_t* const* xtab, const int16_t* const* yofs, const int16_t* const* ibeta,
-                           std::vector<uint64_t>& blob, HsPyrChain& C, size_t lds_max, int tile_rows)
+                           std::vector<uint64_t>& blob, HsPyrChain& C, std::vector<uint64_t>& cols_blob, HsPyrChainCols& CC, size_t lds_max, int tile_rows)
 {
-    C = HsPyrChain{};
+    C = HsPyrChain{}; CC = HsPyrChainCols{};
     if (tile_rows <= 0) tile_rows = FZ_ROWS;
     if (n < 2 || n > HS_PYR_CHAIN_MAX || first < 1) return;
     auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
@@ -646,6 +658,10 @@ void hs_pyramid_plan_chain(const HsLevel* h_lv, int first, int n, const int16_t*
             const size_t oy = blob.size(); blob.resize(oy + 4 * (size_t)nby);
             memcpy(&blob[oy], ty[i].data(), 32 * (size_t)nby);
             S.tx = reinterpret_cast<const HsPyrStageX*>(ox * 8); S.ty = reinterpret_cast<const HsPyrStageY*>(oy * 8);
+            for (int bx = 0; bx < nbx; bx++) {                                       // column records per x tile: the stage's region columns, window offsets relative to the source buffer's first column
+                const size_t oc = hs_pyramid_col_records(xtab[first + i], D.w, txs[i][bx].x0, txs[i][bx].src_x0, cols_blob);
+                if (bx == 0) CC.st[i] = reinterpret_cast<const uint8_t*>(oc);
+            }
         }
         C.tbx = tbx; C.lds_pitch = pitch; C.x_bytes = (int32_t)((x_bytes + 15) & ~(size_t)15); C.h_rows = h_rows; C.grid_x = nbx; C.grid_y = nby; C.valid = 1;
     }
@@ -654,9 +670,9 @@ void hs_pyramid_plan_chain(const HsLevel* h_lv, int first, int n, const int16_t*
 // Host side of the table-driven kernel: for every fused pair the tile records (the geometry the kernel used to compute itself, same
 // expressions) and for both levels of the pair the row records; everything is appended to `blob`, pointers into it are byte offsets.
 void hs_pyramid_build_tables(const HsLevel* h_lv, int nlevels, const int16_t* const* xtab, const int16_t* const* yofs, const int16_t* const* ibeta,
-                             std::vector<uint64_t>& blob, std::vector<HsPyrFuse>& fuse)
+                             std::vector<uint64_t>& blob, std::vector<HsPyrFuse>& fuse, std::vector<uint64_t>& cols_blob, std::vector<HsPyrFuseCols>& fuse_cols)
 {
-    fuse.assign(nlevels, HsPyrFuse{});
+    fuse.assign(nlevels, HsPyrFuse{}); fuse_cols.assign(nlevels, HsPyrFuseCols{});
     auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
     if (blob.empty()) blob.push_back(0);
     for (int l = 1; l + 1 < nlevels; l++) {
@@ -719,6 +735,14 @@ void hs_pyramid_build_tables(const HsLevel* h_lv, int nlevels, const int16_t* co
             }
         }
         F.rowA = reinterpret_cast<const HsPyrRow*>(oa * 8); F.rowB = reinterpret_cast<const HsPyrRow*>(ob * 8); F.slotA = slotA;
+        // column records per x tile: level A from the tile's first region column against the staged source rows, level B from the tile's first column
+        // against the level-A region in LDS
+        for (int pass = 0; pass < 2; pass++)
+            for (int bx = 0; bx < nbx; bx++) {
+                HsPyrXTile t; memcpy(&t, &blob[ox + 4 * (size_t)bx], 32);
+                const size_t oc = pass == 0 ? hs_pyramid_col_records(xA, A.w, t.ax0, t.col0, cols_blob) : hs_pyramid_col_records(xB, B.w, bx * tbx, t.ax0, cols_blob);
+                if (bx == 0) (pass == 0 ? fuse_cols[l].a : fuse_cols[l].b) = reinterpret_cast<const uint8_t*>(oc);
+            }
     }
 }
 
@@ -775,7 +799,8 @@ static int pyr_nw8_wg_per_cu()
     static int v = [] { const char* e = getenv("HS_PYRAMID_NW8"); return e ? atoi(e) : 3; }();
     return v;
 }
-int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse* fuse, const HsPyrChain* chain, int nlevels, HsImg0 img0, int batch, hipStream_t s, const HsPyrChain* deep)
+int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse* fuse, const HsPyrChain* chain, int nlevels, HsImg0 img0, int batch, hipStream_t s, const HsPyrCols& cols,
+                      const HsPyrChain* deep)
 {
     // the deep chains of small batches may want more than the default 64 KB of dynamic LDS (gfx950: 160 KB per CU).  Function attributes are PER DEVICE:
     // the raise is done once for every device a launch sequence is enqueued on (a handle on a second GPU of the process gets its own), and a device
@@ -804,8 +829,8 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
                 dim3 grid(C.grid_x, C.grid_y, batch);
                 // (measured at one 1080p pair per call, levels 1-7 in one launch of 304 workgroups: 27.6 us with 8 waves per workgroup, 28.8 us with 16 — the
                 //  stages are a dependent sequence inside the workgroup, more waves per stage do not shorten it; three launches of the standard plan: 28.6 us)
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0);
-                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0);
+                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0, cols.deep[l]);
+                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0, cols.deep[l]);
                 l += C.nstage - 1;
                 continue;
             }
@@ -817,8 +842,8 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
                 const HsPyrChain& C = chain[l];
                 const size_t lds = (size_t)C.x_bytes + (size_t)C.h_rows * 256 * 2;
                 dim3 grid(C.grid_x, C.grid_y, batch);
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0);
-                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0);
+                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0, cols.chain[l]);
+                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0, cols.chain[l]);
                 l += C.nstage - 1;
                 continue;
             }
@@ -832,8 +857,8 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
                 const size_t lds = (size_t)D.fuse_pitch * D.fuse_sr + (size_t)std::max(D.fuse_sr, D.fuse_ar) * 256 * 2;
                 dim3 grid((B.w + D.fuse_tbx - 1) / D.fuse_tbx, (B.h + FZ_ROWS - 1) / FZ_ROWS, batch);
                 // few workgroups per CU (small batches): 8 waves per workgroup shorten the workgroup's life, which is the launch's duration then
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_two_levels<8>, grid, dim3(512), lds, s, fuse[l], img0);
-                else hipLaunchKernelGGL(k_resize_two_levels<4>, grid, dim3(256), lds, s, fuse[l], img0);
+                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_two_levels<8>, grid, dim3(512), lds, s, fuse[l], img0, cols.fuse[l]);
+                else hipLaunchKernelGGL(k_resize_two_levels<4>, grid, dim3(256), lds, s, fuse[l], img0, cols.fuse[l]);
                 l++;                                           // level l+1 is done too
                 continue;
             }
@@ -850,7 +875,7 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
         const size_t lds_bytes = (size_t)lds_pitch * lds_rows + (size_t)lds_rows * 256 * 2;      // source rectangle + 16-bit horizontal sums
         if (vec16 && lds_bytes <= 60 * 1024 && scx <= 2.0) {
             dim3 grid((D.w + 255) / 256, (D.h + LT_ROWS - 1) / LT_ROWS, batch);
-            hipLaunchKernelGGL(k_resize_level_lds, grid, dim3(256), lds_bytes, s, d_lv, l, img0, lds_pitch, lds_rows);
+            hipLaunchKernelGGL(k_resize_level_lds, grid, dim3(256), lds_bytes, s, d_lv, l, img0, lds_pitch, lds_rows, cols.level[l]);
             continue;
         }
         dim3 block(64, 4, 1);
