@@ -271,7 +271,7 @@ _lib = None
 # with these digests and bench.py only replays a counter whose kernel sources are unchanged
 KERNEL_SOURCES = {
     "k_fast_rows": ["kernels_fast.hip", "hs_internal.h"],
-    "k_resize": ["kernels_pyramid.hip", "hs_internal.h"],
+    "k_resize": ["kernels_pyramid.hip", "hs_pyramid.h", "hs_internal.h"],
     "k_describe": ["kernels_describe.hip", "lean_sincos.h", "hs_internal.h"],
     "k_quadtree": ["kernels_quadtree.hip", "hs_internal.h"],
     "k_qt": ["kernels_quadtree.hip", "hs_internal.h"],

@@ -110,7 +110,7 @@ struct hs_orb {
         HsBuf<uint32_t> d_qhist; HsBuf<unsigned long long> d_qbest; uint32_t qhist_stride = 0, qbest_stride = 0;
         HsBuf<uint8_t> d_qt_rects;         // qt_large: batch_cap * nlevels * hs_quadtree_large_scratch_bytes()
         bool keys_dirty = false;           // a keyed call was enqueued and did not reach its end (any error return of run_extract): d_qhist / d_qbest may hold stale keys -> zeroed before the next call
-        HsBuf<uint8_t> d_pyr_tabs;         // tile / row records of the two-level pyramid kernel (hs_pyramid_build_tables)
+        HsBuf<uint8_t> d_pyr_tabs;         // tile / row records of the fused and chain pyramid kernels (HsPlan::pyr_tabs, made by hs_plan_pyramid.hip)
         std::vector<HsPyrFuse> pyr_fuse;   // [level]: kernel argument of the pair (level, level + 1) when it is fused
         HsBuf<uint8_t> d_pyr_cols;         // column records of the LDS-staged pyramid kernels (HsPlan::pyr_cols)
         std::vector<HsPyrFuseCols> pyr_fuse_cols; std::vector<HsPyrChainCols> pyr_chain_cols, pyr_deep_cols;   // [level]: the records of pyr_fuse / pyr_chain / pyr_deep (in d_pyr_cols)
@@ -563,7 +563,7 @@ void hs_debug_plan_summary(const hs_orb* h, int32_t* out /*[8]*/)
         deep_launches++;
         if (l < (int)h->geo.pyr_deep.size() && h->geo.pyr_deep[l].valid) {
             const HsPyrChain& C = h->geo.pyr_deep[l];
-            if (C.nstage > longest) { longest = C.nstage; lds = C.x_bytes + C.h_rows * 512; }
+            if (C.nstage > longest) { longest = C.nstage; lds = (int)hs_pyr_chain_lds((size_t)C.x_bytes, C.h_rows); }
             l += C.nstage - 1;
         } else if (h->geo.lv[l].chain_n > 0 && l + h->geo.lv[l].chain_n <= L) l += h->geo.lv[l].chain_n - 1;
         else if (h->geo.lv[l].fuse_tbx > 0 && l + 1 < L) l++;

@@ -1,4 +1,4 @@
-// hs_plan.h — the extractor's configuration as a pure host computation (hs_plan.hip): everything hs_orb_reserve decides for one frame size,
+// hs_plan.h — the extractor's configuration as a pure host computation (hs_plan.hip, the pyramid's part in hs_plan_pyramid.hip): everything hs_orb_reserve decides for one frame size,
 // without a HIP call and without the handle.  hs_api.hip allocates from the plan's sizes, uploads its arrays and turns its offsets into pointers.
 #pragma once
 #include "hs_internal.h"
@@ -59,6 +59,8 @@ struct HsPlan {
 
 // HS_OK and the plan, or the status and the text of a refusal (the plan is then unspecified)
 int hs_plan_geometry(const HsPlanInput& in, HsPlan& out, std::string& err);
+// its pyramid step (hs_plan_pyramid.hip), after the levels and the resize tables: the fused pairs, the chains, the small-batch plan and their records
+void hs_plan_pyramid(const HsKnobs& k, HsPlan& P);
 // FNV-1a-style 64-bit hash (xor, multiply by the FNV prime; 8-byte words where possible) over the plan, field by field in the order stated at its definition: equal digests <=> the kernels get the same tables,
 // records and launch geometry
 uint64_t hs_plan_digest(const HsPlan& P);

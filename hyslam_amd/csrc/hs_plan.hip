@@ -1,6 +1,6 @@
 // hs_plan.hip — the extractor's configuration for one frame size as a pure host computation (HsPlan, hs_plan.h): level sizes and cell grid,
-// cv::resize's fixed-point tables, the quadtree's key tables, the pyramid's fusion / chain / small-batch plans, both FAST work-item lists and
-// every per-image size.  No HIP call, no handle: pointer fields hold byte offsets until hs_api.hip has allocated the buffers they point into.
+// cv::resize's fixed-point tables, the quadtree's key tables, the pyramid's fusion / chain / small-batch plans (hs_plan_pyramid.hip), both FAST
+// work-item lists and every per-image size.  No HIP call, no handle: pointer fields hold byte offsets until hs_api.hip has allocated the buffers they point into.
 #include "hs_plan.h"
 #include <cmath>
 #include <cstdlib>
@@ -166,72 +166,6 @@ void plan_quadtree_keys(const HsKnobs& k, HsPlan& P)
     P.qhist_stride = hoff; P.qbest_stride = boff;
 }
 
-// Which launches make the pyramid: the fused level pairs (decided on the host copies of the resize tables), the chains of the standard plan
-// and the small-batch plan.  The planners copy the levels' offsets into their records and append their tile tables to P.pyr_tabs.
-void plan_pyramid(const HsKnobs& k, HsPlan& P)
-{
-    const int L = (int)P.lv.size();
-    std::vector<HsLevel>& lv = P.lv;
-    std::vector<const int16_t*> xt(L, nullptr), yo(L, nullptr), ib(L, nullptr);
-    for (int l = 1; l < L; l++) {
-        const uint8_t* const t = reinterpret_cast<const uint8_t*>(P.tables.data());
-        xt[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].xofs); yo[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].yofs);
-        ib[l] = reinterpret_cast<const int16_t*>(t + (uintptr_t)lv[l].ibeta);
-    }
-    hs_pyramid_plan_fusion(lv.data(), L, xt.data(), yo.data(), k.pyr_tbx_max);
-    if (k.no_fuse) for (int l = 0; l < L; l++) lv[l].fuse_tbx = 0;
-    std::vector<uint64_t>& blob = P.pyr_tabs;
-    std::vector<uint64_t>& cblob = P.pyr_cols;                 // the column records (HsPyrCol): a blob of their own, see hs_plan.h
-    hs_pyramid_build_tables(lv.data(), L, xt.data(), yo.data(), ib.data(), blob, P.pyr_fuse, cblob, P.pyr_fuse_cols);
-    // chains: the last three levels in one launch when the number of levels to make is odd (8 levels: (1,2) (3,4) (5,6,7))
-    P.pyr_chain.assign(L, HsPyrChain{}); P.pyr_chain_cols.assign(L, HsPyrChainCols{});
-    for (int l = 0; l < L; l++) lv[l].chain_n = 0;
-    if (!k.no_fuse && k.chain_mode != 0) {
-        if (k.chain_mode == 2) {
-            for (int l = 1; l + 1 < L; l += 2) {
-                int n = (l + 3 == L) ? 3 : 2;
-                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
-                if (!P.pyr_chain[l].valid && n == 3) hs_pyramid_plan_chain(lv.data(), l, 2, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
-                if (P.pyr_chain[l].valid) { lv[l].chain_n = P.pyr_chain[l].nstage; if (P.pyr_chain[l].nstage == 3) l++; }
-            }
-        } else if (k.pyr_plan_set) {      // tuning knob HS_PYRAMID_PLAN: explicit chain lengths from level 1, e.g. "2,3,2" (1 = a single level, 2 = the two-level kernel unless HS_PYRAMID_CHAIN2=1)
-            const bool chain2 = k.pyr_chain2 != 0;
-            int l = 1;
-            for (const char* q = k.pyr_plan.c_str(); *q && l < L; ) {
-                const int n = std::min(atoi(q), L - l);
-                if (n >= 3 || (n == 2 && (chain2 || !(l & 1)))) {       // (the two-level kernel is planned for pairs that start on an odd level)
-                    hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l], HS_PYR_DEEP_LDS, 0);
-                    if (P.pyr_chain[l].valid) lv[l].chain_n = n;
-                }
-                if (n == 1) lv[l].fuse_tbx = 0;
-                l += std::max(n, 1);
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
-        } else if (L >= 4 && ((L - 1) & 1)) {
-            const int l = L - 3;
-            hs_pyramid_plan_chain(lv.data(), l, 3, xt.data(), yo.data(), ib.data(), blob, P.pyr_chain[l], cblob, P.pyr_chain_cols[l]);
-            if (P.pyr_chain[l].valid) lv[l].chain_n = 3;
-        }
-    }
-    // the small-batch plan: a launch of few frames lasts as long as one workgroup lives and costs ~5 us whatever it does, so the dependent
-    // launches are what counts — greedy: from level 1, the longest chain that fits HS_PYR_DEEP_LDS, then the next (1080p: ONE launch for levels 1-7)
-    // a level made on its own (a pair that is not fused, the level after a pair that fell back for the caller's frame alignment): its column records
-    P.pyr_level_cols.assign(L, nullptr);
-    for (int l = 1; l < L; l++) P.pyr_level_cols[l] = at_offset<uint8_t>(hs_pyramid_level_cols(xt[l], lv[l].w, cblob));
-    P.pyr_deep.assign(L, HsPyrChain{}); P.pyr_deep_cols.assign(L, HsPyrChainCols{});
-    if (!k.no_fuse && k.deep_max_batch > 0) {
-        for (int l = 1; l + 1 < L;) {
-            int took = 0;
-            for (int n = std::min(HS_PYR_CHAIN_MAX, L - l); n >= 2 && !took; n--) {
-                hs_pyramid_plan_chain(lv.data(), l, n, xt.data(), yo.data(), ib.data(), blob, P.pyr_deep[l], cblob, P.pyr_deep_cols[l], HS_PYR_DEEP_LDS, k.deep_rows);
-                if (P.pyr_deep[l].valid) took = n;
-            }
-            l += took ? took : 1;
-        }
-    }
-}
-
 // Both FAST work-item lists.  The narrow list: the same levels with NARROW work items (tiles of 32 dwords: <= 119 px of interior per item), for
 // the launches of small batches: it differs in the grouping of the cells only, so everything downstream of the FAST kernel (the quadtree's
 // gather) reads the grouping it was launched with from ITS copy of the level array (lv_n).  Built last: hs_fast_build_items copies
@@ -315,7 +249,7 @@ int hs_plan_geometry(const HsPlanInput& in, HsPlan& P, std::string& err)
         plan_resize_tables(P);
         order_items(P.lv, in.knobs->fast_order);
         plan_quadtree_keys(*in.knobs, P);
-        plan_pyramid(*in.knobs, P);
+        hs_plan_pyramid(*in.knobs, P);
         r = plan_fast_items(*in.knobs, *in.fast_knobs, P);      // last: the items and the narrow levels copy what the steps above left in the levels
     }
     if (r.code != HS_OK) { err = r.text; return r.code; }

@@ -12,10 +12,10 @@
 // pixels of those 4 outputs span <= 11 bytes (scale <= 2), so each of the two source rows is fetched as up to
 // four aligned dwords and the taps are picked out with v_alignbyte instead of 16 byte loads; the x table is one
 // 8-byte record {sx, a0, a1, -} per output.
+// This file: the kernels, their device helpers and the launch function.  The records they read are declared in hs_pyramid.h and made by the host plan,
+// hs_plan_pyramid.hip.
 #include "hs_internal.h"
 #include <atomic>
-#include <algorithm>
-#include <cstring>
 #include <cstdlib>
 
 template <bool ALIGNED>
@@ -143,6 +143,14 @@ __device__ __forceinline__ HsPyrCol pyr_col_data(const PyrColRaw& r)
     c.coef[0] = r.p1.z; c.coef[1] = r.p1.w; c.coef[2] = r.p2.x; c.coef[3] = r.p2.y;
     return c;
 }
+// the horizontal pass of one staged row for a lane's 4 columns: the lane's 8-byte window out of three dwords, then two packed pairs of (H >> 4)
+__device__ __forceinline__ uint2 pyr_hrow(const uint8_t* row, const HsPyrCol& c)
+{
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(&row[c.wbase]);
+    const uint32_t d0 = w[0], d1 = w[1], d2 = w[2];
+    const uint32_t wlo = __builtin_amdgcn_alignbyte(d1, d0, c.wshift), whi = __builtin_amdgcn_alignbyte(d2, d1, c.wshift);
+    return make_uint2(pyr_hpair(whi, wlo, c.sel[0], c.sel[1], c.coef[0], c.coef[1]), pyr_hpair(whi, wlo, c.sel[2], c.sel[3], c.coef[2], c.coef[3]));
+}
 
 // Source rectangle -> LDS with 16-byte vectors: a wave takes whole source rows, floor(64 / nvec) at a time (no per-lane division by the runtime nvec).
 // FOUR rows per lane are in flight before the first LDS write (round 4): written as `load; store` per row the loop waited for every load on the spot —
@@ -182,7 +190,6 @@ __device__ __forceinline__ void pyr_stage_source(const uint8_t* src0 /*wave-unif
 // ~20 VALU instructions per destination pixel instead of ~43 for the direct form.  (A persistent, software-pipelined variant that
 // prefetched the next tile's vectors into registers was measured slower: 0.164 vs 0.146 ms for the 7 levels of 32 frames.)
 // Needs 16-byte aligned source rows and a scale <= 2 (the 4 columns of a lane then span <= 8 source bytes).
-#define LT_ROWS 16
 __global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restrict__ lv, int level, HsImg0 img0, int lds_pitch, int lds_rows, const uint8_t* cols /*hs_pyramid_level_cols*/)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_src[];
@@ -212,12 +219,7 @@ __global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restr
     const HsPyrCol c = pyr_col_data(pyr_col_request(cols, blockIdx.x, tx));
     __syncthreads();
     // ---- B
-    for (int r = __builtin_amdgcn_readfirstlane(ty); r < nrow; r += 4) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(&s_src[r * lds_pitch + c.wbase]);
-        const uint32_t d0 = w[0], d1 = w[1], d2 = w[2];
-        const uint32_t wlo = __builtin_amdgcn_alignbyte(d1, d0, c.wshift), whi = __builtin_amdgcn_alignbyte(d2, d1, c.wshift);
-        *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = make_uint2(pyr_hpair(whi, wlo, c.sel[0], c.sel[1], c.coef[0], c.coef[1]), pyr_hpair(whi, wlo, c.sel[2], c.sel[3], c.coef[2], c.coef[3]));
-    }
+    for (int r = __builtin_amdgcn_readfirstlane(ty); r < nrow; r += 4) *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = pyr_hrow(&s_src[r * lds_pitch], c);
     __syncthreads();
     // ---- C: the destination row of a wave is uniform, so its source rows and weights come from scalar loads
     if (dx0 >= D.w) return;
@@ -253,10 +255,6 @@ __global__ __launch_bounds__(256) void k_resize_level_lds(const HsLevel* __restr
 // descriptions are a kernel argument, the tile geometry is two 32-byte records (HsPyrXTile / HsPyrYTile), a destination row is one 8-byte
 // record (HsPyrRow: clamped source rows + weights, fetched one row ahead) and stores use a scalar row base + a 32-bit lane offset.
 typedef uint32_t hs_u32x8 __attribute__((ext_vector_type(8)));
-#ifndef FZ_ROWS
-#define FZ_ROWS 16
-#endif
-#define FZ_APITCH 272             // LDS pitch of the level-A region: 256 columns + the 3-dword window over-read of the last lane
 template <typename T> __device__ __forceinline__ void hs_gstore_off(uint8_t* uniform_base, uint32_t lane_off, T v)
 {
     *(HS_GLOBAL T*)((HS_GLOBAL uint8_t*)(uintptr_t)uniform_base + lane_off) = v;
@@ -286,12 +284,7 @@ __global__ __launch_bounds__(64 * NW) void k_resize_two_levels(HsPyrFuse F, HsIm
     pyr_stage_source<NW>(hs_uniform_ptr(sbase + (size_t)Y.sy_first * spitch + X.col0), spitch, s_src, (uint32_t)lds_pitch, nvec, nSr, tx, wave);
     // (the per-lane column data of a horizontal pass — window position, byte-pair selectors, coefficient pairs — is a ready-made record: pyr_col_request / pyr_col_data)
     auto h_pass = [&](const uint8_t* src, int pitch, int nrow, const HsPyrCol& c) {
-        for (int r = wave; r < nrow; r += NW) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(&src[r * pitch + c.wbase]);
-            const uint32_t d0 = w[0], d1 = w[1], d2 = w[2];
-            const uint32_t wlo = __builtin_amdgcn_alignbyte(d1, d0, c.wshift), whi = __builtin_amdgcn_alignbyte(d2, d1, c.wshift);
-            *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = make_uint2(pyr_hpair(whi, wlo, c.sel[0], c.sel[1], c.coef[0], c.coef[1]), pyr_hpair(whi, wlo, c.sel[2], c.sel[3], c.coef[2], c.coef[3]));
-        }
+        for (int r = wave; r < nrow; r += NW) *reinterpret_cast<uint2*>(&s_h[r * 256 + 4 * tx]) = pyr_hrow(&src[r * pitch], c);
     };
     // a destination row = one 8-byte record of the TILE's row table (scalar load): byte offsets of its two source rows in the sums buffer + weights
     const uint8_t* const h_lane = reinterpret_cast<const uint8_t*>(s_h) + 8 * tx;
@@ -468,331 +461,6 @@ __global__ __launch_bounds__(64 * NW) void k_resize_chain(HsPyrChain F, HsImg0 i
 #endif
 }
 
-// Host side of pyr_col_request / pyr_col_data: the 64 column records of one tile column in the plane layout (HsPyrCol, hs_internal.h).  Lane t makes
-// the columns x0 + 4 t + i, i = 0..3; a column past the level's last one repeats it (its pixels land in the row padding or are never stored).
-//   wbase | wshift   byte offset of the lane's 8-byte window in a staged row (origin = first source column the row holds), split into dword and byte part
-//   sel[i]           v_perm selector: bytes q, q + 1 of the window as two 16-bit fields, q = sx[i] - sx[0] (a1 == 0 wherever sx + 1 is past the row)
-//   coef[i]          16 a0 | 16 a1 << 16
-size_t hs_pyramid_col_records(const int16_t* xt, int w, int x0, int origin, std::vector<uint64_t>& blob)
-{
-    if (blob.empty()) blob.push_back(0);
-    if (blob.size() & 1) blob.push_back(0);                     // the planes are read as 16-byte vectors
-    const size_t o = blob.size(); blob.resize(o + HS_PYR_COL_TILE_BYTES / 8, 0);
-    uint32_t* const out = reinterpret_cast<uint32_t*>(&blob[o]);
-    for (int t = 0; t < 64; t++) {
-        const int16_t* e[4];
-        for (int i = 0; i < 4; i++) e[i] = xt + 4 * (size_t)std::min(x0 + 4 * t + i, w - 1);
-        HsPyrCol c;
-        const int o0 = e[0][0] - origin;
-        c.wbase = o0 & ~3; c.wshift = o0 & 3;
-        for (int i = 0; i < 4; i++) {
-            const uint32_t q = (uint32_t)(e[i][0] - e[0][0]);
-            c.sel[i] = q | 0x0c00u | ((q + 1) << 16) | 0x0c000000u;
-            c.coef[i] = ((uint32_t)(uint16_t)e[i][1] << 4) | ((uint32_t)(uint16_t)e[i][2] << 20);
-        }
-        uint32_t* const p0 = out + 4 * t, * const p1 = out + 256 + 4 * t, * const p2 = out + 512 + 4 * t;
-        p0[0] = (uint32_t)c.wbase; p0[1] = (uint32_t)c.wshift; p0[2] = c.sel[0]; p0[3] = c.sel[1];
-        p1[0] = c.sel[2]; p1[1] = c.sel[3]; p1[2] = c.coef[0]; p1[3] = c.coef[1];
-        p2[0] = c.coef[2]; p2[1] = c.coef[3];
-    }
-    return o * 8;
-}
-size_t hs_pyramid_level_cols(const int16_t* xt, int w, std::vector<uint64_t>& blob)
-{
-    size_t first = 0;
-    for (int x0 = 0; x0 < w; x0 += 256) {
-        const size_t o = hs_pyramid_col_records(xt, w, x0, xt[4 * (size_t)x0] & ~15, blob);
-        if (x0 == 0) first = o;
-    }
-    return first;
-}
-
-// Host side of k_resize_chain for the levels [first, first + n): walks the tiles of the LAST level from the largest tile width downwards until every
-// stage's region fits 256 columns and the LDS buffers, with the expressions of hs_pyramid_build_tables / the two-level kernel.
-void hs_pyramid_plan_chain(const HsLevel* h_lv, int first, int n, const int16_t* const* xtab, const int16_t* const* yofs, const int16_t* const* ibeta,
-                           std::vector<uint64_t>& blob, HsPyrChain& C, std::vector<uint64_t>& cols_blob, HsPyrChainCols& CC, size_t lds_max, int tile_rows)
-{
-    C = HsPyrChain{}; CC = HsPyrChainCols{};
-    if (tile_rows <= 0) tile_rows = FZ_ROWS;
-    if (n < 2 || n > HS_PYR_CHAIN_MAX || first < 1) return;
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    for (int i = 0; i < n; i++) {
-        const HsLevel& D = h_lv[first + i]; const HsLevel& S = h_lv[first + i - 1];
-        if ((double)S.w / D.w > 2.0 || (double)S.h / D.h > 2.0 || D.w < 8 || D.h < 1) return;
-    }
-    const HsLevel& LAST = h_lv[first + n - 1];
-    const int nby = (LAST.h + tile_rows - 1) / tile_rows;
-    // ---- rows (independent of the tile width): part starts, owned ends, regions and source spans — the same three steps as for the columns below
-    std::vector<std::vector<HsPyrStageY>> ty(n, std::vector<HsPyrStageY>(nby));
-    int h_rows = 0, x_rows0 = 0, x_rows = 0;
-    for (int by = 0; by < nby; by++) {
-        int y0 = by * tile_rows;
-        for (int i = n - 1; i >= 0; i--) {
-            ty[i][by] = HsPyrStageY{};
-            ty[i][by].y0 = y0;
-            if (i > 0) y0 = by == 0 ? 0 : clampi(yofs[first + i][y0], 0, h_lv[first + i - 1].h - 1);
-        }
-    }
-    for (int by = 0; by < nby; by++)
-        for (int i = n - 1; i >= 0; i--) {
-            HsPyrStageY& t = ty[i][by];
-            t.own_y1 = by + 1 < nby ? ty[i][by + 1].y0 : h_lv[first + i].h;
-            if (t.own_y1 < t.y0) return;
-        }
-    for (int by = 0; by < nby; by++) {
-        int need_last = std::min(by * tile_rows + tile_rows, LAST.h) - 1;          // last row of the stage's level that is really read
-        for (int i = n - 1; i >= 0; i--) {
-            const HsLevel& S = h_lv[first + i - 1];
-            const int16_t* yo = yofs[first + i];
-            HsPyrStageY& t = ty[i][by];
-            t.y_last = std::max(need_last, t.own_y1 - 1);
-            const int src_first = clampi(yo[t.y0], 0, S.h - 1), src_last = clampi(yo[t.y_last] + 1, 0, S.h - 1);
-            if (i > 0) {
-                if (src_first < ty[i - 1][by].y0) return;
-                t.src_y0 = ty[i - 1][by].y0;
-                need_last = src_last;
-            } else {
-                t.src_y0 = src_first; t.n_src = src_last - src_first + 1;
-                x_rows0 = std::max(x_rows0, t.n_src);
-                h_rows = std::max(h_rows, t.n_src);
-            }
-        }
-        for (int i = n - 1; i >= 1; i--) {                                          // the source of stage i is the whole region of stage i - 1
-            ty[i][by].n_src = ty[i - 1][by].y_last - ty[i - 1][by].y0 + 1;
-            x_rows = std::max(x_rows, ty[i][by].n_src);
-            h_rows = std::max(h_rows, ty[i][by].n_src);
-        }
-    }
-    // ---- columns: the largest tile width whose regions fit
-    std::vector<std::vector<HsPyrStageX>> best_txs; int best_tbx = 0, best_pitch = 0; size_t best_xbytes = 0;
-    for (int tbx = 256; tbx >= 64; tbx -= 4) {
-        const int nbx = (LAST.w + tbx - 1) / tbx;
-        std::vector<std::vector<HsPyrStageX>> txs(n, std::vector<HsPyrStageX>(nbx));
-        bool ok = true; int pitch = 0;
-        // first columns of every level's parts, last level first (a part starts at the first source column of the tile's part of the level below it)
-        for (int bx = 0; bx < nbx && ok; bx++) {
-            int x0 = bx * tbx;
-            for (int i = n - 1; i >= 0; i--) {
-                txs[i][bx] = HsPyrStageX{};
-                txs[i][bx].x0 = x0;
-                if (i > 0) x0 = bx == 0 ? 0 : (xtab[first + i][4 * x0] & ~3);
-            }
-        }
-        for (int bx = 0; bx < nbx && ok; bx++)
-            for (int i = n - 1; i >= 0; i--) {
-                const HsLevel& D = h_lv[first + i];
-                HsPyrStageX& t = txs[i][bx];
-                t.own_x1 = bx + 1 < nbx ? txs[i][bx + 1].x0 : ((D.w + 3) & ~3);
-                if (t.own_x1 < t.x0) ok = false;
-            }
-        // regions: last level = the tile; the level below it must hold the columns the region's last column reads
-        for (int bx = 0; bx < nbx && ok; bx++) {
-            int need_last = std::min(bx * tbx + tbx, LAST.w) - 1;                  // last column of the region of stage i that is really read
-            for (int i = n - 1; i >= 0; i--) {
-                const HsLevel& D = h_lv[first + i]; const HsLevel& S = h_lv[first + i - 1];
-                HsPyrStageX& t = txs[i][bx];
-                const int reg_last = std::max(need_last, std::min(t.own_x1, D.w) - 1);
-                t.ncols = ((std::max(reg_last + 1, t.own_x1) - t.x0) + 3) & ~3;
-                if (t.ncols > 256 || t.ncols <= 0) { ok = false; break; }
-                const int16_t* xt = xtab[first + i];
-                const int src_need_first = xt[4 * t.x0], src_need_last = std::min(xt[4 * std::min(reg_last, D.w - 1)] + 1, S.w - 1);
-                if (i > 0) {
-                    const HsPyrStageX& u = txs[i - 1][bx];
-                    if (src_need_first < u.x0) { ok = false; break; }
-                    t.src_x0 = u.x0;
-                    // the window of the last active lane (offset of its first column + 12 bytes) must stay inside the LDS row of the region below
-                    const int lastlane_col = std::min(t.x0 + t.ncols - 4, D.w - 1);
-                    if (xt[4 * lastlane_col] - u.x0 + 12 > FZ_APITCH) { ok = false; break; }
-                    need_last = src_need_last;
-                } else {
-                    t.src_x0 = src_need_first & ~15;
-                    t.nvec = ((src_need_last - t.src_x0) >> 4) + 1;
-                    pitch = std::max(pitch, t.nvec * 16 + 16);
-                    const int lastlane_col = std::min(t.x0 + t.ncols - 4, D.w - 1);
-                    if (xt[4 * lastlane_col] - t.src_x0 + 12 > t.nvec * 16 + 16) { ok = false; break; }
-                }
-            }
-        }
-        if (!ok) continue;
-        pitch = (pitch + 15) & ~15;
-        const size_t x_bytes = std::max((size_t)pitch * x_rows0, (size_t)FZ_APITCH * x_rows);
-        const size_t lds = ((x_bytes + 15) & ~(size_t)15) + (size_t)h_rows * 256 * 2;
-        if (lds > lds_max || h_rows > 127 || x_rows > 127) continue;               // (row records address the sums buffer with 16-bit byte offsets: 512 B per row)
-        best_tbx = tbx; best_pitch = pitch; best_xbytes = x_bytes; best_txs = txs;
-        break;
-    }
-    if (best_tbx == 0) return;
-    {
-        const int tbx = best_tbx, pitch = best_pitch, nbx = (LAST.w + tbx - 1) / tbx;
-        const size_t x_bytes = best_xbytes;
-        const std::vector<std::vector<HsPyrStageX>>& txs = best_txs;
-        // ---- commit
-        if (blob.empty()) blob.push_back(0);
-        C.sbase = first == 1 ? nullptr : h_lv[first - 1].base; C.s_img_stride = h_lv[first - 1].img_stride; C.spitch = h_lv[first - 1].pitch; C.nstage = n;
-        for (int i = 0; i < n; i++) {
-            const HsLevel& D = h_lv[first + i];
-            HsPyrStage& S = C.st[i];
-            S.base = D.base; S.img_stride = D.img_stride; S.pitch = D.pitch; S.w = D.w; S.h = D.h;
-            S.xt = reinterpret_cast<const HsXTab*>(D.xofs);
-            // row records per y tile: rows y0 .. y_last of the tile's region, offsets relative to the first row the tile's source buffer holds;
-            // every slot is padded with copies of its last row (the kernel prefetches one step of <= 8 rows past the end)
-            int slot = 0;
-            for (int by = 0; by < nby; by++) slot = std::max(slot, ty[i][by].y_last - ty[i][by].y0 + 1);
-            slot += 4 * 8;                                                           // (the vertical pass walks 2 NW rows per step and prefetches one step ahead: 4 NW rows past the end at most)
-            const size_t orow = blob.size(); blob.resize(orow + (size_t)slot * nby);
-            const int sh = h_lv[first + i - 1].h;
-            for (int by = 0; by < nby; by++) {
-                const HsPyrStageY& t = ty[i][by];
-                for (int k = 0; k < slot; k++) {
-                    const int dy = std::min(t.y0 + k, t.y_last);
-                    HsPyrRow r;
-                    r.off0 = (uint16_t)((clampi(yofs[first + i][dy], 0, sh - 1) - t.src_y0) * 512);
-                    r.off1 = (uint16_t)((clampi(yofs[first + i][dy] + 1, 0, sh - 1) - t.src_y0) * 512);
-                    r.b0 = (uint16_t)ibeta[first + i][2 * dy]; r.b1 = (uint16_t)ibeta[first + i][2 * dy + 1];
-                    memcpy(&blob[orow + (size_t)by * slot + k], &r, 8);
-                }
-            }
-            S.rows = reinterpret_cast<const HsPyrRow*>(orow * 8); S.slot = slot;
-            const size_t ox = blob.size(); blob.resize(ox + 4 * (size_t)nbx);
-            memcpy(&blob[ox], txs[i].data(), 32 * (size_t)nbx);
-            const size_t oy = blob.size(); blob.resize(oy + 4 * (size_t)nby);
-            memcpy(&blob[oy], ty[i].data(), 32 * (size_t)nby);
-            S.tx = reinterpret_cast<const HsPyrStageX*>(ox * 8); S.ty = reinterpret_cast<const HsPyrStageY*>(oy * 8);
-            for (int bx = 0; bx < nbx; bx++) {                                       // column records per x tile: the stage's region columns, window offsets relative to the source buffer's first column
-                const size_t oc = hs_pyramid_col_records(xtab[first + i], D.w, txs[i][bx].x0, txs[i][bx].src_x0, cols_blob);
-                if (bx == 0) CC.st[i] = reinterpret_cast<const uint8_t*>(oc);
-            }
-        }
-        C.tbx = tbx; C.lds_pitch = pitch; C.x_bytes = (int32_t)((x_bytes + 15) & ~(size_t)15); C.h_rows = h_rows; C.grid_x = nbx; C.grid_y = nby; C.valid = 1;
-    }
-}
-
-// Host side of the table-driven kernel: for every fused pair the tile records (the geometry the kernel used to compute itself, same
-// expressions) and for both levels of the pair the row records; everything is appended to `blob`, pointers into it are byte offsets.
-void hs_pyramid_build_tables(const HsLevel* h_lv, int nlevels, const int16_t* const* xtab, const int16_t* const* yofs, const int16_t* const* ibeta,
-                             std::vector<uint64_t>& blob, std::vector<HsPyrFuse>& fuse, std::vector<uint64_t>& cols_blob, std::vector<HsPyrFuseCols>& fuse_cols)
-{
-    fuse.assign(nlevels, HsPyrFuse{}); fuse_cols.assign(nlevels, HsPyrFuseCols{});
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    if (blob.empty()) blob.push_back(0);
-    for (int l = 1; l + 1 < nlevels; l++) {
-        const HsLevel& A = h_lv[l];
-        if (A.fuse_tbx <= 0) continue;
-        const HsLevel& B = h_lv[l + 1]; const HsLevel& S = h_lv[l - 1];
-        const int16_t* xA = xtab[l]; const int16_t* xB = xtab[l + 1]; const int16_t* yA = yofs[l]; const int16_t* yB = yofs[l + 1];
-        const int tbx = A.fuse_tbx, nbx = (B.w + tbx - 1) / tbx, nby = (B.h + FZ_ROWS - 1) / FZ_ROWS;
-        HsPyrFuse& F = fuse[l];
-        F.sbase = l == 1 ? nullptr : S.base; F.s_img_stride = S.img_stride; F.spitch = S.pitch;
-        F.abase = A.base; F.a_img_stride = A.img_stride; F.apitch = A.pitch; F.aw = A.w; F.ah = A.h;
-        F.bbase = B.base; F.b_img_stride = B.img_stride; F.bpitch = B.pitch; F.bw = B.w; F.bh = B.h;
-        F.xtA = reinterpret_cast<const HsXTab*>(A.xofs); F.xtB = reinterpret_cast<const HsXTab*>(B.xofs);
-        F.tbx = tbx; F.sr = A.fuse_sr; F.lds_pitch = A.fuse_pitch; F.valid = 1;
-        const size_t ox = blob.size(); blob.resize(ox + 4 * (size_t)nbx);
-        for (int bx = 0; bx < nbx; bx++) {
-            const int bx0 = bx * tbx; const bool last_x = bx0 + tbx >= B.w;
-            HsPyrXTile t{};
-            t.ax0 = bx == 0 ? 0 : (xB[4 * bx0] & ~3);
-            t.own_x1 = last_x ? ((A.w + 3) & ~3) : (xB[4 * (bx0 + tbx)] & ~3);
-            const int ax_lastcol = std::min(t.ax0 + 255, A.w - 1);
-            t.col0 = xA[4 * t.ax0] & ~15;
-            const int col_last = std::min(xA[4 * ax_lastcol] + 1, S.w - 1);
-            t.nvec = ((col_last - t.col0) >> 4) + 1;
-            memcpy(&blob[ox + 4 * (size_t)bx], &t, 32);
-        }
-        const size_t oy = blob.size(); blob.resize(oy + 4 * (size_t)nby);
-        for (int by = 0; by < nby; by++) {
-            const int by0 = by * FZ_ROWS, by_last = std::min(by0 + FZ_ROWS, B.h) - 1; const bool last_y = by0 + FZ_ROWS >= B.h;
-            HsPyrYTile t{};
-            t.ay0 = by == 0 ? 0 : clampi(yB[by0], 0, A.h - 1);
-            t.own_y1 = last_y ? A.h : clampi(yB[by0 + FZ_ROWS], 0, A.h - 1);
-            t.ay_last = std::max(clampi(yB[by_last] + 1, 0, A.h - 1), t.own_y1 - 1);
-            t.sy_first = clampi(yA[t.ay0], 0, S.h - 1);
-            t.n_sr = clampi(yA[t.ay_last] + 1, 0, S.h - 1) - t.sy_first + 1;
-            memcpy(&blob[oy + 4 * (size_t)by], &t, 32);
-        }
-        F.xt = reinterpret_cast<const HsPyrXTile*>(ox * 8); F.yt = reinterpret_cast<const HsPyrYTile*>(oy * 8);
-        // row records per y tile (offsets relative to the first row the tile's sums buffer holds), padded with copies of the tile's last row: the
-        // kernel prefetches one step of <= 8 rows past the end
-        const int slotA = A.fuse_ar + 8, slotB = FZ_ROWS + 8;
-        const size_t oa = blob.size(); blob.resize(oa + (size_t)slotA * nby);
-        const size_t ob = blob.size(); blob.resize(ob + (size_t)slotB * nby);
-        for (int by = 0; by < nby; by++) {
-            HsPyrYTile t; memcpy(&t, &blob[oy + 4 * (size_t)by], 32);
-            const int by0 = by * FZ_ROWS;
-            for (int k = 0; k < slotA; k++) {
-                const int ay = std::min(t.ay0 + k, t.ay_last);
-                HsPyrRow r;
-                r.off0 = (uint16_t)((clampi(yA[ay], 0, S.h - 1) - t.sy_first) * 512); r.off1 = (uint16_t)((clampi(yA[ay] + 1, 0, S.h - 1) - t.sy_first) * 512);
-                r.b0 = (uint16_t)ibeta[l][2 * ay]; r.b1 = (uint16_t)ibeta[l][2 * ay + 1];
-                memcpy(&blob[oa + (size_t)by * slotA + k], &r, 8);
-            }
-            for (int k = 0; k < slotB; k++) {
-                const int y = std::min(by0 + k, B.h - 1);
-                HsPyrRow r;
-                r.off0 = (uint16_t)((clampi(yB[y], 0, A.h - 1) - t.ay0) * 512); r.off1 = (uint16_t)((clampi(yB[y] + 1, 0, A.h - 1) - t.ay0) * 512);
-                r.b0 = (uint16_t)ibeta[l + 1][2 * y]; r.b1 = (uint16_t)ibeta[l + 1][2 * y + 1];
-                memcpy(&blob[ob + (size_t)by * slotB + k], &r, 8);
-            }
-        }
-        F.rowA = reinterpret_cast<const HsPyrRow*>(oa * 8); F.rowB = reinterpret_cast<const HsPyrRow*>(ob * 8); F.slotA = slotA;
-        // column records per x tile: level A from the tile's first region column against the staged source rows, level B from the tile's first column
-        // against the level-A region in LDS
-        for (int pass = 0; pass < 2; pass++)
-            for (int bx = 0; bx < nbx; bx++) {
-                HsPyrXTile t; memcpy(&t, &blob[ox + 4 * (size_t)bx], 32);
-                const size_t oc = pass == 0 ? hs_pyramid_col_records(xA, A.w, t.ax0, t.col0, cols_blob) : hs_pyramid_col_records(xB, B.w, bx * tbx, t.ax0, cols_blob);
-                if (bx == 0) (pass == 0 ? fuse_cols[l].a : fuse_cols[l].b) = reinterpret_cast<const uint8_t*>(oc);
-            }
-    }
-}
-
-// Can levels (l, l+1) be fused?  Walks every tile with the host copies of the tables and checks what the kernel assumes: the level-A region of
-// a tile (owned part + halo) fits 256 columns / fuse_ar rows, its source rectangle fits the LDS rectangle, all LDS fits.
-void hs_pyramid_plan_fusion(HsLevel* h_lv, int nlevels, const int16_t* const* xtab, const int16_t* const* yofs, int tbx_max)
-{
-    for (int l = 1; l < nlevels; l++) h_lv[l].fuse_tbx = h_lv[l].fuse_ar = h_lv[l].fuse_sr = h_lv[l].fuse_pitch = 0;
-    for (int l = 1; l + 1 < nlevels; l += 2) {
-        HsLevel& A = h_lv[l]; const HsLevel& B = h_lv[l + 1]; const HsLevel& S = h_lv[l - 1];
-        const double scxA = (double)S.w / A.w, scyA = (double)S.h / A.h, scxB = (double)A.w / B.w, scyB = (double)A.h / B.h;
-        if (scxA > 2.0 || scxB > 2.0 || scyA > 2.0 || scyB > 2.0 || B.w < 8 || B.h < 1) continue;
-        int tbx = std::min(256, ((int)(250.0 / scxB)) & ~3);
-        if (tbx_max >= 64) tbx = std::min(tbx, tbx_max & ~3);      // tuning / experiment knob (HS_PYRAMID_TBX_MAX): narrower level-B tiles
-        if (tbx < 64) continue;
-        const int16_t* xA = xtab[l]; const int16_t* xB = xtab[l + 1]; const int16_t* yA = yofs[l]; const int16_t* yB = yofs[l + 1];
-        auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        int ar = 0, sr = 0, pitch = 0; bool ok = true;
-        for (int by0 = 0; by0 < B.h && ok; by0 += FZ_ROWS) {
-            const int by_last = std::min(by0 + FZ_ROWS, B.h) - 1; const bool last_y = by0 + FZ_ROWS >= B.h;
-            const int ay0 = by0 == 0 ? 0 : clampi(yB[by0], 0, A.h - 1);
-            const int own_y1 = last_y ? A.h : clampi(yB[by0 + FZ_ROWS], 0, A.h - 1);
-            const int ay_last = std::max(clampi(yB[by_last] + 1, 0, A.h - 1), own_y1 - 1);
-            if (own_y1 <= ay0 && !last_y) { /* empty owned range is fine */ }
-            if (clampi(yB[by0], 0, A.h - 1) < ay0) ok = false;                    // rows the tile needs lie at or below its first row
-            ar = std::max(ar, ay_last - ay0 + 1);
-            const int sy_first = clampi(yA[ay0], 0, S.h - 1), sy_last = clampi(yA[ay_last] + 1, 0, S.h - 1);
-            sr = std::max(sr, sy_last - sy_first + 1);
-        }
-        for (int bx0 = 0; bx0 < B.w && ok; bx0 += tbx) {
-            const int bx_last = std::min(bx0 + tbx, B.w) - 1; const bool last_x = bx0 + tbx >= B.w;
-            const int ax0 = bx0 == 0 ? 0 : (xB[4 * bx0] & ~3);
-            const int own_x1 = last_x ? ((A.w + 3) & ~3) : (xB[4 * (bx0 + tbx)] & ~3);
-            const int need_last = std::min(xB[4 * bx_last] + 1, A.w - 1);
-            if (xB[4 * bx0] < ax0 || own_x1 - ax0 > 256 || need_last - ax0 > 255 || own_x1 < ax0) ok = false;
-            // window of the last lane: offset of its first column + 11 bytes must stay inside the LDS row
-            if (xB[4 * std::min(bx0 + tbx - 4, B.w - 1)] - ax0 + 12 > FZ_APITCH) ok = false;
-            const int ax_lastcol = std::min(ax0 + 255, A.w - 1);
-            const int col0 = xA[4 * ax0] & ~15, col_last = std::min(xA[4 * ax_lastcol] + 1, S.w - 1);
-            pitch = std::max(pitch, ((col_last - col0) >> 4) * 16 + 16 + 16);
-            if (xA[4 * ax0] < col0) ok = false;
-        }
-        if (!ok) continue;
-        pitch = (pitch + 15) & ~15;
-        const size_t lds = (size_t)pitch * sr + (size_t)std::max(sr, ar) * 256 * 2;
-        if ((size_t)FZ_APITCH * ar > (size_t)pitch * sr || lds > 60 * 1024) continue;
-        A.fuse_tbx = tbx; A.fuse_ar = ar; A.fuse_sr = sr; A.fuse_pitch = pitch;
-    }
-}
-
 // launches with at most this many workgroups per CU use 8 waves per workgroup (HS_PYRAMID_NW8 = threshold; 0 = never; tuning / parity knob, read once)
 static int pyr_nw8_wg_per_cu()
 {
@@ -817,57 +485,43 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
         state[dev].store(ok ? 1 : 2, std::memory_order_release);
         return ok;
     }();
+    // 16-byte source vectors: always fine for our own levels (pitch % 64 == 0), checked for the caller's frames; a vector may run past the last source
+    // column only inside the row's own pitch
+    const bool frames_vec16 = (((uintptr_t)img0.base | (uintptr_t)img0.base2 | img0.row_stride | img0.img_stride) & 15) == 0 && ((h_lv[0].w + 15) & ~15) <= (int)img0.row_stride;
+    // few workgroups per CU (small batches): 8 waves per workgroup shorten the workgroup's life, which is the launch's duration then
+    auto eight_waves = [](dim3 grid) { return (size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu(); };
+    auto chain_lds = [](const HsPyrChain& C) { return hs_pyr_chain_lds((size_t)C.x_bytes, C.h_rows); };
+    // (measured at one 1080p pair per call, levels 1-7 in one launch of 304 workgroups: 27.6 us with 8 waves per workgroup, 28.8 us with 16 — the
+    //  stages are a dependent sequence inside the workgroup, more waves per stage do not shorten it; three launches of the standard plan: 28.6 us)
+    auto launch_chain = [&](const HsPyrChain& C, const HsPyrChainCols& K) {
+        const dim3 grid(C.grid_x, C.grid_y, batch);
+        if (eight_waves(grid)) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), chain_lds(C), s, C, img0, K);
+        else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), chain_lds(C), s, C, img0, K);
+    };
     int n_launches = 0;      // what this call really enqueued (the plan can fall back per level: caller-frame alignment, LDS attribute refused)
     for (int l = 1; l < nlevels; l++, n_launches++) {
         const HsLevel& D = h_lv[l];
-        if (deep && deep[l].valid && l + deep[l].nstage <= nlevels) {
-            bool vec16 = true;
-            if (l == 1) vec16 = (((uintptr_t)img0.base | (uintptr_t)img0.base2 | img0.row_stride | img0.img_stride) & 15) == 0 && ((h_lv[0].w + 15) & ~15) <= (int)img0.row_stride;
-            const HsPyrChain& C = deep[l];
-            const size_t lds = (size_t)C.x_bytes + (size_t)C.h_rows * 256 * 2;
-            if (vec16 && (lds <= 64 * 1024 || big_lds)) {
-                dim3 grid(C.grid_x, C.grid_y, batch);
-                // (measured at one 1080p pair per call, levels 1-7 in one launch of 304 workgroups: 27.6 us with 8 waves per workgroup, 28.8 us with 16 — the
-                //  stages are a dependent sequence inside the workgroup, more waves per stage do not shorten it; three launches of the standard plan: 28.6 us)
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0, cols.deep[l]);
-                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0, cols.deep[l]);
-                l += C.nstage - 1;
-                continue;
-            }
+        const bool vec16 = l > 1 || frames_vec16;
+        if (deep && deep[l].valid && l + deep[l].nstage <= nlevels && vec16 && (chain_lds(deep[l]) <= 64 * 1024 || big_lds)) {
+            launch_chain(deep[l], cols.deep[l]);
+            l += deep[l].nstage - 1;
+            continue;
         }
-        if (chain && D.chain_n > 0 && chain[l].valid && l + D.chain_n <= nlevels) {
-            bool vec16 = true;
-            if (l == 1) vec16 = (((uintptr_t)img0.base | (uintptr_t)img0.base2 | img0.row_stride | img0.img_stride) & 15) == 0 && ((h_lv[0].w + 15) & ~15) <= (int)img0.row_stride;
-            if (vec16) {
-                const HsPyrChain& C = chain[l];
-                const size_t lds = (size_t)C.x_bytes + (size_t)C.h_rows * 256 * 2;
-                dim3 grid(C.grid_x, C.grid_y, batch);
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_chain<8>, grid, dim3(512), lds, s, C, img0, cols.chain[l]);
-                else hipLaunchKernelGGL(k_resize_chain<4>, grid, dim3(256), lds, s, C, img0, cols.chain[l]);
-                l += C.nstage - 1;
-                continue;
-            }
+        if (chain && D.chain_n > 0 && chain[l].valid && l + D.chain_n <= nlevels && vec16) {
+            launch_chain(chain[l], cols.chain[l]);
+            l += chain[l].nstage - 1;
+            continue;
         }
-        if (D.fuse_tbx > 0 && l + 1 < nlevels && fuse && fuse[l].valid) {
-            // 16-byte source vectors: always fine for our own levels (pitch % 64 == 0), checked for the caller's frames
-            bool vec16 = true;
-            if (l == 1) vec16 = (((uintptr_t)img0.base | (uintptr_t)img0.base2 | img0.row_stride | img0.img_stride) & 15) == 0 && ((h_lv[0].w + 15) & ~15) <= (int)img0.row_stride;
-            if (vec16) {
-                const HsLevel& B = h_lv[l + 1];
-                const size_t lds = (size_t)D.fuse_pitch * D.fuse_sr + (size_t)std::max(D.fuse_sr, D.fuse_ar) * 256 * 2;
-                dim3 grid((B.w + D.fuse_tbx - 1) / D.fuse_tbx, (B.h + FZ_ROWS - 1) / FZ_ROWS, batch);
-                // few workgroups per CU (small batches): 8 waves per workgroup shorten the workgroup's life, which is the launch's duration then
-                if ((size_t)grid.x * grid.y * grid.z <= (size_t)256 * pyr_nw8_wg_per_cu()) hipLaunchKernelGGL(k_resize_two_levels<8>, grid, dim3(512), lds, s, fuse[l], img0, cols.fuse[l]);
-                else hipLaunchKernelGGL(k_resize_two_levels<4>, grid, dim3(256), lds, s, fuse[l], img0, cols.fuse[l]);
-                l++;                                           // level l+1 is done too
-                continue;
-            }
+        if (D.fuse_tbx > 0 && l + 1 < nlevels && fuse && fuse[l].valid && vec16) {
+            const HsLevel& B = h_lv[l + 1];
+            const size_t lds = hs_pyr_fuse_lds(D.fuse_pitch, D.fuse_sr, D.fuse_ar);
+            const dim3 grid((B.w + D.fuse_tbx - 1) / D.fuse_tbx, (B.h + FZ_ROWS - 1) / FZ_ROWS, batch);
+            if (eight_waves(grid)) hipLaunchKernelGGL(k_resize_two_levels<8>, grid, dim3(512), lds, s, fuse[l], img0, cols.fuse[l]);
+            else hipLaunchKernelGGL(k_resize_two_levels<4>, grid, dim3(256), lds, s, fuse[l], img0, cols.fuse[l]);
+            l++;                                           // level l+1 is done too
+            continue;
         }
         const int sw = h_lv[l - 1].w, sh = h_lv[l - 1].h;
-        // 16-byte source vectors: always fine for our own levels (pitch % 64 == 0), checked for the caller's frames;
-        // a vector may run past the last source column only inside the row's own pitch
-        bool vec16 = true;
-        if (l == 1) vec16 = (((uintptr_t)img0.base | (uintptr_t)img0.base2 | img0.row_stride | img0.img_stride) & 15) == 0 && ((sw + 15) & ~15) <= (int)img0.row_stride;
         // worst-case source rectangle of a 256 x LT_ROWS tile
         const double scx = (double)sw / D.w, scy = (double)sh / D.h;
         const int lds_pitch = (((int)(256 * scx) + 2 + 15 + 15) & ~15) + 16;
@@ -887,14 +541,6 @@ int hs_launch_pyramid(const HsLevel* d_lv, const HsLevel* h_lv, const HsPyrFuse*
         else hipLaunchKernelGGL(k_resize_level<false>, grid, block, 0, s, d_lv, l, img0);
     }
     return n_launches;
-}
-
-// launches of one hs_launch_pyramid call when every eligible pair is fused (the caller-frame alignment fallback adds one)
-int hs_pyramid_launch_count(const HsLevel* h_lv, int nlevels)
-{
-    int n = 0;
-    for (int l = 1; l < nlevels; l++) { n++; if (h_lv[l].chain_n > 0 && l + h_lv[l].chain_n <= nlevels) l += h_lv[l].chain_n - 1; else if (h_lv[l].fuse_tbx > 0 && l + 1 < nlevels) l++; }
-    return n;
 }
 
 // ---- calibration kernels of known HBM traffic (hs_debug_stream_copy): one dword / one 16-byte vector per lane, grid-stride

@@ -15,7 +15,7 @@
 #include "../../hyslam_amd/csrc/hs_internal.h"
 
 #define CHECK(c) do { if (!(c)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
-static const int APITCH = 272;      // FZ_APITCH of kernels_pyramid.hip: LDS pitch of a region a later pass reads
+static const int APITCH = 272;      // restated, not included: the value of hs_pyramid.h's FZ_APITCH, the LDS pitch of a region a later pass reads
 
 struct Tally { long tiles = 0, lanes = 0, past_w = 0, past_tile = 0, fused = 0, stages = 0, deep_stages = 0, levels = 0, odd_pairs = 0; };
 

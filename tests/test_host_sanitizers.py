@@ -115,7 +115,7 @@ def test_plan_digests_and_refusals_match_the_recorded_ones():
     build()
     with open(os.path.join(ROOT, "tests", "golden", "plan_digests.json")) as f:
         cases = json.load(f)["cases"]
-    assert len(cases) == 14 + 2 * 16 + 3
+    assert len(cases) == 14 + 2 * 16 + 3 + 6 + 4 + 2 + 5
     clean = {k: v for k, v in os.environ.items() if not k.startswith("HS_")}
     for c in cases:
         r = subprocess.run([EXE, "plan"] + c["args"], env=dict(clean, **c["env"]), capture_output=True, text=True, timeout=300)
