@@ -270,7 +270,7 @@ _lib = None
 # source files each kernel family is compiled from: the committed rocprofv3 counter passes (profiles/*_{hbm_traffic,sq_counters}.json) are stamped
 # with these digests and bench.py only replays a counter whose kernel sources are unchanged
 KERNEL_SOURCES = {
-    "k_fast_rows": ["kernels_fast.hip", "hs_internal.h"],
+    "k_fast_rows": ["kernels_fast.hip", "hs_fast.h", "hs_internal.h"],
     "k_resize": ["kernels_pyramid.hip", "hs_pyramid.h", "hs_internal.h"],
     "k_describe": ["kernels_describe.hip", "lean_sincos.h", "hs_internal.h"],
     "k_quadtree": ["kernels_quadtree.hip", "hs_internal.h"],

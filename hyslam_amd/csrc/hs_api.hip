@@ -75,8 +75,7 @@ struct hs_orb {
     hipStream_t stream = nullptr;
     std::string err;
     uint16_t taps[7];
-    HsKnobs knobs{};                   // the handle's HS_* environment knobs, read once in hs_orb_create (read_knobs has the table); split_mode is also set by hs_orb_set_split
-    HsFastKnobs fast_knobs{};          // HS_FAST_* environment knobs, read once in hs_orb_create
+    HsKnobs knobs{};                   // the handle's HS_* environment knobs, read once in hs_orb_create (hs_read_knobs has the table); split_mode is also set by hs_orb_set_split
     uint32_t fast_epoch = 0;           // FAST launches on this workspace so far (selects the work-queue counter set)
     hipStream_t s_aux = nullptr; hipEvent_t ev_sfork = nullptr, ev_sjoin = nullptr;      // the second launch sequence of the split and its fences
     bool fast_taps = false;            // every tap fits a byte and the 16-bit row sums cannot saturate
@@ -102,7 +101,7 @@ struct hs_orb {
         HsBuf<uint32_t> d_fast_ovf;
         HsBuf<uint8_t> d_pyr;
         HsBuf<int16_t> d_tables;
-        HsBuf<uint8_t> d_qt_tabs;          // geometric-key tables of the count-domain quadtree (hs_quadtree_build_tables)
+        HsBuf<uint8_t> d_qt_tabs;          // geometric-key tables of the count-domain quadtree (hs_plan.hip)
         // round 4: the FAST kernel computes the candidates' geometric keys and leaves their histogram + the best candidate per deepest cell in global
         // memory (HsFastQt, HsLevel::qt_hist_off): u16 key tables, the per-level records, the two arrays ([batch][stride]; all zero between calls:
         // the quadtree kernel zeroes what it consumes)
@@ -240,7 +239,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     hs_orb::Geometry& g = h->geo;
     const int L = h->p.nlevels;
     HsPlan P; std::string refusal;
-    const HsPlanInput in{ &h->p, h->inv_scale.data(), h->scale.data(), h->quota.data(), &h->knobs, &h->fast_knobs, h->qt_large, w, hh };
+    const HsPlanInput in{ &h->p, h->inv_scale.data(), h->scale.data(), h->quota.data(), &h->knobs, h->qt_large, w, hh };
     const int rc = hs_plan_geometry(in, P, refusal);
     if (rc != HS_OK) return hs_fail(h, rc, refusal);
     g.total_cells = P.total_cells; g.max_wcell = P.max_wcell; g.max_hcell = P.max_hcell; g.fast_items = P.fast_items; g.fast_items_n = P.fast_items_n;
@@ -274,9 +273,9 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     HIP_TRY(h, g.d_pyr_cols.grow(std::max<size_t>(P.pyr_cols.size() * 8, 256)));
     HIP_TRY(h, g.d_fast_items.grow(P.items.size()));
     HIP_TRY(h, g.d_fast_items_n.grow(P.items_n.size()));
-    HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(g.max_hcell, std::max(g.fast_items, g.fast_items_n) * batch, h->fast_knobs), 256) / 4));      // (a multiple of 4 bytes)
+    HIP_TRY(h, g.d_fast_ovf.grow(std::max<size_t>(hs_fast_overflow_bytes(h->knobs, g.max_hcell, g.fast_items, g.fast_items_n, batch), 256) / 4));      // (a multiple of 4 bytes)
 
-    // ---- offsets -> addresses.  The FAST items were built by the plan from the levels' offsets (hs_fast_build_items copies HsLevel::base), so
+    // ---- offsets -> addresses.  The FAST items were built by the plan from the levels' offsets (hs_plan_fast.hip copies HsLevel::base), so
     // they are relocated here by HsFastItem::level rather than rebuilt from the relocated levels.
     relocate_levels(g.lv, g); relocate_levels(g.lv_n, g);
     relocate_pyramid(g);
@@ -306,7 +305,7 @@ int configure_impl(hs_orb* h, int w, int hh, int batch)
     return HS_OK;
 }
 
-// The handle's knobs of the environment: name, default, how the value is taken, meaning.  read_knobs is their only reader and runs once, in
+// The handle's knobs of the environment: name, default, how the value is taken, meaning.  hs_read_knobs is their only reader and runs once, in
 // hs_orb_create (a second lane's handle reads them again at its own creation).  INTEGRATION.md has the users' table of every HS_* variable.
 enum KnobRule { K_ANY, K_FLAG /*v != 0*/, K_POSITIVE /*v > 0, else the default*/, K_NONNEG /*v >= 0, else the default*/, K_MIN2 /*v >= 2, else the default*/,
                 K_TRISTATE /*unset (or INT_MIN) = -1, else v != 0*/ };
@@ -320,6 +319,16 @@ const KnobRow KNOBS[] = {
     // (a workgroup's stages are a dependent sequence whose length goes with the rows per wave: more, flatter tiles shorten the launch although their halo rows cost more work)
     { "HS_PYRAMID_DEEP_ROWS",   &HsKnobs::deep_rows,           8,             K_MIN2,     "rows of the LAST level per tile in the small-batch plan" },
     { "HS_FAST_ORDER",          &HsKnobs::fast_order,          1,             K_ANY,      "order of an image's FAST work items: 1 = reduced levels deepest first, level 0 last; 0 = level 0 first (the order until round 3); 2 = reduced levels interleaved, level 0 last" },
+    { "HS_FAST_PCAP",           &HsKnobs::fast_pcap,           0,             K_ANY,      "tuning: cap on the FAST kernel's list length" },
+    { "HS_FAST_LIST_MIN",       &HsKnobs::fast_list_min,       0,             K_ANY,      "tuning: list entries the tallest item must keep (decides the workgroups per CU; 1024 = round 4's layout)" },
+    { "HS_FAST_TEST_SMALL_LISTS", &HsKnobs::fast_small_lists,  0,             K_FLAG,     "parity tests: force the spill paths" },
+    { "HS_FAST_WG_PER_CU",      &HsKnobs::fast_wg_per_cu,      0,             K_ANY,      "tuning: workgroups per CU" },
+    { "HS_FAST_TEST_SCAN_B",    &HsKnobs::fast_scan_b,         0,             K_FLAG,     "parity tests: NMS from the score tile" },
+    { "HS_FAST_IMAGE_MAJOR",    &HsKnobs::fast_image_major,    0,             K_FLAG,     "tuning / parity tests: the work units image-major whatever the batch" },
+    { "HS_FAST_NQ",             &HsKnobs::fast_nq,             0,             K_ANY,      "tuning / parity tests: at most this many work queues (8, 16, 32)" },
+    { "HS_FAST_COLS",           &HsKnobs::fast_cols,           0,             K_ANY,      "tuning / parity tests: 32 / 64 = narrow / wide items whatever the batch (default: by batch)" },
+    { "HS_FAST_NARROW_MAX",     &HsKnobs::fast_narrow_max,     0,             K_ANY,      "tuning: narrow items for launches of at most this many (narrow) work items" },
+    { "HS_FAST_NO_FOLD",        &HsKnobs::fast_no_fold,        0,             K_FLAG,     "tuning / parity tests: work queues even for launches of <= 2 units per workgroup" },
     { "HS_FAST_KEYS",           &HsKnobs::fast_keys,           1,             K_FLAG,     "0: the quadtree kernel gathers the candidates and computes the keys itself (the scheme until round 3)" },
     { "HS_FAST_KEYS_LEVELS",    &HsKnobs::fast_keys_levels,    HS_MAX_LEVELS, K_POSITIVE, "only the levels 0 .. n-1 get keys (tuning)" },
     { "HS_FAST_KEYS_MAX_BATCH", &HsKnobs::fast_keys_max_batch, 16,            K_NONNEG,   "calls of more frames than this run without the keys (see run_extract)" },
@@ -330,7 +339,8 @@ const KnobRow KNOBS[] = {
     { "HS_STEREO_FUSE",         &HsKnobs::stereo_fuse,         1,             K_FLAG,     "0: the stereo front end with a separate k_stereo_strips launch instead of the strips binned by an extra workgroup of the describe launch" },
     { "HS_EXTRACT_SPLIT",       &HsKnobs::split_mode,          -1,            K_TRISTATE, "1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, unset = for small batches (hs_orb_set_split overrides)" },
 };
-HsKnobs read_knobs()
+} // namespace
+HsKnobs hs_read_knobs()
 {
     HsKnobs k{};
     for (const KnobRow& r : KNOBS) {
@@ -352,6 +362,7 @@ HsKnobs read_knobs()
     if (const char* e = getenv("HS_PYRAMID_PLAN")) { k.pyr_plan_set = true; k.pyr_plan = e; }
     return k;
 }
+namespace {
 
 // The result block of a host-pointer extraction, on the device and in pinned host memory: [counts | keypoints | descriptors] of `batch` images
 // of `cap` entries and, for a stereo ticket, [uRight | depth] of `pairs` left images.  Every piece starts on a multiple of 256 bytes.
@@ -405,11 +416,7 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     // split); a 1080p pair gets SLOWER (0.132 -> 0.160 ms: the fork / join between the streams costs more than the overlap saves), 16 pairs too
     // (-7 %), hence the size rule.  Not with stage events (they would serialise the two sequences).  The two concurrent FAST launches rely on every
     // earlier launch of the handle having completed: a handle is driven from ONE stream at a time (include/hyslam_amd.h).
-    // Item width by batch (round 4): a launch of few frames lasts as long as its slowest wave (one stereo pair: 1 904 wide items for 2 816
-    // resident single-wave workgroups), so it gets the NARROW items — twice as many, half as long; measured at 1080p (pairs per call: narrow / wide pairs/s): 1: 9 949 / 8 403,
-    // 2: 16 029 / 15 642, 4: 23 004 / 22 660, 8: 32 657 / 33 240, 16: 40 917 / 41 507 — from ~18 k items on the wide ones win (fewer, fuller tiles).  HS_FAST_COLS = 32 / 64 forces one list, HS_FAST_NARROW_MAX moves the threshold.
-    const int narrow_max = h->fast_knobs.narrow_max > 0 ? h->fast_knobs.narrow_max : 18000;
-    const bool narrow = g.fast_items_n > 0 && (h->fast_knobs.cols == 32 || (h->fast_knobs.cols != 64 && (long long)g.fast_items_n * batch <= narrow_max));
+    const bool narrow = hs_fast_narrow(h->knobs, g.fast_items_n, batch);      // item width by batch
     // Keys by batch as well: the FAST kernel's two global atomics per candidate cost it 5 % at 16 pairs per call (0.162 -> 0.170 ms) and buy the
     // quadtree launch 4 us there (its 256 workgroups fill the chip either way); at one pair per call they cost 1 us and buy 10 (35.1 -> 24.8 us: the
     // level-0 workgroup no longer gathers 5 000 records on one CU).  Both arrays are zero between calls whatever the mode, so the mode may change per call.
@@ -428,15 +435,15 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
     const std::vector<HsLevel>& lvh = narrow ? h->geo.lv_n : h->geo.lv;
     const HsLevel* const d_lv = h->d_lv + (narrow ? L : 0);
     const HsFastItem* const d_items = narrow ? g.d_fast_items_n.p : g.d_fast_items.p;
-    const int n_items = narrow ? g.fast_items_n : g.fast_items, lc = narrow ? 5 : 6;
+    const int n_items = narrow ? g.fast_items_n : g.fast_items;
     const int items0 = lvh[0].ngroups * lvh[0].nrows, first0 = lvh[0].item_begin;      // work items of level 0: the LAST items0 of the item list
     const bool split = !h->prof && L > 1 && items0 > 0 && items0 < n_items && (h->knobs.split_mode == 1 || (h->knobs.split_mode < 0 && batch <= 2 && (size_t)g.w * (size_t)g.h * (size_t)batch >= 6000000));
     auto fast = [&](int item_first, int item_count, int spill_slot, hipStream_t st) -> int {
         // launch N uses work-queue counter set N & 3 and relies on launch N - 2 having zeroed it: the epoch advances only when a launch was
         // enqueued without error; after a failed launch all sets are zeroed again so that the next one starts from a known state
-        const bool launched = hs_launch_fast(d_lv, d_items, L, img0, batch, g.total_cells, n_items, h->p.fast_threshold,
-                                             g.d_cand, g.d_cell_count, g.cand_img_stride, g.max_wcell, g.max_hcell, g.d_fast_ovf, h->fast_epoch, h->fast_knobs,
-                                             item_first, item_count, spill_slot, lc, use_keys ? g.d_fast_qt.p : nullptr, g.d_qhist, g.d_qbest, g.qhist_stride, g.qbest_stride, st);
+        const HsFastLaunch plan = hs_fast_launch_plan(h->knobs, g.max_hcell, g.fast_items, g.fast_items_n, batch, item_first, item_count, spill_slot);
+        const bool launched = hs_launch_fast(plan, d_items, img0, h->p.fast_threshold, g.d_cand, g.d_cell_count, g.cand_img_stride, g.total_cells, g.d_fast_ovf, h->fast_epoch,
+                                             use_keys ? g.d_fast_qt.p : nullptr, g.d_qhist, g.d_qbest, g.qhist_stride, g.qbest_stride, st);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             (void)hipDeviceSynchronize();
@@ -678,8 +685,7 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev) return HS_ERR_NO_DEVICE;
     hs_orb* h = new hs_orb();
     h->p = *p; h->device = device;
-    h->fast_knobs = hs_fast_read_knobs();
-    h->knobs = read_knobs();
+    h->knobs = hs_read_knobs();
     bool zero = true; for (int k = 0; k < 7; k++) zero = zero && p->blur_taps[k] == 0;
     static const uint16_t def[7] = { 18, 34, 49, 55, 49, 34, 18 };
     for (int k = 0; k < 7; k++) h->taps[k] = zero ? def[k] : p->blur_taps[k];
@@ -702,7 +708,7 @@ int hs_orb_create(const hs_orb_params* p, int device, hs_orb** out)
     for (int l = 0; l < L; l++) if (h->quota[l] + 8 > HS_QT_MAX_NODES) h->qt_large = true;
     h->qt_small_ok = true;
     for (int l = 0; l < L; l++) if (h->quota[l] + 8 > hs_quadtree_small_nodes()) h->qt_small_ok = false;
-    if (!h->knobs.qt_small) h->qt_small_ok = false;      // ... and only on request (HS_QT_SMALL, see read_knobs)
+    if (!h->knobs.qt_small) h->qt_small_ok = false;      // ... and only on request (HS_QT_SMALL, see hs_read_knobs)
 
     if (hipSetDevice(device) != hipSuccess) { delete h; return HS_ERR_NO_DEVICE; }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||

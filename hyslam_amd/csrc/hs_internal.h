@@ -70,36 +70,6 @@ struct HsLevel {
     int32_t _r1;
 };
 
-// One work item of the FAST kernel (kernels_fast.hip): `ncell` horizontally adjacent cells of one cell row.  Everything that does not
-// depend on the image index is precomputed on the host, so a wave fetches an item's geometry with a single 64-byte scalar load.
-struct HsFastItem {
-    const uint8_t* base;           // level buffer; nullptr = level 0 (the caller's frame, HsImg0)
-    uint64_t img_stride;           // bytes between images of the level buffer
-    int32_t pitch;                 // row pitch of the level buffer (level 0: HsImg0::row_stride)
-    int32_t gcell0;                // HsLevel::cell_begin + c0: first entry of the item in cell_count
-    int32_t c0;                    // cell index (row-major within the level) of the item's first cell
-    uint32_t slot0;                // HsLevel::cand_off + c0 * ccap: the first cell's slots in the candidate arrays
-    int32_t ccap;                  // slots per cell
-    int32_t inv_w, inv_w1;         // ceil(65536 / wcell), ceil(65536 / (wcell + 1))
-    uint16_t iniY, a0;             // first tile row; first tile column rounded down to a dword
-    uint16_t th, iw;               // tile rows (0: the item yields nothing), interior width
-    uint8_t off, ndw, ncell, level;// tile column of x is off + (x - iniX); dwords per tile row
-    uint16_t xoff, yoff;           // j0 * wCell, i * hCell (ORBExtractor.cpp:463-464)
-    uint32_t _pad;
-};
-static_assert(sizeof(HsFastItem) == 64, "HsFastItem is fetched as one 64-byte record");
-
-// Per-level record of the FAST kernel's key computation (one 32-byte scalar load per work item): u16 tables with the x part of a candidate's
-// geometric key per pixel column — root << 2 DH | the column's cell index at depth DH with its bits spread to the even positions — and the y part
-// per pixel row (bits spread to the odd positions), so that key = xkey[x] | ykey[y] (k_quadtree's geo_key, kernels_quadtree.hip); both padded
-// by 512 entries so that a work item's slice can be fetched without clamping.
-struct HsFastQt { const uint16_t* xkey; const uint16_t* ykey; uint32_t hist_off, best_off; int32_t enabled, _r; };
-static_assert(sizeof(HsFastQt) == 32, "scalar-load record");
-
-// candidate slots per FAST cell: 3x3 NMS leaves at most one survivor per 2x2 block; rounded to 4 so that a cell's records start on
-// a 16-byte boundary (cand_off is a multiple of 4 entries)
-__host__ __device__ inline int hs_cell_cap(int wcell, int hcell) { return ((((wcell + 1) >> 1) * ((hcell + 1) >> 1)) + 3) & ~3; }
-
 struct HsImg0 {                    // level 0 = the caller's frames; images [0,split) from base, the rest from base2
     const uint8_t* base;           // (left / right frames of a stereo batch go through one launch sequence)
     const uint8_t* base2;
@@ -139,6 +109,17 @@ template <typename T> __device__ __forceinline__ T hs_gload_off(const uint8_t* u
     return *(const HS_GLOBAL T*)((const HS_GLOBAL uint8_t*)(uintptr_t)uniform_base + lane_off);
 }
 template <typename T> __device__ __forceinline__ void hs_gstore(void* p, T v) { *(HS_GLOBAL T*)(uintptr_t)p = v; }
+// inclusive prefix sum over the 64 lanes of a wave (DPP row shifts + row broadcasts: six VALU adds, no LDS)
+__device__ __forceinline__ int wave_scan_incl(int x)
+{
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);      // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);      // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);      // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);      // row_shr:8   -> inclusive within each row of 16
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);     // row_bcast:15 into rows 1 and 3
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);     // row_bcast:31 into rows 2 and 3
+    return x;
+}
 
 struct HsOut {                     // extractor outputs, split the same way
     hs_keypoint* kps; uint8_t* desc; int32_t* n;
@@ -148,6 +129,7 @@ struct HsOut {                     // extractor outputs, split the same way
 };
 
 #include "hs_pyramid.h"             // the image pyramid: its records, limits, planners' interface and launch function
+#include "hs_fast.h"                // the FAST stage: its records, limits, work-unit schedule, planner's interface and launch function
 
 #define HS_STRIP_ENTRY_BYTES 16
 #define HS_STRIP_SHIFT 5           // right keypoints are binned into strips of 32 rows (kernels_stereo.hip)
@@ -164,24 +146,6 @@ struct HsStripFuse { int32_t enabled, n_rows, n_strips, _r; float size_ref; int3
 inline int hs_stereo_strips(int n_rows) { return (n_rows > 0 ? ((n_rows - 1) >> 5) : 0) + 1; }
 
 // kernels_*.hip launchers (all asynchronous on `s`)
-int hs_fast_group_cells(int wcell, int ncols, int lc);   // cells per FAST work item for a level (0 when the level has no cells); lc = 6 / 5: wide / narrow tiles
-int hs_fast_max_cell_w(int lc);                          // widest FAST cell the kernel's tile holds at any offset (247 px wide tiles, 119 px narrow ones)
-void hs_fast_build_items(const HsLevel* h_lv, int nlevels, HsFastItem* out /*[sum ngroups*nrows]*/);
-bool hs_fast_item_fits(const HsFastItem& it, int lc);    // the item against the tile k_fast_rows<lc, ...> stages it into
-#define HS_FAST_NQ_MAX 32          // work queues of the FAST kernel: 8, 16 or 32 (kernels_fast.hip: FastSched)
-#define HS_FAST_QUEUE_DWORDS (32 * HS_FAST_NQ_MAX)   // head of the FAST overflow buffer: FOUR rotating sets of up to 32 work-queue counters on 128-byte lines of their own
-struct HsFastKnobs { int pcap, small_lists, wg_per_cu, force_scan_b, image_major, nq, cols, narrow_max, no_fold, list_min; };   // HS_FAST_* test / tuning knobs, read once per handle
-HsFastKnobs hs_fast_read_knobs();
-bool hs_launch_fast(const HsLevel* d_lv, const HsFastItem* d_items, int nlevels, HsImg0 img0, int batch, int total_cells, int items_per_img, int fast_th,
-                    uint2* cand /*{y<<16|x, score<<24|cell} per slot*/, int32_t* cell_count, uint64_t cand_img_stride,
-                    int max_wcell, int max_hcell, uint32_t* overflow /*hs_fast_overflow_bytes(), zero-initialised*/, uint32_t epoch /*launch counter of the handle*/,
-                    const HsFastKnobs& knobs, int item_first, int item_count /*the launch covers items [first, first + count) of every image*/,
-                    int spill_slot /*0 / 1: which half of the spill areas (two launches may be in flight)*/, int lc /*6 / 5: the tile width `d_items` was built for*/,
-                    const HsFastQt* d_qt /*[nlevels]; nullptr: no keys*/, uint32_t* qhist, unsigned long long* qbest, uint32_t qhist_img_stride, uint32_t qbest_img_stride, hipStream_t s);
-size_t hs_fast_overflow_bytes(int max_hcell, int total_work_max, const HsFastKnobs& knobs);   // per-wave spill areas of the FAST kernel for launches over <= total_work_max items
-// host side of the geometric-key tables: appends level `V`'s tables to `blob` (16-byte granules) and returns their offsets; false = the level does
-// not use them (more than 8 roots or a level wider than the tables)
-bool hs_quadtree_build_tables(HsLevel& V, std::vector<uint8_t>& blob, size_t& xoff, size_t& yoff);
 void hs_launch_quadtree(const HsLevel* d_lv, int nlevels, int batch, int total_cells,
                         const uint2* cand, const int32_t* cell_count, uint64_t cand_img_stride,
                         uint32_t* pts_xy, uint32_t* pts_sk, uint16_t* pt_node, int32_t* cand_count,

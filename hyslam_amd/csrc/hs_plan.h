@@ -1,24 +1,25 @@
-// hs_plan.h — the extractor's configuration as a pure host computation (hs_plan.hip, the pyramid's part in hs_plan_pyramid.hip): everything hs_orb_reserve decides for one frame size,
+// hs_plan.h — the extractor's configuration as a pure host computation (hs_plan.hip, the pyramid's part in hs_plan_pyramid.hip, the FAST stage's in hs_plan_fast.hip): everything hs_orb_reserve decides for one frame size,
 // without a HIP call and without the handle.  hs_api.hip allocates from the plan's sizes, uploads its arrays and turns its offsets into pointers.
 #pragma once
 #include "hs_internal.h"
 
-// The handle's tuning / parity-test knobs of the environment, read ONCE per handle by read_knobs (hs_api.hip: the table of names, defaults and
-// meanings is there; INTEGRATION.md lists them for users).  Flags are 0 / 1.  HsFastKnobs (kernels_fast.hip) and HS_PYRAMID_NW8
-// (kernels_pyramid.hip) are read where they are used.
+// The handle's tuning / parity-test knobs of the environment, read ONCE per handle by hs_read_knobs (hs_api.hip: the table of names, defaults and
+// meanings is there; INTEGRATION.md lists them for users).  Flags are 0 / 1.  HS_PYRAMID_NW8 (kernels_pyramid.hip) is read where it is used.
 struct HsKnobs {
     int no_fuse, stereo_fuse, fast_keys, fast_keys_levels, fast_keys_max_batch, fast_order;
+    int fast_pcap, fast_list_min, fast_small_lists, fast_wg_per_cu, fast_scan_b, fast_image_major, fast_nq, fast_cols, fast_narrow_max, fast_no_fold;   // the FAST launch plan's (hs_plan_fast.hip)
     int chain_mode, pyr_chain2, pyr_tbx_max, deep_max_batch, deep_rows;
     int qt_point_domain, qt_small, split_mode;
     bool pyr_plan_set = false;         // HS_PYRAMID_PLAN is in the environment (an empty string is a plan too: no chain at all)
     std::string pyr_plan;
 };
+HsKnobs hs_read_knobs();              // hs_api.hip: every row of the table from the environment
 
 // What the plan is made from: the extractor's parameters, its constructor tables (ORBExtractor.cpp:86-118), the knobs and the frame size.
 struct HsPlanInput {
     const hs_orb_params* p;
     const float* inv_scale; const float* scale; const int* quota;      // [nlevels]
-    const HsKnobs* knobs; const HsFastKnobs* fast_knobs;
+    const HsKnobs* knobs;
     bool qt_large;
     int w, h;
 };
@@ -61,6 +62,8 @@ struct HsPlan {
 int hs_plan_geometry(const HsPlanInput& in, HsPlan& out, std::string& err);
 // its pyramid step (hs_plan_pyramid.hip), after the levels and the resize tables: the fused pairs, the chains, the small-batch plan and their records
 void hs_plan_pyramid(const HsKnobs& k, HsPlan& P);
+// its last step (hs_plan_fast.hip): the order of an image's FAST work items and both item lists; nullptr, or the text of the refusal (HS_ERR_INVALID)
+const char* hs_plan_fast_items(const HsKnobs& k, HsPlan& P);
 // FNV-1a-style 64-bit hash (xor, multiply by the FNV prime; 8-byte words where possible) over the plan, field by field in the order stated at its definition: equal digests <=> the kernels get the same tables,
 // records and launch geometry
 uint64_t hs_plan_digest(const HsPlan& P);

@@ -1,6 +1,6 @@
 // hs_plan.hip — the extractor's configuration for one frame size as a pure host computation (HsPlan, hs_plan.h): level sizes and cell grid,
 // cv::resize's fixed-point tables, the quadtree's key tables, the pyramid's fusion / chain / small-batch plans (hs_plan_pyramid.hip), both FAST
-// work-item lists and every per-image size.  No HIP call, no handle: pointer fields hold byte offsets until hs_api.hip has allocated the buffers they point into.
+// work-item lists (hs_plan_fast.hip) and every per-image size.  No HIP call, no handle: pointer fields hold byte offsets until hs_api.hip has allocated the buffers they point into.
 #include "hs_plan.h"
 #include <cmath>
 #include <cstdlib>
@@ -110,20 +110,41 @@ void plan_resize_tables(HsPlan& P)
     }
 }
 
-// Order of the FAST work items of an image: the REDUCED levels first, deepest level first, level 0 last.  An item of a reduced level
-// costs 2-3 times an item of level 0 (the same number of pixels, denser corners), and the persistent FAST kernel walks the items in this
-// order: with the cheap, uniform level-0 items at the end of every queue the tail of the launch — waves finishing their last item while
-// the queues are empty — is short (a 32-frame launch spent ~17 % more per frame than a 128-frame launch with the expensive items last).
-int order_items(std::vector<HsLevel>& lv, int fast_order)
+// Host side of the quadtree kernel's geometric-key tables (see k_quadtree): the expressions of the kernel's former in-kernel build, evaluated once
+// per plan.  Appends level `V`'s tables to `blob` (16-byte granules) and returns their offsets; false = the level does not use them (more than 8 roots
+// or a level wider than the tables).  This file is compiled with -ffp-contract=off and IEEE division, like the device code, so the floats agree.
+bool quadtree_build_tables(HsLevel& V, std::vector<uint8_t>& blob, size_t& xoff, size_t& yoff)
 {
-    const int L = (int)lv.size();
-    int pos = 0;
-    if (fast_order == 0) { for (int l = 0; l < L; l++) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; } }
-    else {
-        for (int l = L - 1; l >= 1; l--) { lv[l].item_begin = pos; pos += lv[l].ngroups * lv[l].nrows; }
-        lv[0].item_begin = pos; pos += lv[0].ngroups * lv[0].nrows;
+    V.qt_xtab = V.qt_ytab = nullptr;
+    for (int i = 0; i < 8; i++) V.qt_rbound[i] = 0;
+    const int nIni = V.n_ini;
+    if (nIni < 1 || nIni > 8 || V.qt_w <= 0 || V.qt_h <= 0 || V.qt_w >= 8192 - 16 || V.qt_h >= 4096 - 16) return false;
+    const float hX = V.hx;
+    const int DH = nIni <= 2 ? 6 : 5;
+    auto root_of = [&](int x) { return std::min((int)((float)x / hX), nIni - 1); };
+    auto descend = [&](int x, int x0, int x1) {
+        int idx = 0;
+        for (int d = 0; d < DH; d++) {
+            const int mx = x0 + ((x1 - x0 + 1) >> 1);
+            if (x < mx) { x1 = mx; idx = 2 * idx; } else { x0 = mx; idx = 2 * idx + 1; }
+        }
+        return idx;
+    };
+    for (int r = 1; r < nIni; r++) {                                 // smallest x that lands in root r: around r * hX
+        int bnd = (int)(hX * (float)r);
+        while (bnd > 0 && root_of(bnd - 1) >= r) bnd--;
+        while (root_of(bnd) < r) bnd++;
+        V.qt_rbound[r] = bnd;
     }
-    return pos;
+    auto grow = [&](size_t n) { const size_t o = (blob.size() + 15) & ~(size_t)15; blob.resize(o + ((n + 15) & ~(size_t)15), 0); return o; };
+    xoff = grow((size_t)V.qt_w + 1);
+    for (int x = 0; x <= V.qt_w; x++) {
+        const int r = root_of(x);
+        blob[xoff + x] = (uint8_t)descend(x, (int16_t)(int)(hX * (float)r), (int16_t)(int)(hX * (float)(r + 1)));
+    }
+    yoff = grow((size_t)V.qt_h + 1);
+    for (int y = 0; y <= V.qt_h; y++) blob[yoff + y] = (uint8_t)descend(y, 0, (int16_t)V.qt_h);
+    return true;
 }
 
 // Geometric-key tables of the quadtree kernel, and the FAST kernel's side of the same keys (HsFastQt): u16 tables
@@ -135,7 +156,7 @@ void plan_quadtree_keys(const HsKnobs& k, HsPlan& P)
     std::vector<uint8_t>& qblob = P.qt_tabs;
     std::vector<size_t> xo(L, 0), yo2(L, 0); std::vector<char> has(L, 0);
     for (int l = 0; l < L; l++) {
-        has[l] = hs_quadtree_build_tables(P.lv[l], qblob, xo[l], yo2[l]) ? 1 : 0;
+        has[l] = quadtree_build_tables(P.lv[l], qblob, xo[l], yo2[l]) ? 1 : 0;
         if (has[l]) { P.lv[l].qt_xtab = at_offset<uint8_t>(xo[l]); P.lv[l].qt_ytab = at_offset<uint8_t>(yo2[l]); }
     }
     auto spread = [](uint32_t v) { v = (v | (v << 4)) & 0x0F0Fu; v = (v | (v << 2)) & 0x3333u; v = (v | (v << 1)) & 0x5555u; return v; };
@@ -166,47 +187,6 @@ void plan_quadtree_keys(const HsKnobs& k, HsPlan& P)
     P.qhist_stride = hoff; P.qbest_stride = boff;
 }
 
-// Both FAST work-item lists.  The narrow list: the same levels with NARROW work items (tiles of 32 dwords: <= 119 px of interior per item), for
-// the launches of small batches: it differs in the grouping of the cells only, so everything downstream of the FAST kernel (the quadtree's
-// gather) reads the grouping it was launched with from ITS copy of the level array (lv_n).  Built last: hs_fast_build_items copies
-// HsLevel::base (here: the level's offset), and the narrow levels are a copy of the finished wide ones.
-Refusal plan_fast_items(const HsKnobs& k, const HsFastKnobs& fk, HsPlan& P)
-{
-    const int L = (int)P.lv.size();
-    P.lv_n = P.lv;
-    bool narrow_ok = fk.cols != 64;
-    for (int l = 0; l < L; l++) if (P.lv[l].wcell > hs_fast_max_cell_w(5)) narrow_ok = false;
-    if (narrow_ok) {
-        for (int l = 0; l < L; l++) {
-            HsLevel& V = P.lv_n[l];
-            V.grp_cells = hs_fast_group_cells(V.wcell, V.ncols, 5);
-            V.ngroups = V.grp_cells > 0 ? (V.ncols + V.grp_cells - 1) / V.grp_cells : 0;
-        }
-        P.fast_items_n = order_items(P.lv_n, k.fast_order);
-    }
-    bool items_fit = true;                                 // every item against the tile the kernel stages it into (hs_fast_item_fits: columns, score-tile column, cells)
-    auto build = [&](const std::vector<HsLevel>& lv, int n_items, std::vector<HsFastItem>& fi, int lc) {
-        fi.assign(std::max(n_items, 1), HsFastItem{});
-        hs_fast_build_items(lv.data(), L, fi.data());
-        for (int i = 0; i < n_items; i++) items_fit = items_fit && hs_fast_item_fits(fi[i], lc);
-        if (k.fast_order == 2 && L > 2) {                  // experiment: the reduced levels interleaved in proportion (every stretch of the list has the same mix of levels), level 0 last
-            const int n_red = lv[0].item_begin;
-            std::vector<std::pair<double, int>> key(n_red);
-            for (int l = 1; l < L; l++) {
-                const int n = lv[l].ngroups * lv[l].nrows;
-                for (int j = 0; j < n; j++) key[lv[l].item_begin + j] = { (j + 0.5) / n, lv[l].item_begin + j };
-            }
-            std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
-            std::vector<HsFastItem> t(fi.begin(), fi.begin() + n_red);
-            for (int i = 0; i < n_red; i++) fi[i] = t[key[i].second];
-        }
-    };
-    build(P.lv, P.fast_items, P.items, 6);
-    if (P.fast_items_n > 0) build(P.lv_n, P.fast_items_n, P.items_n, 5);
-    if (!items_fit) return { HS_ERR_INVALID, "internal: a FAST work item does not fit its tile (hs_fast_group_cells); geometry refused" };
-    return OK;
-}
-
 struct Fnv {
     uint64_t v = 0xcbf29ce484222325ull;
     // FNV-1a's xor-then-multiply step, over 8-byte words where there are that many and over bytes for the rest: one multiply per word keeps the
@@ -235,7 +215,7 @@ void hash_level(Fnv& H, const HsLevel& V)          // every field in declaration
 }
 
 // the records below are hashed as bytes: no padding (the sizes are the sums of their fields), and every one starts from a zero-initialised
-// record (HsFastQt{}, HsPyrFuse{}, HsPyrChain{} by the planners, memset in hs_fast_build_items)
+// record (HsFastQt{}, HsPyrFuse{}, HsPyrChain{} by the planners, memset in hs_plan_fast.hip's build_items)
 static_assert(sizeof(HsFastQt) == 32 && sizeof(HsPyrFuse) == 152 && sizeof(HsPyrStage) == 64 && sizeof(HsPyrChain) == 56 + 64 * HS_PYR_CHAIN_MAX && sizeof(HsFastItem) == 64,
               "hs_plan_digest hashes these records as bytes: a record that gains padding must be hashed field by field");
 
@@ -247,10 +227,9 @@ int hs_plan_geometry(const HsPlanInput& in, HsPlan& P, std::string& err)
     Refusal r = plan_levels(in, P);
     if (r.code == HS_OK) {
         plan_resize_tables(P);
-        order_items(P.lv, in.knobs->fast_order);
         plan_quadtree_keys(*in.knobs, P);
         hs_plan_pyramid(*in.knobs, P);
-        r = plan_fast_items(*in.knobs, *in.fast_knobs, P);      // last: the items and the narrow levels copy what the steps above left in the levels
+        if (const char* why = hs_plan_fast_items(*in.knobs, P)) r = { HS_ERR_INVALID, why };      // last: the items and the narrow levels copy what the steps above left in the levels
     }
     if (r.code != HS_OK) { err = r.text; return r.code; }
     P.digest = hs_plan_digest(P);

@@ -30,7 +30,7 @@
 // The list has a fixed capacity; when a block would overflow it the scan runs the corner passes on what it has and spills the scored
 // corners to a per-wave area in global memory; they come back into the score tile before the NMS, which then walks the non-zero
 // bytes of the tile instead of the list.  Saturated images stay correct and merely lose batching.  Work distribution, geometry table
-// and LDS budget: see the kernel and its launcher.
+// and LDS budget: see the kernel, hs_fast.h (the schedule) and hs_plan_fast.hip (the launch plan).
 // Output: each ITEM owns a fixed slot range (the slots of its cells, contiguous; no global atomics), filled from its first slot upwards in NO
 // particular order — every order-dependent decision downstream uses the (cell, y, x) key of the reference's candidate order:
 //   cand[slot] = { y<<16 | x,  score<<24 | cell }   (coordinates relative to (16,16), as in vToDistributeKeys; cell = row-major cell index
@@ -45,9 +45,6 @@
 // unaligned ds_read_b64 per ring 2 250 ns against 17 ds_read_u8 600 ns per wave-iteration at 12 waves per CU), and aligned chunks need two reads + a
 // per-lane byte shift per ring row.  HBM bytes = P per frame, read once (measured 1.05-1.06 x).
 #include "hs_internal.h"
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 // The workgroup is one wave: its LDS operations execute in program order, so a hand-off through LDS only needs the LDS queue
 // drained (no s_barrier, and no vmcnt wait that would expose the latency of the next item's prefetch).
@@ -140,11 +137,6 @@ __device__ __forceinline__ uint32_t fr_field_flags(us2 s, uint32_t ones)
     return r;
 }
 
-// LDS of a workgroup: [0, th * PITCH) the item's pixel tile (later its score tile) | the pixel list of THIS item — 2 bytes of position + 1 byte of score per
-// entry, as many entries as fit before the counters: an item of fewer rows than the tallest one of the launch has the longer list (round 5) | [off_cnt, total)
-// the per-cell counters.  pcap_max: tuning / test cap on the list length (HS_FAST_PCAP, HS_FAST_TEST_SMALL_LISTS).
-struct FastRowsLds { int32_t off_cnt, pcap_max, pcap_min, total; };
-
 struct RowGeom {            // wave-uniform description of one work item in one image
     int img;
     int ncell, c0, gcell0;  // cells in this item, cell index of its first cell (within the level / within the image)
@@ -159,68 +151,6 @@ struct RowGeom {            // wave-uniform description of one work item in one 
     int level;
 };
 
-// How the work units of a launch are spread over the work queues (host: fast_sched()).  The item list of an image is ordered expensive items
-// first (the reduced levels, deepest first; level 0 last: hs_api.hip); a queue hands out its units in order, so its LAST units should be cheap —
-// every wave still holds its current and its pre-grabbed next item when the queue runs dry, and with heavy items among them the launch ended with
-// a third of its time spent draining (63 of 192 us at 32 frames; `tools/fast_wave_timeline.py`).  And there should be MANY queues: a queue is
-// one counter, a counter serves same-address atomics one after the other, and with 8 of them for 30 000 items the grabs themselves were late
-// (8 -> 32 queues: 0.175 -> 0.158 ms per 32 frames).
-//   mode 1  the batch is a multiple of the queue count: a queue owns `par` whole images and walks them ITEM-major (item 0 of its images, item 1,
-//           ...): its expensive items all go out early, its last units are the level-0 items of all its images
-//   mode 2  the queue count is a multiple of the batch: an image is dealt round-robin to `par` queues (item i -> queue i % par), every one of
-//           which sees the same mix of levels in the same order
-//   mode 3  anything else: the item-major list of ALL images (item 0 of every image, item 1, ...) dealt round-robin to the queues
-//   mode 0  contiguous ranges of the image-major order (HS_FAST_IMAGE_MAJOR=1: the scheme until the end of round 3, kept as a parity variant)
-//   mode 4  FOLDED STATIC schedule for small launches (at most two units per workgroup; round 4): workgroup b takes unit b of the item-major
-//           list of all images and then unit 2 * grid - 1 - b — the list is ordered expensive first, so the workgroups whose first item is the
-//           cheapest get the (cheap) second items and the heaviest items run alone; no counter, no look-ahead grab.  At one stereo pair per
-//           call the launch lasts as long as its slowest wave: with the look-ahead of the work queues the waves that started on the HEAVIEST
-//           items were the first to grab a second one (`tools/fast_b1_timeline.py`: 28.8 us span, the slowest waves all "level 7 + another")
-struct FastSched { int32_t nq_log, mode, par, par_log, per_q; uint32_t m_per_q, m_par, m_items; };     // m_x = ceil(2^32 / x): fast_div()
-// floor(a / d) for 0 <= a < 2^31 and d >= 1 with m = ceil(2^32 / d): the high product is floor(a / d) or one more (its error a * (m * d - 2^32) / (d * 2^32)
-// is below a / 2^32 < 1/2), one compare corrects it.  Wave-uniform operands: two scalar multiplies instead of the ~20-instruction v_rcp_iflag sequence
-// of an integer division, twice per work item on the critical path of every wave.
-__device__ __forceinline__ int fast_div(int a, int d, uint32_t m)
-{
-    int q = (int)__umulhi((uint32_t)a, m);
-    if (d == 1) q = a;                                          // (ceil(2^32 / 1) does not fit 32 bits)
-    if (q * d > a) q--;
-    return q;
-}
-__device__ __forceinline__ int fast_queue_size(const FastSched& S, int qq, int total_work, int items_per_img)
-{
-    if (S.mode == 1) return S.per_q;
-    if (S.mode == 2) return (items_per_img - (qq & (S.par - 1)) + S.par - 1) >> S.par_log;
-    if (S.mode == 3) return (total_work - qq + (1 << S.nq_log) - 1) >> S.nq_log;
-    return min(max(total_work - qq * S.per_q, 0), S.per_q);
-}
-// work unit w -> (item of the launch's item list, image)
-__device__ __forceinline__ int unit_decode(int items_per_img, const FastSched& S, int w, int* img)
-{
-    struct { int img; } g;
-    int item;
-    if (S.mode == 1) {
-        const int q = fast_div(w, S.per_q, S.m_per_q), u = w - q * S.per_q;
-        item = fast_div(u, S.par, S.m_par);
-        g.img = q * S.par + (u - item * S.par);
-    } else if (S.mode == 2) {
-        const int q = fast_div(w, S.per_q, S.m_per_q), u = w - q * S.per_q;
-        g.img = q >> S.par_log;
-        item = (u << S.par_log) + (q & (S.par - 1));
-    } else if (S.mode == 3) {
-        const int q = fast_div(w, S.per_q, S.m_per_q), u = w - q * S.per_q, gidx = (u << S.nq_log) + q;      // position in the item-major list of all S.par images
-        item = fast_div(gidx, S.par, S.m_par);
-        g.img = gidx - item * S.par;
-    } else if (S.mode == 4) {
-        item = fast_div(w, S.par, S.m_par);                          // w = position in the item-major list of all S.par images
-        g.img = w - item * S.par;
-    } else {
-        g.img = fast_div(w, items_per_img, S.m_items);
-        item = w - g.img * items_per_img;
-    }
-    *img = g.img;
-    return item;
-}
 // An item's record as ONE 64-byte scalar load.  Read field by field (`items[i]`) the compiler fetches the dword-sized fields with scalar loads and the
 // byte / half-word ones (off, ndw, ...) with a VECTOR load whose round trip through L2 the wave then waits for — once per work item, on its critical path.
 typedef uint32_t hs_u32x16 __attribute__((ext_vector_type(16)));
@@ -255,10 +185,6 @@ __device__ __forceinline__ RowGeom row_geom(const HsFastItem* __restrict__ items
 // FR_FENCE marks the hand-over points (define it as WAVE_LDS_FENCE() to wait for the LDS queue there).
 #ifndef FR_FENCE
 #define FR_FENCE() do {} while (0)
-#endif
-#define FR_MAXG 8            // cells per item (one per-cell counter each)
-#ifndef FR_PAD
-#define FR_PAD 16            // row padding of the LDS tiles, bytes (multiple of 16)
 #endif
 
 // Instruction-budget builds (tools/fast_instr_breakdown.sh): make EXTRA=-DFR_STOP=n cuts the item short after phase n — 1 scan A masks,
@@ -295,18 +221,6 @@ extern "C" void hs_debug_fast_profile(unsigned long long* out16)
 #else
 #define FR_W(i) do {} while (0)
 #endif
-
-// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts, no LDS)
-__device__ __forceinline__ int wave_scan_incl(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);      // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);      // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);      // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);      // row_shr:8   -> inclusive within each row of 16
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);     // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);     // row_bcast:31 into rows 2 and 3
-    return x;
-}
 
 // TR = tile rows held in LDS (6 + 8*RS*blocks); the item's tile (th <= TR rows) is fetched with 16-byte loads, 64/LPR rows per load
 // KEYS: the quadtree's geometric keys are produced by this launch (calls of <= 16 frames: hs_api.hip).  A template parameter, not a runtime
@@ -837,208 +751,21 @@ __global__ __launch_bounds__(64, (LC == 5 && TR <= 44 ? 4 : 1)) void k_fast_rows
 #endif
 }
 
-// Cells per work item for a level: as many as fit the tile (<= FR_MAXG), spread evenly over the row.  A tile row holds 4*COLS bytes starting at the
-// item's first column rounded DOWN to a dword (a0 = iniX & ~3: the staging loads are dword-aligned), so an item of n cells fits when
-//     (iniX & 3) + n * wcell + 6 <= 4*COLS        for every item of the row (iniX = HS_BORDER + first cell * wcell)
-// and its corners fit the score tile's 8-bit column (one spare column per cell: column = 1 + px + cell <= 255).  Round 5: the test is made with
-// the items' REAL offsets instead of the worst one (3): the standard geometry (cells of 31 px) takes 8 cells per item instead of 7 — 8 * 31 is
-// a multiple of 4, every item starts on a dword — which is 12 % fewer items per frame (861 instead of 975 at 1080p / 1.2), each scanning the
-// same 256 columns: the lanes of a scan block that hold interior pixels go from 86 % to 97 %.
-// Tile width: LC = 6 (64 dwords: the throughput shape) or LC = 5 (32 dwords, two half-waves on different rows).  A handle keeps BOTH item lists;
-// the launcher picks per call (hs_api.hip: narrow items for small batches, where the launch lasts as long as its slowest wave and twice as many,
-// half as long items are what shortens it).
-int hs_fast_max_cell_w(int lc) { return 4 * (1 << lc) - 9; }      // a single cell at the worst offset
-int hs_fast_group_cells(int wcell, int ncols, int lc)
+// The launch: everything it decides is in the record (hs_fast_launch_plan, hs_plan_fast.hip); here it only picks the instance.
+bool hs_launch_fast(const HsFastLaunch& P, const HsFastItem* d_items, HsImg0 img0, int fast_th, uint2* cand, int32_t* cell_count, uint64_t cand_img_stride, int total_cells,
+                    uint32_t* overflow, uint32_t epoch, const HsFastQt* d_qt, uint32_t* qhist, unsigned long long* qbest, uint32_t qhist_img_stride, uint32_t qbest_img_stride, hipStream_t s)
 {
-    if (wcell <= 0 || ncols <= 0) return 0;
-    const int tile_w = 4 * (1 << lc);
-    auto fits = [&](int g) {
-        if (g * wcell + g > 256) return false;                                   // score tile column 1 + px + cell of the last corner
-        for (int j0 = 0; j0 < ncols; j0 += g) {
-            const int n = std::min(g, ncols - j0);
-            if (((HS_BORDER + j0 * wcell) & 3) + n * wcell + 6 > tile_w) return false;
-        }
-        return true;
-    };
-    const int gcap = std::max(1, std::min(FR_MAXG, (tile_w - 6) / wcell));
-    for (int ngroups = (ncols + gcap - 1) / gcap; ngroups <= ncols; ngroups++) {
-        const int g = (ncols + ngroups - 1) / ngroups;                              // even spread over `ngroups` items
-        if (fits(g)) return g;
-    }
-    return 1;                                                                       // configure() rejects wcell > hs_fast_max_cell_w(6) and builds no narrow list for wcell > hs_fast_max_cell_w(5)
-}
-
-// what k_fast_rows assumes of an item: its tile row (offset + interior + 6 px of apron) inside the 4 << lc bytes of an LDS row, at most FR_MAXG cells, the last
-// corner's score-tile column (1 + px + cell) in 8 bits, at most 64 dwords per row.  Checked for every item when a geometry is configured (hs_api.hip).
-bool hs_fast_item_fits(const HsFastItem& it, int lc)
-{
-    if (it.th == 0) return true;                                                 // yields nothing; staged from (0, 0)
-    const int tile_w = 4 << lc;
-    return it.off < 4 && (int)it.off + (int)it.iw + 6 <= tile_w && (int)it.ndw * 4 <= tile_w && it.ncell >= 1 && it.ncell <= FR_MAXG && (int)it.iw + (int)it.ncell <= 256;
-}
-
-void hs_fast_build_items(const HsLevel* h_lv, int nlevels, HsFastItem* out)
-{
-    for (int l = 0; l < nlevels; l++) {
-        const HsLevel& L = h_lv[l];
-        for (int ci = 0; ci < L.nrows; ci++)
-            for (int gj = 0; gj < L.ngroups; gj++) {
-                HsFastItem& it = out[L.item_begin + ci * L.ngroups + gj];
-                memset(&it, 0, sizeof(it));
-                const int j0 = gj * L.grp_cells, ncell = std::min(L.grp_cells, L.ncols - j0);
-                const int xoff = j0 * L.wcell, yoff = ci * L.hcell;
-                const int iniX = HS_BORDER + xoff, iniY = HS_BORDER + yoff;
-                const int maxX = std::min(iniX + ncell * L.wcell + 6, L.w - HS_BORDER), maxY = std::min(iniY + L.hcell + 6, L.h - HS_BORDER);
-                const int tw = maxX - iniX, th = maxY - iniY;
-                const bool valid = tw >= 7 && th >= 7;            // reference skip rules (:435,444) / cv::FAST on < 7 rows or columns
-                const int a0 = iniX & ~3;
-                it.base = l == 0 ? nullptr : L.base; it.img_stride = L.img_stride; it.pitch = L.pitch;
-                it.c0 = ci * L.ncols + j0; it.gcell0 = L.cell_begin + it.c0;
-                it.ccap = hs_cell_cap(L.wcell, L.hcell);
-                it.slot0 = (uint32_t)(L.cand_off + (uint64_t)it.c0 * it.ccap);
-                it.inv_w = L.inv_wcell; it.inv_w1 = L.inv_wcell1;
-                it.iniY = valid ? (uint16_t)iniY : 0; it.a0 = valid ? (uint16_t)a0 : 0;   // invalid items still prefetch (harmlessly) from (0,0)
-                it.th = valid ? (uint16_t)th : 0; it.iw = valid ? (uint16_t)(tw - 6) : 0;
-                it.off = (uint8_t)(iniX - a0); it.ndw = valid ? (uint8_t)((iniX - a0 + tw + 3) >> 2) : 1;
-                it.ncell = (uint8_t)ncell; it.level = (uint8_t)l;
-                it.xoff = (uint16_t)xoff; it.yoff = (uint16_t)yoff;
-            }
-    }
-}
-
-// test / tuning knobs: read from the environment ONCE per handle (hs_orb_create), never on the launch path
-HsFastKnobs hs_fast_read_knobs()
-{
-    HsFastKnobs k{};
-    if (const char* e = getenv("HS_FAST_PCAP")) k.pcap = atoi(e);                         // tuning: cap on the list length
-    if (const char* e = getenv("HS_FAST_LIST_MIN")) k.list_min = atoi(e);                 // tuning: list entries the tallest item must keep (decides the workgroups per CU; 1024 = round 4's layout)
-    if (const char* e = getenv("HS_FAST_TEST_SMALL_LISTS")) k.small_lists = atoi(e) != 0; // parity tests: force the spill paths
-    if (const char* e = getenv("HS_FAST_WG_PER_CU")) k.wg_per_cu = atoi(e);               // tuning: workgroups per CU
-    if (const char* e = getenv("HS_FAST_TEST_SCAN_B")) k.force_scan_b = atoi(e) != 0;     // parity tests: NMS from the score tile
-    if (const char* e = getenv("HS_FAST_IMAGE_MAJOR")) k.image_major = atoi(e) != 0;      // tuning / parity tests: the work units image-major whatever the batch
-    if (const char* e = getenv("HS_FAST_NQ")) k.nq = atoi(e);                             // tuning / parity tests: at most this many work queues (8, 16, 32)
-    if (const char* e = getenv("HS_FAST_COLS")) k.cols = atoi(e);                         // tuning / parity tests: 32 / 64 = narrow / wide items whatever the batch (default: by batch)
-    if (const char* e = getenv("HS_FAST_NARROW_MAX")) k.narrow_max = atoi(e);             // tuning: narrow items for launches of at most this many (narrow) work items
-    if (const char* e = getenv("HS_FAST_NO_FOLD")) k.no_fold = atoi(e) != 0;              // tuning / parity tests: work queues even for launches of <= 2 units per workgroup
-    return k;
-}
-
-// launch configuration shared by the launcher and by hs_fast_overflow_bytes()
-struct FastRowsCfg { int lc, tr, per_cu; uint32_t ovf_stride; FastRowsLds lds; };
-static FastRowsCfg fast_rows_cfg(int max_hcell, const HsFastKnobs& knobs, int lc)
-{
-    FastRowsCfg c;
-    c.lc = lc;
-    const int cols = 1 << c.lc, pitch = 4 * cols + FR_PAD;
-    // Tile rows = the tallest tile of the launch (template instances below).
-    const int th_max = max_hcell + 6;
-    c.tr = th_max <= 38 ? 38 : th_max <= 40 ? 40 : th_max <= 44 ? 44 : th_max <= 54 ? 54 : th_max <= 70 ? 70 : th_max <= 102 ? 102 : 134;
-    FastRowsLds& L = c.lds;
-    // LDS is granted in 1280-byte granules on gfx950 (160 KB / 128), and a persistent grid sized for more workgroups per CU than really fit runs its
-    // surplus in a second round (measured: +25 % kernel time).  The kernel is latency-bound — measured at 6 / 8 / 11 workgroups per CU (wide items, 128
-    // frames): 0.801 / 0.661 / 0.546 ms = 0.240 + 3.37 / n — so a workgroup more per CU is worth more than a long list as long as the list of the
-    // TALLEST item keeps `min_entries` (a list of 624 instead of 1056 entries cost 4 % at equal occupancy, one of 800 1.6 %: shorter items, whose
-    // list starts where their tile ends, keep 800-900).  Wide tiles of 40 rows: 10 granules = 12 800 bytes = 12 per CU (round 4: 14 080 = 11).
-    constexpr int GRAN = 1280, LDS_CU = 160 * 1024;
-    const int cnt_bytes = 4 * FR_MAXG;
-    const int rs = 64 / cols, blk_rows = 8 * rs;
-    const int over_rows = blk_rows * ((c.tr - 6 + blk_rows - 1) / blk_rows) + 6;      // the last scan block of a lane reads whole blocks: up to this many tile rows (the extra ones are masked out)
-    // floor: one row step of a scan block (64 lanes x 4 pixels, whatever the tile width) must fit an empty list — the scored corners leave
-    // their scores in `pscore` while the rest of the list is still being read, so the list may never run past its end
-    const int min_entries = std::max(256, knobs.list_min > 0 ? knobs.list_min : 608);
-    const int floor_bytes = std::max(c.tr * pitch + 3 * (min_entries + 16) + cnt_bytes, over_rows * pitch);
-    int granules = (floor_bytes + GRAN - 1) / GRAN;
-    while (LDS_CU / (granules * GRAN) > 16 && LDS_CU / ((granules + 1) * GRAN) >= 16) granules++;      // at most 16 workgroups per CU anyway (narrow tiles: 4 waves per SIMD by registers): the list takes the LDS that would stay unused
-    L.total = granules * GRAN;
-    L.off_cnt = L.total - cnt_bytes;
-    L.pcap_min = ((L.off_cnt - c.tr * pitch) / 3) & ~15;       // list entries of the tallest item (2 bytes position + 1 byte score each)
-    L.pcap_max = knobs.small_lists ? 256 : knobs.pcap > 0 ? std::max(256, knobs.pcap & ~15) : (1 << 20);
-    c.per_cu = std::max(1, std::min(16, LDS_CU / ((L.total + GRAN - 1) / GRAN * GRAN)));
-    if (knobs.wg_per_cu > 0) c.per_cu = std::max(1, std::min(c.per_cu, knobs.wg_per_cu));
-    c.ovf_stride = (uint32_t)((4 * cols - 6) * std::max(max_hcell, 1));       // every interior pixel of an item a corner
-    return c;
-}
-// workgroups of a launch over `total_work` items (non-decreasing in total_work)
-static int fast_rows_grid(const FastRowsCfg& c, int total_work)
-{
-    int nblk = (256 * c.per_cu) & ~(HS_FAST_NQ_MAX - 1);         // a multiple of every queue count
-    while (nblk >= 2 * HS_FAST_NQ_MAX && (nblk / 2) % HS_FAST_NQ_MAX == 0 && nblk / 2 >= total_work) nblk /= 2;   // tiny jobs: fewer idle workgroups
-    return nblk;
-}
-// queue count and unit order of a launch over `batch` images with `nblk` workgroups (see FastSched)
-static FastSched fast_sched_plan(int batch, int items_per_img, const HsFastKnobs& knobs, int nblk)
-{
-    FastSched S{};
-    if (!knobs.no_fold && !knobs.image_major && batch > 0 && (long long)items_per_img * batch <= 2LL * nblk) {
-        S.nq_log = 3; S.mode = 4; S.par = batch; S.per_q = items_per_img * batch;
-        return S;
-    }
-    int nq_log = 3;
-    const int want = knobs.nq > 0 ? knobs.nq : HS_FAST_NQ_MAX;
-    while ((2 << nq_log) <= want) nq_log++;
-    const int nq = 1 << nq_log;
-    S.nq_log = nq_log;
-    if (!knobs.image_major && batch >= nq && batch % nq == 0) { S.mode = 1; S.par = batch / nq; S.per_q = S.par * items_per_img; }
-    else if (!knobs.image_major && batch > 0 && nq % batch == 0) {
-        S.mode = 2; S.par = nq / batch;
-        while ((1 << S.par_log) < S.par) S.par_log++;
-        S.per_q = (items_per_img + S.par - 1) / S.par;
-    } else if (!knobs.image_major && batch > 0) { S.mode = 3; S.par = batch; S.per_q = (items_per_img * batch + nq - 1) / nq; }
-    else { S.mode = 0; S.per_q = (items_per_img * batch + nq - 1) / nq; }
-    return S;
-}
-static FastSched fast_sched(int batch, int items_per_img, const HsFastKnobs& knobs, int nblk)
-{
-    FastSched S = fast_sched_plan(batch, items_per_img, knobs, nblk);
-    auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };       // ceil(2^32 / d); d <= 1: unused (fast_div)
-    S.m_per_q = magic(S.per_q); S.m_par = magic(S.par); S.m_items = magic(items_per_img);
-    return S;
-}
-size_t hs_fast_overflow_bytes(int max_hcell, int total_work_max, const HsFastKnobs& knobs)
-{
-    size_t spill = 0;                                             // either tile width may be launched on this workspace
-    for (int lc = 5; lc <= 6; lc++) {
-        const FastRowsCfg c = fast_rows_cfg(max_hcell, knobs, lc);
-        spill = std::max(spill, (size_t)2 * fast_rows_grid(c, total_work_max) * c.ovf_stride * 4);      // two launches may be in flight
-    }
-    return (size_t)4 * HS_FAST_QUEUE_DWORDS * 4 + spill;
-}
-
-static bool launch_fast_rows(const HsFastItem* d_items, HsImg0 img0, int batch, int total_cells, int items_per_img, int fast_th,
-                             uint2* cand, int32_t* cell_count, uint64_t cand_img_stride,
-                             int max_wcell, int max_hcell, uint32_t* overflow, uint32_t epoch, const HsFastKnobs& knobs, int item_first, int spill_slot, int items_all, int lc_in,
-                             const HsFastQt* d_qt, uint32_t* qhist, unsigned long long* qbest, uint32_t qhist_img_stride, uint32_t qbest_img_stride, hipStream_t s)
-{
-    (void)max_wcell;
-    const FastRowsCfg c = fast_rows_cfg(max_hcell, knobs, lc_in);
-    const FastRowsLds& L = c.lds;
-    const int lc = c.lc, tr = c.tr;
-    const int total_work = items_per_img * batch;
-    if (total_work <= 0) return false;
-    const int nblk = fast_rows_grid(c, total_work);
-    const int force_scan_b = knobs.force_scan_b;
-    const FastSched S = fast_sched(batch, items_per_img, knobs, nblk);
-    const uint32_t spill_base = (uint32_t)spill_slot * (uint32_t)fast_rows_grid(c, items_all * batch) * c.ovf_stride;      // the second spill half starts after a full-size first one
-#define FR_LAUNCH_K(LC_, TR_, K_) hipLaunchKernelGGL((k_fast_rows<LC_, TR_, K_>), dim3(nblk), dim3(64), L.total, s, d_items, img0, fast_th, cand, \
-                                               cell_count, cand_img_stride, total_cells, items_per_img, total_work, L, force_scan_b, overflow, c.ovf_stride, epoch, item_first, spill_base, S, \
+    if (total_cells <= 0 || P.total_work <= 0) return false;
+#define FR_LAUNCH_K(LC_, TR_, K_) hipLaunchKernelGGL((k_fast_rows<LC_, TR_, K_>), dim3(P.nblk), dim3(64), P.lds.total, s, d_items, img0, fast_th, cand, \
+                                               cell_count, cand_img_stride, total_cells, P.items_per_img, P.total_work, P.lds, P.force_scan_b, overflow, P.ovf_stride, epoch, P.item_first, P.spill_base, P.S, \
                                                d_qt, qhist, qbest, qhist_img_stride, qbest_img_stride)
-#define FR_LAUNCH(LC_, TR_) do { if (d_qt != nullptr) FR_LAUNCH_K(LC_, TR_, true); else FR_LAUNCH_K(LC_, TR_, false); } while (0)
-    if (lc == 6) { if (tr == 38) FR_LAUNCH(6, 38); else if (tr == 40) FR_LAUNCH(6, 40); else if (tr == 44) FR_LAUNCH(6, 44); else if (tr == 54) FR_LAUNCH(6, 54); else if (tr == 70) FR_LAUNCH(6, 70); else if (tr == 102) FR_LAUNCH(6, 102); else FR_LAUNCH(6, 134); }
-    else         { if (tr == 38) FR_LAUNCH(5, 38); else if (tr == 40) FR_LAUNCH(5, 40); else if (tr == 44) FR_LAUNCH(5, 44); else if (tr == 54) FR_LAUNCH(5, 54); else if (tr == 70) FR_LAUNCH(5, 70); else if (tr == 102) FR_LAUNCH(5, 102); else FR_LAUNCH(5, 134); }
+#define FR_LAUNCH(LC_, TR_) if (P.tr == TR_) { if (d_qt != nullptr) FR_LAUNCH_K(LC_, TR_, true); else FR_LAUNCH_K(LC_, TR_, false); }
+#define FR_WIDE(TR_) FR_LAUNCH(6, TR_)
+#define FR_NARROW(TR_) FR_LAUNCH(5, TR_)
+    if (P.lc == 6) { HS_FAST_TILE_ROWS(FR_WIDE) } else { HS_FAST_TILE_ROWS(FR_NARROW) }
+#undef FR_NARROW
+#undef FR_WIDE
 #undef FR_LAUNCH
 #undef FR_LAUNCH_K
     return true;
-}
-
-// returns whether a kernel was enqueued: a launch consumes one work-queue counter set (`epoch` & 1) and zeroes it for the launch after next,
-// so the caller advances its epoch only for launches that happened
-bool hs_launch_fast(const HsLevel* d_lv, const HsFastItem* d_items, int nlevels, HsImg0 img0, int batch, int total_cells, int items_per_img, int fast_th,
-                    uint2* cand, int32_t* cell_count, uint64_t cand_img_stride,
-                    int max_wcell, int max_hcell, uint32_t* overflow, uint32_t epoch, const HsFastKnobs& knobs, int item_first, int item_count, int spill_slot, int lc,
-                    const HsFastQt* d_qt, uint32_t* qhist, unsigned long long* qbest, uint32_t qhist_img_stride, uint32_t qbest_img_stride, hipStream_t s)
-{
-    (void)d_lv; (void)nlevels;
-    if (total_cells <= 0 || item_count <= 0) return false;
-    return launch_fast_rows(d_items, img0, batch, total_cells, item_count, fast_th, cand, cell_count, cand_img_stride, max_wcell, max_hcell, overflow, epoch, knobs,
-                            item_first, spill_slot, items_per_img, lc, d_qt, qhist, qbest, qhist_img_stride, qbest_img_stride, s);
 }

@@ -63,17 +63,6 @@ struct QtNodes {                 // a view of buffer `c`
     int16_t *x0, *x1, *y0, *y1; uint32_t* cnt; uint16_t* ekey;
 };
 
-// inclusive scan over the wavefront with DPP row shifts / row broadcasts (six VALU adds, no LDS crossbar round trips)
-__device__ __forceinline__ int wave_scan_incl(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);      // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);      // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);      // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);      // row_shr:8   -> inclusive within each row of 16
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);     // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);     // row_bcast:31 into rows 2 and 3
-    return x;
-}
 __device__ __forceinline__ int wave_sum(int x) { return __builtin_amdgcn_readlane(wave_scan_incl(x), 63); }
 
 // exclusive scan of one int per thread over the 1024-thread block; returns prefix, writes total.  s_wave holds TWO sets of per-wave sums
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
     static_assert(sizeof(s_idx3) >= 8192 + 4096, "geometric-key tables");
     const bool use_tab = cf_geom && L.qt_xtab != nullptr;              // (qt_w < 8192 - 16 and qt_h < 4096 - 16: the host's condition)
     auto root_of = [&](int x) { return min((int)((float)x / hX), nIni - 1); };      // vpIniNodes[kp.pt.x/hX]
-    // the tables depend on the level geometry alone: the host builds them once per configuration (hs_quadtree_build_tables: the same
+    // the tables depend on the level geometry alone: the host builds them once per configuration (hs_plan.hip, quadtree_build_tables: the same
     // expressions, IEEE float division and multiplication), the workgroup copies them with 16-byte loads when it needs them — i.e. when it
     // gathers the candidates (round 4: normally it does not, see `have_keys` below).  They live in LDS that is idle then (s_idx3).
     auto load_key_tables = [&]() {
@@ -1010,18 +999,13 @@ void hs_launch_quadtree(const HsLevel* d_lv, int nlevels, int batch, int total_c
     dim3 grid(level_count, batch, 1);
     // more workgroups than CUs and every list fits the small instance: two workgroups per CU (77 KB of LDS each) instead of rounds of 256
     const bool small = list_mode == 1 && (long long)level_count * batch > 256;
-    if (list_mode == 2)      // a quota above HS_QT_MAX_NODES - 8 (the reference's init extractor of its "Imaging" camera: 9000 features @1.4 -> 2758 on level 0)
-        hipLaunchKernelGGL((k_quadtree<HS_QT_LARGE_NODES, 0, true>), grid, dim3(QT_T), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride,
-                           pts_xy, pts_sk, pt_node, cand_count, sel_xys, sel_count, sel_img_stride, sel_perm, force_point_domain, level_first,
-                           qhist, qbest, qhist_img_stride, qbest_img_stride, keep_points, rect_scratch);
-    else if (small)
-        hipLaunchKernelGGL((k_quadtree<QT_M_SMALL, 0, false>), grid, dim3(QT_T), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride,
-                           pts_xy, pts_sk, pt_node, cand_count, sel_xys, sel_count, sel_img_stride, sel_perm, force_point_domain, level_first,
-                           qhist, qbest, qhist_img_stride, qbest_img_stride, keep_points, nullptr);
-    else
-        hipLaunchKernelGGL((k_quadtree<HS_QT_MAX_NODES, QT_PTS_BIG, false>), grid, dim3(QT_T), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride,
-                           pts_xy, pts_sk, pt_node, cand_count, sel_xys, sel_count, sel_img_stride, sel_perm, force_point_domain, level_first,
-                           qhist, qbest, qhist_img_stride, qbest_img_stride, keep_points, nullptr);
+#define QT_LAUNCH(M_, PTS_, RECT_, scratch_) hipLaunchKernelGGL((k_quadtree<M_, PTS_, RECT_>), grid, dim3(QT_T), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride, \
+                           pts_xy, pts_sk, pt_node, cand_count, sel_xys, sel_count, sel_img_stride, sel_perm, force_point_domain, level_first, \
+                           qhist, qbest, qhist_img_stride, qbest_img_stride, keep_points, scratch_)
+    if (list_mode == 2) QT_LAUNCH(HS_QT_LARGE_NODES, 0, true, rect_scratch);      // a quota above HS_QT_MAX_NODES - 8 (the reference's init extractor of its "Imaging" camera: 9000 features @1.4 -> 2758 on level 0)
+    else if (small) QT_LAUNCH(QT_M_SMALL, 0, false, nullptr);
+    else QT_LAUNCH(HS_QT_MAX_NODES, QT_PTS_BIG, false, nullptr);
+#undef QT_LAUNCH
 }
 
 // bytes of global scratch ONE workgroup (one (image, level)) of the large-list instance needs for its two rectangle buffers
@@ -1029,39 +1013,3 @@ size_t hs_quadtree_large_scratch_bytes() { return 2 * sizeof(QtRects<HS_QT_LARGE
 
 // largest list the small instance holds (hs_api.hip: every level's quota + 8 must fit)
 int hs_quadtree_small_nodes() { return QT_M_SMALL; }
-
-// Host side of the geometric-key tables (see k_quadtree): the expressions of the kernel's former in-kernel build, evaluated once per
-// configuration.  hs_api.hip is compiled with -ffp-contract=off and IEEE division, like the device code, so the floats agree.
-bool hs_quadtree_build_tables(HsLevel& V, std::vector<uint8_t>& blob, size_t& xoff, size_t& yoff)
-{
-    V.qt_xtab = V.qt_ytab = nullptr;
-    for (int i = 0; i < 8; i++) V.qt_rbound[i] = 0;
-    const int nIni = V.n_ini;
-    if (nIni < 1 || nIni > 8 || V.qt_w <= 0 || V.qt_h <= 0 || V.qt_w >= 8192 - 16 || V.qt_h >= 4096 - 16) return false;
-    const float hX = V.hx;
-    const int DH = nIni <= 2 ? 6 : 5;
-    auto root_of = [&](int x) { return std::min((int)((float)x / hX), nIni - 1); };
-    auto descend = [&](int x, int x0, int x1) {
-        int idx = 0;
-        for (int d = 0; d < DH; d++) {
-            const int mx = x0 + ((x1 - x0 + 1) >> 1);
-            if (x < mx) { x1 = mx; idx = 2 * idx; } else { x0 = mx; idx = 2 * idx + 1; }
-        }
-        return idx;
-    };
-    for (int r = 1; r < nIni; r++) {                                 // smallest x that lands in root r: around r * hX
-        int bnd = (int)(hX * (float)r);
-        while (bnd > 0 && root_of(bnd - 1) >= r) bnd--;
-        while (root_of(bnd) < r) bnd++;
-        V.qt_rbound[r] = bnd;
-    }
-    auto grow = [&](size_t n) { const size_t o = (blob.size() + 15) & ~(size_t)15; blob.resize(o + ((n + 15) & ~(size_t)15), 0); return o; };
-    xoff = grow((size_t)V.qt_w + 1);
-    for (int x = 0; x <= V.qt_w; x++) {
-        const int r = root_of(x);
-        blob[xoff + x] = (uint8_t)descend(x, (int16_t)(int)(hX * (float)r), (int16_t)(int)(hX * (float)(r + 1)));
-    }
-    yoff = grow((size_t)V.qt_h + 1);
-    for (int y = 0; y <= V.qt_h; y++) blob[yoff + y] = (uint8_t)descend(y, 0, (int16_t)V.qt_h);
-    return true;
-}

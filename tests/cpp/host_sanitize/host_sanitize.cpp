@@ -15,6 +15,8 @@
 //        host_sanitize threads [seed]                         prints "HOST SANITIZE THREADS OK ..."
 //        host_sanitize plan W H [nfeat scale levels [cell]]   the host-side plan of a geometry
 //        host_sanitize refusals [list]                        prints "HOST SANITIZE REFUSALS OK ..." (list: every call's status first)
+//        host_sanitize fastplan                               the FAST launch plan under the environment's knobs: one digest line per tile width, one for the narrow / wide choice
+//        host_sanitize fastsched                              the FAST work-unit schedule, host half and device half together; prints "FAST SCHEDULE OK ..."
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -31,6 +33,7 @@
 #include <limits>
 #include <unistd.h>
 #include "../../../include/hyslam_amd.h"
+#include "../../../hyslam_amd/csrc/hs_plan.h"   // the FAST launch plan and schedule (hs_fast.h) and the knob table's reader: pure host code, called directly
 void hs_orb_borrow(hs_orb* h, int delta);      // hs_api.hip (internal: what hs_comm_create / hs_comm_destroy call)
 
 extern "C" long hip_stub_launches();
@@ -987,8 +990,118 @@ static int run(bool list /*print every call's status: two commits that refuse th
 #undef P
 }  // namespace refusals
 
+// ---- host_sanitize fastplan: hs_fast_launch_plan and hs_fast_overflow_bytes over a fixed table, under the knobs the environment sets (read through the
+// knob table, as a handle reads them).  One line per tile width: a digest over every field of every launch record of the table and the overflow bytes
+// of its geometry; then the narrow / wide choice.  tests/golden/fast_launch_digests.json holds the lines of the commit before the plan function existed.
+namespace fastplan {
+struct Fnv64 { uint64_t v = 0xcbf29ce484222325ull; void add(uint64_t x) { v ^= x; v *= 0x100000001b3ull; } };
+static int run()
+{
+    const HsKnobs env = hs_read_knobs();
+    static const int HCELL[] = { 32, 33, 34, 35, 38, 39, 48, 49, 64, 65, 96, 97, 125 }, BATCH[] = { 1, 2, 3, 8, 12, 32, 64, 128, 256 }, ITEMS[] = { 1, 7, 861, 1904 };
+    for (int lc = 5; lc <= 6; lc++) {
+        HsKnobs k = env; k.fast_cols = 4 << (lc - 2);           // 32 / 64: this tile width whatever the batch
+        Fnv64 H; long n = 0;
+        for (int hc : HCELL) for (int b : BATCH) for (int it : ITEMS) {
+            const int n0 = it / 3;                                // the split's level-0 tail: the last third of the list
+            const int range[3][3] = { { 0, it, 0 }, { 0, it - n0, 0 }, { it - n0, n0, 1 } };      // the whole list; head with spill slot 0; tail with slot 1
+            for (int r = 0; r < (n0 > 0 ? 3 : 1); r++) {
+                const HsFastLaunch P = hs_fast_launch_plan(k, hc, it, it, b, range[r][0], range[r][1], range[r][2]);
+                CHECK(P.lc == lc && P.narrow == (lc == 5));
+                const int64_t f[] = { P.lc, P.narrow, P.tr, P.lds.off_cnt, P.lds.pcap_max, P.lds.pcap_min, P.lds.total, P.nblk, P.ovf_stride, P.spill_base, P.item_first, P.items_per_img,
+                                      P.total_work, P.force_scan_b, P.S.nq_log, P.S.mode, P.S.par, P.S.par_log, P.S.per_q, P.S.m_per_q, P.S.m_par, P.S.m_items };
+                for (int64_t x : f) H.add((uint64_t)x);
+                n++;
+            }
+            H.add((uint64_t)hs_fast_overflow_bytes(k, hc, it, it, b));
+        }
+        printf("fastplan lc %d: %ld launches, digest %016llx\n", lc, n, (unsigned long long)H.v);
+    }
+    Fnv64 H;
+    for (int it : { 861, 1904 }) for (int b = 1; b <= 128; b++) H.add((uint64_t)hs_fast_narrow(env, it, b));
+    printf("fastplan narrow: digest %016llx\n", (unsigned long long)H.v);
+    return 0;
+}
+}  // namespace fastplan
+
+// ---- host_sanitize fastsched: the work-unit schedule of k_fast_rows on the CPU.  The host half (hs_fast_launch_plan: mode, queue count, magic divisors)
+// and the device half (hs_fast.h: fast_queue_size, unit_decode, fast_div — the very functions the kernel inlines) must together hand out every (item, image)
+// of a launch exactly once.  Units are enumerated the way the kernel reaches them: per queue in modes 0-3, as [0, total_work) in the folded mode 4.
+namespace fastsched {
+static int check_div(const char* what, int a, int d, uint32_t m, int w)
+{
+    if (d >= 1 && fast_div(a, d, m) == a / d) return 0;
+    printf("FAST SCHEDULE FAILED: unit %d: fast_div(%d, %d, %u) [%s] = %d, not %d\n", w, a, d, m, what, d >= 1 ? fast_div(a, d, m) : -1, d >= 1 ? a / d : -1);
+    return 1;
+}
+static int launch(const HsKnobs& k, int lc, int batch, int items, long& units, long modes[5])
+{
+    HsKnobs kk = k; kk.fast_cols = 4 << (lc - 2);
+    const HsFastLaunch P = hs_fast_launch_plan(kk, 31, items, items, batch, 0, items, 0);
+    const FastSched& S = P.S;
+    const int nq = 1 << S.nq_log;
+    char where[160]; snprintf(where, sizeof(where), "batch %d, %d items, lc %d, nq knob %d, image_major %d, no_fold %d: mode %d, %d queues, %d workgroups", batch, items, lc, k.fast_nq, k.fast_image_major, k.fast_no_fold, S.mode, nq, P.nblk);
+    if (P.total_work != items * batch || P.nblk < nq || P.nblk % nq != 0) { printf("FAST SCHEDULE FAILED: %s: the workgroups are no multiple of the queues\n", where); return 1; }
+    if (S.mode < 0 || S.mode > 4) { printf("FAST SCHEDULE FAILED: %s: unknown mode\n", where); return 1; }
+    std::vector<uint8_t> seen((size_t)P.total_work, 0);
+    auto unit = [&](int w, int q, int idx) {
+        // fast_div's operand pairs of this unit, restated from unit_decode
+        int bad = 0;
+        if (S.mode == 1 || S.mode == 2 || S.mode == 3) {
+            bad += check_div("per_q", w, S.per_q, S.m_per_q, w);
+            const int qq = S.per_q >= 1 ? w / S.per_q : 0, u = w - qq * S.per_q;
+            if (S.mode == 1) bad += check_div("par", u, S.par, S.m_par, w);
+            if (S.mode == 3) bad += check_div("par", (u << S.nq_log) + qq, S.par, S.m_par, w);
+        } else if (S.mode == 4) bad += check_div("par", w, S.par, S.m_par, w);
+        else bad += check_div("items", w, P.items_per_img, S.m_items, w);
+        if (bad) { printf("  in %s (queue %d, index %d)\n", where, q, idx); return 1; }
+        int img = -1;
+        const int item = unit_decode(P.items_per_img, S, w, &img);
+        const bool in_range = item >= 0 && item < items && img >= 0 && img < batch;
+        if (!in_range || seen[(size_t)img * items + item]) {
+            printf("FAST SCHEDULE FAILED: %s: unit %d (queue %d, index %d) decodes to item %d of image %d: %s\n", where, w, q, idx, item, img, in_range ? "handed out twice" : "out of range");
+            return 1;
+        }
+        seen[(size_t)img * items + item] = 1;
+        units++;
+        return 0;
+    };
+    if (S.mode == 4) {
+        if (P.total_work > 2 * P.nblk) { printf("FAST SCHEDULE FAILED: %s: a folded launch of more than two units per workgroup\n", where); return 1; }
+        for (int w = 0; w < P.total_work; w++) if (unit(w, -1, w)) return 1;
+    } else {
+        for (int q = 0; q < nq; q++) {
+            const int size = fast_queue_size(S, q, P.total_work, P.items_per_img);
+            if (size > S.per_q) { printf("FAST SCHEDULE FAILED: %s: queue %d holds %d units, more than per_q = %d\n", where, q, size, S.per_q); return 1; }
+            for (int idx = 0; idx < size; idx++) if (unit(q * S.per_q + idx, q, idx)) return 1;
+        }
+    }
+    for (size_t i = 0; i < seen.size(); i++)
+        if (!seen[i]) { printf("FAST SCHEDULE FAILED: %s: item %d of image %d is never handed out\n", where, (int)(i % items), (int)(i / items)); return 1; }
+    modes[S.mode]++;
+    return 0;
+}
+static int run()
+{
+    const HsKnobs env = hs_read_knobs();
+    long units = 0, launches = 0, modes[5] = {};
+    for (int nq : { 0, 8, 16 }) for (int variant = 0; variant < 3; variant++) {         // HS_FAST_NQ unset / 8 / 16, each plain, with HS_FAST_IMAGE_MAJOR and with HS_FAST_NO_FOLD
+        HsKnobs k = env; k.fast_nq = nq; k.fast_image_major = variant == 1; k.fast_no_fold = variant == 2;
+        for (int batch : { 1, 2, 3, 5, 8, 16, 24, 32, 33, 64 }) for (int items : { 1, 2, 7, 61 }) for (int lc = 5; lc <= 6; lc++) {
+            if (launch(k, lc, batch, items, units, modes)) return 1;
+            launches++;
+        }
+    }
+    for (int m = 0; m < 5; m++) if (modes[m] == 0) { printf("FAST SCHEDULE FAILED: the table never reaches mode %d\n", m); return 1; }
+    printf("FAST SCHEDULE OK: %ld launches (modes 0-4: %ld %ld %ld %ld %ld), %ld units, every (item, image) exactly once\n", launches, modes[0], modes[1], modes[2], modes[3], modes[4], units);
+    return 0;
+}
+}  // namespace fastsched
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "fastplan")) return fastplan::run();
+    if (argc > 1 && !strcmp(argv[1], "fastsched")) return fastsched::run();
     if (argc > 1 && !strcmp(argv[1], "refusals")) { const int rc = refusals::run(argc > 2 && !strcmp(argv[2], "list")); fflush(stdout); return rc; }      // (a failed run leaves its handle behind: its lines come before the leak report)
     if (argc > 3 && !strcmp(argv[1], "plan")) {                 // host_sanitize plan W H [nfeat scale levels [cell]]: the host-side plan of a geometry, or its refusal
         hs_orb_params p; hs_orb_default_params(&p);

@@ -1,4 +1,4 @@
-"""The exact magic-number division of k_fast_rows' work-unit decode (hyslam_amd/csrc/kernels_fast.hip: fast_div, fast_sched): floor(a / d) as one high
+"""The exact magic-number division of k_fast_rows' work-unit decode (hyslam_amd/csrc/hs_fast.h: fast_div; the divisors: hs_plan_fast.hip): floor(a / d) as one high
 multiply by m = ceil(2^32 / d) and one correction.  The same integer arithmetic restated in Python and checked against // over the ranges the
 kernel uses (work units < 2^31; divisors = items per queue / images per queue / items per image) and far beyond them."""
 import numpy as np
