@@ -89,13 +89,14 @@ KNOWN_ENTRIES = {
 }
 
 
-def random_batch(seed, L, n_max=40, big=(), special=True):
+def random_batch(seed, L, n_max=40, big=(), special=True, rate=1.0, p_empty=0.03):
     """-> (entries [L] ENTRY_DTYPE, obs_offsets int64 [L+1], obs OBS_DTYPE, descriptor lists).  Scales from 1e-3 to 1e20, N from 0 to n_max
     (`big`: (landmark, N) overrides), and with `special`: camera centres on the point, signed zeros, keypoints without or with another landmark,
-    zero and huge keypoint sizes, reference key frames outside the observations."""
+    zero and huge keypoint sizes, reference key frames outside the observations.  rate: a factor on the densities of the special values; p_empty:
+    the share of landmarks that lose all their observations."""
     rng = np.random.default_rng(seed)
     n = rng.integers(0, n_max + 1, L)
-    n[rng.random(L) < 0.03] = 0
+    n[rng.random(L) < p_empty] = 0
     for i, m in big:
         n[i] = m
     off = np.zeros(L + 1, np.int64)
@@ -119,7 +120,7 @@ def random_batch(seed, L, n_max=40, big=(), special=True):
     ob["assoc_pos"] = ent["pos"][owner]
     ob["assoc"] = 1
     if special and T:
-        pick = lambda p: rng.random(T) < p
+        pick = lambda p: rng.random(T) < p * rate
         m = pick(0.002); ob["Ow"][m] = ent["pos"][owner[m]]                                   # camera centre on the point
         m = pick(0.03); ob["assoc"][m] = 0                                                    # hasAssociation(idx) == NULL
         m = pick(0.03); ob["assoc_pos"][m] = (ob["assoc_pos"][m] * rng.uniform(0.5, 2, (m.sum(), 1))).astype(f32)   # another landmark
@@ -127,7 +128,7 @@ def random_batch(seed, L, n_max=40, big=(), special=True):
         m = pick(0.01); ob["kp_size"][m] = 3e30
         m = pick(0.01); ob["Ow"][m, 2] = -0.0
         m = pick(0.005); ob["Ow"][m] = rng.normal(0, 1e-3, (m.sum(), 3)).astype(f32)
-        z = rng.random(L) < 0.01; ent["pos"][z, 2] = -0.0
+        z = rng.random(L) < 0.01 * rate; ent["pos"][z, 2] = -0.0
     descs = []
     for i in range(L):
         k = int(rng.integers(0, n[i] + 2)) if n[i] < 64 else int(n[i]) - int(rng.integers(0, 3))   # a descriptor set of its own size

@@ -210,9 +210,10 @@ def random_cases():
 
 
 # ---- replay states for the view-order replay: a view in at most one op, a landmark in at most one
-def replay_state(seed, n, L=None):
+def replay_state(seed, n, L=None, p_own=0.33, p_skip=0.03, **state):
+    """TC.replay_state's frame state (`state`: its densities) with ops that name every view and every landmark at most once"""
     rng = np.random.default_rng(seed)
-    s = TC.replay_state(seed, n, n, L)
+    s = TC.replay_state(seed, n, n, L, **state)
     L = s["L"]
     views = rng.permutation(n)
     k = int(min(n, L) * rng.uniform(0.3, 1.0))
@@ -220,13 +221,38 @@ def replay_state(seed, n, L=None):
     lms = rng.permutation(L)[:k]
     for j in range(k):                                                      # a third of the ops name a view that already holds their landmark
         at = np.nonzero(s["kp_lm"] == lms[j])[0]
-        if len(at) and rng.random() < 0.33 and at[0] not in op_view:
+        if len(at) and rng.random() < p_own and at[0] not in op_view:
             op_view[j] = at[0] if rng.random() < 0.5 or at[-1] in op_view else at[-1]
         else:
             free = views[~np.isin(views, op_view)]
             op_view[j] = free[0]
         op_lm[j] = lms[j]
-    op_view[rng.random(n) < 0.03] = -1                                       # skipped ops
-    op_lm[rng.random(n) < 0.03] = -1
+    op_view[rng.random(n) < p_skip] = -1                                     # skipped ops
+    op_lm[rng.random(n) < p_skip] = -1
     p = rng.permutation(n)
     return dict(kp_lm=s["kp_lm"], kp_outl=s["kp_outl"], n_matches=s["n_matches"], op_view=op_view[p], op_lm=op_lm[p], L=L)
+
+
+def random_search(seed, n, kf_sizes, L, n_nodes, p_lm=0.9, p_bad=0.05, p_twin=0.3, p_turned=0.15, max_flip=14, p_no_node=0.05):
+    """inputs of the key-frame / frame BoW search without a vocabulary: a frame of n keypoints with random descriptors, angles and nodes, and a store
+    of key frames with kf_sizes keypoints each, every one a copy of a frame keypoint (with repeats: twins that compete for one view) with up to
+    max_flip bits flipped, its node and its angle, a share turned away (the rotation histogram removes those).  Some keypoints have no node or no
+    weight, on both sides.  -> (K, lm_bad, fkps, fdesc, fnode, fweight)"""
+    rng = np.random.default_rng(seed)
+    fdesc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    fkps = np.zeros(n, TC.KP_DTYPE)
+    fkps["angle"] = rng.uniform(0, 360, n).astype(np.float32)
+    fnode = np.where(rng.random(n) < p_no_node, -1, rng.integers(0, max(n_nodes, 1), n)).astype(np.int32)
+    fweight = np.where(rng.random(n) < p_no_node, 0.0, rng.uniform(0.1, 3, n)).astype(np.float32)
+    off = np.zeros(len(kf_sizes) + 1, np.int64)
+    np.cumsum(kf_sizes, out=off[1:])
+    total = int(off[-1])
+    src = rng.integers(0, n, total)
+    twin = rng.random(total) < p_twin
+    if total > 1:
+        src[1:][twin[1:]] = src[:-1][twin[1:]]
+    K = dict(n_kf=len(kf_sizes), kf_off=off, kps=np.zeros(total, TC.KP_DTYPE), desc=scenes.flip_bits(rng, fdesc[src], rng.integers(0, max_flip + 1, total)),
+             kp_lm=np.where(rng.random(total) < p_lm, rng.integers(0, max(L, 1), total), -1).astype(np.int32))
+    K["kps"]["angle"] = ((fkps["angle"][src] + 300 + rng.normal(0, 4, total) + (rng.random(total) < p_turned) * rng.uniform(0, 360, total)) % 360).astype(np.float32)
+    K["node"] = np.where(rng.random(total) < p_no_node, -1, fnode[src]).astype(np.int32)
+    return K, (rng.random(L) < p_bad).astype(np.uint8), fkps, fdesc, fnode, fweight

@@ -117,14 +117,15 @@ def test_search_by_bow_kf_beyond_one_pass(tracker):
 
 
 # ---------------------------------------------------------------- the replay alone
-def associate_views_device(tracker, s, order=None):
+def associate_views_device(tracker, s, order=None, stream=None):
+    """stream: anything with .ptr and .synchronize() (default: a stream of its own)"""
     n, L = len(s["kp_lm"]), s["L"]
     ov, ol = (s["op_view"], s["op_lm"]) if order is None else (s["op_view"][order], s["op_lm"][order])
     d_lm, d_outl, d_nm = guarded(s["kp_lm"]), guarded(s["kp_outl"]), guarded(np.array([s["n_matches"]], np.int32))
     d_ov, d_ol = dev(ov), dev(ol)
     nbytes = tracker.track_refkf_work_bytes(n, 0, L)
     work = out_buf(nbytes)
-    st = hipmem.Stream()
+    st = stream or hipmem.Stream()
     tracker.frame_associate_views_device(n, L, d_lm.ptr, d_outl.ptr, d_nm.ptr, d_ov.ptr, d_ol.ptr, work.ptr, st.ptr)
     st.synchronize()
     read(work, np.uint8, nbytes)

@@ -62,13 +62,14 @@ ASSOC_SIZES = [(1, 1), (1, 65), (63, 65), (64, 64), (65, 63), (130, 130), (100, 
                (1023, 1025), (1024, 1024), (1025, 1023), (300, 1025), (1025, 1)]
 
 
-def associate_device(tracker, s, order=None):
+def associate_device(tracker, s, order=None, stream=None):
+    """stream: anything with .ptr and .synchronize() (default: a stream of its own)"""
     n, L = len(s["kp_lm"]), s["L"]
     ov, ol = (s["op_view"], s["op_lm"]) if order is None else (s["op_view"][order], s["op_lm"][order])
     d_lm, d_outl, d_nm = guarded(s["kp_lm"]), guarded(s["kp_outl"]), guarded(np.array([s["n_matches"]], np.int32))
     d_ov, d_ol = dev(ov), dev(ol)
     work = out_buf(tracker.track_work_bytes(n, 0, L, 0))
-    st = hipmem.Stream()
+    st = stream or hipmem.Stream()
     tracker.frame_associate_device(n, L, d_lm.ptr, d_outl.ptr, d_nm.ptr, len(ov), d_ov.ptr, d_ol.ptr, work.ptr, st.ptr)
     st.synchronize()
     read(work, np.uint8, tracker.track_work_bytes(n, 0, L, 0))
@@ -351,30 +352,38 @@ def _discard_numpy(mode, sensor, edges_kp, ne, outlier, ran, kp_lm, kp_outl, nm,
     return kp_lm, kp_outl, nm, count
 
 
+def discard_device(tracker, mode, sensor, edges_kp, n_edges, edge_cap, outlier, status, kp_lm, kp_outl, nm, lm_nobs, stream=None):
+    """hs_track_discard_device on guarded copies -> (kp_lm, kp_outl, n_matches, count); n_edges: the value of *d_n_edges (may exceed edge_cap)"""
+    from hyslam_amd import _native as N
+    n, L = len(kp_lm), len(lm_nobs)
+    edges = np.zeros(len(edges_kp), N.POSE_EDGE_DTYPE)
+    edges["kp"] = edges_kp
+    result = np.zeros(1, N.POSE_RESULT_DTYPE)
+    result["status"] = status
+    d_nobs = dev(lm_nobs)
+    KT = N.KfTable(L, 0, None, None, None, None, d_nobs.ptr, None, None)
+    d_lm, d_outl, d_nm, d_cnt = guarded(kp_lm), guarded(kp_outl), guarded(np.array([nm], np.int32)), out_buf(4)
+    ins = dev(edges), dev(np.array([n_edges], np.int32)), dev(outlier), dev(result)
+    st = stream or hipmem.Stream()
+    tracker.track_discard_device(mode, ins[0].ptr, ins[1].ptr, edge_cap, ins[2].ptr, ins[3].ptr, KT, sensor, d_lm.ptr, d_outl.ptr, d_nm.ptr, d_cnt.ptr, st.ptr)
+    st.synchronize()
+    return read(d_lm, np.int32, n), read(d_outl, np.uint8, n), int(read(d_nm, np.int32, 1)[0]), int(read(d_cnt, np.int32, 1)[0])
+
+
 @pytest.mark.parametrize("mode,sensor,status,truncate", [(0, 1, 0, False), (0, 0, 0, True), (1, 1, 0, False), (1, 0, 0, False), (1, 2, 2, True), (0, 1, 1, False),
                                                          (1, 1, 1, False)])
 def test_discard_against_numpy(tracker, mode, sensor, status, truncate):
-    from hyslam_amd import _native as N
     n, L = 1500, 700
     rng = np.random.default_rng(100 * mode + 10 * sensor + status)
     kp_lm = np.where(rng.random(n) < 0.7, rng.integers(0, L, n), -1).astype(np.int32)
     kp_outl = rng.integers(0, 3, n).astype(np.uint8)            # also what the chain never makes: a held view without an entry, a flagged empty view
     lm_nobs = rng.integers(0, 3, L).astype(np.int32)
     with_edge = (kp_lm >= 0) | (rng.random(n) < 0.1)            # ... and an edge on a view that holds nothing
-    edges = np.zeros(int(with_edge.sum()), N.POSE_EDGE_DTYPE)
-    edges["kp"] = np.nonzero(with_edge)[0]
-    outlier = (rng.random(len(edges)) < 0.3).astype(np.uint8)
-    cap = len(edges) // 2 if truncate else len(edges)
-    result = np.zeros(1, N.POSE_RESULT_DTYPE)
-    result["status"] = status
-    want = _discard_numpy(mode, sensor, edges["kp"], min(len(edges), cap), outlier, status != 1, kp_lm, kp_outl, 900, lm_nobs)
-    d_nobs = dev(lm_nobs)
-    KT = N.KfTable(L, 0, None, None, None, None, d_nobs.ptr, None, None)
-    d_lm, d_outl, d_nm, d_cnt = guarded(kp_lm), guarded(kp_outl), guarded(np.array([900], np.int32)), out_buf(4)
-    ins = dev(edges), dev(np.array([len(edges)], np.int32)), dev(outlier), dev(result)
-    tracker.track_discard_device(mode, ins[0].ptr, ins[1].ptr, cap, ins[2].ptr, ins[3].ptr, KT, sensor, d_lm.ptr, d_outl.ptr, d_nm.ptr, d_cnt.ptr)
-    tracker._ex.synchronize()
-    got = read(d_lm, np.int32, n), read(d_outl, np.uint8, n), int(read(d_nm, np.int32, 1)[0]), int(read(d_cnt, np.int32, 1)[0])
+    edges_kp = np.nonzero(with_edge)[0]
+    outlier = (rng.random(len(edges_kp)) < 0.3).astype(np.uint8)
+    cap = len(edges_kp) // 2 if truncate else len(edges_kp)
+    want = _discard_numpy(mode, sensor, edges_kp, min(len(edges_kp), cap), outlier, status != 1, kp_lm, kp_outl, 900, lm_nobs)
+    got = discard_device(tracker, mode, sensor, edges_kp, len(edges_kp), cap, outlier, status, kp_lm, kp_outl, 900, lm_nobs)
     for w, g, what in zip(want, got, ("kp_lm", "kp_outl", "n_matches", "count")):
         assert np.array_equal(w, g), what
     if status == 1:
@@ -383,26 +392,39 @@ def test_discard_against_numpy(tracker, mode, sensor, status, truncate):
         assert (~stays).any() == (mode == 0 or sensor == 1)
 
 
+def _frame_views_numpy(kp_lm, kp_outl, nm, lm_bad, lm_nobs, drop_bad):
+    """-> (kp_lm, kp_outl, n_matches, kp_lm_obs)"""
+    bad = (kp_lm >= 0) & (lm_bad[np.maximum(kp_lm, 0)] != 0) & bool(drop_bad)
+    want_lm = np.where(bad, -1, kp_lm)
+    want_outl = np.where(bad, 0, kp_outl)
+    want_obs = np.where(want_lm >= 0, lm_nobs[np.maximum(want_lm, 0)], -1)
+    return want_lm, want_outl, nm - int(bad.sum()), want_obs
+
+
+def frame_views_device(tracker, kp_lm, kp_outl, nm, lm_bad, lm_nobs, drop_bad, stream=None):
+    from hyslam_amd import _native as N
+    n, L = len(kp_lm), len(lm_nobs)
+    tabs = dev(lm_bad), dev(lm_nobs)
+    KT = N.KfTable(L, 0, None, None, None, tabs[0].ptr, tabs[1].ptr, None, None)
+    d_lm, d_outl, d_nm, d_obs = guarded(kp_lm), guarded(kp_outl), guarded(np.array([nm], np.int32)), out_buf(n * 4)
+    st = stream or hipmem.Stream()
+    tracker.frame_views_device(n, d_lm.ptr, d_outl.ptr, d_nm.ptr, KT, drop_bad, d_obs.ptr, st.ptr)
+    st.synchronize()
+    return read(d_lm, np.int32, n), read(d_outl, np.uint8, n), int(read(d_nm, np.int32, 1)[0]), read(d_obs, np.int32, n)
+
+
 @pytest.mark.parametrize("drop_bad", [0, 1])
 @pytest.mark.parametrize("n", [1, 1023, 1025, 3000])
 def test_frame_views_against_numpy(tracker, n, drop_bad):
-    from hyslam_amd import _native as N
     L = 500
     rng = np.random.default_rng(n + drop_bad)
     kp_lm = np.where(rng.random(n) < 0.7, rng.integers(0, L, n), -1).astype(np.int32)
     kp_outl = rng.integers(0, 3, n).astype(np.uint8)
     lm_nobs, lm_bad = rng.integers(0, 5, L).astype(np.int32), (rng.random(L) < 0.2).astype(np.uint8)
-    bad = (kp_lm >= 0) & (lm_bad[np.maximum(kp_lm, 0)] != 0) & bool(drop_bad)
-    want_lm = np.where(bad, -1, kp_lm)
-    want_outl = np.where(bad, 0, kp_outl)
-    want_obs = np.where(want_lm >= 0, lm_nobs[np.maximum(want_lm, 0)], -1)
-    tabs = dev(lm_bad), dev(lm_nobs)
-    KT = N.KfTable(L, 0, None, None, None, tabs[0].ptr, tabs[1].ptr, None, None)
-    d_lm, d_outl, d_nm, d_obs = guarded(kp_lm), guarded(kp_outl), guarded(np.array([n], np.int32)), out_buf(n * 4)
-    tracker.frame_views_device(n, d_lm.ptr, d_outl.ptr, d_nm.ptr, KT, drop_bad, d_obs.ptr)
-    tracker._ex.synchronize()
-    assert np.array_equal(read(d_lm, np.int32, n), want_lm) and np.array_equal(read(d_outl, np.uint8, n), want_outl)
-    assert np.array_equal(read(d_obs, np.int32, n), want_obs) and int(read(d_nm, np.int32, 1)[0]) == n - int(bad.sum())
+    want = _frame_views_numpy(kp_lm, kp_outl, n, lm_bad, lm_nobs, drop_bad)
+    got = frame_views_device(tracker, kp_lm, kp_outl, n, lm_bad, lm_nobs, drop_bad)
+    for w, g, what in zip(want, got, ("kp_lm", "kp_outl", "n_matches", "kp_lm_obs")):
+        assert np.array_equal(w, g), what
 
 
 # ---------------------------------------------------------------- end to end against the reference

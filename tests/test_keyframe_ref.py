@@ -22,41 +22,64 @@ def _check(c, tag):
     return a
 
 
-def test_exhaustive_depth_patterns():
+def depth_pattern_cases():
     """up to 5 views: every depth pattern x every n_min_points, the associations and the landmark table cycling through all of theirs"""
-    count, inserted, cut = 0, 0, 0
     for n in range(1, 6):
         for k, depth in enumerate(itertools.product(DEPTHS, repeat=n)):
             for nmp in range(4):
                 kinds = [VIEW_KINDS[(k * 7 + nmp * 5 + 5 * i) % 12] for i in range(n)]
                 nobs, bad = TABLES[(k + 3 * nmp) % 64]
-                c = KC.make(depth, [v[0] for v in kinds], [v[1] for v in kinds], lm_nobs=nobs, lm_bad=bad, n_min_points=nmp)
-                r = _check(c, (depth, nmp, kinds, nobs, bad))
-                count += 1
-                inserted += r["result"]["n_new"] > 0
-                cut += r["result"]["n_processed"] < r["result"]["n_candidates"]
-    assert count == 4 * sum(4 ** n for n in range(1, 6)) and inserted > 1000 and cut > 200
+                yield (depth, nmp, kinds, nobs, bad), KC.make(depth, [v[0] for v in kinds], [v[1] for v in kinds], lm_nobs=nobs, lm_bad=bad, n_min_points=nmp)
 
 
-def test_exhaustive_associations():
+def association_cases():
     """up to 3 views: every (association, flag) pattern x every lm_nobs pattern, lm_bad / depths / n_min_points cycling"""
-    count = 0
     for n in range(1, 4):
         for k, kinds in enumerate(itertools.product(VIEW_KINDS, repeat=n)):
             for t, nobs in enumerate(itertools.product((0, 1), repeat=3)):
                 bad = TABLES[(k + t) % 64][1]
                 depth = [DEPTHS[(k + t + 3 * i) % 4] for i in range(n)]
-                _check(KC.make(depth, [v[0] for v in kinds], [v[1] for v in kinds], lm_nobs=nobs, lm_bad=bad, n_min_points=(k + t) % 4), (kinds, nobs, bad, depth))
-                count += 1
-    assert count == 8 * (12 + 144 + 1728)
+                yield (kinds, nobs, bad, depth), KC.make(depth, [v[0] for v in kinds], [v[1] for v in kinds], lm_nobs=nobs, lm_bad=bad, n_min_points=(k + t) % 4)
 
 
-def test_exhaustive_tables_on_two_views():
+def table_cases():
     """two views: every association pattern x every (lm_nobs, lm_bad) table x both gates"""
     for lms in itertools.product((-1, 0, 1, 2), repeat=2):
         for t, (nobs, bad) in enumerate(TABLES):
             for ok in (0, 1):
-                _check(KC.make([10.0, 50.0], lms, [1 + (t & 1), 2 - (t & 1)], lm_nobs=nobs, lm_bad=bad, ok_override=ok, n_min_points=t % 3), (lms, nobs, bad, ok))
+                yield (lms, nobs, bad, ok), KC.make([10.0, 50.0], lms, [1 + (t & 1), 2 - (t & 1)], lm_nobs=nobs, lm_bad=bad, ok_override=ok, n_min_points=t % 3)
+
+
+def exhaustive_cases():
+    """the three spaces one after the other (22 576 cases): what tools/fuzz_map.py and tests/test_gpu_fuzz_map.py run on the device"""
+    for cases in (depth_pattern_cases, association_cases, table_cases):
+        yield from cases()
+
+
+def test_exhaustive_depth_patterns():
+    count, inserted, cut = 0, 0, 0
+    for tag, c in depth_pattern_cases():
+        r = _check(c, tag)
+        count += 1
+        inserted += r["result"]["n_new"] > 0
+        cut += r["result"]["n_processed"] < r["result"]["n_candidates"]
+    assert count == 4 * sum(4 ** n for n in range(1, 6)) and inserted > 1000 and cut > 200
+
+
+def test_exhaustive_associations():
+    count = 0
+    for tag, c in association_cases():
+        _check(c, tag)
+        count += 1
+    assert count == 8 * (12 + 144 + 1728)
+
+
+def test_exhaustive_tables_on_two_views():
+    count = 0
+    for tag, c in table_cases():
+        _check(c, tag)
+        count += 1
+    assert count == 16 * 64 * 2
 
 
 @pytest.mark.parametrize("name", sorted(KC.DIRECTED))

@@ -167,16 +167,17 @@ def random_cases():
 
 
 # ---- replay states
-def replay_state(seed, n, n_ops, L=None):
+def replay_state(seed, n, n_ops, L=None, p_held=0.5, p_dup=0.3, p_stale=0.3, p_own=0.33, p_skip=0.05):
     """a frame state with duplicated landmarks, stale outlier entries (with and without a landmark on the view), and ops that hit held views, their
-    own view, views of other ops' landmarks and empty views; every landmark in at most one op; ops in shuffled array order, some skipped"""
+    own view, views of other ops' landmarks and empty views; every landmark in at most one op; ops in shuffled array order, some skipped.  The p_*
+    are the densities of held views, duplicates, stale entries on empty views, ops onto their landmark's holder and skipped ops"""
     rng = np.random.default_rng(seed)
     L = L or max(4, (n + n_ops) * 2 // 3)
-    kp_lm = np.where(rng.random(n) < 0.5, rng.integers(0, L, n), -1).astype(np.int32)
-    dup = rng.random(n) < 0.3
+    kp_lm = np.where(rng.random(n) < p_held, rng.integers(0, L, n), -1).astype(np.int32)
+    dup = rng.random(n) < p_dup
     if n > 1:
         kp_lm[dup] = kp_lm[rng.integers(0, n, int(dup.sum()))]
-    kp_outl = np.where(kp_lm >= 0, rng.integers(1, 3, n), np.where(rng.random(n) < 0.3, rng.integers(1, 3, n), 0)).astype(np.uint8)
+    kp_outl = np.where(kp_lm >= 0, rng.integers(1, 3, n), np.where(rng.random(n) < p_stale, rng.integers(1, 3, n), 0)).astype(np.uint8)
     n_real = min(n_ops, L)
     op_lm = np.full(n_ops, -1, np.int32)
     op_lm[:n_real] = rng.permutation(L)[:n_real]
@@ -184,8 +185,8 @@ def replay_state(seed, n, n_ops, L=None):
     held = np.nonzero(kp_lm >= 0)[0]
     for j in range(n_real):                                                 # a third of the ops name the view that already holds their landmark
         at = np.nonzero(kp_lm == op_lm[j])[0]
-        if len(at) and rng.random() < 0.33:
+        if len(at) and rng.random() < p_own:
             op_view[j] = at[0] if rng.random() < 0.5 else at[-1]              # the first holder is hasAssociation(lm)'s answer
-    op_view[rng.random(n_ops) < 0.05] = -1
-    op_lm[rng.random(n_ops) < 0.05] = -1
+    op_view[rng.random(n_ops) < p_skip] = -1
+    op_lm[rng.random(n_ops) < p_skip] = -1
     return dict(kp_lm=kp_lm, kp_outl=kp_outl, n_matches=int(rng.integers(0, n + 3)), op_view=op_view, op_lm=op_lm, L=L)
