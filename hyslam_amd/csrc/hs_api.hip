@@ -4,6 +4,7 @@
 // sequence.  The whole extraction of a batch is GPU-resident: pyramid -> FAST/NMS cells -> quadtree
 // distribution -> blur+orientation+rBRIEF, 10 kernel launches for an 8-level pyramid regardless of batch size.
 #include "hs_plan.h"
+#include "hs_stereo.h"
 #include "hs_track.h"               // hs_search_by_projection_why / _enqueue: the search is a stage of the track chains
 #include <atomic>
 #include <climits>
@@ -337,7 +338,8 @@ const KnobRow KNOBS[] = {
     //  sweep goes through L2, which costs a workgroup more than sharing the CU buys.  Kept as a parity / tuning variant: tests/test_gpu_parity.py runs it.)
     { "HS_QT_SMALL",            &HsKnobs::qt_small,            0,             K_FLAG,     "the quadtree kernel's small instance (two workgroups per CU) where every level's list fits it" },
     { "HS_STEREO_FUSE",         &HsKnobs::stereo_fuse,         1,             K_FLAG,     "0: the stereo front end with a separate k_stereo_strips launch instead of the strips binned by an extra workgroup of the describe launch" },
-    { "HS_EXTRACT_SPLIT",       &HsKnobs::split_mode,          -1,            K_TRISTATE, "1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, unset = for small batches (hs_orb_set_split overrides)" },
+    { "HS_STEREO_KPW",          &HsKnobs::stereo_kpw,          0,             K_ANY,      "tuning / parity tests: left keypoints per wavefront of the stereo matcher: 0 = by batch, 1 / 2 = k_stereo_match, 4 / 8 = k_stereo_match_compact, whatever the batch" },
+    { "HS_EXTRACT_SPLIT",       &HsKnobs::split_mode,         -1,            K_TRISTATE, "1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, unset = for small batches (hs_orb_set_split overrides)" },
 };
 } // namespace
 HsKnobs hs_read_knobs()
@@ -516,8 +518,8 @@ void run_stereo(hs_orb* h, bool binned, const hs_keypoint* kL, const uint8_t* dL
 {
     mark(h, 4, s);
     h->last_stereo_launches = binned ? 1 : 2;
-    if (binned) hs_launch_stereo_match_only(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, s);
-    else hs_launch_stereo(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, s);
+    if (binned) hs_launch_stereo_match_only_kpw(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, h->knobs.stereo_kpw, s);
+    else hs_launch_stereo_kpw(kL, dL, nL, kR, dR, nR, pairs, cap, sp, ur, depth, h->st.bd, h->d_strip_count, h->d_strip_list, h->knobs.stereo_kpw, s);
     mark(h, 5, s);
     hs_launch_stereo_median(nL, pairs, cap, ur, depth, h->st.bd, sp.th_high, h->d_strip_count, sp.n_rows, s);
     mark(h, -1, s);

@@ -6,7 +6,7 @@
 // The handle's tuning / parity-test knobs of the environment, read ONCE per handle by hs_read_knobs (hs_api.hip: the table of names, defaults and
 // meanings is there; INTEGRATION.md lists them for users).  Flags are 0 / 1.  HS_PYRAMID_NW8 (kernels_pyramid.hip) is read where it is used.
 struct HsKnobs {
-    int no_fuse, stereo_fuse, fast_keys, fast_keys_levels, fast_keys_max_batch, fast_order;
+    int no_fuse, stereo_fuse, stereo_kpw, fast_keys, fast_keys_levels, fast_keys_max_batch, fast_order;
     int fast_pcap, fast_list_min, fast_small_lists, fast_wg_per_cu, fast_scan_b, fast_image_major, fast_nq, fast_cols, fast_narrow_max, fast_no_fold;   // the FAST launch plan's (hs_plan_fast.hip)
     int chain_mode, pyr_chain2, pyr_tbx_max, deep_max_batch, deep_rows;
     int qt_point_domain, qt_small, split_mode;
