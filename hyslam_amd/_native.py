@@ -262,7 +262,7 @@ EXPORTS = [
     "hs_place_db_clear", "hs_place_db_size", "hs_place_query_reloc", "hs_place_query_loop", "hs_place_query_reloc_device", "hs_place_query_loop_device",
     "hs_comm_available", "hs_comm_unavailable_reason", "hs_orb_borrowers", "hs_comm_get_unique_id", "hs_comm_create", "hs_comm_destroy", "hs_comm_rccl_ranks", "hs_comm_rccl_rank", "hs_comm_rccl_version", "hs_comm_world", "hs_comm_rank", "hs_comm_last_error", "hs_comm_allgather_records",
     "hs_orb_stage_launches", "hs_orb_profile_begin", "hs_orb_profile_pause", "hs_orb_profile_end", "hs_debug_stream_copy", "hs_debug_poison", "hs_debug_poison_violations", "hs_debug_poison_selftest",
-    "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected",
+    "hs_orb_debug_level", "hs_orb_set_debug", "hs_orb_debug_candidates", "hs_orb_debug_selected", "hs_orb_debug_quadtree_replay", "hs_debug_quadtree_level_fallbacks",
 ]
 
 _lib = None
@@ -486,6 +486,9 @@ def lib():
     L.hs_orb_set_debug.argtypes = [vp, C.c_int]
     L.hs_orb_debug_candidates.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp]
     L.hs_orb_debug_selected.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    L.hs_debug_quadtree_level_fallbacks.restype = C.c_longlong
+    L.hs_debug_quadtree_level_fallbacks.argtypes = [C.c_int]
+    L.hs_orb_debug_quadtree_replay.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     _lib = L
     return L
 

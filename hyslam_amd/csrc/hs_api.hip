@@ -138,6 +138,7 @@ struct hs_orb {
     // hs_orb_extract_batch (host-pointer call): one pinned block the three outputs come back into
     HsPinned<uint8_t> h_pin_out;
     // (the two below outlive a reconfiguration: the matcher has no geometry, and the published results live in d_out / a slot's block, not in the workspace)
+    int last_qt_launches = 1;          // launches of stage 2 in the last call: 2 when the upper levels ran on the level instance (run_extract)
     int last_stereo_launches = 2;      // launches of stage 4 in the last stereo call: strips + match (run_stereo) or match only (the front end with the strips inside the describe launch)
     // where the last host-pointer extraction (hs_orb_extract[_batch], hs_orb_wait) left its results on the DEVICE: what hs_frame_publish keeps
     const hs_keypoint* pub_kps = nullptr; const uint8_t* pub_desc = nullptr; int pub_cap = 0, pub_batch = 0;
@@ -337,6 +338,8 @@ const KnobRow KNOBS[] = {
     // (measured at 32 / 64 pairs per call the two-per-CU instance is SLOWER (quadtree 0.0631 against 0.0606 ms, 0.1198 against 0.1117): without the points in LDS every
     //  sweep goes through L2, which costs a workgroup more than sharing the CU buys.  Kept as a parity / tuning variant: tests/test_gpu_parity.py runs it.)
     { "HS_QT_SMALL",            &HsKnobs::qt_small,            0,             K_FLAG,     "the quadtree kernel's small instance (two workgroups per CU) where every level's list fits it" },
+    { "HS_QT_SMALL_FROM",       &HsKnobs::qt_small_from,       -1,            K_ANY,      "calls of more than 256 (image, level) workgroups without the FAST keys: the levels from this one run on the quadtree kernel's level instance (eight waves, four workgroups per CU) where the plan allows it (hs_quadtree_small_from); -1 = from the plan's first such level, nlevels = off" },
+    { "HS_QT_SMALL_THREADS",    &HsKnobs::qt_small_threads,    512,           K_ANY,      "tuning / parity tests: 256 = the level instance with four waves instead of eight" },
     { "HS_STEREO_FUSE",         &HsKnobs::stereo_fuse,         1,             K_FLAG,     "0: the stereo front end with a separate k_stereo_strips launch instead of the strips binned by an extra workgroup of the describe launch" },
     { "HS_STEREO_KPW",          &HsKnobs::stereo_kpw,          0,             K_ANY,      "tuning / parity tests: left keypoints per wavefront of the stereo matcher: 0 = by batch, 1 / 2 = k_stereo_match, 4 / 8 = k_stereo_match_compact, whatever the batch" },
     { "HS_EXTRACT_SPLIT",       &HsKnobs::split_mode,         -1,            K_TRISTATE, "1 = always run level 0's FAST + quadtree beside the pyramid, 0 = never, unset = for small batches (hs_orb_set_split overrides)" },
@@ -458,12 +461,28 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         if (launched) h->fast_epoch++;
         return HS_OK;
     };
-    auto quadtree = [&](int level_first, int level_count, hipStream_t st) {
+    auto quadtree = [&](int level_first, int level_count, hipStream_t st, int level_mode = 0) {
         hs_launch_quadtree(d_lv, L, batch, g.total_cells, g.d_cand, g.d_cell_count, g.cand_img_stride,
                            g.d_pts_xy, g.d_pts_sk, g.d_pt_node, g.d_cand_count, g.d_sel, g.d_sel_count, g.sel_img_stride, g.d_sel_perm, h->knobs.qt_point_domain ? 1 : 0,
                            level_first, level_count, use_keys ? g.d_qhist.p : nullptr, g.d_qbest, g.qhist_stride, g.qbest_stride, h->keep_points ? 1 : 0,
-                           h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0), g.d_qt_rects, st);
+                           level_mode ? level_mode : (h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0)), g.d_qt_rects, st);
     };
+    // A launch of more than 256 workgroups runs in rounds of one 16-wave workgroup per CU whatever the level holds: the levels from `qt_from`
+    // (all of them small enough for it: hs_quadtree_small_from) go to the level instance (eight waves) in a launch of their own, four workgroups per CU.
+    // Not with the FAST keys (their histogram is one level deeper than that instance's pyramid) and not on a large-list handle.
+    // Whether that pays goes by the rounds of 256 the single launch needs: the levels below qt_from still run in rounds and the level launch costs
+    // about one more, so the default (HS_QT_SMALL_FROM unset) splits only where at least two rounds go away.  Measured at 1080p, k = 2: 128 frames
+    // (4 rounds -> 1 + the level launch) 0.112 -> 0.076 ms; 64 frames (2 rounds -> 1 + the level launch) 0.061 -> 0.071 ms, hence not there.
+    // A level given in HS_QT_SMALL_FROM forces the split for every call of more than 256 workgroups.
+    int qt_from = L;
+    if (!use_keys && !h->qt_large && !h->qt_small_ok && (long long)L * batch > 256) {
+        const int k = hs_quadtree_small_from(lvh.data(), L);
+        auto rounds = [&](int levels) { return ((long long)levels * batch + 255) / 256; };
+        if (h->knobs.qt_small_from >= 0) qt_from = std::min(L, std::max(h->knobs.qt_small_from, k));
+        else if (rounds(L) - rounds(k) >= 2) qt_from = k;
+    }
+    const int qt_level_mode = h->knobs.qt_small_threads == 256 ? 3 : 4;
+    h->last_qt_launches = 1;
     if (split) {
         if (!h->s_aux) {
             HIP_TRY(h, hipStreamCreateWithFlags(&h->s_aux, hipStreamNonBlocking));
@@ -488,7 +507,9 @@ int run_extract(hs_orb* h, HsImg0 img0, int batch, HsOut out, hipStream_t s, con
         const int rc = fast(0, n_items, 0, s);
         if (rc != HS_OK) return rc;
         mark(h, 2, s);
-        quadtree(0, L, s);
+        quadtree(0, qt_from, s);                                          // (a range of no levels launches nothing)
+        if (qt_from < L) quadtree(qt_from, L - qt_from, s, qt_level_mode);
+        h->last_qt_launches = (qt_from > 0) + (qt_from < L);
     }
     mark(h, 3, s);
     hs_launch_describe(h->d_lv, L, img0, batch, g.d_sel, g.d_sel_count, g.d_sel_perm, g.sel_img_stride, g.max_kp,
@@ -1818,7 +1839,7 @@ int hs_orb_stage_launches(const hs_orb* h, int stage)
         if (h->geo.last_batch > 0 && h->geo.last_batch <= h->knobs.deep_max_batch && !h->geo.pyr_deep.empty()) { int32_t o[8]; hs_debug_plan_summary(h, o); return o[1]; }
         return hs_pyramid_launch_count(h->geo.lv.data(), h->p.nlevels);
     }
-    return stage == 4 ? h->last_stereo_launches : 1;
+    return stage == 4 ? h->last_stereo_launches : (stage == 2 ? h->last_qt_launches : 1);
 }
 
 int hs_orb_profile_begin(hs_orb* h)
@@ -1952,6 +1973,39 @@ int hs_orb_debug_selected(hs_orb* h, int image, int level, int32_t* xys, int cap
     *n = cnt;
     if (cnt > cap) return hs_fail(h, HS_ERR_CAPACITY, "more keypoints than buffer");
     if (cnt) HIP_TRY(h, hipMemcpy(xys, h->geo.d_sel + ((size_t)image * h->geo.sel_img_stride + V.sel_off) * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost));
+    return HS_OK;
+}
+
+int hs_orb_debug_quadtree_replay(hs_orb* h, int level_first, int level_count, int threads, int reps, float* ms_per_launch)
+{
+    if (!h) return HS_ERR_INVALID;
+    const int L = h->p.nlevels, batch = h->geo.last_batch;
+    if (!ms_per_launch || batch <= 0 || level_first < 0 || level_count < 1 || level_first + level_count > L || reps < 1 || (threads != 0 && threads != 256 && threads != 512))
+        return hs_fail(h, HS_ERR_INVALID, "bad argument");
+    if (threads != 0 && (h->qt_large || level_first < hs_quadtree_small_from(h->geo.lv.data(), L))) return hs_fail(h, HS_ERR_INVALID, "hs_orb_debug_quadtree_replay: a level of the range does not fit the level instance");
+    // with the keys the quadtree launch consumes (and zeroes) what the FAST launch left: only a call that ran without them can be replayed
+    if (h->knobs.fast_keys && h->geo.d_fast_qt.p != nullptr && batch <= h->knobs.fast_keys_max_batch)
+        return hs_fail(h, HS_ERR_INVALID, "hs_orb_debug_quadtree_replay: the last call ran with the FAST keys (HS_FAST_KEYS=0, or more frames per call than HS_FAST_KEYS_MAX_BATCH)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    hs_orb::Geometry& g = h->geo;
+    const HsLevel* const d_lv = h->d_lv + (hs_fast_narrow(h->knobs, g.fast_items_n, batch) ? L : 0);
+    hipEvent_t e0, e1;
+    HIP_TRY(h, hipEventCreate(&e0));
+    HIP_TRY(h, hipEventCreate(&e1));
+    (void)hipEventRecord(e0, h->stream);
+    for (int r = 0; r < reps; r++)
+        hs_launch_quadtree(d_lv, L, batch, g.total_cells, g.d_cand, g.d_cell_count, g.cand_img_stride, g.d_pts_xy, g.d_pts_sk, g.d_pt_node, g.d_cand_count,
+                           g.d_sel, g.d_sel_count, g.sel_img_stride, g.d_sel_perm, h->knobs.qt_point_domain ? 1 : 0, level_first, level_count,
+                           nullptr, g.d_qbest, g.qhist_stride, g.qbest_stride, h->keep_points ? 1 : 0, threads == 256 ? 3 : (threads == 512 ? 4 : (h->qt_large ? 2 : (h->qt_small_ok ? 1 : 0))), g.d_qt_rects, h->stream);
+    (void)hipEventRecord(e1, h->stream);
+    const hipError_t e = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(h, e);
+    HIP_TRY(h, hipGetLastError());
+    *ms_per_launch = t / (float)reps;
     return HS_OK;
 }
 

@@ -9,7 +9,7 @@ struct HsKnobs {
     int no_fuse, stereo_fuse, stereo_kpw, fast_keys, fast_keys_levels, fast_keys_max_batch, fast_order;
     int fast_pcap, fast_list_min, fast_small_lists, fast_wg_per_cu, fast_scan_b, fast_image_major, fast_nq, fast_cols, fast_narrow_max, fast_no_fold;   // the FAST launch plan's (hs_plan_fast.hip)
     int chain_mode, pyr_chain2, pyr_tbx_max, deep_max_batch, deep_rows;
-    int qt_point_domain, qt_small, split_mode;
+    int qt_point_domain, qt_small, qt_small_from, qt_small_threads, split_mode;
     bool pyr_plan_set = false;         // HS_PYRAMID_PLAN is in the environment (an empty string is a plan too: no chain at all)
     std::string pyr_plan;
 };
@@ -67,3 +67,17 @@ const char* hs_plan_fast_items(const HsKnobs& k, HsPlan& P);
 // FNV-1a-style 64-bit hash (xor, multiply by the FNV prime; 8-byte words where possible) over the plan, field by field in the order stated at its definition: equal digests <=> the kernels get the same tables,
 // records and launch geometry
 uint64_t hs_plan_digest(const HsPlan& P);
+
+// The quadtree kernel's LEVEL instance (kernels_quadtree.hip: eight waves — or four — and 39 KB of LDS per workgroup, four workgroups per CU) sizes its scratch
+// by these instead of by the largest level any configuration may have.  Launch modes 3 / 4 of hs_launch_quadtree (256 / 512 threads) select it; a
+// launch that passes the FAST kernel's key histogram ignores them (the histogram is one level deeper than the instance's pyramid).
+#define HS_QT_LEVEL_NODES 512      // list capacity (>= quota + 8)
+#define HS_QT_LEVEL_XTAB 2048      // bytes of the x key table in LDS (>= qt_w + 1)
+#define HS_QT_LEVEL_YTAB 1024      // ... of the y key table (>= qt_h + 1)
+#define HS_QT_LEVEL_TILES 256      // 64-px tiles of the spatial order
+#define HS_QT_LEVEL_HPYR 2736      // histogram pyramid entries: n_ini * (4^(DH+1) - 1) / 3 <= 2730 for (n_ini <= 2, DH = 5) and (n_ini <= 8, DH = 4)
+// true exactly when the level instance can take the level: quota + 8 list entries, both key tables, the tile counters and a histogram pyramid of
+// depth >= 4 fit it.  A function of the level record alone: nothing of it enters the plan's digest.
+bool hs_quadtree_small_level(const HsLevel& V);
+// the first level from which EVERY level passes hs_quadtree_small_level (nlevels: none)
+int hs_quadtree_small_from(const HsLevel* lv, int nlevels);

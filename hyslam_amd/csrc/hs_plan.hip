@@ -221,6 +221,25 @@ static_assert(sizeof(HsFastQt) == 32 && sizeof(HsPyrFuse) == 152 && sizeof(HsPyr
 
 } // namespace
 
+bool hs_quadtree_small_level(const HsLevel& V)
+{
+    if (V.quota + 8 > HS_QT_LEVEL_NODES) return false;
+    if (V.qt_w + 1 > HS_QT_LEVEL_XTAB || V.qt_h + 1 > HS_QT_LEVEL_YTAB) return false;
+    if ((long long)((V.w + 63) >> 6) * ((V.h + 63) >> 6) > HS_QT_LEVEL_TILES) return false;
+    // the count domain's pyramid one depth above the key tables' (6 for <= 2 roots, else 5), at least 4 deep; more than 8 roots have no tables at all
+    if (V.n_ini == 0) return true;                      // a level without a FAST cell: no candidates, no tree
+    if (V.n_ini < 1 || V.n_ini > 8) return false;
+    const int DH = (V.n_ini <= 2 ? 6 : 5) - 1;
+    return DH >= 4 && (long long)V.n_ini * (((1ll << (2 * DH + 2)) - 1) / 3) <= HS_QT_LEVEL_HPYR;
+}
+
+int hs_quadtree_small_from(const HsLevel* lv, int nlevels)
+{
+    int k = nlevels;
+    while (k > 0 && hs_quadtree_small_level(lv[k - 1])) k--;
+    return k;
+}
+
 int hs_plan_geometry(const HsPlanInput& in, HsPlan& P, std::string& err)
 {
     P = HsPlan{};

@@ -2,7 +2,7 @@
 // with ExtractorNode::DivideNode (:121-177).
 //
 // The reference is a sequential std::list algorithm.  Its observable behaviour is restated here as a
-// level-synchronous, order-preserving parallel algorithm; one 1024-thread workgroup owns one (image, level):
+// level-synchronous, order-preserving parallel algorithm; one workgroup (QT_T threads: 1024, the level instance 512) owns one (image, level):
 //
 //   * The std::list is an array in list order.  Every new node is push_front'ed, so after a pass that
 //     creates T children (creation order = processing order of the parent, then n1..n4) the list is
@@ -39,40 +39,54 @@
 // Inputs are the per-item candidate slots written by k_fast_rows (gathered into a dense list first; its order is irrelevant: every
 // order-dependent decision uses the (cell, y, x) key of the reference's candidate order).  Outputs per (image, level):
 // selected (x,y,score) in final list order + count.  Bound: LDS latency / barriers; HBM traffic negligible.
-#include "hs_internal.h"
+#include "hs_plan.h"
 #include <cstdlib>
 
-#define QT_T HS_QT_THREADS
-// The kernel is a template over <QT_M, QT_PTS> (round 5):
+// The kernel is a template over <QT_M, QT_PTS, RECT_GLOBAL, QT_T> (round 5; the thread count since the level instance):
 //   QT_M    list capacity in LDS (>= the largest per-level quota + 8)
 //   QT_PTS  points kept in LDS (a 1080p level has ~5000 candidates); more fall back to the global arrays
+//   QT_T    threads per workgroup.  1024 for the three instances that take any level.  Fewer threads select the LEVEL instance's traits (QtTraits):
+//           its scratch is sized by what one level needs — <HS_QT_LEVEL_NODES = 512, 1536, false, 512>: 39 KB of LDS, FOUR workgroups per CU.  A
+//           workgroup's life is mostly fixed cost (every block-wide step is issued by all of its waves whatever the level holds), so a launch of
+//           more than 256 workgroups gains from eight waves per workgroup and four workgroups per CU where 16 waves and one did not gain from two:
+//           128 frames, levels 2..7: 74.5 us as one launch of the general instance, 36.4 us on the level instance (40.9 with four waves).
+//           run_extract (hs_api.hip) decides which calls split, hs_quadtree_small_level (hs_plan.hip) which levels fit.
 // <HS_QT_MAX_NODES = 2048, 6144> is the general instance: 152 KB of LDS, ONE workgroup per CU — every sweep over the points runs from LDS, which is what a
 // launch of few workgroups (one per (image, level): 16 for a stereo pair) wants.  <1024, 0> keeps no points in LDS (the sweeps read them through L2)
 // and fits 77 KB: TWO workgroups per CU, for launches of more than 256 workgroups (more than 16 stereo pairs per call), which used to run in
 // rounds of 256.  The arrays that double as scratch (histogram pyramid, marks, key tables, gather offsets) are sized by what they must hold, not by QT_M.
 #define QT_PTS_BIG 6144
 #define QT_M_SMALL 1024
+#define QT_PTS_LEVEL 1536         // the level instance: with 512 list entries and the level-sized scratch 39 KB of LDS, FOUR workgroups per CU (2048 points would take it past 40 KB)
 
-#define QT_HPYR 10928             // histogram pyramid entries (u16): n_ini * (4^(DH+1) - 1) / 3 <= 10922 for (n_ini <= 2, DH = 6) and (n_ini <= 8, DH = 5)
+// What the scratch arrays must hold goes with the instance's thread count: the 1024-thread instances take any level, the level instance
+// (fewer threads, hs_quadtree_small_level decides which levels it takes) only levels whose tables, tiles and pyramid fit the smaller arrays.
+template <int QT_T> struct QtTraits {
+    static constexpr bool LEVEL = QT_T < HS_QT_THREADS;
+    // histogram pyramid entries (u16): n_ini * (4^(DH+1) - 1) / 3 <= 10922 for (n_ini <= 2, DH = 6) and (n_ini <= 8, DH = 5); the level instance runs one depth less: <= 2730
+    static constexpr int HPYR = LEVEL ? HS_QT_LEVEL_HPYR : 10928;
+    static constexpr int XTAB = LEVEL ? HS_QT_LEVEL_XTAB : 8192, YTAB = LEVEL ? HS_QT_LEVEL_YTAB : 4096;      // bytes of the geometric-key tables in LDS
+    static constexpr int MAXT = LEVEL ? HS_QT_LEVEL_TILES : 4096;      // 64-px tiles of a level that the spatial order of the kept keypoints is built for (more: list order)
+    static constexpr int DH_LESS = LEVEL ? 1 : 0;                       // the pyramid is this much shallower than the host's key tables
+};
 
 // Node list, double buffered.  Rectangles are only kept in the point domain; in the count domain their LDS holds the histogram pyramid.
 template <int QT_M> struct alignas(16) QtRects { int16_t x0[QT_M], x1[QT_M], y0[QT_M], y1[QT_M]; };
 constexpr int qt_cmax(int a, int b) { return a > b ? a : b; }
-#define QT_MAXT 4096              // 64-px tiles of a level that the spatial order of the kept keypoints is built for (more: list order)
 struct QtNodes {                 // a view of buffer `c`
     int16_t *x0, *x1, *y0, *y1; uint32_t* cnt; uint16_t* ekey;
 };
 
 __device__ __forceinline__ int wave_sum(int x) { return __builtin_amdgcn_readlane(wave_scan_incl(x), 63); }
 
-// exclusive scan of one int per thread over the 1024-thread block; returns prefix, writes total.  s_wave holds TWO sets of per-wave sums
+// exclusive scan of one int per thread over the QT_T-thread block; returns prefix, writes total.  s_wave holds TWO sets of per-wave sums
 // used alternately (`flip`): a set is only rewritten two scans later, and the barrier of the scan in between orders that write after the
 // last read — one barrier per scan.
-__device__ __forceinline__ int block_scan_excl(int v, int* s_wave /*[2][16]*/, int& flip, int& total)
+template <int QT_T> __device__ __forceinline__ int block_scan_excl(int v, int* s_wave /*[2][QT_T / 64]*/, int& flip, int& total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int incl = wave_scan_incl(v);
-    int* const sw = s_wave + 16 * (flip & 1);
+    int* const sw = s_wave + (QT_T / 64) * (flip & 1);
     flip ^= 1;
     if (lane == 63) sw[wave] = incl;
     __syncthreads();
@@ -113,7 +127,18 @@ extern "C" void hs_debug_qt_profile(unsigned long long* out128) { (void)hipDevic
 #else
 #define QT_MARK(tag)
 #endif
-template <int QT_M, int QT_PTS, bool RECT_GLOBAL>
+// workgroups of the level instance that left the count domain for the point-domain passes (a node deeper than its pyramid): its pyramid is one
+// depth shallower than the general instance's, this says how often that matters (hs_debug_quadtree_level_fallbacks; tools/quadtree_level_times.py)
+__device__ unsigned int g_qt_level_fallbacks;
+extern "C" long long hs_debug_quadtree_level_fallbacks(int reset)
+{
+    unsigned int v = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_qt_level_fallbacks), sizeof v) != hipSuccess) return -1;
+    const unsigned int zero = 0;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_qt_level_fallbacks), &zero, sizeof zero) != hipSuccess) return -1;
+    return (long long)v;
+}
+template <int QT_M, int QT_PTS, bool RECT_GLOBAL, int QT_T>
 __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ lv, int nlevels, int total_cells,
                                                    const uint2* __restrict__ cand,
                                                    const int32_t* __restrict__ cell_count, uint64_t cand_img_stride,
@@ -124,6 +149,9 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                                                    uint32_t* __restrict__ qhist, unsigned long long* __restrict__ qbest, uint32_t qhist_img_stride, uint32_t qbest_img_stride,
                                                    int keep_points, uint8_t* __restrict__ rect_scratch)
 {
+    using TR = QtTraits<QT_T>;
+    constexpr int QT_HPYR = TR::HPYR, QT_MAXT = TR::MAXT;
+    static_assert(QT_T % 64 == 0 && QT_T >= 256 && QT_PTS % QT_T == 0, "the pyramid build and the closed-form list give every piece a thread of its own: at least 256 of them");
     // point domain: node rectangles; count domain: the histogram pyramid (u16) — sized for the larger of the two.  RECT_GLOBAL (the large-list
     // instance): the rectangles live in a per-workgroup piece of global scratch instead and the LDS only holds the pyramid
     __shared__ alignas(16) uint8_t s_r1[RECT_GLOBAL ? QT_HPYR * 2 : qt_cmax(2 * (int)sizeof(QtRects<QT_M>), QT_HPYR * 2)];
@@ -136,7 +164,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
     constexpr int CCOUNT_BYTES = qt_cmax(qt_cmax(16 * QT_M, QT_HPYR * 2), qt_cmax(8 * QT_M + 4 * QT_MAXT, (QT_M + 3) * 8));
     __shared__ alignas(16) uint32_t ccount[CCOUNT_BYTES / 4];
     // three per-node index arrays (idle during the gather: the geometric-key tables, 8192 + 4096 bytes, live here then)
-    __shared__ alignas(16) int16_t s_idx3[qt_cmax(3 * QT_M, (8192 + 4096) / 2)];
+    __shared__ alignas(16) int16_t s_idx3[qt_cmax(3 * QT_M, (TR::XTAB + TR::YTAB) / 2)];
     int16_t* const proc_rank = s_idx3;                                                  // processing rank of a node in this pass, -1 = not split
     int16_t* const order_node = s_idx3 + QT_M;                                          // rank -> node
     uint16_t* const new_index = reinterpret_cast<uint16_t*>(s_idx3 + 2 * QT_M);         // surviving node -> index in the next list
@@ -168,7 +196,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
     const float hX = L.hx;
     // ---- count domain set-up: pyramid depth, offsets (deepest level first so that it is 4-byte aligned for the packed atomics)
     const bool cf_geom = nIni >= 1 && nIni <= 8 && !force_point_domain;       // uniform
-    const int DH = nIni <= 2 ? 6 : 5;
+    const int DH = (nIni <= 2 ? 6 : 5) - TR::DH_LESS;      // (the host tables hold the cell index one level deeper than the level instance goes: its top bits)
     uint16_t* const hist = reinterpret_cast<uint16_t*>(s_rect);
     auto hoff = [&](int d) { return nIni * (((1 << (2 * DH + 2)) - (1 << (2 * d + 2))) / 3); };     // entries of the levels deeper than d
     // geometric key of a point: root << 2 DH | its DivideNode decisions down to depth DH (:121-177, :209).  DivideNode halves x and y
@@ -176,10 +204,10 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
     // per pixel row, built by the host, copied into LDS that is idle during the gather) replace the six-step descent per point; the root comes
     // from comparisons with the first column that the reference's float division assigns to each root.
     uint8_t* const xtab = reinterpret_cast<uint8_t*>(s_idx3);             // [qt_w + 1] cell index along x within the column's root
-    uint8_t* const ytab = xtab + 8192;                                   // [qt_h + 1]
+    uint8_t* const ytab = xtab + TR::XTAB;                                   // [qt_h + 1]
     __shared__ int s_rbound[8];                                          // first x of root i (i >= 1)
-    static_assert(sizeof(s_idx3) >= 8192 + 4096, "geometric-key tables");
-    const bool use_tab = cf_geom && L.qt_xtab != nullptr;              // (qt_w < 8192 - 16 and qt_h < 4096 - 16: the host's condition)
+    static_assert(sizeof(s_idx3) >= TR::XTAB + TR::YTAB, "geometric-key tables");
+    const bool use_tab = cf_geom && L.qt_xtab != nullptr && (!TR::LEVEL || (L.qt_w < TR::XTAB && L.qt_h < TR::YTAB));              // (qt_w < 8192 - 16 and qt_h < 4096 - 16: the host's condition)
     auto root_of = [&](int x) { return min((int)((float)x / hX), nIni - 1); };      // vpIniNodes[kp.pt.x/hX]
     // the tables depend on the level geometry alone: the host builds them once per configuration (hs_plan.hip, quadtree_build_tables: the same
     // expressions, IEEE float division and multiplication), the workgroup copies them with 16-byte loads when it needs them — i.e. when it
@@ -196,7 +224,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
         if (use_tab) {
             int r = 0;
             for (int i = 1; i < nIni; i++) r += x >= s_rbound[i];
-            return (int)(((uint32_t)r << (2 * DH)) | spread(xtab[min(x, L.qt_w)]) | (spread(ytab[min(y, L.qt_h)]) << 1));
+            return (int)(((uint32_t)r << (2 * DH)) | spread((uint32_t)xtab[min(x, L.qt_w)] >> TR::DH_LESS) | (spread((uint32_t)ytab[min(y, L.qt_h)] >> TR::DH_LESS) << 1));
         }
         const int r = root_of(x);
         int x0 = (int16_t)(int)(hX * (float)r), x1 = (int16_t)(int)(hX * (float)(r + 1)), y0 = 0, y1 = (int16_t)L.qt_h;
@@ -215,7 +243,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
     //      below (a third of the level-0 workgroup's time: item scan, run search, record fetch, key computation, LDS atomics) only runs when
     //      the points themselves are needed: point-domain passes (clustered corners, > 65535 points, HS_QT_POINT_DOMAIN) or the debug taps.
     //      Whatever happens, the workgroup leaves both global arrays ZERO for the next call.
-    const bool have_keys = qhist != nullptr && L.qt_hist_off != 0xFFFFFFFFu;    // uniform; the level has key tables (nIni <= 8)
+    const bool have_keys = !TR::LEVEL && qhist != nullptr && L.qt_hist_off != 0xFFFFFFFFu;    // uniform; the level has key tables (nIni <= 8)
     const int ncell = nIni << (2 * DH);                                         // deepest cells (have_keys: nIni <= 8, so <= 8192)
     uint32_t* const ghist = have_keys ? qhist + (size_t)img * qhist_img_stride + L.qt_hist_off : nullptr;
     unsigned long long* const gbest = have_keys ? qbest + (size_t)img * qbest_img_stride + L.qt_best_off : nullptr;
@@ -231,7 +259,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
         if (have_keys) {
             // the deepest level of the pyramid comes from global memory (16 bytes per thread and round: <= 8192 cells are ONE round) and goes back
             // to zero there; the levels above it are written in full by the pyramid build below, so nothing else needs clearing
-            if (tid < 16) s_wave[tid] = 0;
+            if (tid < QT_T / 64) s_wave[tid] = 0;
             __syncthreads();
             int local = 0;
             for (int i = tid * 4; i < ncell / 2; i += QT_T * 4) {
@@ -289,7 +317,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                 c0 = ci * L.ncols + gj * L.grp_cells;
                 k = min(max(ccnt[c0], 0), min(L.grp_cells, L.ncols - gj * L.grp_cells) * ccap);
             }
-            int tot; const int pre = block_scan_excl(k, s_wave, sflip, tot);
+            int tot; const int pre = block_scan_excl<QT_T>(k, s_wave, sflip, tot);
             if (tid < ni) { s_pre[tid] = (uint32_t)pre; s_src0[tid] = (uint32_t)(c0 * ccap - pre); }      // (no division per record later)
             if (tid == 0) s_pre[ni] = (uint32_t)tot;
             if (nitem <= QT_T && tot <= QT_PTS) keys_to_global = false;
@@ -525,7 +553,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                 w[0] = c;
                 if (ex && (d == P || c == 1)) flags = 1u;
             }
-            int tot; int pre = block_scan_excl(__popc(flags), s_wave, sflip, tot);
+            int tot; int pre = block_scan_excl<QT_T>(__popc(flags), s_wave, sflip, tot);
             if (single) { if (flags) { C.ekey[pre] = (uint16_t)((d << 13) | bblock); C.cnt[pre] = w[0]; } }
             else if (flags) {
 #pragma unroll
@@ -579,6 +607,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
         // leave the count domain when a node that may be split has no children in the pyramid: label the points, build the rectangles
         if (cm && (!phase2 || (T_prev > 0 && (int)(s_ekey[cur][0] >> 13) >= DH))) {
             const QtNodes C = view(cur);
+            if constexpr (TR::LEVEL) { if (tid == 0) atomicAdd(&g_qt_level_fallbacks, 1u); }
             if (have_keys && !gathered) { gather(false); zero_gbest(); }      // the point-domain passes need the points after all: fetch them now (keys into s_pnode / pnode)
             relabel_from_keys(C);                       // the pyramid is dead from here on: its LDS becomes the rectangles
             for (int i = tid; i < S; i += QT_T) {
@@ -611,7 +640,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                 flags[k] = (i < S && C.cnt[i] > 1) ? 1 : 0;
                 local += flags[k];
             }
-            int tot; int pre = block_scan_excl(local, s_wave, sflip, tot);
+            int tot; int pre = block_scan_excl<QT_T>(local, s_wave, sflip, tot);
 #pragma unroll
             for (int k = 0; k < (QT_M + QT_T - 1) / QT_T; k++) {
                 int i = tid * ((QT_M + QT_T - 1) / QT_T) + k;
@@ -743,7 +772,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                 nc[k] = (cc4[k].x > 0) + (cc4[k].y > 0) + (cc4[k].z > 0) + (cc4[k].w > 0) + (((cc4[k].x > 1) + (cc4[k].y > 1) + (cc4[k].z > 1) + (cc4[k].w > 1)) << 16);
                 local += nc[k];
             }
-            int tot; const int pre0 = block_scan_excl((int)local, s_wave, sflip, tot);
+            int tot; const int pre0 = block_scan_excl<QT_T>((int)local, s_wave, sflip, tot);
             if (tid == 0) { s_misc[1] = E; s_misc[3] = tot; }
             __syncthreads();
             if (phase2) {
@@ -802,7 +831,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
                 fl[k] = (i < S) && !(r >= 0 && r < P);
                 local += fl[k];
             }
-            int pre = block_scan_excl(local, s_wave, sflip, nsurv);
+            int pre = block_scan_excl<QT_T>(local, s_wave, sflip, nsurv);
 #pragma unroll
             for (int k = 0; k < (QT_M + QT_T - 1) / QT_T; k++) {
                 int i = tid * ((QT_M + QT_T - 1) / QT_T) + k;
@@ -954,7 +983,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
         static_assert(sizeof(ccount) >= (2 * QT_M + MAXT) * 4, "tile counters");
         const int ntx = (L.w + 63) >> 6, ntiles = ntx * ((L.h + 63) >> 6);
         if (ntiles <= MAXT) {
-            constexpr int TPT = MAXT / QT_T;                           // tiles per thread in the scan
+            constexpr int TPT = (MAXT + QT_T - 1) / QT_T;                           // tiles per thread in the scan
             for (int t = tid; t < ntiles; t += QT_T) tcnt[t] = 0;
             __syncthreads();
             int tile[(QT_M + QT_T - 1) / QT_T];
@@ -972,7 +1001,7 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(const HsLevel* __restrict__ l
             int c[TPT], local = 0;
 #pragma unroll
             for (int k = 0; k < TPT; k++) { const int t = tid * TPT + k; c[k] = t < ntiles ? (int)tcnt[t] : 0; local += c[k]; }
-            int tot; int pre = block_scan_excl(local, s_wave, sflip, tot);
+            int tot; int pre = block_scan_excl<QT_T>(local, s_wave, sflip, tot);
 #pragma unroll
             for (int k = 0; k < TPT; k++) { const int t = tid * TPT + k; if (t < ntiles) tcnt[t] = (uint32_t)pre; pre += c[k]; }
             __syncthreads();
@@ -999,12 +1028,14 @@ void hs_launch_quadtree(const HsLevel* d_lv, int nlevels, int batch, int total_c
     dim3 grid(level_count, batch, 1);
     // more workgroups than CUs and every list fits the small instance: two workgroups per CU (77 KB of LDS each) instead of rounds of 256
     const bool small = list_mode == 1 && (long long)level_count * batch > 256;
-#define QT_LAUNCH(M_, PTS_, RECT_, scratch_) hipLaunchKernelGGL((k_quadtree<M_, PTS_, RECT_>), grid, dim3(QT_T), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride, \
+#define QT_LAUNCH(M_, PTS_, RECT_, T_, scratch_) hipLaunchKernelGGL((k_quadtree<M_, PTS_, RECT_, T_>), grid, dim3(T_), 0, s, d_lv, nlevels, total_cells, cand, cell_count, cand_img_stride, \
                            pts_xy, pts_sk, pt_node, cand_count, sel_xys, sel_count, sel_img_stride, sel_perm, force_point_domain, level_first, \
                            qhist, qbest, qhist_img_stride, qbest_img_stride, keep_points, scratch_)
-    if (list_mode == 2) QT_LAUNCH(HS_QT_LARGE_NODES, 0, true, rect_scratch);      // a quota above HS_QT_MAX_NODES - 8 (the reference's init extractor of its "Imaging" camera: 9000 features @1.4 -> 2758 on level 0)
-    else if (small) QT_LAUNCH(QT_M_SMALL, 0, false, nullptr);
-    else QT_LAUNCH(HS_QT_MAX_NODES, QT_PTS_BIG, false, nullptr);
+    if (list_mode == 2) QT_LAUNCH(HS_QT_LARGE_NODES, 0, true, HS_QT_THREADS, rect_scratch);      // a quota above HS_QT_MAX_NODES - 8 (the reference's init extractor of its "Imaging" camera: 9000 features @1.4 -> 2758 on level 0)
+    else if (list_mode == 3 && qhist == nullptr) QT_LAUNCH(HS_QT_LEVEL_NODES, QT_PTS_LEVEL, false, 256, nullptr);      // the level instance (the caller has asked hs_quadtree_small_level)
+    else if (list_mode == 4 && qhist == nullptr) QT_LAUNCH(HS_QT_LEVEL_NODES, QT_PTS_LEVEL, false, 512, nullptr);      // ... with eight waves (HS_QT_SMALL_THREADS=512)
+    else if (small) QT_LAUNCH(QT_M_SMALL, 0, false, HS_QT_THREADS, nullptr);
+    else QT_LAUNCH(HS_QT_MAX_NODES, QT_PTS_BIG, false, HS_QT_THREADS, nullptr);
 #undef QT_LAUNCH
 }
 

@@ -422,6 +422,12 @@ class ORBExtractor:
         N.check(self._h, self._lib.hs_orb_debug_selected(self._h, image, level, out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return out[:n.value].copy()
 
+    def debug_quadtree_replay(self, level_first, level_count, reps=20, threads=0):
+        """mean milliseconds of the last call's quadtree launch restricted to the given levels (hs_orb_debug_quadtree_replay)"""
+        ms = C.c_float()
+        N.check(self._h, self._lib.hs_orb_debug_quadtree_replay(self._h, level_first, level_count, threads, reps, C.byref(ms)))
+        return float(ms.value)
+
 
 def stereo_params(camera, settings=None, size_ref=31.0):
     settings = settings or FeatureMatcherSettings()

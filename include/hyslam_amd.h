@@ -1260,6 +1260,14 @@ int  hs_orb_set_debug(hs_orb* h, int on);
 int  hs_orb_debug_candidates(hs_orb* h, int image, int level, int32_t* xys, int cap, int32_t* n);
 /* keypoints kept by DistributeOctTree for that level, in list order: (x,y,score) level coords; :475-487 */
 int  hs_orb_debug_selected(hs_orb* h, int image, int level, int32_t* xys, int cap, int32_t* n);
+/* measurement: enqueues the quadtree launch of the last call again, for the levels [level_first, level_first + level_count) alone, `reps` times on
+ * the handle's stream, and writes the mean milliseconds per launch (HIP events).  Same inputs, same outputs: the launch only reads what the FAST
+ * stage left.  threads: 0 = the instance the call itself used for a single launch of all levels, 256 / 512 = the four- / eight-wave level instance (every
+ * level of the range must fit it).  Only after a call that ran without the FAST keys (more frames than HS_FAST_KEYS_MAX_BATCH, or HS_FAST_KEYS=0); synchronous. */
+/* (image, level) workgroups of the quadtree kernel's level instance that had to leave its count domain (a node deeper than its histogram pyramid) since
+ * the process started or the last reset, on the current device; synchronises the device; -1 on a HIP error */
+long long hs_debug_quadtree_level_fallbacks(int reset);
+int  hs_orb_debug_quadtree_replay(hs_orb* h, int level_first, int level_count, int threads, int reps, float* ms_per_launch);
 
 #ifdef __cplusplus
 }
