@@ -96,6 +96,39 @@ class PoseResult(C.Structure):
                 ("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("status", C.c_int32)]
 
 
+# hs_pnp_* (include/hyslam_amd.h): relocalisation, EPnP inside RANSAC
+PNP_CORR_DTYPE = np.dtype([("Xw", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("sigma2", "<f4"), ("kp", "<i4"), ("_pad", "<i4")])
+PNP_PARAMS_DTYPE = np.dtype([("probability", "<f8"), ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("min_set", "<i4"), ("epsilon", "<f4"), ("th2", "<f4"),
+                             ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("_pad", "<i4"), ("seed", "<u8")])
+PNP_STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_Tcw", "<f4", 16)])
+PNP_RESULT_DTYPE = np.dtype([("Tcw_d", "<f8", 16), ("Tcw", "<f4", 16), ("status", "<i4"), ("n_inliers", "<i4"), ("at_iteration", "<i4"), ("iterations", "<i4"),
+                             ("hypotheses_run", "<i4"), ("refines_run", "<i4")])
+HS_PNP_TOO_FEW, HS_PNP_REFINED, HS_PNP_BEST, HS_PNP_NONE, HS_PNP_NONFINITE = 0, 1, 2, 3, 4
+HS_PNP_MAX_SET = _header_constant("HS_PNP_MAX_SET")
+
+
+class PnpCorr(C.Structure):
+    _fields_ = [("Xw", C.c_float * 3), ("u", C.c_float), ("v", C.c_float), ("sigma2", C.c_float), ("kp", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PnpParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float),
+                ("th2", C.c_float), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("_pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PnpPlan(C.Structure):
+    _fields_ = [("min_inliers", C.c_int32), ("epsilon", C.c_float), ("max_iterations", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PnpState(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("best_inliers", C.c_int32), ("best_Tcw", C.c_float * 16)]
+
+
+class PnpResult(C.Structure):
+    _fields_ = [("Tcw_d", C.c_double * 16), ("Tcw", C.c_float * 16), ("status", C.c_int32), ("n_inliers", C.c_int32), ("at_iteration", C.c_int32),
+                ("iterations", C.c_int32), ("hypotheses_run", C.c_int32), ("refines_run", C.c_int32)]
+
+
 # hs_pose_view / hs_track_* (include/hyslam_amd.h): frame tracking on resident tables
 POSE_VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), ("_pad", "<f4")])
 TRACK_RESULT_DTYPE = np.dtype([("status", "<i4"), ("used_wide", "<i4"), ("n_narrow", "<i4"), ("n_wide", "<i4"), ("n_matches_map", "<i4"), ("n_inliers", "<i4"),
@@ -252,6 +285,7 @@ EXPORTS = [
     "hs_local_keyframes", "hs_local_keyframes_device", "hs_local_points", "hs_local_points_device", "hs_local_points_work_bytes",
     "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
+    "hs_pnp_plan", "hs_pnp_state_init", "hs_pnp_work_bytes", "hs_pnp_iterate", "hs_pnp_iterate_device",
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
     "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
     "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes",
@@ -401,6 +435,11 @@ def lib():
     L.hs_pose_optimize_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.hs_pose_work_bytes.argtypes, L.hs_pose_work_bytes.restype = [C.c_int, C.c_int64], C.c_size_t
     L.hs_pose_edges_device.argtypes = [vp, C.POINTER(FrameView), vp, C.c_int, vp, f32, vp, C.c_int, vp, vp, vp]
+    L.hs_pnp_plan.argtypes = [C.c_int, C.POINTER(PnpParams), C.POINTER(PnpPlan)]
+    L.hs_pnp_state_init.argtypes, L.hs_pnp_state_init.restype = [C.POINTER(PnpState)], None
+    L.hs_pnp_work_bytes.argtypes, L.hs_pnp_work_bytes.restype = [C.c_int, C.c_int64, C.c_int], C.c_size_t
+    L.hs_pnp_iterate.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.hs_pnp_iterate_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.hs_pose_views_device.argtypes = [vp, vp, vp, vp]
     L.hs_search_by_projection_posed_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, C.c_int, C.POINTER(ProjParams), vp, vp, vp, vp]
     L.hs_local_map_search_posed_device.argtypes = [vp, C.POINTER(KfTable), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameView), vp, vp,

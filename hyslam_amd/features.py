@@ -863,6 +863,118 @@ class Optimizer:
         return res["Tcw"][0].reshape(4, 4).copy(), outlier, int(res["n_good"][0])
 
 
+class PnPsolver:
+    """HYSLAM::PnPsolver (src/estimators/PnPsolver.h:61-72) on flat arrays: EPnP inside RANSAC for one candidate key frame, computed by
+    hs_pnp_iterate (include/hyslam_amd.h).  Built from the frame's arrays — kps (KP_DTYPE), the landmark positions and matches
+    (matches[i] = landmark index of keypoint i, or < 0: no landmark / a bad one), in ascending keypoint index as the reference's constructor walks
+    them — or from ready correspondences (PNP_CORR_DTYPE).  camera: (fx, fy, cx, cy).  `seed` replaces the process-wide rand() stream the
+    reference's solvers share; `draws` (uint32 [cap, HS_PNP_MAX_SET]) directs the samples of the first cap iterations."""
+
+    def __init__(self, camera, kps=None, landmarks=None, matches=None, corrs=None, n_keypoints=None, size_ref=31.0, sigma_ref=1.0, seed=0, draws=None,
+                 extractor=None):
+        self._ex = extractor or ORBExtractor()
+        if corrs is None:
+            corrs = self.correspondences(kps, landmarks, matches, size_ref, sigma_ref)
+            n_keypoints = len(kps)
+        self.corrs = np.ascontiguousarray(corrs, N.PNP_CORR_DTYPE).reshape(-1)
+        self.n_keypoints = int(n_keypoints) if n_keypoints is not None else (int(self.corrs["kp"].max()) + 1 if len(self.corrs) else 0)
+        self.camera = tuple(np.float32(c) for c in camera[:4])
+        self.seed = int(seed)
+        self.draws = None if draws is None else np.ascontiguousarray(draws, np.uint32).reshape(-1, N.HS_PNP_MAX_SET)
+        self.state = np.zeros(1, N.PNP_STATE_DTYPE)
+        self.best_mask = np.zeros(len(self.corrs), np.uint8)
+        self.result = None
+        self.SetRansacParameters()
+
+    @staticmethod
+    def correspondences(kps, landmarks, matches, size_ref=31.0, sigma_ref=1.0):
+        """PnPsolver.cc:69-116: one record per keypoint i with 0 <= matches[i] < len(landmarks), in ascending i; sigma2 = determineSigma2(kp.size)
+        in float, the quantity whose reciprocal hs_pose_edge::inv_sigma2 holds."""
+        matches = np.asarray(matches, np.int64).reshape(-1)
+        pos = landmarks["pos"] if getattr(landmarks, "dtype", None) is not None and landmarks.dtype.names else np.asarray(landmarks, np.float32).reshape(-1, 3)
+        idx = np.nonzero((matches >= 0) & (matches < len(pos)))[0]
+        c = np.zeros(len(idx), N.PNP_CORR_DTYPE)
+        c["Xw"], c["u"], c["v"], c["kp"] = pos[matches[idx]], kps["x"][idx], kps["y"][idx], idx
+        s = kps["size"][idx].astype(np.float32) / np.float32(size_ref)
+        c["sigma2"] = np.float32(sigma_ref) * (s * s)
+        return c
+
+    def params(self):
+        p = np.zeros(1, N.PNP_PARAMS_DTYPE)
+        p["probability"], p["min_inliers"], p["max_iterations"], p["min_set"], p["epsilon"], p["th2"] = self._ransac
+        p["fx"], p["fy"], p["cx"], p["cy"] = self.camera
+        p["seed"] = self.seed
+        return p
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4, th2=5.991):
+        """PnPsolver::SetRansacParameters with the header's defaults (PnPsolver.h:63); the effective values are in self.plan"""
+        self._ransac = (probability, minInliers, maxIterations, minSet, epsilon, th2)
+        plan, p = N.PnpPlan(), self.params()
+        st = self._ex._lib.hs_pnp_plan(len(self.corrs), p.ctypes.data_as(C.POINTER(N.PnpParams)), C.byref(plan))
+        if st != N.HS_OK:
+            raise HsError(st, "hs_pnp_plan: bad RANSAC parameters")
+        self.plan = (plan.min_inliers, plan.epsilon, plan.max_iterations)
+
+    @staticmethod
+    def iterate_batch(solvers, nIterations):
+        """iterate(nIterations) of every solver in ONE call (the candidates of a relocalisation): a list of iterate's tuples.  A pose that holds a NaN or an
+        infinity (HS_PNP_NONFINITE) is handed out as no pose with bNoMore true, also where Refine() produced it; solver.result keeps the record."""
+        ex, Q = solvers[0]._ex, len(solvers)
+        par = np.concatenate([s.params() for s in solvers])
+        off = np.zeros(Q + 1, np.int64)
+        off[1:] = np.cumsum([len(s.corrs) for s in solvers])
+        corrs = np.concatenate([s.corrs for s in solvers])
+        cap = max([0] + [len(s.draws) for s in solvers if s.draws is not None])
+        draws = np.zeros((Q, cap, N.HS_PNP_MAX_SET), np.uint32)
+        for q, s in enumerate(solvers):
+            if cap and (s.draws is None or len(s.draws) < cap):    # a table shorter than the call's: the generator's own words fill it
+                draws[q] = s._generator_words(cap)
+            if s.draws is not None:
+                draws[q, :len(s.draws)] = s.draws
+        states = np.concatenate([s.state for s in solvers])
+        best = np.concatenate([s.best_mask for s in solvers])
+        inl, res = np.zeros(len(corrs), np.uint8), np.zeros(Q, N.PNP_RESULT_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_pnp_iterate(ex._h, Q, p(par), p(off), p(corrs), int(nIterations), p(draws) if cap else None, cap, p(states), p(best), p(res),
+                                              p(inl)))
+        out = []
+        for q, s in enumerate(solvers):
+            s.state, s.best_mask, s.result = states[q:q + 1].copy(), best[off[q]:off[q + 1]].copy(), res[q].copy()
+            status = int(res["status"][q])
+            no_more = status != N.HS_PNP_REFINED
+            if status in (N.HS_PNP_REFINED, N.HS_PNP_BEST):
+                flags = np.zeros(s.n_keypoints, bool)
+                flags[s.corrs["kp"][inl[off[q]:off[q + 1]] != 0]] = True
+                out.append((res["Tcw"][q].reshape(4, 4).copy(), no_more, flags, int(res["n_inliers"][q])))
+            else:
+                out.append((None, no_more, np.zeros(0, bool), 0))
+        return out
+
+    def _generator_words(self, cap):
+        """the words the generator of DESIGN.md D18 gives iterations 0 .. cap-1: SplitMix64's finaliser on the counters seed + it * min_set + k (the
+        elements of synth.splitmix64(0, .) from index `seed` on, formed directly because a seed may be any 64-bit number)"""
+        ms = self._ransac[3]
+        w = np.zeros((cap, N.HS_PNP_MAX_SET), np.uint32)
+        with np.errstate(over="ignore"):
+            c = np.uint64(self.seed) + np.arange(cap * ms, dtype=np.uint64)
+            z = (c + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            z = z ^ (z >> np.uint64(31))
+        w[:, :ms] = (z >> np.uint64(32)).astype(np.uint32).reshape(cap, ms)
+        return w
+
+    def iterate(self, nIterations):
+        """cv::Mat iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers): (Tcw float32 4x4 or None, bNoMore, vbInliers by
+        KEYPOINT INDEX — empty without a pose, as the reference clears it —, nInliers).  The state persists across calls as the reference's does."""
+        return PnPsolver.iterate_batch([self], nIterations)[0]
+
+    def find(self):
+        """cv::Mat find(vector<bool> &vbInliers, int &nInliers): iterate(mRansacMaxIts) without the flag"""
+        Tcw, _, flags, n = self.iterate(self.plan[2])
+        return Tcw, flags, n
+
+
 class _DevBuf:
     """a block of device memory on the extractor's device for FrameTracker's numpy calls (hs_device_alloc / hs_device_copy / hs_device_free)"""
 

@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h", "HipPnPsolver.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
@@ -85,7 +85,10 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    const std::vector<HYSLAM::KeyFrame*> gone = kg.cullRedundant(pkf, pmap, kcp);\n"
              "    struct { int N_max_local_keyframes = 80; int N_neighbor_keyframes = 10; } tlp;   // TrackLocalMapParameters' two fields (its header needs g2o)\n"
              "    const HYSLAM::HipKeyFrameGraph::LocalMap lmap = kg.localMap(*pf, pmap, tlp);\n"
-             "    return (int)k.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size() + (int)lmap.map_points.size();\n}\n")
+             "    std::vector<HYSLAM::MapPoint*> mps; HYSLAM::HipPnPsolver pnp(*pf, mps, 7); pnp.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);\n"
+             "    bool no_more; std::vector<bool> inl; int n_inl; cv::Mat Tcw = pnp.iterate(5, no_more, inl, n_inl); Tcw = pnp.find(inl, n_inl);\n"
+             "    std::vector<HYSLAM::HipPnPsolver*> cand(1, &pnp); std::vector<HYSLAM::HipPnPsolver::Result> pres; HYSLAM::HipPnPsolver::iterate(cand, 5, pres);\n"
+             "    return (int)k.size() + n_inl + (int)pres.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size() + (int)lmap.map_points.size();\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
           ["-I" + os.path.join(ROOT, "tests", "cpp", "thirdparty_stubs"), "-I" + host_dir, "-I" + os.path.join(ROOT, "include"), tu]
