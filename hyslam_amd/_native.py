@@ -129,6 +129,42 @@ class PnpResult(C.Structure):
                 ("iterations", C.c_int32), ("hypotheses_run", C.c_int32), ("refines_run", C.c_int32)]
 
 
+# hs_sim3_* (include/hyslam_amd.h): loop closing, Horn's closed form inside RANSAC
+SIM3_CORR_DTYPE = np.dtype([("X1c", "<f4", 3), ("sigma2_1", "<f4"), ("X2c", "<f4", 3), ("sigma2_2", "<f4"), ("idx1", "<i4"), ("_pad", "<i4", 3)])
+SIM3_PARAMS_DTYPE = np.dtype([("probability", "<f8"), ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("fix_scale", "<i4"), ("_pad", "<i4"),
+                              ("fx1", "<f4"), ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"), ("fy2", "<f4"), ("cx2", "<f4"), ("cy2", "<f4"),
+                              ("seed", "<u8")])
+SIM3_STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3), ("s", "<f4"), ("T12", "<f4", 16), ("_pad", "<i4")])
+SIM3_RESULT_DTYPE = np.dtype([("T12", "<f4", 16), ("R", "<f4", 9), ("t", "<f4", 3), ("s", "<f4"), ("status", "<i4"), ("n_inliers", "<i4"), ("at_iteration", "<i4"),
+                              ("iterations", "<i4"), ("hypotheses_run", "<i4")])
+HS_SIM3_TOO_FEW, HS_SIM3_FOUND, HS_SIM3_CONTINUE, HS_SIM3_EXHAUSTED, HS_SIM3_NONFINITE = 0, 1, 2, 3, 4
+HS_SIM3_DRAW_STRIDE = _header_constant("HS_SIM3_DRAW_STRIDE")
+
+
+class Sim3Corr(C.Structure):
+    _fields_ = [("X1c", C.c_float * 3), ("sigma2_1", C.c_float), ("X2c", C.c_float * 3), ("sigma2_2", C.c_float), ("idx1", C.c_int32), ("_pad", C.c_int32 * 3)]
+
+
+class Sim3Params(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("fix_scale", C.c_int32), ("_pad", C.c_int32),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float), ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float),
+                ("cy2", C.c_float), ("seed", C.c_uint64)]
+
+
+class Sim3Plan(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("epsilon", C.c_float)]
+
+
+class Sim3State(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("best_inliers", C.c_int32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("T12", C.c_float * 16),
+                ("_pad", C.c_int32)]
+
+
+class Sim3Result(C.Structure):
+    _fields_ = [("T12", C.c_float * 16), ("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("status", C.c_int32), ("n_inliers", C.c_int32),
+                ("at_iteration", C.c_int32), ("iterations", C.c_int32), ("hypotheses_run", C.c_int32)]
+
+
 # hs_pose_view / hs_track_* (include/hyslam_amd.h): frame tracking on resident tables
 POSE_VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), ("_pad", "<f4")])
 TRACK_RESULT_DTYPE = np.dtype([("status", "<i4"), ("used_wide", "<i4"), ("n_narrow", "<i4"), ("n_wide", "<i4"), ("n_matches_map", "<i4"), ("n_inliers", "<i4"),
@@ -286,6 +322,7 @@ EXPORTS = [
     "hs_landmark_gather_device", "hs_local_map_work_bytes", "hs_local_map_search_device",
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
     "hs_pnp_plan", "hs_pnp_state_init", "hs_pnp_work_bytes", "hs_pnp_iterate", "hs_pnp_iterate_device",
+    "hs_sim3_plan", "hs_sim3_state_init", "hs_sim3_work_bytes", "hs_sim3_iterate", "hs_sim3_iterate_device",
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
     "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
     "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes",
@@ -440,6 +477,11 @@ def lib():
     L.hs_pnp_work_bytes.argtypes, L.hs_pnp_work_bytes.restype = [C.c_int, C.c_int64, C.c_int], C.c_size_t
     L.hs_pnp_iterate.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.hs_pnp_iterate_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.hs_sim3_plan.argtypes = [C.c_int, C.POINTER(Sim3Params), C.POINTER(Sim3Plan)]
+    L.hs_sim3_state_init.argtypes, L.hs_sim3_state_init.restype = [C.POINTER(Sim3State)], None
+    L.hs_sim3_work_bytes.argtypes, L.hs_sim3_work_bytes.restype = [C.c_int, C.c_int64, C.c_int], C.c_size_t
+    L.hs_sim3_iterate.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.hs_sim3_iterate_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.hs_pose_views_device.argtypes = [vp, vp, vp, vp]
     L.hs_search_by_projection_posed_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, C.c_int, C.POINTER(ProjParams), vp, vp, vp, vp]
     L.hs_local_map_search_posed_device.argtypes = [vp, C.POINTER(KfTable), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameView), vp, vp,

@@ -975,6 +975,140 @@ class PnPsolver:
         return Tcw, flags, n
 
 
+class Sim3Solver:
+    """HYSLAM::Sim3Solver (src/estimators/Sim3Solver.h) on flat arrays: Horn's closed form inside RANSAC for one loop candidate, computed by
+    hs_sim3_iterate (include/hyslam_amd.h).  Built from ready correspondences (SIM3_CORR_DTYPE; `correspondences` gathers them as the
+    reference's constructor does) and the two cameras (fx, fy, cx, cy).  n_matches is mN1, the length of vpMatched12 and of the returned vbInliers.
+    `seed` replaces the process-wide generator the reference's solvers share; `draws` (uint32 [cap, HS_SIM3_DRAW_STRIDE]) directs the samples of the
+    first cap iterations."""
+
+    def __init__(self, camera1, camera2, corrs, n_matches=None, fix_scale=True, seed=0, draws=None, extractor=None):
+        self._ex = extractor or ORBExtractor()
+        self.corrs = np.ascontiguousarray(corrs, N.SIM3_CORR_DTYPE).reshape(-1)
+        self.n_matches = int(n_matches) if n_matches is not None else (int(self.corrs["idx1"].max()) + 1 if len(self.corrs) else 0)
+        self.camera1, self.camera2 = tuple(np.float32(c) for c in camera1[:4]), tuple(np.float32(c) for c in camera2[:4])
+        self.fix_scale, self.seed = bool(fix_scale), int(seed)
+        self.draws = None if draws is None else np.ascontiguousarray(draws, np.uint32).reshape(-1, N.HS_SIM3_DRAW_STRIDE)
+        self.state = np.zeros(1, N.SIM3_STATE_DTYPE)
+        self.best_mask = np.zeros(len(self.corrs), np.uint8)
+        self.result = None
+        self.SetRansacParameters()
+
+    @staticmethod
+    def correspondences(matched12, points1, pos1, pos2, bad1, bad2, index1, index2, kps1, kps2, Tcw1, Tcw2, size_ref=31.0, sigma_ref=1.0):
+        """Sim3Solver.cc:66-107.  matched12[i1]: the landmark of key frame 2 matched to keypoint i1 of key frame 1, or < 0 (a null match); points1[i1]:
+        key frame 1's own landmark at i1, or < 0; pos1 / pos2 [L, 3]: world positions; bad1 / bad2 [L]: isBad(); index1 / index2 [L]:
+        GetIndexInKeyFrame in the landmark's own key frame (< 0: not seen); kps1 / kps2: KP_DTYPE; Tcw1 / Tcw2: 4x4 poses.  Walks i1 in ascending order
+        and skips a null match, a null own point, a bad point on either side and a negative index on either side.  X = Rcw Xw + tcw is one product
+        (double accumulation in index order, one narrowing: DESIGN.md D19)."""
+        matched12, points1 = np.asarray(matched12, np.int64).reshape(-1), np.asarray(points1, np.int64).reshape(-1)
+        i1 = np.nonzero((matched12 >= 0) & (points1 >= 0))[0]
+        m1, m2 = points1[i1], matched12[i1]
+        keep = ~(np.asarray(bad1, bool)[m1] | np.asarray(bad2, bool)[m2])
+        i1, m1, m2 = i1[keep], m1[keep], m2[keep]
+        k1, k2 = np.asarray(index1, np.int64)[m1], np.asarray(index2, np.int64)[m2]
+        keep = (k1 >= 0) & (k2 >= 0)
+        i1, m1, m2, k1, k2 = i1[keep], m1[keep], m2[keep], k1[keep], k2[keep]
+        c = np.zeros(len(i1), N.SIM3_CORR_DTYPE)
+
+        def to_camera(T, X):
+            T, X = np.asarray(T, np.float32).reshape(4, 4).astype(np.float64), np.asarray(X, np.float32).reshape(-1, 3).astype(np.float64)
+            return np.stack([(((T[i, 0] * X[:, 0] + T[i, 1] * X[:, 1]) + T[i, 2] * X[:, 2]) + T[i, 3]).astype(np.float32) for i in range(3)], 1)
+
+        def sigma2(kps, k):
+            s = kps["size"][k].astype(np.float32) / np.float32(size_ref)
+            return np.float32(sigma_ref) * (s * s)
+        c["X1c"], c["X2c"] = to_camera(Tcw1, np.asarray(pos1, np.float32).reshape(-1, 3)[m1]), to_camera(Tcw2, np.asarray(pos2, np.float32).reshape(-1, 3)[m2])
+        c["sigma2_1"], c["sigma2_2"], c["idx1"] = sigma2(kps1, k1), sigma2(kps2, k2), i1
+        return c
+
+    def params(self):
+        p = np.zeros(1, N.SIM3_PARAMS_DTYPE)
+        p["probability"], p["min_inliers"], p["max_iterations"] = self._ransac
+        p["fix_scale"], p["seed"] = int(self.fix_scale), self.seed
+        p["fx1"], p["fy1"], p["cx1"], p["cy1"] = self.camera1
+        p["fx2"], p["fy2"], p["cx2"], p["cy2"] = self.camera2
+        return p
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        """Sim3Solver::SetRansacParameters with the header's defaults (Sim3Solver.h:41); the effective mRansacMaxIts is self.max_iterations.  Resets
+        mnIterations, as the reference does, and nothing else."""
+        self._ransac = (probability, minInliers, maxIterations)
+        plan, p = N.Sim3Plan(), self.params()
+        st = self._ex._lib.hs_sim3_plan(len(self.corrs), p.ctypes.data_as(C.POINTER(N.Sim3Params)), C.byref(plan))
+        if st != N.HS_OK:
+            raise HsError(st, "hs_sim3_plan: bad RANSAC parameters")
+        self.max_iterations, self.epsilon = plan.max_iterations, plan.epsilon
+        self.state["iterations"] = 0
+
+    @staticmethod
+    def iterate_batch(solvers, nIterations):
+        """iterate(nIterations) of every solver in ONE call (the consistent candidates of LoopClosing::ComputeSim3): a list of iterate's tuples"""
+        ex, Q = solvers[0]._ex, len(solvers)
+        par = np.concatenate([s.params() for s in solvers])
+        off = np.zeros(Q + 1, np.int64)
+        off[1:] = np.cumsum([len(s.corrs) for s in solvers])
+        corrs = np.concatenate([s.corrs for s in solvers])
+        cap = max([0] + [len(s.draws) for s in solvers if s.draws is not None])
+        draws = np.zeros((Q, cap, N.HS_SIM3_DRAW_STRIDE), np.uint32)
+        for q, s in enumerate(solvers):
+            if cap and (s.draws is None or len(s.draws) < cap):    # a table shorter than the call's: the generator's own words fill it
+                draws[q] = s._generator_words(cap)
+            if s.draws is not None:
+                draws[q, :len(s.draws)] = s.draws
+        states = np.concatenate([s.state for s in solvers])
+        best = np.concatenate([s.best_mask for s in solvers])
+        inl, res = np.zeros(len(corrs), np.uint8), np.zeros(Q, N.SIM3_RESULT_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_sim3_iterate(ex._h, Q, p(par), p(off), p(corrs), int(nIterations), p(draws) if cap else None, cap, p(states), p(best), p(res),
+                                               p(inl)))
+        out = []
+        for q, s in enumerate(solvers):
+            s.state, s.best_mask, s.result = states[q:q + 1].copy(), best[off[q]:off[q + 1]].copy(), res[q].copy()
+            status = int(res["status"][q])
+            flags = np.zeros(s.n_matches, bool)                    # vbInliers: always mN1 long (:147)
+            flags[s.corrs["idx1"][inl[off[q]:off[q + 1]] != 0]] = True
+            no_more = status in (N.HS_SIM3_TOO_FEW, N.HS_SIM3_EXHAUSTED)
+            T12 = res["T12"][q].reshape(4, 4).copy() if status in (N.HS_SIM3_FOUND, N.HS_SIM3_NONFINITE) else None
+            out.append((T12, no_more, flags, int(res["n_inliers"][q])))
+        return out
+
+    @staticmethod
+    def find_batch(solvers):
+        """find() of every solver in ONE call: every solver runs to its own mRansacMaxIts (the loop's AND stops each at its plan)"""
+        return [(T12, flags, n) for T12, _, flags, n in Sim3Solver.iterate_batch(solvers, max(s.max_iterations for s in solvers))]
+
+    def _generator_words(self, cap):
+        """the words the generator gives iterations 0 .. cap-1: SplitMix64's finaliser on the counters seed + 3 it + k"""
+        w = np.zeros((cap, N.HS_SIM3_DRAW_STRIDE), np.uint32)
+        with np.errstate(over="ignore"):
+            c = np.uint64(self.seed) + np.arange(cap * 3, dtype=np.uint64)
+            z = (c + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            z = z ^ (z >> np.uint64(31))
+        w[:, :3] = (z >> np.uint64(32)).astype(np.uint32).reshape(cap, 3)
+        return w
+
+    def iterate(self, nIterations):
+        """cv::Mat iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers): (T12 float32 4x4 or None, bNoMore, vbInliers by
+        index into vpMatched12, nInliers).  The state persists across calls as the reference's does."""
+        return Sim3Solver.iterate_batch([self], nIterations)[0]
+
+    def find(self):
+        """cv::Mat find(vector<bool> &vbInliers12, int &nInliers): iterate(mRansacMaxIts) without the flag"""
+        return Sim3Solver.find_batch([self])[0]
+
+    def GetEstimatedRotation(self):
+        return self.state["R"][0].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return self.state["t"][0].copy()
+
+    def GetEstimatedScale(self):
+        return float(self.state["s"][0])
+
+
 class _DevBuf:
     """a block of device memory on the extractor's device for FrameTracker's numpy calls (hs_device_alloc / hs_device_copy / hs_device_free)"""
 

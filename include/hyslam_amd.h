@@ -859,6 +859,79 @@ int  hs_pnp_iterate_device(hs_orb* h, int Q, const hs_pnp_params* params, const 
                            const uint32_t* d_draws, int draw_cap, hs_pnp_state* d_states, uint8_t* d_best_masks, hs_pnp_result* d_results,
                            uint8_t* d_inlier_masks, void* d_work, void* stream);
 
+/* ================= loop closing: Sim3Solver, Horn's closed form inside RANSAC (src/estimators/Sim3Solver.cc) =================
+ * A call takes Q independent problems (the consistent candidates of LoopClosing::ComputeSim3) and runs, for each, what Sim3Solver::iterate(n) runs:
+ * every hypothesis of the call at once (one LANE each: three sampled correspondences, Horn's closed form, the inlier count over all N in both
+ * directions), then, one wave per problem, the walk over the counts in order.  DESIGN.md 5.19 lists the behaviour item by item.  No atomics and no
+ * sum shared between lanes: the same call gives the same bytes.  Two stated rules for what cannot be reproduced:
+ *   - DESIGN.md D19 defines what OpenCV does inside ComputeSim3: every matrix-product entry accumulated in double in index order and narrowed once,
+ *     the eigenvector by a cyclic Jacobi in double (HS_SIM3_EIG_SWEEPS sweeps, + - x / sqrt only), R directly from the quaternion;
+ *   - draws follow D18 with a set of 3: draw k of absolute iteration `it` is element seed + 3 it + k of the SplitMix64 sequence, randi =
+ *     (hi32(r) * avail) >> 32.  A table draws[q][it][k] (uint32, HS_SIM3_DRAW_STRIDE words per iteration, draw_cap iterations per problem)
+ *     overrides it for it < draw_cap. */
+#define HS_SIM3_DRAW_STRIDE 4
+#define HS_SIM3_EIG_SWEEPS 10
+typedef struct hs_sim3_corr {
+    float X1c[3];                      /* Rcw1 * pMP1->GetWorldPos() + tcw1, formed by the caller (:98-99)            */
+    float sigma2_1;                    /* orb_params_KF1.determineSigma2(kp1.size)                                    */
+    float X2c[3];                      /* Rcw2 * pMP2->GetWorldPos() + tcw2 (:101-102)                                */
+    float sigma2_2;
+    int32_t idx1;                      /* mvnIndices1: i1; carried, not read                                          */
+    int32_t _pad[3];
+} hs_sim3_corr;                        /* 48 bytes; arrays are 16-byte aligned */
+typedef struct hs_sim3_params {
+    double probability;                /* SetRansacParameters' arguments (LoopClosing.cc: 0.99, 20, 300)              */
+    int32_t min_inliers, max_iterations;
+    int32_t fix_scale;                 /* mbFixScale: ms12i = 1.0f                                                    */
+    int32_t _pad;
+    float fx1, fy1, cx1, cy1;          /* mK1                                                                         */
+    float fx2, fy2, cx2, cy2;          /* mK2                                                                         */
+    uint64_t seed;                     /* replaces the process-wide generator                                         */
+} hs_sim3_params;                      /* 64 bytes */
+typedef struct hs_sim3_plan_t {        /* (hs_sim3_plan is the function)                                              */
+    int32_t max_iterations;            /* mRansacMaxIts after SetRansacParameters                                     */
+    float epsilon;                     /* (float)minInliers / N                                                       */
+} hs_sim3_plan_t;
+typedef struct hs_sim3_state {         /* what persists between two calls of iterate; the best mask is a u8 [N] array of the caller's */
+    int32_t iterations;                /* mnIterations                                                                */
+    int32_t best_inliers;              /* mnBestInliers                                                               */
+    float R[9], t[3], s;               /* mBestRotation, mBestTranslation, mBestScale                                 */
+    float T12[16];                     /* mBestT12, row-major 4x4                                                     */
+    int32_t _pad;
+} hs_sim3_state;                       /* 128 bytes */
+#define HS_SIM3_TOO_FEW 0              /* N below min_inliers, or below 3: nothing ran (bNoMore true, no pose)        */
+#define HS_SIM3_FOUND 1                /* a hypothesis with more than min_inliers inliers: its pose, bNoMore false    */
+#define HS_SIM3_CONTINUE 2             /* the call's iterations ran out, the plan's did not: no pose, bNoMore false   */
+#define HS_SIM3_EXHAUSTED 3            /* mnIterations reached mRansacMaxIts: no pose, bNoMore true                   */
+#define HS_SIM3_NONFINITE 4            /* HS_SIM3_FOUND whose pose holds a NaN or an infinity                         */
+typedef struct hs_sim3_result {
+    float T12[16];                     /* what iterate returns (zeros without a pose)                                 */
+    float R[9], t[3], s;
+    int32_t status;                    /* HS_SIM3_*                                                                   */
+    int32_t n_inliers;                 /* nInliers (0 without a pose)                                                 */
+    int32_t at_iteration;              /* mnIterations at the return out of the loop (FOUND), else 0                  */
+    int32_t iterations;                /* mnIterations after the call                                                 */
+    int32_t hypotheses_run;            /* hypotheses the call evaluated (all of its range, also past an early return)  */
+} hs_sim3_result;                      /* 136 bytes */
+/* SetRansacParameters (:118-142) for N correspondences: pure host arithmetic (glibc's log and pow).  HS_ERR_INVALID for NULL, N < 0. */
+int  hs_sim3_plan(int N, const hs_sim3_params* params, hs_sim3_plan_t* plan);
+void hs_sim3_state_init(hs_sim3_state* state);   /* everything 0 */
+/* bytes of d_work for a call of Q problems over n_corr_total correspondences that runs at most max_hypotheses hypotheses per problem:
+ * min(n_iterations, the largest params.max_iterations) always serves (the loop's AND). */
+size_t hs_sim3_work_bytes(int Q, int64_t n_corr_total, int max_hypotheses);
+/* Sim3Solver::iterate(n_iterations) for Q problems.  Problem q owns corrs [corr_offsets[q], corr_offsets[q + 1]) and the same range of best_masks
+ * (state, read and written) and inlier_masks (output, u8, 1 = inlier by correspondence; ALWAYS written: all 0 but for HS_SIM3_FOUND / NONFINITE).
+ * draws may be NULL with draw_cap = 0.  Host form: host pointers, synchronous, staged through the handle's scratch.  HS_ERR_INVALID, nothing enqueued
+ * and no output touched: NULL pointers, Q < 1, n_iterations < 1, negative or decreasing offsets, a problem above 2^31 - 1 correspondences,
+ * min_inliers < 0, a state with a negative count (host form only: the device form cannot see it and reads a negative count as 0). */
+int  hs_sim3_iterate(hs_orb* h, int Q, const hs_sim3_params* params, const int64_t* corr_offsets, const hs_sim3_corr* corrs, int n_iterations,
+                     const uint32_t* draws, int draw_cap, hs_sim3_state* states, uint8_t* best_masks, hs_sim3_result* results, uint8_t* inlier_masks);
+/* The same with device pointers, enqueued on `stream` (NULL = the handle's own), nothing synchronises; params and corr_offsets stay host arrays
+ * (the plan is host arithmetic) and are read before the call returns.  d_corrs and d_work (hs_sim3_work_bytes bytes) are 16-byte aligned. */
+int  hs_sim3_iterate_device(hs_orb* h, int Q, const hs_sim3_params* params, const int64_t* corr_offsets, const hs_sim3_corr* d_corrs, int n_iterations,
+                            const uint32_t* d_draws, int draw_cap, hs_sim3_state* d_states, uint8_t* d_best_masks, hs_sim3_result* d_results,
+                            uint8_t* d_inlier_masks, void* d_work, void* stream);
+
 /* ================= frame tracking on resident tables: TrackMotionModel::track + TrackLocalMap::track =================
  * (src/slam/tracking/TrackMotionModel.cpp:14-83, TrackLocalMap.cpp:9-78, src/core/LandMarkMatches.cpp:26-64, Frame::UpdatePoseMatrices,
  * FeatureMatcher.cc:57-176.)  The glue between the device entry points above, as kernels: a pose that a kernel left in HBM feeds the next search,

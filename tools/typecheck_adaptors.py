@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h", "HipPnPsolver.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h", "HipPnPsolver.h", "HipSim3Solver.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
@@ -88,6 +88,10 @@ def compile_mode(ref, host_dir, mode, tmp):
              "    std::vector<HYSLAM::MapPoint*> mps; HYSLAM::HipPnPsolver pnp(*pf, mps, 7); pnp.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);\n"
              "    bool no_more; std::vector<bool> inl; int n_inl; cv::Mat Tcw = pnp.iterate(5, no_more, inl, n_inl); Tcw = pnp.find(inl, n_inl);\n"
              "    std::vector<HYSLAM::HipPnPsolver*> cand(1, &pnp); std::vector<HYSLAM::HipPnPsolver::Result> pres; HYSLAM::HipPnPsolver::iterate(cand, 5, pres);\n"
+             "    HYSLAM::HipSim3Solver sim3(pkf, pkf, mps, true, 7); sim3.SetRansacParameters(0.99, 20, 300);\n"
+             "    cv::Mat T12 = sim3.iterate(5, no_more, inl, n_inl); T12 = sim3.find(inl, n_inl); T12 = sim3.GetEstimatedRotation(); T12 = sim3.GetEstimatedTranslation();\n"
+             "    std::vector<HYSLAM::HipSim3Solver*> loop(1, &sim3); std::vector<HYSLAM::HipSim3Solver::Result> sres; HYSLAM::HipSim3Solver::iterate(loop, 5, sres);\n"
+             "    n_inl += (int)sres.size() + (int)sim3.GetEstimatedScale();\n"
              "    return (int)k.size() + n_inl + (int)pres.size() + (m ? 1 : 0) + (int)best.size() + (int)ent.size() + nrm.rows + (int)lc.size() + (int)rc.size() + (int)con.ordered.size() + vo.max_count + (int)gone.size() + (int)lmap.map_points.size();\n}\n")
     open(tu, "w").write(body)
     cmd = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused", "-Wno-reorder", "-Wno-sign-compare"] + flags + first + inc + \
