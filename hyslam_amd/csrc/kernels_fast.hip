@@ -15,9 +15,11 @@
 // round 2 and 0.143 ms in round 5.
 //   stage   the item's tile (interior + 3 px apron, <= 256 x 70 px) is fetched with 16-byte loads into registers while the PREVIOUS
 //           item is processed, then written to LDS; the only HBM traffic of the kernel is this one read of each level
-//   scan A  quick reject on the four compass points, 4 pixel columns x 8 rows per lane and block: 14 tile rows in registers, reduced to 6
+//   scan A  quick reject on the four compass points, 4 pixel columns x 8 rows per lane and block: the block's 14 tile rows, reduced to 6
 //           bits so that four pixels fit one plain 32-bit ALU operation; the horizontal ring pixels come from the neighbouring lanes (DPP
-//           wave shifts), the vertical differences are shared between the pixels three rows apart; the masks of a block are byte-
+//           wave shifts), the vertical differences are shared between the pixels three rows apart; on wide items a block loads and reduces
+//           only its 8 new rows: the six it shares with the block above and their three difference pairs stay in registers (two sets that
+//           swap roles, no moves; narrow items put their half-waves on different rows and share nothing); the masks of a block are byte-
 //           transposed across lanes (a cluster of hits would otherwise keep one lane busy for 18 rounds) and their bits go to an LDS
 //           list as codes (wave prefix sum of popcounts, one short bit loop per lane)
 //   corners maybe pixels (decoded on dense lanes): the exact compass test picks the ONE polarity a pixel can still be a corner of, and
@@ -598,60 +600,151 @@ __global__ __launch_bounds__(64, (LC == 5 && TR <= 44 ? 4 : 1)) void k_fast_rows
             }
         };
 
-        // ---- scan A: quick reject.  A lane takes 4 pixel columns x 8 rows per block: 14 tile rows in registers, the horizontal ring
-        //      pixels from the neighbouring lanes (DPP wave shifts), all compares as v_pk_*_u16 on two pixels at a time.
+        // ---- scan A: quick reject.  A lane takes 4 pixel columns x 8 rows per block: 14 tile rows (wide items: the 8 the block above has not
+        //      already reduced), the horizontal ring pixels from the neighbouring lanes (DPP wave shifts), four pixels per 32-bit operation.
         FR_T(t3);
         {
             const int yend = 3 + cur.ih;
             const int nblock = (cur.ih + BR * RS - 1) / (BR * RS);               // uniform trip count (the half-waves take different rows)
-            for (int b = 0; b < nblock; b++) {
-                const int y0 = 3 + BR * (RS * b + sub);
+            // Four pixels per 32-bit operation: every byte holds a pixel reduced to 6 bits (q = v >> 2), which leaves two guard bits per
+            // byte, so byte-wise differences never borrow across bytes.  With bias = 0x80 - k per byte, bit 7 of (q_a + bias - q_b) is
+            // set exactly when q_a - q_b >= k (the byte stays within [0x80 - k - 0x3F, 0x80 - k + 0x3F]).  With k = (t + 1) / 4, "b darker than a by more than t" implies q_a - q_b >= k (floor((a - m) / 4)
+            // <= floor(a / 4) - floor(m / 4)), so the byte test is a NECESSARY condition for the exact compass test of the 16-bit version it
+            // replaces (measured: 3.7 % of the pixels pass instead of 3.6 %); the segment test on the full bytes follows as before.
+            // ~26 plain 32-bit ALU operations per row of 4 pixels instead of ~34 packed-16-bit ones, which also issue slower.
+            auto reduce6 = [&](const uint32_t* tp, int k) { return (tp[k * PD] >> 2) & 0x3F3F3F3Fu; };
+            // The block's mask from its centre rows QC / GC (tile rows 3 .. 10 of the block) and its 11 vertical differences.
+            // "x darker than C": bit 7 of (q_C + bias) - q_x; "x brighter": bit 7 of q_x + (bias - q_C).  Vertically the four differences
+            // of a pixel are shared with the pixels three rows above and below it: with D1[y] = G[y] - Q[y+3] and D2[y] = G[y+3] - Q[y],
+            // row c sees "top or bottom darker" = D2[c-3] | D1[c] and "top or bottom brighter" = D1[c-3] | D2[c] — two subtractions per
+            // tile row instead of four per centre row (the same 32-bit values as the direct form, so the masks are the same bits).
+            auto block_mask = [&](const uint32_t* QC, const uint32_t* GC, const uint32_t* D1, const uint32_t* D2, int y0) -> uint32_t {
                 uint32_t M = 0;
-                {
-                    // Four pixels per 32-bit operation: every byte holds a pixel reduced to 6 bits (q = v >> 2), which leaves two guard bits per
-                    // byte, so byte-wise differences never borrow across bytes.  With bias = 0x80 - k per byte, bit 7 of (q_a + bias - q_b) is
-                    // set exactly when q_a - q_b >= k (the byte stays within [0x80 - k - 0x3F, 0x80 - k + 0x3F]).  With k = (t + 1) / 4, "b darker than a by more than t" implies q_a - q_b >= k (floor((a - m) / 4)
-                    // <= floor(a / 4) - floor(m / 4)), so the byte test is a NECESSARY condition for the exact compass test of the 16-bit version it
-                    // replaces (measured: 3.7 % of the pixels pass instead of 3.6 %); the segment test on the full bytes follows as before.
-                    // ~26 plain 32-bit ALU operations per row of 4 pixels instead of ~34 packed-16-bit ones, which also issue slower.
-                    const uint32_t* tp = tile32 + (y0 - 3) * PD + col;
-                    uint32_t Q[BR + 6], G[BR + 6];
 #pragma unroll
-                    for (int k = 0; k < BR + 6; k++) { Q[k] = (tp[k * PD] >> 2) & 0x3F3F3F3Fu; G[k] = Q[k] + kbias; }
-                    // "x darker than C": bit 7 of (q_C + bias) - q_x; "x brighter": bit 7 of q_x + (bias - q_C).  Vertically the four differences
-                    // of a pixel are shared with the pixels three rows above and below it: with D1[y] = G[y] - Q[y+3] and D2[y] = G[y+3] - Q[y],
-                    // row c sees "top or bottom darker" = D2[c-3] | D1[c] and "top or bottom brighter" = D1[c-3] | D2[c] — two subtractions per
-                    // tile row instead of four per centre row (the same 32-bit values as the direct form, so the masks are the same bits).
-                    uint32_t D1[BR + 3], D2[BR + 3];
-#pragma unroll
-                    for (int y = 0; y < BR + 3; y++) { D1[y] = G[y] - Q[y + 3]; D2[y] = G[y + 3] - Q[y]; }
-#pragma unroll
-                    for (int r = 0; r < BR; r++) {
-                        const uint32_t qC = Q[r + 3];
-                        const uint32_t gC = G[r + 3], nC = kbias - qC;
-                        const uint32_t qCm = lane_from_below(qC), qCp = lane_from_above(qC);
-                        const uint32_t qL = __builtin_amdgcn_alignbyte(qC, qCm, 1);          // the pixels 3 columns to the left / right of this lane's four
-                        const uint32_t qR = __builtin_amdgcn_alignbyte(qCp, qC, 3);
-                        const uint32_t dark = (D2[r] | D1[r + 3]) & ((gC - qL) | (gC - qR));           // (top or bottom darker) and (left or right darker)
-                        const uint32_t bright = (D1[r] | D2[r + 3]) & ((qL + nC) | (qR + nC));
-                        M = (M >> 1) | ((dark | bright) & 0x80808080u);                      // row r ends up at bit r of its pixel's byte
-                    }
-                    const int nrow = min(max(yend - y0, 0), BR);                     // rows of this block inside the interior
-                    M &= vmask8 & (((1u << nrow) - 1u) * 0x01010101u);
+                for (int r = 0; r < BR; r++) {
+                    const uint32_t qC = QC[r];
+                    const uint32_t gC = GC[r], nC = kbias - qC;
+                    const uint32_t qCm = lane_from_below(qC), qCp = lane_from_above(qC);
+                    const uint32_t qL = __builtin_amdgcn_alignbyte(qC, qCm, 1);          // the pixels 3 columns to the left / right of this lane's four
+                    const uint32_t qR = __builtin_amdgcn_alignbyte(qCp, qC, 3);
+                    const uint32_t dark = (D2[r] | D1[r + 3]) & ((gC - qL) | (gC - qR));           // (top or bottom darker) and (left or right darker)
+                    const uint32_t bright = (D1[r] | D2[r + 3]) & ((qL + nC) | (qR + nC));
+                    M = (M >> 1) | ((dark | bright) & 0x80808080u);                      // row r ends up at bit r of its pixel's byte
                 }
+                const int nrow = min(max(yend - y0, 0), BR);                     // rows of this block inside the interior
+                M &= vmask8 & (((1u << nrow) - 1u) * 0x01010101u);
                 // The maybe-pixels come in clusters (both sides of a slanted edge): on the bench scene a block has its ~120 hits in ~14 of
                 // its 64 lanes, and the bit loop of emit_mask runs as long as the busiest lane has hits (17.7 rounds on average).  Each lane
                 // therefore keeps byte 0 (its first pixel column) and takes byte j from the lane 4 j to its left in its row of 16 lanes (DPP
                 // row rotate): the four columns of a lane's word are 16 px apart and a cluster's columns land in different lanes (9.3
                 // rounds; 8.4 with the lanes 16 j apart, but then neighbouring list entries come from areas 64 px apart and the ring reads
                 // of the segment test collide in the LDS banks).  corners_and_scores undoes it when it decodes a code.
-                {
-                    const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x124, 0xF, 0xF, false), t2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x128, 0xF, 0xF, false),
-                                   t3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x12C, 0xF, 0xF, false);      // row_ror:4 / 8 / 12
-                    M = (M & 0xFFu) | (t1 & 0xFF00u) | (t2 & 0xFF0000u) | (t3 & 0xFF000000u);
+                const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x124, 0xF, 0xF, false), t2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x128, 0xF, 0xF, false),
+                               t3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x12C, 0xF, 0xF, false);      // row_ror:4 / 8 / 12
+                return (M & 0xFFu) | (t1 & 0xFF00u) | (t2 & 0xFF0000u) | (t3 & 0xFF000000u);
+            };
+            if constexpr (RS == 1) {
+                // Consecutive blocks of a lane start 8 tile rows apart, so tile rows 8 .. 13 of a block are rows 0 .. 5 of the next one and its
+                // differences D1 / D2[8 .. 10] are the next one's D1 / D2[0 .. 2].  What the next block still needs of them is CARRIED in registers
+                // (rows 3 .. 5 reduced and biased, the three difference pairs; rows 0 .. 2 themselves only ever enter D2[0 .. 2]): a block loads and
+                // reduces its 8 new rows and forms its 8 new difference pairs.  The item's first block takes its carry from a prologue over tile
+                // rows 0 .. 5 — what it would have computed anyway — so carried state never crosses items.  Valid because nothing writes the pixel
+                // tile during the scan (corners_and_scores reads it; list and scores start at row th), and because a block that runs has y0 < 3 + ih,
+                // so its rows 0 .. 5 lie below row th: list memory (rows >= th, rewritten between blocks) is only ever read as a block's NEW rows,
+                // exactly as before, and only reaches centre rows that the nrow mask removes.
+                // Two register sets swap roles from block to block (the loop below is unrolled by two: even steps read ca and write cb, odd ones the
+                // reverse), so the carry costs no register moves.  Only the usual hand-over of a block's codes — they fit the list — is part of that
+                // loop (emit_codes); a block whose codes need room first leaves it with its mask, goes through emit_mask (the one copy of the
+                // corner pass, which the carried values are NOT live across: the kernel's register peak is there) and the scan resumes behind it
+                // from a fresh prologue.
+                struct ScanCarry { uint32_t q[3], g[3], d1[3], d2[3]; };
+                auto carried_block = [&](const ScanCarry& in, ScanCarry& out, int y0) -> uint32_t {
+                    const uint32_t* tp = tile32 + (y0 - 3) * PD + col;
+                    uint32_t Q[BR + 3], G[BR + 3];                                   // tile rows 3 .. 13 of the block
+                    uint32_t D1[BR + 3], D2[BR + 3];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { Q[k] = in.q[k]; G[k] = in.g[k]; D1[k] = in.d1[k]; D2[k] = in.d2[k]; }
+#pragma unroll
+                    for (int k = 3; k < BR + 3; k++) { Q[k] = reduce6(tp, k + 3); G[k] = Q[k] + kbias; }
+#pragma unroll
+                    for (int y = 3; y < BR + 3; y++) { D1[y] = G[y - 3] - Q[y]; D2[y] = G[y] - Q[y - 3]; }
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { out.q[k] = Q[BR + k]; out.g[k] = G[BR + k]; out.d1[k] = D1[BR + k]; out.d2[k] = D2[BR + k]; }
+                    return block_mask(Q, G, D1, D2, y0);
+                };
+                // the usual case of emit_mask: the block's codes fit the list as it is.  false: nothing was written, the block needs emit_mask
+                auto emit_codes = [&](uint32_t M, int blk) -> bool {
+                    const int incl = wave_scan_incl((int)__popc(M));
+                    const int total = __builtin_amdgcn_readlane(incl, 63);
+                    if (npx + total > pcap) return false;
+                    const uint32_t code0 = ((uint32_t)blk << 11) | ((uint32_t)tid << 5);
+                    int pos = npx + incl - (int)__popc(M);
+                    while (M) {
+                        const int bit = __ffs((int)M) - 1;
+                        M &= M - 1;
+                        plist[pos++] = (uint16_t)(code0 | (uint32_t)bit);
+                    }
+                    npx += total;
+                    return true;
+                };
+                for (int b = 0; b < nblock; b++) {
+                    ScanCarry ca, cb;
+                    {                                                                // the carry into block b from its tile rows 0 .. 5
+                        const uint32_t* tp = tile32 + BR * b * PD + col;
+                        uint32_t Q[6], G[6];
+#pragma unroll
+                        for (int k = 0; k < 6; k++) { Q[k] = reduce6(tp, k); G[k] = Q[k] + kbias; }
+#pragma unroll
+                        for (int k = 0; k < 3; k++) { ca.q[k] = Q[k + 3]; ca.g[k] = G[k + 3]; ca.d1[k] = G[k] - Q[k + 3]; ca.d2[k] = G[k + 3] - Q[k]; }
+                    }
+                    uint32_t M;
+                    for (;;) {
+                        M = carried_block(ca, cb, 3 + BR * b);
+                        if (FR_STOP <= 1) { if (M == 0x12345u) plist[tid] = 1; }     // keeps M live
+                        else if (!emit_codes(M, b)) break;
+                        if (++b >= nblock) break;
+                        M = carried_block(cb, ca, 3 + BR * b);
+                        if (FR_STOP <= 1) { if (M == 0x12345u) plist[tid] = 1; }
+                        else if (!emit_codes(M, b)) break;
+                        if (++b >= nblock) break;
+                    }
+                    if (b < nblock) emit_mask(M, 3 + BR * b, false, b);
                 }
-                if (FR_STOP <= 1) { if (M == 0x12345u) plist[tid] = 1; continue; }      // keeps M live
-                emit_mask(M, y0, false, b);
+            } else {
+                // half-waves on different rows: a lane's consecutive blocks are 16 rows apart and share nothing (the scan as it was)
+                for (int b = 0; b < nblock; b++) {
+                    const int y0 = 3 + BR * (RS * b + sub);
+                    uint32_t M = 0;
+                    {
+                        const uint32_t* tp = tile32 + (y0 - 3) * PD + col;
+                        uint32_t Q[BR + 6], G[BR + 6];
+#pragma unroll
+                        for (int k = 0; k < BR + 6; k++) { Q[k] = (tp[k * PD] >> 2) & 0x3F3F3F3Fu; G[k] = Q[k] + kbias; }
+                        uint32_t D1[BR + 3], D2[BR + 3];
+#pragma unroll
+                        for (int y = 0; y < BR + 3; y++) { D1[y] = G[y] - Q[y + 3]; D2[y] = G[y + 3] - Q[y]; }
+#pragma unroll
+                        for (int r = 0; r < BR; r++) {
+                            const uint32_t qC = Q[r + 3];
+                            const uint32_t gC = G[r + 3], nC = kbias - qC;
+                            const uint32_t qCm = lane_from_below(qC), qCp = lane_from_above(qC);
+                            const uint32_t qL = __builtin_amdgcn_alignbyte(qC, qCm, 1);          // the pixels 3 columns to the left / right of this lane's four
+                            const uint32_t qR = __builtin_amdgcn_alignbyte(qCp, qC, 3);
+                            const uint32_t dark = (D2[r] | D1[r + 3]) & ((gC - qL) | (gC - qR));           // (top or bottom darker) and (left or right darker)
+                            const uint32_t bright = (D1[r] | D2[r + 3]) & ((qL + nC) | (qR + nC));
+                            M = (M >> 1) | ((dark | bright) & 0x80808080u);                      // row r ends up at bit r of its pixel's byte
+                        }
+                        const int nrow = min(max(yend - y0, 0), BR);                     // rows of this block inside the interior
+                        M &= vmask8 & (((1u << nrow) - 1u) * 0x01010101u);
+                    }
+                    {
+                        const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x124, 0xF, 0xF, false), t2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x128, 0xF, 0xF, false),
+                                       t3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)M, 0x12C, 0xF, 0xF, false);      // row_ror:4 / 8 / 12
+                        M = (M & 0xFFu) | (t1 & 0xFF00u) | (t2 & 0xFF0000u) | (t3 & 0xFF000000u);
+                    }
+                    if (FR_STOP <= 1) { if (M == 0x12345u) plist[tid] = 1; continue; }      // keeps M live
+                    emit_mask(M, y0, false, b);
+                }
             }
             FR_W(3);
             corners_and_scores();
