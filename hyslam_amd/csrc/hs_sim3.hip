@@ -1,10 +1,18 @@
 // hs_sim3.hip — entry points of the batched Horn Sim3 RANSAC (include/hyslam_amd.h): hs_sim3_plan, hs_sim3_state_init, hs_sim3_work_bytes and
-// hs_sim3_iterate(_device).  The kernels and their launcher are in kernels_sim3.hip.  Both forms run the same predicate (hs_sim3_iterate_why) before
-// anything is enqueued; the host form stages through HsStage, its work area included, so both forms run the same launches on the same layout.
+// hs_sim3_iterate(_device) as the two bodies the RANSAC estimators share (hs_ransac.h) over HsSim3Entry.  The kernels are in kernels_sim3.hip.
 #include "hs_sim3.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+
+struct HsSim3Entry {
+    static constexpr int draw_stride = HS_SIM3_DRAW_STRIDE;
+    static constexpr bool mask_inout = false;                     // always written (Sim3Solver.cc:147)
+    static constexpr const char* state_init = "hs_sim3_state_init";
+    static const char* problem_why(const hs_sim3_params& p) { return p.min_inliers < 0 ? "min_inliers must not be negative" : nullptr; }
+    static size_t work_bytes(const HsSim3Args& a) { return HsSim3Work::bytes(a.Q, a.corr_offsets[a.Q], hs_sim3_call_bound(a.Q, a.params, a.corr_offsets, a.n_iterations)); }
+    static void launch(const HsSim3Args& a, void* d_work, hipStream_t s) { hs_launch_sim3_iterate(a, d_work, s); }
+};
 
 extern "C" {
 
@@ -35,38 +43,14 @@ int hs_sim3_iterate_device(hs_orb* h, int Q, const hs_sim3_params* params, const
                            const uint32_t* d_draws, int draw_cap, hs_sim3_state* d_states, uint8_t* d_best_masks, hs_sim3_result* d_results,
                            uint8_t* d_inlier_masks, void* d_work, void* stream)
 {
-    const char* why = hs_sim3_iterate_why(Q, params, corr_offsets, d_corrs, n_iterations, d_draws, draw_cap, d_states, d_best_masks, d_results, d_inlier_masks, true);
-    if (!why && (!d_work || ((uintptr_t)d_work & 15))) why = "d_work is required and 16-byte aligned";
-    return hs_device_call(h, why, stream, [&](hipStream_t s) {
-        hs_launch_sim3_iterate(Q, params, corr_offsets, d_corrs, n_iterations, d_draws, draw_cap, d_states, d_best_masks, d_results, d_inlier_masks, d_work, s);
-    });
+    return hs_ransac_iterate_device<HsSim3Entry>(
+        h, HsSim3Args{ Q, params, corr_offsets, d_corrs, n_iterations, d_draws, draw_cap, d_states, d_best_masks, d_results, d_inlier_masks }, d_work, stream);
 }
 
 int hs_sim3_iterate(hs_orb* h, int Q, const hs_sim3_params* params, const int64_t* corr_offsets, const hs_sim3_corr* corrs, int n_iterations,
                     const uint32_t* draws, int draw_cap, hs_sim3_state* states, uint8_t* best_masks, hs_sim3_result* results, uint8_t* inlier_masks)
 {
-    if (!h) return HS_ERR_INVALID;
-    if (const char* why = hs_sim3_iterate_why(Q, params, corr_offsets, corrs, n_iterations, draws, draw_cap, states, best_masks, results, inlier_masks, false))
-        return hs_fail(h, HS_ERR_INVALID, why);
-    for (int q = 0; q < Q; q++)
-        if (states[q].iterations < 0 || states[q].best_inliers < 0) return hs_fail(h, HS_ERR_INVALID, "a state holds a negative count: start from hs_sim3_state_init");
-    const size_t n_total = (size_t)corr_offsets[Q];
-    HIP_TRY(h, hipSetDevice(hs_orb_device_of(h)));
-    const int H = hs_sim3_call_bound(Q, params, corr_offsets, n_iterations);
-    HsStage st(h);
-    hs_sim3_corr* d_corrs; uint32_t* d_draws; hs_sim3_state* d_states; uint8_t *d_best, *d_inl, *d_work; hs_sim3_result* d_res;
-    st.in(&d_corrs, n_total, corrs);
-    st.in(&d_draws, (size_t)Q * (size_t)draw_cap * HS_SIM3_DRAW_STRIDE, draws);
-    st.inout(&d_states, (size_t)Q, states);
-    st.inout(&d_best, n_total, best_masks);
-    st.out(&d_res, (size_t)Q, results);
-    st.out(&d_inl, n_total, inlier_masks);                         // always written (Sim3Solver.cc:147)
-    st.temp(&d_work, HsSim3Work::bytes(Q, (int64_t)n_total, H));
-    const int rc = st.begin();
-    if (rc != HS_OK) return rc;
-    hs_launch_sim3_iterate(Q, params, corr_offsets, d_corrs, n_iterations, draw_cap > 0 ? d_draws : nullptr, draw_cap, d_states, d_best, d_res, d_inl, d_work,
-                           st.stream());
-    return st.finish();
+    return hs_ransac_iterate_host<HsSim3Entry>(h, HsSim3Args{ Q, params, corr_offsets, corrs, n_iterations, draws, draw_cap, states, best_masks, results, inlier_masks });
 }
 
 }  // extern "C"

@@ -418,46 +418,10 @@ PNP_HD bool pnp_inlier(const double* R, const double* t, const PnpCam& cam, cons
     return error2 < c.sigma2 * th2;
 }
 
-// SplitMix64's finaliser on counter c
-PNP_HD unsigned long long pnp_mix(unsigned long long c)
-{
-    unsigned long long z = 0x9E3779B97F4A7C15ull * (c + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the sample of absolute iteration `it` (:194-207): min_set draws without replacement, "take avail[randi], move the back element into its place,
-// pop".  avail starts as 0 .. n-1, so only the places a draw wrote differ from their index: at most min_set of them are kept.  randi < avail by
-// the integer reduction, and avail >= 1 because n >= min_inliers >= min_set.
+// the sample of absolute iteration `it` (:194-207): min_set draws, swap-with-back (hs_ransac.h).  n >= min_inliers >= min_set.
 PNP_HD void pnp_sample(const HsPnpProblem& p, long long it, const uint32_t* draws, int draw_cap, int* sample)
 {
-    int pos[HS_PNP_MAX_SET], val[HS_PNP_MAX_SET], n_mod = 0;
-    unsigned int avail = (unsigned int)p.n;
-    for (int k = 0; k < p.min_set; k++) {
-        const unsigned int r32 = it >= 0 && it < draw_cap ? draws[((size_t)p.q * (size_t)draw_cap + (size_t)it) * HS_PNP_MAX_SET + k]
-                                               : (unsigned int)(pnp_mix(p.seed + (unsigned long long)it * (unsigned long long)p.min_set + (unsigned long long)k) >> 32);
-        const int randi = (int)(((unsigned long long)r32 * (unsigned long long)avail) >> 32);
-        const int back = (int)avail - 1;
-        int at_r = randi, at_b = back, slot = -1;
-        for (int m = 0; m < n_mod; m++) {
-            if (pos[m] == randi) { at_r = val[m]; slot = m; }
-            if (pos[m] == back) at_b = val[m];
-        }
-        sample[k] = at_r;
-        if (slot < 0) { slot = n_mod++; pos[slot] = randi; }
-        val[slot] = at_b;
-        avail--;
-    }
-}
-
-// mnIterations as a call reads it: a negative count (a state no call of this library and no hs_pnp_state_init wrote; the host form refuses it, the
-// device form cannot see it) counts as 0, so no iteration index is negative and the draws table is never indexed below its start
-PNP_HD int pnp_it0(int iterations) { return iterations < 0 ? 0 : iterations; }
-// iterations a call runs when nothing returns early: the loop's OR (:188).  Never more than H, the bound the work area was carved for.
-PNP_HD int pnp_passes(int it0, int max_its, int n_iterations, int H)
-{
-    const int passes = it0 < max_its && max_its - it0 > n_iterations ? max_its - it0 : n_iterations;
-    return passes < H ? passes : H;
+    hs_ransac_sample<HS_PNP_MAX_SET, /*WRITE_AT_VALUE=*/false>(p, p.min_set, draws, draw_cap, HS_PNP_MAX_SET, it, sample);
 }
 
 __device__ __forceinline__ PnpCam pnp_cam(const HsPnpProblem& p) { return PnpCam{ (double)p.fx, (double)p.fy, (double)p.cx, (double)p.cy }; }
@@ -492,9 +456,9 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(const HsPnpBatch B, const
     __shared__ int s_cnt;
     const HsPnpProblem& p = B.p[blockIdx.y];
     if (p.n < p.min_inliers) return;
-    const int it0 = pnp_it0(states[p.q].iterations);
+    const int it0 = hs_ransac_it0(states[p.q].iterations);
     const int j = blockIdx.x;
-    if (j >= pnp_passes(it0, p.max_its, n_iterations, H)) return;
+    if (j >= hs_ransac_passes_or(it0, p.max_its, n_iterations, H)) return;
     const hs_pnp_corr* pc = corrs + p.off;
     if (threadIdx.x == 0) pnp_sample(p, (long long)it0 + j, draws, draw_cap, s_sample);
     __syncthreads();
@@ -550,8 +514,8 @@ __global__ __launch_bounds__(64) void k_pnp_select(const HsPnpBatch B, const hs_
     // the refine's points: in LDS when the problem's N fits (every loop over the points is then an LDS read, not a trip to memory), else in the work area
     double* pts = p.n <= PNP_LDS_POINTS ? s_pts : pts_all + 5 * (size_t)p.off;
     const PnpCam cam = pnp_cam(p);
-    const int it0 = pnp_it0(st->iterations);
-    const int passes = pnp_passes(it0, p.max_its, n_iterations, H);
+    const int it0 = hs_ransac_it0(st->iterations);
+    const int passes = hs_ransac_passes_or(it0, p.max_its, n_iterations, H);
     int best = st->best_inliers;
     int eval = 0, refined_cnt = 0, refines = 0, record = -1;     // eval of the current best set: 0 not yet, 1 Refine() failed, 2 succeeded
     __syncthreads();                                              // the state is read before lane 0 writes it
@@ -618,33 +582,31 @@ int hs_pnp_call_bound(int Q, const hs_pnp_params* params, const int64_t* corr_of
     int H = n_iterations;
     for (int q = 0; q < Q; q++) {
         hs_pnp_plan_t plan;
-        if (hs_pnp_plan((int)(corr_offsets[q + 1] - corr_offsets[q]), &params[q], &plan) == HS_OK) H = hs_pnp_bound(plan.max_iterations, H);
+        if (hs_pnp_plan((int)(corr_offsets[q + 1] - corr_offsets[q]), &params[q], &plan) == HS_OK) H = hs_ransac_passes_or(0, plan.max_iterations, H, INT_MAX);
     }
     return H;
 }
 
-void hs_launch_pnp_iterate(int Q, const hs_pnp_params* params, const int64_t* corr_offsets, const hs_pnp_corr* d_corrs, int n_iterations, const uint32_t* d_draws,
-                           int draw_cap, hs_pnp_state* d_states, uint8_t* d_best_masks, hs_pnp_result* d_results, uint8_t* d_inlier_masks, void* d_work, hipStream_t s)
+void hs_launch_pnp_iterate(const HsPnpArgs& a, void* d_work, hipStream_t s)
 {
-    const int H = hs_pnp_call_bound(Q, params, corr_offsets, n_iterations);
+    const int H = hs_pnp_call_bound(a.Q, a.params, a.corr_offsets, a.n_iterations);
     HsWorkCursor cur(d_work);
-    const HsPnpWork w(cur, Q, corr_offsets[Q], H);
-    for (int q0 = 0; q0 < Q; q0 += HS_PNP_BATCH) {
-        const int nb = Q - q0 < HS_PNP_BATCH ? Q - q0 : HS_PNP_BATCH;
+    const HsPnpWork w(cur, a.Q, a.corr_offsets[a.Q], H);
+    hs_ransac_for_batches(a.Q, HS_PNP_BATCH, [&](int q0, int nb) {
         HsPnpBatch B{};
         for (int b = 0; b < nb; b++) {
             const int q = q0 + b;
-            const hs_pnp_params& pp = params[q];
+            const hs_pnp_params& pp = a.params[q];
             hs_pnp_plan_t plan;
             HsPnpProblem& o = B.p[b];
-            o.off = corr_offsets[q]; o.n = (int)(corr_offsets[q + 1] - corr_offsets[q]); o.seed = pp.seed; o.min_set = pp.min_set;
+            o.off = a.corr_offsets[q]; o.n = (int)(a.corr_offsets[q + 1] - a.corr_offsets[q]); o.seed = pp.seed; o.min_set = pp.min_set;
             (void)hs_pnp_plan(o.n, &pp, &plan);
             o.min_inliers = plan.min_inliers; o.max_its = plan.max_iterations;
             o.th2 = pp.th2; o.fx = pp.fx; o.fy = pp.fy; o.cx = pp.cx; o.cy = pp.cy; o.q = q;
         }
-        hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)H, (unsigned)nb), dim3(64), 0, s, B, d_corrs, n_iterations, d_draws, draw_cap, d_states, H, w.hyp_count,
+        hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)H, (unsigned)nb), dim3(64), 0, s, B, a.corrs, a.n_iterations, a.draws, a.draw_cap, a.states, H, w.hyp_count,
                            w.hyp_pose);
-        hipLaunchKernelGGL(k_pnp_select, dim3((unsigned)nb), dim3(64), 0, s, B, d_corrs, n_iterations, d_states, d_best_masks, d_results, d_inlier_masks, H,
-                           w.hyp_count, w.hyp_pose, w.pts, w.tmp_mask);
-    }
+        hipLaunchKernelGGL(k_pnp_select, dim3((unsigned)nb), dim3(64), 0, s, B, a.corrs, a.n_iterations, a.states, a.best_masks, a.results, a.inlier_masks, H, w.hyp_count,
+                           w.hyp_pose, w.pts, w.tmp_mask);
+    });
 }

@@ -156,50 +156,10 @@ SIM3_HD void sim3_transforms(const Sim3Pose& o, Sim3Xf* xf)
     }
 }
 
-// SplitMix64's finaliser on counter c
-SIM3_HD unsigned long long sim3_mix(unsigned long long c)
-{
-    unsigned long long z = 0x9E3779B97F4A7C15ull * (c + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the sample of absolute iteration `it` (:167-181): idx = avail[randi]; avail[idx] = avail.back(); pop.  The write goes to the place named by the
-// VALUE idx.  avail starts as 0 .. n-1, so only the places a draw wrote differ from their index: at most three are kept.  A write to a place
-// that was popped already has no effect.  n >= 3, so avail >= 1 at every draw and randi < avail by the integer reduction.
+// the sample of absolute iteration `it` (:167-181): three draws that write the back element to the place named by the drawn VALUE (hs_ransac.h)
 SIM3_HD void sim3_sample(const HsSim3Problem& p, long long it, const uint32_t* draws, int draw_cap, int* sample)
 {
-    int pos[3], val[3], n_mod = 0;
-    unsigned int avail = (unsigned int)p.n;
-    for (int k = 0; k < 3; k++) {
-        const unsigned int r32 = it >= 0 && it < draw_cap ? draws[((size_t)p.q * (size_t)draw_cap + (size_t)it) * HS_SIM3_DRAW_STRIDE + k]
-                                                          : (unsigned int)(sim3_mix(p.seed + (unsigned long long)it * 3ull + (unsigned long long)k) >> 32);
-        const int randi = (int)(((unsigned long long)r32 * (unsigned long long)avail) >> 32);
-        const int back = (int)avail - 1;
-        int idx = randi, at_b = back;
-        for (int m = 0; m < n_mod; m++) {
-            if (pos[m] == randi) idx = val[m];
-            if (pos[m] == back) at_b = val[m];
-        }
-        sample[k] = idx;
-        if ((unsigned int)idx < avail) {
-            int slot = -1;
-            for (int m = 0; m < n_mod; m++) if (pos[m] == idx) slot = m;
-            if (slot < 0) { slot = n_mod++; pos[slot] = idx; }
-            val[slot] = at_b;
-        }
-        avail--;
-    }
-}
-
-// mnIterations as a call reads it: a negative count (the host form refuses it, the device form cannot see it) counts as 0
-SIM3_HD int sim3_it0(int iterations) { return iterations < 0 ? 0 : iterations; }
-// iterations a call runs: the loop's AND (:162).  Never more than H, the bound the work area was carved for.
-SIM3_HD int sim3_passes(int it0, int max_its, int n_iterations, int H)
-{
-    int passes = it0 < max_its ? max_its - it0 : 0;
-    if (passes > n_iterations) passes = n_iterations;
-    return passes < H ? passes : H;
+    hs_ransac_sample<3, /*WRITE_AT_VALUE=*/true>(p, 3, draws, draw_cap, HS_SIM3_DRAW_STRIDE, it, sample);
 }
 // the acceptance (:187-204) over the counts c[0 .. m) of hypotheses base .. base+m-1: returns the index that returns out of the loop, or -1
 SIM3_HD int sim3_walk(const int* c, int m, int base, int min_inliers, int* best, int* rec)
@@ -228,8 +188,8 @@ __global__ __launch_bounds__(64) void k_sim3_hypotheses(const HsSim3Batch B, con
     __shared__ float s_rec[HS_SIM3_CHUNK * SIM3_REC];
     const HsSim3Problem& p = B.p[blockIdx.y];
     if (p.n < p.min_inliers || p.n < 3) return;
-    const int it0 = sim3_it0(states[p.q].iterations);
-    const int passes = sim3_passes(it0, p.max_its, n_iterations, H);
+    const int it0 = hs_ransac_it0(states[p.q].iterations);
+    const int passes = hs_ransac_passes_and(it0, p.max_its, n_iterations, H);
     if ((int)(blockIdx.x * 64) >= passes) return;                 // the whole workgroup
     const int lane = threadIdx.x;
     const int j = (int)(blockIdx.x * 64) + lane;
@@ -279,7 +239,7 @@ __global__ __launch_bounds__(64) void k_sim3_select(const HsSim3Batch B, const h
     uint8_t* best_mask = best_masks + p.off;
     uint8_t* out_mask = inlier_masks + p.off;
     const int iterations0 = st->iterations;
-    int best = sim3_it0(st->best_inliers);                         // a negative count reads as 0, like mnIterations
+    int best = hs_ransac_it0(st->best_inliers);                    // a negative count reads as 0, like mnIterations
     __syncthreads();                                              // the state is read before lane 0 writes it
     if (p.n < p.min_inliers || p.n < 3) {                          // :150-154; below three points the reference would sample from an empty list
         for (long long i = lane; i < p.n; i += 64) out_mask[i] = 0;
@@ -290,8 +250,8 @@ __global__ __launch_bounds__(64) void k_sim3_select(const HsSim3Batch B, const h
         }
         return;
     }
-    const int it0 = sim3_it0(iterations0);
-    const int passes = sim3_passes(it0, p.max_its, n_iterations, H);
+    const int it0 = hs_ransac_it0(iterations0);
+    const int passes = hs_ransac_passes_and(it0, p.max_its, n_iterations, H);
     int rec = -1, found = -1;
     for (int base = 0; base < passes && found < 0; base += 64) {
         const int m = passes - base < 64 ? passes - base : 64;
@@ -353,36 +313,35 @@ int hs_sim3_call_bound(int Q, const hs_sim3_params* params, const int64_t* corr_
     int H = 1;
     for (int q = 0; q < Q; q++) {
         hs_sim3_plan_t plan;
-        if (hs_sim3_plan((int)(corr_offsets[q + 1] - corr_offsets[q]), &params[q], &plan) == HS_OK) H = std::max(H, hs_sim3_bound(plan.max_iterations, n_iterations));
+        if (hs_sim3_plan((int)(corr_offsets[q + 1] - corr_offsets[q]), &params[q], &plan) == HS_OK)
+            H = std::max(H, hs_ransac_passes_and(0, plan.max_iterations, n_iterations, INT_MAX));
     }
     return H;
 }
 
-void hs_launch_sim3_iterate(int Q, const hs_sim3_params* params, const int64_t* corr_offsets, const hs_sim3_corr* d_corrs, int n_iterations, const uint32_t* d_draws,
-                            int draw_cap, hs_sim3_state* d_states, uint8_t* d_best_masks, hs_sim3_result* d_results, uint8_t* d_inlier_masks, void* d_work, hipStream_t s)
+void hs_launch_sim3_iterate(const HsSim3Args& a, void* d_work, hipStream_t s)
 {
-    const int H = hs_sim3_call_bound(Q, params, corr_offsets, n_iterations);
+    const int H = hs_sim3_call_bound(a.Q, a.params, a.corr_offsets, a.n_iterations);
     HsWorkCursor cur(d_work);
-    const HsSim3Work w(cur, Q, corr_offsets[Q], H);
-    for (int q0 = 0; q0 < Q; q0 += HS_SIM3_BATCH) {
-        const int nb = Q - q0 < HS_SIM3_BATCH ? Q - q0 : HS_SIM3_BATCH;
+    const HsSim3Work w(cur, a.Q, a.corr_offsets[a.Q], H);
+    hs_ransac_for_batches(a.Q, HS_SIM3_BATCH, [&](int q0, int nb) {
         HsSim3Batch B{};
         for (int b = 0; b < nb; b++) {
             const int q = q0 + b;
-            const hs_sim3_params& pp = params[q];
+            const hs_sim3_params& pp = a.params[q];
             hs_sim3_plan_t plan;
             HsSim3Problem& o = B.p[b];
-            o.off = corr_offsets[q]; o.n = (int)(corr_offsets[q + 1] - corr_offsets[q]); o.seed = pp.seed;
+            o.off = a.corr_offsets[q]; o.n = (int)(a.corr_offsets[q + 1] - a.corr_offsets[q]); o.seed = pp.seed;
             (void)hs_sim3_plan(o.n, &pp, &plan);
             o.min_inliers = pp.min_inliers; o.max_its = plan.max_iterations; o.fix_scale = pp.fix_scale;
             o.k1[0] = pp.fx1; o.k1[1] = pp.fy1; o.k1[2] = pp.cx1; o.k1[3] = pp.cy1;
             o.k2[0] = pp.fx2; o.k2[1] = pp.fy2; o.k2[2] = pp.cx2; o.k2[3] = pp.cy2;
             o.q = q;
         }
-        hipLaunchKernelGGL(k_sim3_hypotheses, dim3(((unsigned)H + 63u) / 64u, (unsigned)nb), dim3(64), 0, s, B, d_corrs, n_iterations, d_draws, draw_cap, d_states, H,
+        hipLaunchKernelGGL(k_sim3_hypotheses, dim3(((unsigned)H + 63u) / 64u, (unsigned)nb), dim3(64), 0, s, B, a.corrs, a.n_iterations, a.draws, a.draw_cap, a.states, H,
                            w.hyp_count, w.hyp_pose);
-        hipLaunchKernelGGL(k_sim3_select, dim3((unsigned)nb), dim3(64), 0, s, B, d_corrs, n_iterations, d_states, d_best_masks, d_results, d_inlier_masks, H, w.hyp_count,
+        hipLaunchKernelGGL(k_sim3_select, dim3((unsigned)nb), dim3(64), 0, s, B, a.corrs, a.n_iterations, a.states, a.best_masks, a.results, a.inlier_masks, H, w.hyp_count,
                            w.hyp_pose);
-    }
+    });
 }
 #endif

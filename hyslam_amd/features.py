@@ -863,6 +863,47 @@ class Optimizer:
         return res["Tcw"][0].reshape(4, 4).copy(), outlier, int(res["n_good"][0])
 
 
+def _ransac_words(seed, cap, set, stride):
+    """the words the generator of DESIGN.md D18 gives iterations 0 .. cap-1 of a solver that draws `set` per iteration, as rows of a draws table of
+    `stride` words: SplitMix64's finaliser on the counters seed + it * set + k (the elements of synth.splitmix64(0, .) from index `seed` on, formed
+    directly because a seed may be any 64-bit number)"""
+    w = np.zeros((cap, stride), np.uint32)
+    with np.errstate(over="ignore"):
+        c = np.uint64(seed) + np.arange(cap * set, dtype=np.uint64)
+        z = (c + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    w[:, :set] = (z >> np.uint64(32)).astype(np.uint32).reshape(cap, set)
+    return w
+
+
+def _ransac_iterate(solvers, nIterations, entry, stride, sets, result_dtype):
+    """what PnPsolver.iterate_batch and Sim3Solver.iterate_batch share: ONE call of `entry` (hs_pnp_iterate / hs_sim3_iterate) for all solvers, whose
+    draws tables have `stride` words a row and who draw sets[q] per iteration; every solver's state, best_mask and result are brought up to date.
+    Returns (res, inl, off): the results, the concatenated inlier masks and the offsets of the solvers' correspondences in them."""
+    ex, Q = solvers[0]._ex, len(solvers)
+    par = np.concatenate([s.params() for s in solvers])
+    off = np.zeros(Q + 1, np.int64)
+    off[1:] = np.cumsum([len(s.corrs) for s in solvers])
+    corrs = np.concatenate([s.corrs for s in solvers])
+    cap = max([0] + [len(s.draws) for s in solvers if s.draws is not None])
+    draws = np.zeros((Q, cap, stride), np.uint32)
+    for q, s in enumerate(solvers):
+        if cap and (s.draws is None or len(s.draws) < cap):        # a table shorter than the call's: the generator's own words fill it
+            draws[q] = _ransac_words(s.seed, cap, sets[q], stride)
+        if s.draws is not None:
+            draws[q, :len(s.draws)] = s.draws
+    states = np.concatenate([s.state for s in solvers])
+    best = np.concatenate([s.best_mask for s in solvers])
+    inl, res = np.zeros(len(corrs), np.uint8), np.zeros(Q, result_dtype)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    N.check(ex._h, getattr(ex._lib, entry)(ex._h, Q, p(par), p(off), p(corrs), int(nIterations), p(draws) if cap else None, cap, p(states), p(best), p(res), p(inl)))
+    for q, s in enumerate(solvers):
+        s.state, s.best_mask, s.result = states[q:q + 1].copy(), best[off[q]:off[q + 1]].copy(), res[q].copy()
+    return res, inl, off
+
+
 class PnPsolver:
     """HYSLAM::PnPsolver (src/estimators/PnPsolver.h:61-72) on flat arrays: EPnP inside RANSAC for one candidate key frame, computed by
     hs_pnp_iterate (include/hyslam_amd.h).  Built from the frame's arrays — kps (KP_DTYPE), the landmark positions and matches
@@ -919,27 +960,9 @@ class PnPsolver:
     def iterate_batch(solvers, nIterations):
         """iterate(nIterations) of every solver in ONE call (the candidates of a relocalisation): a list of iterate's tuples.  A pose that holds a NaN or an
         infinity (HS_PNP_NONFINITE) is handed out as no pose with bNoMore true, also where Refine() produced it; solver.result keeps the record."""
-        ex, Q = solvers[0]._ex, len(solvers)
-        par = np.concatenate([s.params() for s in solvers])
-        off = np.zeros(Q + 1, np.int64)
-        off[1:] = np.cumsum([len(s.corrs) for s in solvers])
-        corrs = np.concatenate([s.corrs for s in solvers])
-        cap = max([0] + [len(s.draws) for s in solvers if s.draws is not None])
-        draws = np.zeros((Q, cap, N.HS_PNP_MAX_SET), np.uint32)
-        for q, s in enumerate(solvers):
-            if cap and (s.draws is None or len(s.draws) < cap):    # a table shorter than the call's: the generator's own words fill it
-                draws[q] = s._generator_words(cap)
-            if s.draws is not None:
-                draws[q, :len(s.draws)] = s.draws
-        states = np.concatenate([s.state for s in solvers])
-        best = np.concatenate([s.best_mask for s in solvers])
-        inl, res = np.zeros(len(corrs), np.uint8), np.zeros(Q, N.PNP_RESULT_DTYPE)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)
-        N.check(ex._h, ex._lib.hs_pnp_iterate(ex._h, Q, p(par), p(off), p(corrs), int(nIterations), p(draws) if cap else None, cap, p(states), p(best), p(res),
-                                              p(inl)))
+        res, inl, off = _ransac_iterate(solvers, nIterations, "hs_pnp_iterate", N.HS_PNP_MAX_SET, [s._ransac[3] for s in solvers], N.PNP_RESULT_DTYPE)
         out = []
         for q, s in enumerate(solvers):
-            s.state, s.best_mask, s.result = states[q:q + 1].copy(), best[off[q]:off[q + 1]].copy(), res[q].copy()
             status = int(res["status"][q])
             no_more = status != N.HS_PNP_REFINED
             if status in (N.HS_PNP_REFINED, N.HS_PNP_BEST):
@@ -949,20 +972,6 @@ class PnPsolver:
             else:
                 out.append((None, no_more, np.zeros(0, bool), 0))
         return out
-
-    def _generator_words(self, cap):
-        """the words the generator of DESIGN.md D18 gives iterations 0 .. cap-1: SplitMix64's finaliser on the counters seed + it * min_set + k (the
-        elements of synth.splitmix64(0, .) from index `seed` on, formed directly because a seed may be any 64-bit number)"""
-        ms = self._ransac[3]
-        w = np.zeros((cap, N.HS_PNP_MAX_SET), np.uint32)
-        with np.errstate(over="ignore"):
-            c = np.uint64(self.seed) + np.arange(cap * ms, dtype=np.uint64)
-            z = (c + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-            z = z ^ (z >> np.uint64(31))
-        w[:, :ms] = (z >> np.uint64(32)).astype(np.uint32).reshape(cap, ms)
-        return w
 
     def iterate(self, nIterations):
         """cv::Mat iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers): (Tcw float32 4x4 or None, bNoMore, vbInliers by
@@ -1044,27 +1053,9 @@ class Sim3Solver:
     @staticmethod
     def iterate_batch(solvers, nIterations):
         """iterate(nIterations) of every solver in ONE call (the consistent candidates of LoopClosing::ComputeSim3): a list of iterate's tuples"""
-        ex, Q = solvers[0]._ex, len(solvers)
-        par = np.concatenate([s.params() for s in solvers])
-        off = np.zeros(Q + 1, np.int64)
-        off[1:] = np.cumsum([len(s.corrs) for s in solvers])
-        corrs = np.concatenate([s.corrs for s in solvers])
-        cap = max([0] + [len(s.draws) for s in solvers if s.draws is not None])
-        draws = np.zeros((Q, cap, N.HS_SIM3_DRAW_STRIDE), np.uint32)
-        for q, s in enumerate(solvers):
-            if cap and (s.draws is None or len(s.draws) < cap):    # a table shorter than the call's: the generator's own words fill it
-                draws[q] = s._generator_words(cap)
-            if s.draws is not None:
-                draws[q, :len(s.draws)] = s.draws
-        states = np.concatenate([s.state for s in solvers])
-        best = np.concatenate([s.best_mask for s in solvers])
-        inl, res = np.zeros(len(corrs), np.uint8), np.zeros(Q, N.SIM3_RESULT_DTYPE)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)
-        N.check(ex._h, ex._lib.hs_sim3_iterate(ex._h, Q, p(par), p(off), p(corrs), int(nIterations), p(draws) if cap else None, cap, p(states), p(best), p(res),
-                                               p(inl)))
+        res, inl, off = _ransac_iterate(solvers, nIterations, "hs_sim3_iterate", N.HS_SIM3_DRAW_STRIDE, [3] * len(solvers), N.SIM3_RESULT_DTYPE)
         out = []
         for q, s in enumerate(solvers):
-            s.state, s.best_mask, s.result = states[q:q + 1].copy(), best[off[q]:off[q + 1]].copy(), res[q].copy()
             status = int(res["status"][q])
             flags = np.zeros(s.n_matches, bool)                    # vbInliers: always mN1 long (:147)
             flags[s.corrs["idx1"][inl[off[q]:off[q + 1]] != 0]] = True
@@ -1077,18 +1068,6 @@ class Sim3Solver:
     def find_batch(solvers):
         """find() of every solver in ONE call: every solver runs to its own mRansacMaxIts (the loop's AND stops each at its plan)"""
         return [(T12, flags, n) for T12, _, flags, n in Sim3Solver.iterate_batch(solvers, max(s.max_iterations for s in solvers))]
-
-    def _generator_words(self, cap):
-        """the words the generator gives iterations 0 .. cap-1: SplitMix64's finaliser on the counters seed + 3 it + k"""
-        w = np.zeros((cap, N.HS_SIM3_DRAW_STRIDE), np.uint32)
-        with np.errstate(over="ignore"):
-            c = np.uint64(self.seed) + np.arange(cap * 3, dtype=np.uint64)
-            z = (c + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-            z = z ^ (z >> np.uint64(31))
-        w[:, :3] = (z >> np.uint64(32)).astype(np.uint32).reshape(cap, 3)
-        return w
 
     def iterate(self, nIterations):
         """cv::Mat iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers): (T12 float32 4x4 or None, bNoMore, vbInliers by

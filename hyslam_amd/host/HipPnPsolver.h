@@ -23,6 +23,7 @@
 #include <vector>
 #include "../../include/hyslam_amd.h"
 #include "HipORBExtractor.h"
+#include "HipRansacBatch.h"
 
 namespace HYSLAM {
 
@@ -80,39 +81,19 @@ public:
     static void iterate(const std::vector<HipPnPsolver*>& solvers, int nIterations, std::vector<Result>& results) {
         const int Q = (int)solvers.size();
         results.assign(Q, Result());
-        if (Q == 0) return;
-        std::vector<hs_pnp_params> params(Q);
-        std::vector<int64_t> offsets(Q + 1, 0);
-        std::vector<hs_pnp_state> states(Q);
+        const hip_detail::RansacBatch<HipPnPsolver, hs_pnp_result> b(solvers, nIterations, "HipPnPsolver", hs_pnp_iterate);
         for (int q = 0; q < Q; q++) {
-            params[q] = solvers[q]->params_; states[q] = solvers[q]->state_;
-            offsets[q + 1] = offsets[q] + (int64_t)solvers[q]->corrs_.size();
-        }
-        std::vector<hs_pnp_corr> corrs; std::vector<uint8_t> best;
-        corrs.reserve((size_t)offsets[Q]); best.reserve((size_t)offsets[Q]);
-        for (int q = 0; q < Q; q++) {
-            corrs.insert(corrs.end(), solvers[q]->corrs_.begin(), solvers[q]->corrs_.end());
-            best.insert(best.end(), solvers[q]->best_mask_.begin(), solvers[q]->best_mask_.end());
-        }
-        std::vector<uint8_t> inliers(corrs.size(), 0);
-        std::vector<hs_pnp_result> res(Q);
-        hs_orb* use = solvers[0]->handle_ ? solvers[0]->handle_ : hip_detail::thread_handle(hip_detail::default_device().load(), "HipPnPsolver");
-        const int st = hs_pnp_iterate(use, Q, params.data(), offsets.data(), corrs.data(), nIterations, nullptr, 0, states.data(), best.data(), res.data(), inliers.data());
-        if (st != HS_OK) throw std::runtime_error(std::string("HipPnPsolver: ") + hs_status_string(st) + ": " + hs_orb_last_error(use));
-        for (int q = 0; q < Q; q++) {
-            HipPnPsolver& s = *solvers[q];
-            s.state_ = states[q];
-            s.best_mask_.assign(best.begin() + offsets[q], best.begin() + offsets[q + 1]);
+            const HipPnPsolver& s = *solvers[q];
             Result& r = results[q];
-            r.info = res[q];
-            r.bNoMore = res[q].status != HS_PNP_REFINED;                                             // HS_PNP_NONFINITE: no pose and bNoMore, also where it replaces REFINED (info keeps the record)
-            if (res[q].status != HS_PNP_REFINED && res[q].status != HS_PNP_BEST) continue;           // no pose: vbInliers stays empty, nInliers 0, an empty cv::Mat
-            r.nInliers = res[q].n_inliers;
+            r.info = b.res[q];
+            r.bNoMore = b.res[q].status != HS_PNP_REFINED;                                           // HS_PNP_NONFINITE: no pose and bNoMore, also where it replaces REFINED (info keeps the record)
+            if (b.res[q].status != HS_PNP_REFINED && b.res[q].status != HS_PNP_BEST) continue;       // no pose: vbInliers stays empty, nInliers 0, an empty cv::Mat
+            r.nInliers = b.res[q].n_inliers;
             r.vbInliers.assign(s.n_matches_, false);
-            for (int64_t k = offsets[q]; k < offsets[q + 1]; k++)
-                if (inliers[(size_t)k]) r.vbInliers[(size_t)corrs[(size_t)k].kp] = true;
+            for (int64_t k = b.offsets[q]; k < b.offsets[q + 1]; k++)
+                if (b.inliers[(size_t)k]) r.vbInliers[(size_t)b.corrs[(size_t)k].kp] = true;
             r.Tcw = cv::Mat(4, 4, CV_32F);
-            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.Tcw.at<float>(i, j) = res[q].Tcw[4 * i + j];
+            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.Tcw.at<float>(i, j) = b.res[q].Tcw[4 * i + j];
         }
     }
 
@@ -121,6 +102,7 @@ public:
     const hs_pnp_state& state() const { return state_; }
 
 private:
+    friend struct hip_detail::RansacBatch<HipPnPsolver, hs_pnp_result>;
     hs_orb* handle_;
     size_t n_matches_;
     std::vector<hs_pnp_corr> corrs_;

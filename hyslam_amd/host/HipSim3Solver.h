@@ -24,6 +24,7 @@
 #include <vector>
 #include "../../include/hyslam_amd.h"
 #include "HipORBExtractor.h"
+#include "HipRansacBatch.h"
 
 namespace HYSLAM {
 
@@ -90,39 +91,19 @@ public:
     static void iterate(const std::vector<HipSim3Solver*>& solvers, int nIterations, std::vector<Result>& results) {
         const int Q = (int)solvers.size();
         results.assign(Q, Result());
-        if (Q == 0) return;
-        std::vector<hs_sim3_params> params(Q);
-        std::vector<int64_t> offsets(Q + 1, 0);
-        std::vector<hs_sim3_state> states(Q);
+        const hip_detail::RansacBatch<HipSim3Solver, hs_sim3_result> b(solvers, nIterations, "HipSim3Solver", hs_sim3_iterate);
         for (int q = 0; q < Q; q++) {
-            params[q] = solvers[q]->params_; states[q] = solvers[q]->state_;
-            offsets[q + 1] = offsets[q] + (int64_t)solvers[q]->corrs_.size();
-        }
-        std::vector<hs_sim3_corr> corrs; std::vector<uint8_t> best;
-        corrs.reserve((size_t)offsets[Q] + 1); best.reserve((size_t)offsets[Q] + 1);
-        for (int q = 0; q < Q; q++) {
-            corrs.insert(corrs.end(), solvers[q]->corrs_.begin(), solvers[q]->corrs_.end());
-            best.insert(best.end(), solvers[q]->best_mask_.begin(), solvers[q]->best_mask_.end());
-        }
-        std::vector<uint8_t> inliers(corrs.size() + 1, 0);
-        std::vector<hs_sim3_result> res(Q);
-        hs_orb* use = solvers[0]->handle_ ? solvers[0]->handle_ : hip_detail::thread_handle(hip_detail::default_device().load(), "HipSim3Solver");
-        const int st = hs_sim3_iterate(use, Q, params.data(), offsets.data(), corrs.data(), nIterations, nullptr, 0, states.data(), best.data(), res.data(), inliers.data());
-        if (st != HS_OK) throw std::runtime_error(std::string("HipSim3Solver: ") + hs_status_string(st) + ": " + hs_orb_last_error(use));
-        for (int q = 0; q < Q; q++) {
-            HipSim3Solver& s = *solvers[q];
-            s.state_ = states[q];
-            s.best_mask_.assign(best.begin() + offsets[q], best.begin() + offsets[q + 1]);
+            const HipSim3Solver& s = *solvers[q];
             Result& r = results[q];
-            r.info = res[q];
-            r.bNoMore = res[q].status == HS_SIM3_TOO_FEW || res[q].status == HS_SIM3_EXHAUSTED;
-            r.nInliers = res[q].n_inliers;
+            r.info = b.res[q];
+            r.bNoMore = b.res[q].status == HS_SIM3_TOO_FEW || b.res[q].status == HS_SIM3_EXHAUSTED;
+            r.nInliers = b.res[q].n_inliers;
             r.vbInliers.assign(s.n_matches_, false);               // always mN1 long (:147)
-            for (int64_t k = offsets[q]; k < offsets[q + 1]; k++)
-                if (inliers[(size_t)k]) r.vbInliers[(size_t)corrs[(size_t)k].idx1] = true;
-            if (res[q].status != HS_SIM3_FOUND && res[q].status != HS_SIM3_NONFINITE) continue;      // no pose: an empty cv::Mat
+            for (int64_t k = b.offsets[q]; k < b.offsets[q + 1]; k++)
+                if (b.inliers[(size_t)k]) r.vbInliers[(size_t)b.corrs[(size_t)k].idx1] = true;
+            if (b.res[q].status != HS_SIM3_FOUND && b.res[q].status != HS_SIM3_NONFINITE) continue;  // no pose: an empty cv::Mat
             r.T12 = cv::Mat(4, 4, CV_32F);
-            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.T12.at<float>(i, j) = res[q].T12[4 * i + j];
+            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.T12.at<float>(i, j) = b.res[q].T12[4 * i + j];
         }
     }
 
@@ -143,6 +124,7 @@ private:
                               (double)R.at<float>(i, 2) * (double)X.at<float>(2)) + (double)t.at<float>(i));
     }
 
+    friend struct hip_detail::RansacBatch<HipSim3Solver, hs_sim3_result>;
     hs_orb* handle_;
     size_t n_matches_;
     std::vector<hs_sim3_corr> corrs_;

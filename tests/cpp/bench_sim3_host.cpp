@@ -39,7 +39,7 @@ int main(int argc, char** argv)
             p.k1[0] = pp.fx1; p.k1[1] = pp.fy1; p.k1[2] = pp.cx1; p.k1[3] = pp.cy1; p.k2[0] = pp.fx2; p.k2[1] = pp.fy2; p.k2[2] = pp.cx2; p.k2[3] = pp.cy2;
             const hs_sim3_corr* pc = corrs.data() + (size_t)q * N;
             for (int i = 0; i < N; i++) sim3_record(pc[i], p.k1, p.k2, &rec[(size_t)i * SIM3_REC]);
-            const int passes = sim3_passes(0, pp.max_iterations, H, H);
+            const int passes = hs_ransac_passes_and(0, pp.max_iterations, H, H);
             for (int j = 0; j < passes; j++) {
                 int s[3];
                 float x1[3][3], x2[3][3];

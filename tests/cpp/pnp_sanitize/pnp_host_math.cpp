@@ -2,9 +2,13 @@
 // kernels run, with one "lane" on the host) as a host program, so that tests/test_pnp_abi.py can hold it to LITERAL of tests/ref_pnp.py bit for bit
 // without a device.  For every iteration of the file's problem: the sample, EPnP on it, the inlier count; where the count reaches min_inliers, EPnP
 // over those inliers and the recount (what Refine() does with that set).  Doubles are printed as hexadecimal floats.
-//   pnp_host_math <file>      file: int32 N, min_set, n_hypotheses, min_inliers; uint64 seed; float th2, fx, fy, cx, cy; hs_pnp_corr [N]
+//   pnp_host_math <file> [<draws>] [--samples]
+//     file: int32 N, min_set, n_hypotheses, min_inliers; uint64 seed; float th2, fx, fy, cx, cy; hs_pnp_corr [N]
+//     draws: a table of uint32 [cap][HS_PNP_MAX_SET] that directs the samples of the first cap iterations (none: the generator alone)
+//     --samples: the S lines only, no EPnP
 #include "kernels_pnp.hip"
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 static void put(const char* tag, int it, int cnt, const PnpWs& ws)
@@ -17,8 +21,23 @@ static void put(const char* tag, int it, int cnt, const PnpWs& ws)
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
+    const char* files[2] = { nullptr, nullptr };
+    bool samples_only = false;
+    for (int a = 1, n = 0; a < argc; a++) {
+        if (!std::strcmp(argv[a], "--samples")) samples_only = true;
+        else if (n < 2) files[n++] = argv[a];
+    }
+    if (!files[0]) return 2;
+    std::vector<uint32_t> draws;
+    if (files[1]) {
+        FILE* d = std::fopen(files[1], "rb");
+        if (!d) return 2;
+        uint32_t row[HS_PNP_MAX_SET];
+        while (std::fread(row, 4, HS_PNP_MAX_SET, d) == HS_PNP_MAX_SET) draws.insert(draws.end(), row, row + HS_PNP_MAX_SET);
+        std::fclose(d);
+    }
+    const int draw_cap = (int)(draws.size() / HS_PNP_MAX_SET);
+    FILE* f = std::fopen(files[0], "rb");
     if (!f) return 2;
     int32_t hdr[4]; unsigned long long seed; float c5[5];
     if (std::fread(hdr, 4, 4, f) != 4 || std::fread(&seed, 8, 1, f) != 1 || std::fread(c5, 4, 5, f) != 5) return 2;
@@ -34,10 +53,11 @@ int main(int argc, char** argv)
     auto load = [&](int i, double* d) { const hs_pnp_corr& c = corrs[i]; d[0] = c.Xw[0]; d[1] = c.Xw[1]; d[2] = c.Xw[2]; d[3] = c.u; d[4] = c.v; };
     for (int it = 0; it < nh; it++) {
         int s[HS_PNP_MAX_SET];
-        pnp_sample(p, it, nullptr, 0, s);
+        pnp_sample(p, it, draw_cap ? draws.data() : nullptr, draw_cap, s);
         std::printf("S %d", it);
         for (int k = 0; k < ms; k++) { std::printf(" %d", s[k]); load(s[k], ws.pts + 5 * k); }
         std::printf("\n");
+        if (samples_only) continue;
         pnp_epnp(&ws, ws.pts, ms, cam);
         std::vector<int> in;
         for (int i = 0; i < N; i++) if (pnp_inlier(ws.R, ws.t, cam, corrs[i], c5[0])) in.push_back(i);

@@ -143,3 +143,38 @@ def test_kernel_math_on_the_host_equals_literal(tmp_path):
             assert int(w[2]) == want_cnt, (name, ln[:40])
             assert np.array_equal(got, np.concatenate([Rm.reshape(-1), t]), equal_nan=True), (name, w[0], it, float(np.nanmax(np.abs(got - np.concatenate([Rm.reshape(-1), t])))))
     assert poses == 33 and refines >= 4
+
+
+@pytest.mark.skipif((shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc")) or not os.path.exists(os.path.join(SAN, "..", "host_sanitize", "Makefile")),
+                    reason="needs hipcc (host-only compile) and tests/cpp/host_sanitize/, whose objects it links")
+def test_sampler_over_every_randi_sequence_equals_the_reference(tmp_path):
+    """pnp_host_math --samples with a directed table: every sequence of randi for n = 4 .. 7 with min_set 4 and n = 5, 6 with min_set 5, each printed
+    sample against sample() of tests/ref_pnp.py on the same words.  The enumeration holds the samples on which the write at the place randi
+    (PnPsolver.cc:194-207) and the write by VALUE (Sim3Solver.cc:167-181) give different results — a draw that hits a place an earlier draw of the
+    same sample modified — counted from the two references over the first three draws, the set the Sim3 reference takes."""
+    import struct
+
+    import numpy as np
+
+    import ref_pnp as R
+    import ref_sim3
+    from ransac_enum import randi_table
+    subprocess.check_call(["make", "-s", "-j4", "-C", SAN], timeout=1500)
+    diverging = checked = 0
+    for n, ms in ((4, 4), (5, 4), (6, 4), (7, 4), (5, 5), (6, 5)):
+        table = randi_table(n, ms, R.MAX_SET)
+        want = [R.sample(n, ms, row) for row in table]
+        diverging += sum(w[:3] != ref_sim3.sample(n, row) for w, row in zip(want, table))
+        path, dpath = str(tmp_path / ("enum%d_%d.bin" % (n, ms))), str(tmp_path / ("enum%d_%d.draws" % (n, ms)))
+        with open(path, "wb") as f:
+            f.write(struct.pack("<iiiiQ5f", n, ms, len(table), ms, 0, *[1.0] * 5))
+            f.write(np.zeros(n, R.CORR_DTYPE).tobytes())
+        table.tofile(dpath)
+        r = subprocess.run([os.path.join(SAN, "_build", "pnp_host_math"), path, dpath, "--samples"], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (n, ms, r.stderr[-2000:])
+        lines = [ln.split() for ln in r.stdout.strip().split("\n")]
+        assert [w[0] for w in lines] == ["S"] * len(table) and [int(w[1]) for w in lines] == list(range(len(table))), (n, ms)
+        for w, s in zip(lines, want):
+            assert [int(x) for x in w[2:]] == s, (n, ms, w, s)
+            checked += 1
+    assert checked == 24 + 120 + 360 + 840 + 120 + 720 and diverging > 0

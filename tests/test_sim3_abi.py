@@ -174,3 +174,35 @@ def test_kernel_math_on_the_host_equals_the_reference(tmp_path):
                 found, rec, best = R.loop_form([int(m.sum()) for m in masks], 0, c["params"]["min_inliers"])
                 assert [int(x) for x in w[1:]] == [-1 if found is None else found, -1 if rec is None else rec, best], (name, "walk")
     assert poses == 122
+
+
+@needs_hipcc
+def test_sampler_over_every_randi_sequence_equals_the_reference(tmp_path):
+    """sim3_host_math --samples with a directed table: every sequence of randi for n = 3 .. 7 (at most 7 * 6 * 5 samples per n), each printed sample
+    against sample() of tests/ref_sim3.py on the same words.  The enumeration holds the samples on which the write by VALUE (Sim3Solver.cc:167-181)
+    and the write at the place randi (PnPsolver.cc:194-207) give different results — a draw that hits a place an earlier draw of the same sample
+    modified — counted from the two references, which is where a sampler shared by both solvers can be merged wrongly."""
+    import struct
+
+    import ref_pnp
+    import ref_sim3 as R
+    from ransac_enum import randi_table
+    subprocess.check_call(["make", "-s", "-j4", "-C", SAN], timeout=1500)
+    diverging = checked = 0
+    for n in (3, 4, 5, 6, 7):
+        table = randi_table(n, 3, R.DRAW_STRIDE)
+        want = [R.sample(n, row) for row in table]
+        diverging += sum(w != ref_pnp.sample(n, 3, row) for w, row in zip(want, table))
+        path, dpath = str(tmp_path / ("enum%d.bin" % n)), str(tmp_path / ("enum%d.draws" % n))
+        with open(path, "wb") as f:
+            f.write(struct.pack("<iiiiQ8f", n, len(table), 1, 0, 0, *[1.0] * 8))
+            f.write(np.zeros(n, R.CORR_DTYPE).tobytes())
+        table.tofile(dpath)
+        r = subprocess.run([os.path.join(SAN, "_build", "sim3_host_math"), path, dpath, "--samples"], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (n, r.stderr[-2000:])
+        lines = [ln.split() for ln in r.stdout.strip().split("\n")]
+        assert [w[0] for w in lines] == ["S"] * len(table) and [int(w[1]) for w in lines] == list(range(len(table))), n
+        for w, s in zip(lines, want):
+            assert [int(x) for x in w[2:]] == s, (n, w, s)
+            checked += 1
+    assert checked == 6 + 24 + 60 + 120 + 210 and diverging > 0

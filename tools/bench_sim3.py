@@ -30,7 +30,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def build_host_math():
     src = os.path.join(ROOT, "tests", "cpp", "bench_sim3_host.cpp")
     exe = os.path.join(ROOT, "tests", "cpp", "_build", "bench_sim3_host")
-    deps = [src, os.path.join(ROOT, "hyslam_amd", "csrc", "kernels_sim3.hip"), os.path.join(ROOT, "hyslam_amd", "csrc", "hs_sim3.h")]
+    deps = [src, os.path.join(ROOT, "hyslam_amd", "csrc", "kernels_sim3.hip"), os.path.join(ROOT, "hyslam_amd", "csrc", "hs_sim3.h"),
+            os.path.join(ROOT, "hyslam_amd", "csrc", "hs_ransac.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(os.path.dirname(exe), exist_ok=True)
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

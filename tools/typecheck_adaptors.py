@@ -21,7 +21,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h", "HipPnPsolver.h", "HipSim3Solver.h"]
+HEADERS = ["HipORBFactory.h", "HipFeatureMatcher.h", "HipAssociationReplay.h", "HipORBExtractor.h", "HipLandmarkDescriptors.h", "HipLandmarkEntries.h", "HipPlaceRecognizer.h", "HipKeyFrameGraph.h", "HipPoseOptimizer.h", "HipRansacBatch.h", "HipPnPsolver.h", "HipSim3Solver.h"]
 SEARCHES = ("SearchByProjection", "SearchByBoW", "SearchByBoW2", "SearchForTriangulation", "SearchForInitialization", "Fuse", "SearchBySim3")
 
 
