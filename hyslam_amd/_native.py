@@ -165,6 +165,29 @@ class Sim3Result(C.Structure):
                 ("at_iteration", C.c_int32), ("iterations", C.c_int32), ("hypotheses_run", C.c_int32)]
 
 
+# hs_monoinit_* (include/hyslam_amd.h): monocular initialisation, homography / fundamental RANSAC and reconstruction
+MONOINIT_PARAMS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("sigma", "<f4"), ("max_iterations", "<i4"), ("min_triangulated", "<i4"),
+                                  ("min_frac_triangulated", "<f4"), ("min_parallax_deg", "<f4"), ("_pad", "<i4"), ("seed", "<u8")])
+MONOINIT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("model", "<i4"), ("best_solution", "<i4"), ("best_it_h", "<i4"), ("best_it_f", "<i4"),
+                                  ("n_triangulated", "<i4"), ("_pad", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"), ("rh", "<f4"), ("cos_parallax", "<f4"),
+                                  ("H21", "<f4", 9), ("F21", "<f4", 9), ("n_good", "<i4", 8), ("R21", "<f4", 9), ("t21", "<f4", 3)])
+HS_MONOINIT_TOO_FEW, HS_MONOINIT_FAILED, HS_MONOINIT_OK_H, HS_MONOINIT_OK_F, HS_MONOINIT_NONFINITE = 0, 1, 2, 3, 4
+HS_MONOINIT_MODEL_NONE, HS_MONOINIT_MODEL_H, HS_MONOINIT_MODEL_F = 0, 1, 2
+HS_MONOINIT_DRAW_STRIDE = _header_constant("HS_MONOINIT_DRAW_STRIDE")
+HS_MONOINIT_MAX_ITERATIONS = _header_constant("HS_MONOINIT_MAX_ITERATIONS")
+
+
+class MonoinitParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("sigma", C.c_float), ("max_iterations", C.c_int32),
+                ("min_triangulated", C.c_int32), ("min_frac_triangulated", C.c_float), ("min_parallax_deg", C.c_float), ("_pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class MonoinitResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_matches", C.c_int32), ("model", C.c_int32), ("best_solution", C.c_int32), ("best_it_h", C.c_int32), ("best_it_f", C.c_int32),
+                ("n_triangulated", C.c_int32), ("_pad", C.c_int32), ("score_h", C.c_float), ("score_f", C.c_float), ("rh", C.c_float), ("cos_parallax", C.c_float),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("n_good", C.c_int32 * 8), ("R21", C.c_float * 9), ("t21", C.c_float * 3)]
+
+
 # hs_pose_view / hs_track_* (include/hyslam_amd.h): frame tracking on resident tables
 POSE_VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), ("_pad", "<f4")])
 TRACK_RESULT_DTYPE = np.dtype([("status", "<i4"), ("used_wide", "<i4"), ("n_narrow", "<i4"), ("n_wide", "<i4"), ("n_matches_map", "<i4"), ("n_inliers", "<i4"),
@@ -323,6 +346,7 @@ EXPORTS = [
     "hs_pose_optimize", "hs_pose_optimize_device", "hs_pose_work_bytes", "hs_pose_edges_device",
     "hs_pnp_plan", "hs_pnp_state_init", "hs_pnp_work_bytes", "hs_pnp_iterate", "hs_pnp_iterate_device",
     "hs_sim3_plan", "hs_sim3_state_init", "hs_sim3_work_bytes", "hs_sim3_iterate", "hs_sim3_iterate_device",
+    "hs_monoinit_work_bytes", "hs_monoinit_check", "hs_monoinit_estimate", "hs_monoinit_estimate_device", "hs_debug_monoinit_layout",
     "hs_pose_views_device", "hs_search_by_projection_posed_device", "hs_local_map_search_posed_device", "hs_track_work_bytes", "hs_frame_associate_device",
     "hs_frame_views_device", "hs_track_discard_device", "hs_track_motion_model_device", "hs_track_local_map_device", "hs_track_frame_device",
     "hs_search_by_bow_kf_device", "hs_frame_associate_views_device", "hs_track_refkf_work_bytes",
@@ -482,6 +506,11 @@ def lib():
     L.hs_sim3_work_bytes.argtypes, L.hs_sim3_work_bytes.restype = [C.c_int, C.c_int64, C.c_int], C.c_size_t
     L.hs_sim3_iterate.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.hs_sim3_iterate_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.hs_monoinit_work_bytes.argtypes, L.hs_monoinit_work_bytes.restype = [C.c_int, C.c_int64, C.c_int], C.c_size_t
+    L.hs_monoinit_check.argtypes, L.hs_monoinit_check.restype = [C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp], C.c_char_p
+    L.hs_debug_monoinit_layout.argtypes = [C.c_int]
+    L.hs_monoinit_estimate.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hs_monoinit_estimate_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.hs_pose_views_device.argtypes = [vp, vp, vp, vp]
     L.hs_search_by_projection_posed_device.argtypes = [vp, C.POINTER(FrameView), vp, vp, C.c_int, C.POINTER(ProjParams), vp, vp, vp, vp]
     L.hs_local_map_search_posed_device.argtypes = [vp, C.POINTER(KfTable), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameView), vp, vp,

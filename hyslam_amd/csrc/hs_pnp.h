@@ -8,7 +8,6 @@
 #include "hs_work.h"
 
 #define HS_PNP_BATCH 16                 // problems per launch pair: their planned records travel as kernel arguments
-#define HS_PNP_SVD_SWEEPS 30            // cap on the sweeps of the one-sided Jacobi SVD
 
 // one planned problem, as the kernels read it
 struct HsPnpProblem {

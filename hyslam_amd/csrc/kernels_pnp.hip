@@ -12,22 +12,21 @@
 // changes (HS_PNP_SVD_SWEEPS sweeps, 5 Gauss-Newton steps, `passes` hypotheses); a NaN makes every comparison false and therefore skips a rotation.
 // The math is __host__ __device__ with one "lane" on the host, so a host build of this file computes the same bits.
 #include "hs_pnp.h"
+#include "hs_jacobi.h"
 #include <cfloat>
 #include <cmath>
 
 static_assert(sizeof(hs_pnp_corr) == 32 && sizeof(hs_pnp_params) == 56 && sizeof(hs_pnp_state) == 72 && sizeof(hs_pnp_result) == 216 && sizeof(hs_pnp_plan_t) == 16,
               "include/hyslam_amd.h states these layouts");
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PNP_LANE ((int)threadIdx.x)
-#define PNP_LANES 64
-#define PNP_SYNC() __syncthreads()
-#else
-#define PNP_LANE 0
-#define PNP_LANES 1
-#define PNP_SYNC() ((void)0)
-#endif
-#define PNP_HD __host__ __device__
+// the one decomposition is hs_jacobi.h's, under the names this file has always used
+#define PNP_LANE HS_JACOBI_LANE
+#define PNP_LANES HS_JACOBI_LANES
+#define PNP_SYNC() HS_JACOBI_SYNC()
+#define PNP_HD HS_JACOBI_HD
+#define HS_PNP_SVD_SWEEPS HS_JACOBI_SWEEPS
+#define pnp_svd hs_jacobi_svd<true>
+#define pnp_cut hs_jacobi_cut
 #define PNP_LDS_POINTS 1024              // k_pnp_select keeps the compacted inliers of a problem of at most this many correspondences in LDS (40 KB)
 
 namespace {
@@ -49,59 +48,6 @@ struct PnpWs {
     int perm[12];
 };
 
-// ---- the one decomposition: one-sided cyclic Jacobi SVD of G (m x n, row-major), G <- U Sigma, V accumulated -----------------
-PNP_HD void pnp_svd(double* G, int m, int n, double* V, double* sig, int* perm)
-{
-    const int lane = PNP_LANE;
-    for (int e = lane; e < n * n; e += PNP_LANES) V[e] = (e / n == e % n) ? 1.0 : 0.0;
-    double f2 = 0.0;
-    for (int e = 0; e < m * n; e++) f2 = f2 + G[e] * G[e];
-    const double tiny = ((double)n * DBL_EPSILON) * ((double)n * DBL_EPSILON) * f2;
-    PNP_SYNC();
-    for (int sweep = 0; sweep < HS_PNP_SVD_SWEEPS; sweep++) {
-        bool rotated = false;
-        for (int p = 0; p < n - 1; p++)
-            for (int q = p + 1; q < n; q++) {
-                double a = 0.0, b = 0.0, g = 0.0;
-                for (int i = 0; i < m; i++) {
-                    const double gp = G[i * n + p], gq = G[i * n + q];
-                    a = a + gp * gp; b = b + gq * gq; g = g + gp * gq;
-                }
-                if (!(a > tiny) || !(b > tiny) || !(fabs(g) > DBL_EPSILON * sqrt(a * b))) continue;      // the same decision in every lane
-                const double zeta = (b - a) / (2.0 * g);
-                const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                PNP_SYNC();                                       // every lane has read the two columns
-                for (int r = lane; r < m + n; r += PNP_LANES) {
-                    double* row = r < m ? G + r * n : V + (r - m) * n;
-                    const double x = row[p], y = row[q];
-                    row[p] = c * x - s * y; row[q] = s * x + c * y;
-                }
-                PNP_SYNC();
-                rotated = true;
-            }
-        if (!rotated) break;
-    }
-    if (lane == 0) {
-        for (int j = 0; j < n; j++) {
-            double s = 0.0;
-            for (int i = 0; i < m; i++) s = s + G[i * n + j] * G[i * n + j];
-            sig[j] = sqrt(s);
-        }
-        for (int j = 0; j < n; j++) {                              // stable insertion sort, descending
-            int k = j;
-            while (k > 0 && sig[perm[k - 1]] < sig[j]) { perm[k] = perm[k - 1]; k--; }
-            perm[k] = j;
-        }
-    }
-    PNP_SYNC();
-}
-PNP_HD double pnp_cut(const double* sig, const int* perm, int n)
-{
-    double s = 0.0;
-    for (int r = 0; r < n; r++) s = s + sig[perm[r]];
-    return 2.0 * DBL_EPSILON * s;
-}
 // x = pinv(A) b from the image of pnp_svd (lane 0)
 PNP_HD void pnp_pinv_solve(const double* G, int m, int n, const double* V, const double* sig, const int* perm, const double* b, double* x)
 {

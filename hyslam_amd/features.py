@@ -1088,6 +1088,125 @@ class Sim3Solver:
         return float(self.state["s"][0])
 
 
+class MonoEstimator:
+    """HYSLAM::MonoEstimator (src/initializers/MonoEstimator.h) on flat arrays: homography and fundamental RANSAC on shared 8-point sets, the choice
+    between the two models and the reconstruction of the first pose and points, computed by hs_monoinit_estimate (include/hyslam_amd.h; DESIGN.md
+    5.21).  Built from the reference frame's key points (KP_DTYPE, or [n, 2] pixel coordinates), the camera (fx, fy, cx, cy) and
+    MonoEstimatorParams.  `seed` replaces SeedRandOnce(0) + RandomInt; `draws` (uint32 [cap, HS_MONOINIT_DRAW_STRIDE]) directs the samples of the
+    first cap iterations.  The call keeps no state: every Initialize starts afresh, as the reference's does."""
+
+    def __init__(self, kps1, camera, sigma=1.0, MaxIterations=200, minTriangulated=50, minFracTriangulated=0.9, minParallax=1.0, seed=0, draws=None, extractor=None):
+        self._ex = extractor or ORBExtractor()
+        self.kps1 = self.keypoints(kps1)
+        self.camera = tuple(np.float32(c) for c in camera[:4])
+        self.sigma, self.MaxIterations, self.minTriangulated = float(sigma), int(MaxIterations), int(minTriangulated)
+        self.minFracTriangulated, self.minParallax, self.seed = float(minFracTriangulated), float(minParallax), int(seed)
+        self.draws = None if draws is None else np.ascontiguousarray(draws, np.uint32).reshape(-1, N.HS_MONOINIT_DRAW_STRIDE)
+        self.result = None
+
+    @staticmethod
+    def keypoints(kps):
+        """KP_DTYPE records from KP_DTYPE records or from [n, 2] pixel coordinates (only x and y are read)"""
+        if getattr(kps, "dtype", None) is not None and kps.dtype.names:
+            return np.ascontiguousarray(kps, N.KP_DTYPE).reshape(-1)
+        xy = np.asarray(kps, np.float32).reshape(-1, 2)
+        out = np.zeros(len(xy), N.KP_DTYPE)
+        out["x"], out["y"] = xy[:, 0], xy[:, 1]
+        return out
+
+    def params(self):
+        p = np.zeros(1, N.MONOINIT_PARAMS_DTYPE)
+        p["fx"], p["fy"], p["cx"], p["cy"] = self.camera
+        p["sigma"], p["max_iterations"], p["min_triangulated"] = self.sigma, self.MaxIterations, self.minTriangulated
+        p["min_frac_triangulated"], p["min_parallax_deg"], p["seed"] = self.minFracTriangulated, self.minParallax, self.seed
+        return p
+
+    @staticmethod
+    def _draws(estimators):
+        """the call's draws table [Q, cap, stride] or None; a table shorter than the call's is continued with the generator's own words"""
+        cap = max([0] + [len(e.draws) for e in estimators if e.draws is not None])
+        if not cap:
+            return None, 0
+        draws = np.zeros((len(estimators), cap, N.HS_MONOINIT_DRAW_STRIDE), np.uint32)
+        for q, e in enumerate(estimators):
+            draws[q] = _ransac_words(e.seed, cap, 8, N.HS_MONOINIT_DRAW_STRIDE)
+            if e.draws is not None:
+                draws[q, :len(e.draws)] = e.draws
+        return draws, cap
+
+    @staticmethod
+    def parallax_deg(result):
+        """the reference's parallax of the motion that decided, in degrees, from the cosine the library reports"""
+        import math
+        c = float(result["cos_parallax"])
+        return math.degrees(math.acos(max(-1.0, min(1.0, c)))) if c == c else float("nan")
+
+    @staticmethod
+    def initialize_batch(estimators, kps2_list, matches12_list):
+        """Initialize of Q estimators (one per monocular camera) in ONE call: a list of Initialize's tuples"""
+        ex, Q = estimators[0]._ex, len(estimators)
+        k2 = [MonoEstimator.keypoints(k) for k in kps2_list]
+        m12 = [np.ascontiguousarray(m, np.int32).reshape(-1) for m in matches12_list]
+        for e, m in zip(estimators, m12):
+            if len(m) != len(e.kps1):
+                raise ValueError("matches12 holds one entry per key point of the reference frame")
+        off1, off2 = np.zeros(Q + 1, np.int64), np.zeros(Q + 1, np.int64)
+        off1[1:], off2[1:] = np.cumsum([len(e.kps1) for e in estimators]), np.cumsum([len(k) for k in k2])
+        kps1, kps2, matches = np.concatenate([e.kps1 for e in estimators]), np.concatenate(k2), np.concatenate(m12)
+        par = np.concatenate([e.params() for e in estimators])
+        draws, cap = MonoEstimator._draws(estimators)
+        n1 = int(off1[Q])
+        res = np.zeros(Q, N.MONOINIT_RESULT_DTYPE)
+        inl_h, inl_f, p3d, tri = np.zeros(n1, np.uint8), np.zeros(n1, np.uint8), np.zeros((n1, 3), np.float32), np.zeros(n1, np.uint8)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_monoinit_estimate(ex._h, Q, p(par), p(off1), p(kps1), p(off2), p(kps2), p(matches), p(draws) if cap else None, cap, p(res), p(inl_h),
+                                                    p(inl_f), p(p3d), p(tri)))
+        out = []
+        for q, e in enumerate(estimators):
+            sl = slice(off1[q], off1[q + 1])
+            e.result, e.inliers_h, e.inliers_f = res[q].copy(), inl_h[sl].copy(), inl_f[sl].copy()
+            ok = int(res["status"][q]) in (N.HS_MONOINIT_OK_H, N.HS_MONOINIT_OK_F)
+            out.append((ok, res["R21"][q].reshape(3, 3).copy() if ok else None, res["t21"][q].copy() if ok else None, p3d[sl].copy(), tri[sl].astype(bool), e.result))
+        return out
+
+    def Initialize(self, kps2, matches12):
+        """bool Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated): (ok, R21 3x3 or None, t21 or None, vP3D [n1, 3], vbTriangulated
+        [n1], the result record).  A pose that holds a NaN or an infinity (HS_MONOINIT_NONFINITE) is handed out as a failure."""
+        return MonoEstimator.initialize_batch([self], [kps2], [matches12])[0]
+
+    @staticmethod
+    def draws_table(estimators):
+        """(uint32 [Q, cap, HS_MONOINIT_DRAW_STRIDE] or None, cap): the call's draws table, for a caller of initialize_batch_device to put on the device"""
+        return MonoEstimator._draws(estimators)
+
+    @staticmethod
+    def work_bytes(estimators, n1_total):
+        ex = estimators[0]._ex
+        return int(ex._lib.hs_monoinit_work_bytes(len(estimators), int(n1_total), max(e.MaxIterations for e in estimators)))
+
+    @staticmethod
+    def initialize_batch_device(estimators, d_kps1, key_offsets1, d_kps2, key_offsets2, d_matches12, d_results, d_inliers_h, d_inliers_f, d_p3d, d_triangulated,
+                                d_work, d_draws=None, draw_cap=0, stream=None):
+        """the enqueue-only form (hs_monoinit_estimate_device) on memory of the extractor's device that the CALLER owns, inputs, outputs and work area
+        alike: every d_* is a raw address or an object that names one through data_ptr() (a torch tensor) or .ptr.  d_kps1 / d_kps2 hold hs_keypoint
+        records, d_matches12 int32 [n1_total]; the offsets are host sequences of Q + 1; d_results takes Q records of MONOINIT_RESULT_DTYPE, d_inliers_h /
+        d_inliers_f / d_triangulated n1_total bytes, d_p3d n1_total x 3 floats, d_work work_bytes(estimators, n1_total) bytes.  d_draws / draw_cap: the
+        table of draws_table(estimators) on the device, where one is wanted.  Enqueues on `stream` (None: the handle's own) and synchronises
+        nothing: the caller orders its reads behind the call on that stream and keeps every buffer alive until then."""
+        ex, Q = estimators[0]._ex, len(estimators)
+        off1, off2 = np.ascontiguousarray(key_offsets1, np.int64), np.ascontiguousarray(key_offsets2, np.int64)
+        par = np.concatenate([e.params() for e in estimators])
+
+        def ptr(x):
+            if x is None:
+                return None
+            return C.c_void_p(int(x.data_ptr() if hasattr(x, "data_ptr") else x.ptr if hasattr(x, "ptr") else x))
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(ex._h, ex._lib.hs_monoinit_estimate_device(ex._h, Q, p(par), p(off1), ptr(d_kps1), p(off2), ptr(d_kps2), ptr(d_matches12),
+                                                           ptr(d_draws) if draw_cap else None, int(draw_cap), ptr(d_results), ptr(d_inliers_h), ptr(d_inliers_f),
+                                                           ptr(d_p3d), ptr(d_triangulated), ptr(d_work), ptr(stream)))
+
+
 class _DevBuf:
     """a block of device memory on the extractor's device for FrameTracker's numpy calls (hs_device_alloc / hs_device_copy / hs_device_free)"""
 

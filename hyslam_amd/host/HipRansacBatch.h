@@ -1,4 +1,5 @@
-// HipRansacBatch.h — what the static iterate(solvers, nIterations, results) of HipPnPsolver and HipSim3Solver share: gather every solver's parameters,
+// HipRansacBatch.h — what the static batched forms of HipPnPsolver, HipSim3Solver and HipMonoEstimator share (the handle and the error of one call
+// for all: batch_handle, batch_check) and what the static iterate(solvers, nIterations, results) of the first two share: gather every solver's parameters,
 // state, correspondences and best mask into the flat arrays of hs_pnp_iterate / hs_sim3_iterate (include/hyslam_amd.h), make ONE call on the first
 // solver's handle, and put every solver's state and best mask back.  What a status means, and the Result it becomes, stays with each solver.
 #pragma once
@@ -9,6 +10,13 @@
 
 namespace HYSLAM {
 namespace hip_detail {
+
+// the handle a batched call runs on (the first solver's, or the calling thread's own) and the exception a failed call becomes: shared by RansacBatch
+// below and by HipMonoEstimator's static Initialize, whose call has no state and therefore no RansacBatch
+inline hs_orb* batch_handle(hs_orb* first, const char* who) { return first ? first : thread_handle(default_device().load(), who); }
+inline void batch_check(int st, hs_orb* use, const char* who) {
+    if (st != HS_OK) throw std::runtime_error(std::string(who) + ": " + hs_status_string(st) + ": " + hs_orb_last_error(use));
+}
 
 // Solver has handle_, params_, state_, corrs_ and best_mask_ (and names this struct a friend); Info is the hs_*_result of its C entry point `iterate`.
 // After construction offsets, corrs, inliers and res hold the call's arrays: solver q owns [offsets[q], offsets[q + 1]) of corrs and inliers.
@@ -38,9 +46,9 @@ template <class Solver, class Info> struct RansacBatch {
         // accept — they ask for corrs and the two masks only where corr_offsets[Q] > 0, and stage, copy and index nothing of an empty array.
         inliers.assign(corrs.size(), 0);
         res.resize(Q);
-        hs_orb* use = solvers[0]->handle_ ? solvers[0]->handle_ : thread_handle(default_device().load(), who);
+        hs_orb* use = batch_handle(solvers[0]->handle_, who);
         const int st = iterate(use, Q, params.data(), offsets.data(), corrs.data(), nIterations, nullptr, 0, states.data(), best.data(), res.data(), inliers.data());
-        if (st != HS_OK) throw std::runtime_error(std::string(who) + ": " + hs_status_string(st) + ": " + hs_orb_last_error(use));
+        batch_check(st, use, who);
         for (int q = 0; q < Q; q++) {
             solvers[q]->state_ = states[q];
             solvers[q]->best_mask_.assign(best.begin() + offsets[q], best.begin() + offsets[q + 1]);

@@ -21,6 +21,7 @@
 
 namespace cv {
 struct Point2f { float x = 0, y = 0; Point2f() {} Point2f(float x_, float y_) : x(x_), y(y_) {} };
+struct Point3f { float x = 0, y = 0, z = 0; Point3f() {} Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {} };
 struct KeyPoint {                      // field names of cv::KeyPoint (opencv2/core/types.hpp)
     Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1;
 };
@@ -137,6 +138,9 @@ public:
     float cy() const { return K.at<float>(1, 2); }
     float mb() const { return mbf / K.at<float>(0, 0); }
 };
+
+// src/initializers/MonoEstimator.h:39-45
+struct MonoEstimatorParams { float sigma = 1.0f; int minTriangulated = 50; float minFracTriangulated = 0.9f; int MaxIterations = 200; };
 
 // src/main/ORBSLAM_datastructs.h:34-45 — the parameter block Optimizer::PoseOptimization takes and does not read
 struct optInfo { bool realtime = false; int GBAinterval = 0; int GBAtype = 0; };

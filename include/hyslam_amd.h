@@ -932,6 +932,85 @@ int  hs_sim3_iterate_device(hs_orb* h, int Q, const hs_sim3_params* params, cons
                             const uint32_t* d_draws, int draw_cap, hs_sim3_state* d_states, uint8_t* d_best_masks, hs_sim3_result* d_results,
                             uint8_t* d_inlier_masks, void* d_work, void* stream);
 
+/* ================= monocular initialisation: MonoEstimator, homography and fundamental RANSAC, then reconstruction =================
+ * (src/initializers/MonoEstimator.cpp.)  A call takes Q independent problems (one per monocular camera) and runs, for each, what
+ * MonoEstimator::Initialize runs: the compaction of matches12 into mvMatches12, Normalize of both frames, max_iterations homography and as many
+ * fundamental hypotheses on the SAME 8-point sets, each scored over all N matches, the choice between the two models by RH = SH / (SH + SF), and
+ * ReconstructH (8 motions) or ReconstructF (4 motions) with CheckRT over the model's inliers.  One call, no state between calls.  N is known only
+ * on the device: nothing of a call depends on a host read.  DESIGN.md 5.21 lists the behaviour item by item.  No float atomics, every float sum is
+ * one lane's in the reference's order: the same call gives the same bytes.  Three stated rules for what cannot be reproduced:
+ *   - DESIGN.md D20 defines the linear algebra OpenCV does inside (SVDecomp, inv, determinant, norm): float operands widened, D17's Jacobi in
+ *     double, one narrowing where the reference holds a float Mat; 3x3 products by D19;
+ *   - DESIGN.md D21: no transcendental on the device.  The parallax is reported and compared as a COSINE, against the float nearest
+ *     cos(min_parallax_deg * pi / 180), formed on the host;
+ *   - draws follow D18 with a set of 8: draw k of iteration `it` is element seed + 8 it + k of the SplitMix64 sequence, randi =
+ *     (hi32(r) * avail) >> 32, swap-with-back.  A table draws[q][it][k] (uint32, HS_MONOINIT_DRAW_STRIDE words per iteration, draw_cap iterations
+ *     per problem) overrides it for it < draw_cap. */
+#define HS_MONOINIT_DRAW_STRIDE 8
+typedef struct hs_monoinit_params {
+    float fx, fy, cx, cy;              /* mK                                                                          */
+    float sigma;                       /* MonoEstimatorParams::sigma (1.0)                                            */
+    int32_t max_iterations;            /* MaxIterations (200): hypotheses per model; 1 .. HS_MONOINIT_MAX_ITERATIONS   */
+    int32_t min_triangulated;          /* minTriangulated (50)                                                        */
+    float min_frac_triangulated;       /* minFracTriangulated (0.9f)                                                  */
+    float min_parallax_deg;            /* the 1.0 Initialize passes to ReconstructH / ReconstructF; must be > 0       */
+    int32_t _pad;
+    uint64_t seed;                     /* replaces SeedRandOnce(0) + RandomInt                                        */
+} hs_monoinit_params;                  /* 48 bytes */
+#define HS_MONOINIT_MAX_ITERATIONS 65535
+#define HS_MONOINIT_TOO_FEW 0          /* N < 8: nothing ran, every output zero                                       */
+#define HS_MONOINIT_FAILED 1           /* Initialize returns false: R21, t21, p3d and triangulated are zero           */
+#define HS_MONOINIT_OK_H 2             /* true, reconstructed from the homography                                     */
+#define HS_MONOINIT_OK_F 3             /* true, reconstructed from the fundamental matrix                             */
+#define HS_MONOINIT_NONFINITE 4        /* true, yet R21 or t21 holds a NaN or an infinity                             */
+#define HS_MONOINIT_MODEL_NONE 0
+#define HS_MONOINIT_MODEL_H 1
+#define HS_MONOINIT_MODEL_F 2
+typedef struct hs_monoinit_result {
+    int32_t status;                    /* HS_MONOINIT_*                                                               */
+    int32_t n_matches;                 /* N = mvMatches12.size()                                                      */
+    int32_t model;                     /* HS_MONOINIT_MODEL_*: the one handed to reconstruction (NONE: TOO_FEW, or both scores 0) */
+    int32_t best_solution;             /* the motion that decided (H: bestSolutionIdx; F: the first with maxGood), -1: none */
+    int32_t best_it_h, best_it_f;      /* the iteration whose model won; -1: no hypothesis scored above 0             */
+    int32_t n_triangulated;            /* true entries of `triangulated`                                              */
+    int32_t _pad;
+    float score_h, score_f, rh;        /* SH, SF, RH = SH / (SH + SF)                                                 */
+    float cos_parallax;                /* the selected cosine of best_solution (1 where it has no good point or there is none) */
+    float H21[9], F21[9];              /* the winning models, row-major (zeros where best_it is -1)                   */
+    int32_t n_good[8];                 /* nGood of every motion (H: 8, F: the first 4)                                */
+    float R21[9], t21[3];
+} hs_monoinit_result;                  /* 200 bytes */
+/* bytes of d_work for a call of Q problems whose frames 1 hold n1_total key points, with at most max_iterations hypotheses per model */
+size_t hs_monoinit_work_bytes(int Q, int64_t n1_total, int max_iterations);
+/* The predicate of both forms below: pure host code over the by-value arguments and the three host arrays (params, key_offsets1, key_offsets2);
+ * the pointers are only compared with NULL and, for device != 0, with their alignment.  Returns NULL where the call would be accepted, else
+ * the refusal's text: NULL pointers, Q < 1, negative or decreasing offsets, a frame above 2^31 - 1 key points, max_iterations outside
+ * [1, HS_MONOINIT_MAX_ITERATIONS], sigma or a focal length that is not positive and finite, min_parallax_deg outside (0, 180),
+ * min_frac_triangulated not finite, draw_cap < 0 or a table without words; device form: d_kps1, d_kps2 or d_work not 16-byte aligned. */
+const char* hs_monoinit_check(int Q, const hs_monoinit_params* params, const int64_t* key_offsets1, const hs_keypoint* kps1, const int64_t* key_offsets2,
+                              const hs_keypoint* kps2, const int32_t* matches12, const uint32_t* draws, int draw_cap, const hs_monoinit_result* results,
+                              const uint8_t* inliers_h, const uint8_t* inliers_f, const float* p3d, const uint8_t* triangulated, int device, const void* d_work);
+/* MonoEstimator::Initialize for Q problems.  Problem q owns kps1 [key_offsets1[q], key_offsets1[q + 1]) (n1 key points of the reference frame),
+ * the same range of matches12 (matches12[i] = key point of frame 2 matched to key point i, a value outside [0, n2): none), of inliers_h and
+ * inliers_f (u8 per COMPACTED match: entry j < N belongs to the j-th match in ascending i; entries from N on are 0), of p3d ([n1][3] float) and of
+ * triangulated (u8 [n1], by key point of frame 1 like vP3D / vbTriangulated), and kps2 [key_offsets2[q], key_offsets2[q + 1]).  Every output is
+ * ALWAYS written.  draws may be NULL with draw_cap = 0.  Host form: host pointers, synchronous, staged through the handle's scratch.
+ * HS_ERR_INVALID, nothing enqueued and no output touched: what hs_monoinit_check refuses. */
+int  hs_monoinit_estimate(hs_orb* h, int Q, const hs_monoinit_params* params, const int64_t* key_offsets1, const hs_keypoint* kps1, const int64_t* key_offsets2,
+                          const hs_keypoint* kps2, const int32_t* matches12, const uint32_t* draws, int draw_cap, hs_monoinit_result* results,
+                          uint8_t* inliers_h, uint8_t* inliers_f, float* p3d, uint8_t* triangulated);
+/* The same with device pointers, enqueued on `stream` (NULL = the handle's own), nothing synchronises; params and the two offset arrays stay host
+ * arrays and are read before the call returns.  d_kps1, d_kps2 and d_work (hs_monoinit_work_bytes bytes) are 16-byte aligned. */
+int  hs_monoinit_estimate_device(hs_orb* h, int Q, const hs_monoinit_params* params, const int64_t* key_offsets1, const hs_keypoint* d_kps1,
+                                 const int64_t* key_offsets2, const hs_keypoint* d_kps2, const int32_t* d_matches12, const uint32_t* d_draws, int draw_cap,
+                                 hs_monoinit_result* d_results, uint8_t* d_inliers_h, uint8_t* d_inliers_f, float* d_p3d, uint8_t* d_triangulated,
+                                 void* d_work, void* stream);
+
+/* Measurement and parity tests: which of the two layouts of stage 2 the next calls launch, 0 (the default: one wave per hypothesis and model,
+ * k_mono_hypotheses) or 1 (one lane per hypothesis, k_mono_hypotheses_lane).  Both give the same bytes.  Returns the previous value; any other
+ * argument changes nothing.  Process-wide. */
+int  hs_debug_monoinit_layout(int layout);
+
 /* ================= frame tracking on resident tables: TrackMotionModel::track + TrackLocalMap::track =================
  * (src/slam/tracking/TrackMotionModel.cpp:14-83, TrackLocalMap.cpp:9-78, src/core/LandMarkMatches.cpp:26-64, Frame::UpdatePoseMatrices,
  * FeatureMatcher.cc:57-176.)  The glue between the device entry points above, as kernels: a pose that a kernel left in HBM feeds the next search,
